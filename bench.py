@@ -8,6 +8,12 @@ on one synthetic batch per GPU that is already resident in HBM: bf16 MFMA operan
 stream / master weights, the per-step refresh of the bf16 weight shadows (what autocast re-does every step in the
 reference, Siglip2sidafrozen.py:1375) and, for N > 1, the bucketed gradient all-reduce over RCCL overlapped with
 backward.  No optimizer step (metric is train fwd+bwd).  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  `--full` adds every other measurement
+after the headline (N = 1): kernel roofline and per-family step breakdown, secondary configurations, the optimizer step
+and the full training step, the CPU oracle baseline and the tolerance / strict-mode leg.  `--dump-outputs DIR` writes what
+the last timed step handed its caller (pooled output, loss, a fixed sample of the last hidden state, per-parameter
+gradient norms and a fixed sample of the gradients) as float32 / float64 .npy files, to compare two builds output for output.
 """
 from __future__ import annotations
 
@@ -39,14 +45,21 @@ def parse():
     ap.add_argument("--mode", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--freeze-below", type=int, default=0,
                     help="secondary metric (SURVEY.md 8d): freeze embeddings and blocks < K as Siglip2sidafrozen.py:757-768")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run the other legs (N = 1): roofline, step breakdown, secondary metrics, "
+                         "optimizer step, full train step, CPU baseline, tolerance; a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, fixed samples "
+                         "of the large tensors)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline leg")
     ap.add_argument("--cpu-steps", type=int, default=3)
     ap.add_argument("--kernel-reps", type=int, default=20,
-                    help="launches per kernel for the roofline / breakdown legs; 0 skips them (clean rocprofv3 traces)")
+                    help="--full: launches per kernel for the roofline / breakdown legs; 0 skips them")
     ap.add_argument("--no-optimizer", action="store_true",
-                    help="skip the optimizer-step and full-train-step legs (clean rocprofv3 traces of the timed step)")
+                    help="--full: skip the optimizer-step and full-train-step legs")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the secondary metrics of SURVEY.md 8d (batch sweep, base-patch16-224 B=256, frozen prefix)")
+                    help="--full: skip the secondary metrics of SURVEY.md 8d (batch sweep, base-patch16-224 B=256, "
+                         "frozen prefix)")
     ap.add_argument("--wire", default="fp32", choices=["fp32", "bf16"],
                     help="N > 1: gradient exchange format (ddp.GradBucketReducer)")
     ap.add_argument("--max-buckets", type=int, default=8, help="N > 1: gradient chunks (= collectives) per step")
@@ -531,20 +544,24 @@ def set_frozen_prefix(model, k):
             p.requires_grad = i >= k
 
 
-def timed_steps(model, x, warmup, steps, world=1):
+def timed_steps(model, x, warmup, steps, world=1, keep=None):
     """W untimed steps, then K steps bracketed by barrier + synchronize on both sides (the contract's wall clock), with a
-    HIP event between steps on the launch stream for the per-step distribution.  Returns (seconds, [ms per step])."""
-    params = [p for p in model.parameters()]
+    HIP event between steps on the launch stream for the per-step distribution.  Returns (seconds, [ms per step]).
+    `keep` (a dict) receives the last timed step's output, loss and (name, gradient) pairs."""
+    named = list(model.named_parameters())
+    params = [p for _, p in named]
     trainable = [p for p in params if p.requires_grad]
     st = torch.cuda.current_stream()
 
-    def step():
+    def step(keep=None):
         # an optimizer step happened: every trainable parameter changed, so its bf16 shadows are re-cast in this step
         # (what autocast re-does per step in the reference, Siglip2sidafrozen.py:1375); frozen tensors keep theirs
         torch.autograd.graph.increment_version(trainable)
         out = model(pixel_values=x, interpolate_pos_encoding=True)
         loss = out.pooler_output.square().mean()
         loss.backward()
+        if keep is not None:
+            keep.update(out=out, loss=loss, grads=[(n, p.grad) for n, p in named if p.grad is not None])
         for p in params:
             p.grad = None
 
@@ -558,7 +575,7 @@ def timed_steps(model, x, warmup, steps, world=1):
     t0 = time.perf_counter()
     evs[0].record(st)
     for i in range(steps):
-        step()
+        step(keep if i == steps - 1 else None)
         evs[i + 1].record(st)
     torch.cuda.synchronize()
     if world > 1:
@@ -566,6 +583,38 @@ def timed_steps(model, x, warmup, steps, world=1):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     return dt, [evs[i].elapsed_time(evs[i + 1]) for i in range(steps)]
+
+
+def dump_outputs(path, kept, hidden_rows=2048, grad_sample=4096, seed=0):
+    """--dump-outputs: what the last timed step handed its caller, copied to the host as .npy files (about 14 MB at the
+    default workload).  The large tensors are sampled at positions drawn from a fixed seed, so two runs with the same
+    arguments sample the same elements:
+      pooler_output.npy            [B, D] float32, complete
+      loss.npy                     []     float64, mean(pooler_output^2)
+      last_hidden_state_rows.npy   [R, D] float32, R token rows of the flattened [B*N, D] tensor (sorted row indices)
+      grad_norms.npy               [P]    float64, L2 norm of every parameter gradient, in named_parameters() order
+      grad_sample.npy              [S]    float32, up to `grad_sample` elements of each gradient, concatenated in that order"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    g = torch.Generator().manual_seed(seed)
+    out = kept["out"]
+
+    def save(name, t, dtype=np.float32):
+        np.save(os.path.join(path, name + ".npy"), t.detach().cpu().numpy().astype(dtype))
+
+    save("pooler_output", out.pooler_output.float())
+    save("loss", kept["loss"].double(), np.float64)
+    rows = out.last_hidden_state.reshape(-1, out.last_hidden_state.shape[-1])
+    idx = torch.randperm(rows.shape[0], generator=g)[:hidden_rows].sort().values
+    save("last_hidden_state_rows", rows[idx.to(rows.device)].float())
+    norms, samples = [], []
+    for _, gr in kept["grads"]:
+        flat = gr.reshape(-1)
+        norms.append(flat.double().norm())
+        pick = torch.randint(0, flat.numel(), (min(grad_sample, flat.numel()),), generator=g)
+        samples.append(flat[pick.to(flat.device)].float())
+    save("grad_norms", torch.stack(norms), np.float64)
+    save("grad_sample", torch.cat(samples))
 
 
 def frozen_prefix_flops(cfg, gh, k):
@@ -656,13 +705,17 @@ def main():
         reducer = pkg.GradBucketReducer(wire=args.wire, max_buckets=args.max_buckets).attach(model)
         reducer.time_exposed = True
     x = pkg.weights.seeded_pixels(args.batch, res, res, seed=1234 + rank).to(dev)
+    kept = {} if args.dump_outputs and rank == 0 else None
 
     if reducer is not None:     # warm-up first, then measure only the timed region's exposed waits
         dt_w, _ = timed_steps(model, x, args.warmup, 0, world)
         reducer.exposed_ms()
-        dt, per = timed_steps(model, x, 0, args.steps, world)
+        dt, per = timed_steps(model, x, 0, args.steps, world, keep=kept)
     else:
-        dt, per = timed_steps(model, x, args.warmup, args.steps, world)
+        dt, per = timed_steps(model, x, args.warmup, args.steps, world, keep=kept)
+    if kept is not None:
+        dump_outputs(args.dump_outputs, kept)
+        kept = None
     my_rate = args.batch * args.steps / dt
     rates = [my_rate]
     exposed = reducer.exposed_ms() if reducer is not None else []
@@ -710,9 +763,10 @@ def main():
         line["backend"] = backend
         line["rccl_max_nchannels"] = os.environ.get("NCCL_MAX_NCHANNELS")
     if rank == 0:
-        print(f"[bench] {value:.1f} images/s, {ms_per_step:.1f} ms/step; measuring kernel roofline + CPU baseline ...",
-              file=sys.stderr, flush=True)
-        if world == 1:
+        if world == 1 and args.full:
+            print(f"[bench] {value:.1f} images/s, {ms_per_step:.1f} ms/step; measuring kernel roofline + CPU baseline ...",
+                  file=sys.stderr, flush=True)
+
             def leg(key, fn, into=None):
                 """Optional legs never cost the headline: a failure is reported in the line instead of killing it."""
                 try:
