@@ -109,4 +109,27 @@ __device__ __forceinline__ void epi_apply(const EpiParams& p, int row, int col, 
   }
 }
 
+// Host side: calls launch(EpiTag<EPI, TOut>{}) for a runtime (epilogue, output dtype) pair, so that every GEMM family
+// instantiates the same table: bf16 or fp32 outputs for the first four epilogues (fp32 = bf16x3 strict mode on the MFMA
+// kernels), fp32 for the others.
+template <int EPI, typename TOut>
+struct EpiTag {
+  static constexpr int epi = EPI;
+  using out = TOut;
+};
+template <typename Launch>
+hipError_t dispatch_epilogue(int epi, int out_dtype, Launch&& launch) {
+  const bool b16 = out_dtype == DT_BF16;
+  switch (epi) {
+    case EPI_STORE: return b16 ? launch(EpiTag<EPI_STORE, bf16>{}) : launch(EpiTag<EPI_STORE, float>{});
+    case EPI_BIAS_GELU: return b16 ? launch(EpiTag<EPI_BIAS_GELU, bf16>{}) : launch(EpiTag<EPI_BIAS_GELU, float>{});
+    case EPI_QKV: return b16 ? launch(EpiTag<EPI_QKV, bf16>{}) : launch(EpiTag<EPI_QKV, float>{});
+    case EPI_GELU_BWD: return b16 ? launch(EpiTag<EPI_GELU_BWD, bf16>{}) : launch(EpiTag<EPI_GELU_BWD, float>{});
+    case EPI_RES_F32: return launch(EpiTag<EPI_RES_F32, float>{});
+    case EPI_POS_F32: return launch(EpiTag<EPI_POS_F32, float>{});
+    case EPI_F32: return launch(EpiTag<EPI_F32, float>{});
+  }
+  return hipErrorInvalidValue;
+}
+
 }  // namespace sgl

@@ -19,8 +19,6 @@
 // residual, head-major QKV scatter, ...) works on 8 consecutive columns per lane with 16-byte global accesses.
 //
 // Roofline: MFMA-bound (arithmetic intensity K/2... >> machine balance); algorithmic FLOPs = 2*M*N*K.
-#include <stdlib.h>
-
 #include "common.hip.h"
 #include "epilogue.hip.h"
 #include "kernels.h"
@@ -313,180 +311,101 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const bf16* __restrict_
 // ------------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------------
-// 256x256-tile LDS-DMA generation (gemm_bf16_v2.hip); used whenever the problem is large enough to fill the chip
-hipError_t gemm_nt2_bf16(const void* A, int lda, const void* B, int ldb, int M, int N, int K, int epi, int out_dtype,
-                         const EpiParams& p, hipStream_t s);
-hipError_t gemm_tn2_bf16(const void* A, int lda, const void* B, int ldb, int Mred, int N1, int N2, int m_per,
-                         int splits, const EpiParams& p, hipStream_t s);
-#ifdef SGL_AB   // developer A/B build (make AB=1): the measured-slower generations 7 / 8 and the "generation 1 everywhere" switch
-// persistent generation 7 (gemm_bf16_v3.hip); hipErrorNotSupported = outside its envelope, fall back to generation 6
-hipError_t gemm_nt7_bf16(const void* A, int lda, const void* B, int ldb, int M, int N, int K, int epi, int out_dtype,
-                         const EpiParams& p, hipStream_t s);
-// four-wave generation 8 (gemm_bf16_v4.hip), opt-in with SGL_GEMM_GEN=8; hipErrorNotSupported = fall back to generation 6
-hipError_t gemm_nt8_bf16(const void* A, int lda, const void* B, int ldb, int M, int N, int K, int epi, int out_dtype,
-                         const EpiParams& p, hipStream_t s);
-// SGL_GEMM_GEN=1 forces the 128x128 register-staged kernels (A/B comparisons)
-static int gemm_generation() {
-  static int gen = -1;
-  if (gen < 0) {
-    const char* e = getenv("SGL_GEMM_GEN");
-    gen = (e && e[0] == '1') ? 1 : 2;
-  }
-  return gen;
-}
-#else
-static inline int gemm_generation() { return 2; }
-#endif
-static bool g_attr_done = false;
+// 256x256-tile LDS-DMA kernels (gemm_bf16_v2.hip), used whenever the problem is large enough to fill the chip
+hipError_t gemm_nt256_bf16(const void* A, int lda, const void* B, int ldb, int M, int N, int K, int epi, int out_dtype,
+                           const EpiParams& p, hipStream_t s);
+hipError_t gemm_tn256_bf16(const void* A, int lda, const void* B, int ldb, int Mred, int N1, int N2, int m_per,
+                           int splits, const EpiParams& p, hipStream_t s);
 
 template <int EPI, typename TOut>
 static hipError_t launch_nt(const bf16* A, int lda, const bf16* B, int ldb, int M, int N, int K, const EpiParams& p,
                             hipStream_t s) {
-  static bool attr = false;
-  if (!attr) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_kernel<EPI, TOut>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, G_LDS);
-    if (e != hipSuccess) return e;
-    attr = true;
-  }
+  const hipError_t e = set_max_dynamic_lds_once<&gemm_nt_kernel<EPI, TOut>>(G_LDS);
+  if (e != hipSuccess) return e;
   const int tiles = ((M + G_BM - 1) / G_BM) * ((N + G_BN - 1) / G_BN);
   hipLaunchKernelGGL((gemm_nt_kernel<EPI, TOut>), dim3(tiles), dim3(256), G_LDS, s, A, lda, B, ldb, M, N, K, p);
   return hipGetLastError();
 }
 
-hipError_t gemm_nt_bf16(const void* A_, int lda, const void* B_, int ldb, int M, int N, int K, int epi, int out_dtype,
+hipError_t gemm_nt_bf16(const void* A, int lda, const void* B, int ldb, int M, int N, int K, int epi, int out_dtype,
                         const EpiParams& p, hipStream_t s) {
   if (M == 0 || N == 0) return hipSuccess;
   if ((lda % 8) || (ldb % 8) || (K % 8) || K <= 0) return hipErrorInvalidValue;
   if (epi != EPI_F32 && (N % 8)) return hipErrorInvalidValue;
   if ((size_t)M * lda * 2 >= (1ull << 32) || (size_t)N * ldb * 2 >= (1ull << 32)) return hipErrorInvalidValue;
-#ifndef SGL_NT6_MIN_N
-#define SGL_NT6_MIN_N 256
-#endif
-  if (gemm_generation() != 1 && M >= 2048 && N >= SGL_NT6_MIN_N) {
-#ifdef SGL_AB
-    // generation 7 (persistent tile loop, gemm_bf16_v3.hip): measured equal-or-slower than generation 6 on the encoder's
-    // shapes (negative results); A/B build only: SGL_GEMM_GEN=7
-    static const bool gen7 = getenv("SGL_GEMM_GEN") && atoi(getenv("SGL_GEMM_GEN")) == 7;
-    if (gen7) {
-      const hipError_t e = gemm_nt7_bf16(A_, lda, B_, ldb, M, N, K, epi, out_dtype, p, s);
-      if (e != hipErrorNotSupported) return e;
-    }
-    static const bool gen8 = getenv("SGL_GEMM_GEN") && atoi(getenv("SGL_GEMM_GEN")) == 8;
-    if (gen8) {
-      const hipError_t e = gemm_nt8_bf16(A_, lda, B_, ldb, M, N, K, epi, out_dtype, p, s);
-      if (e != hipErrorNotSupported) return e;
-    }
-#endif
-    return gemm_nt2_bf16(A_, lda, B_, ldb, M, N, K, epi, out_dtype, p, s);
-  }
-  const bf16* A = (const bf16*)A_;
-  const bf16* B = (const bf16*)B_;
-#define SGL_CASE(E)                                                                   \
-  case E:                                                                             \
-    return out_dtype == DT_BF16 ? launch_nt<E, bf16>(A, lda, B, ldb, M, N, K, p, s)   \
-                                : launch_nt<E, float>(A, lda, B, ldb, M, N, K, p, s);
-  switch (epi) {
-    SGL_CASE(EPI_STORE)
-    case EPI_BIAS_GELU:
-      return out_dtype == DT_BF16 ? launch_nt<EPI_BIAS_GELU, bf16>(A, lda, B, ldb, M, N, K, p, s)
-                                  : launch_nt<EPI_BIAS_GELU, float>(A, lda, B, ldb, M, N, K, p, s);   // bf16x3 strict mode
-    case EPI_QKV:
-      return out_dtype == DT_BF16 ? launch_nt<EPI_QKV, bf16>(A, lda, B, ldb, M, N, K, p, s)
-                                  : launch_nt<EPI_QKV, float>(A, lda, B, ldb, M, N, K, p, s);   // bf16x3 strict mode
-    case EPI_GELU_BWD:
-      return out_dtype == DT_BF16 ? launch_nt<EPI_GELU_BWD, bf16>(A, lda, B, ldb, M, N, K, p, s)
-                                  : launch_nt<EPI_GELU_BWD, float>(A, lda, B, ldb, M, N, K, p, s);   // bf16x3 strict mode
-    case EPI_RES_F32: return launch_nt<EPI_RES_F32, float>(A, lda, B, ldb, M, N, K, p, s);
-    case EPI_POS_F32: return launch_nt<EPI_POS_F32, float>(A, lda, B, ldb, M, N, K, p, s);
-    case EPI_F32: return launch_nt<EPI_F32, float>(A, lda, B, ldb, M, N, K, p, s);
-  }
-#undef SGL_CASE
-  return hipErrorInvalidValue;
+  if (M >= 2048 && N >= 256) return gemm_nt256_bf16(A, lda, B, ldb, M, N, K, epi, out_dtype, p, s);
+  return dispatch_epilogue(epi, out_dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return launch_nt<T::epi, typename T::out>((const bf16*)A, lda, (const bf16*)B, ldb, M, N, K, p, s);
+  });
 }
 
-hipError_t gemm_tn_bf16(const void* A_, int lda, const void* B_, int ldb, int Mred, int N1, int N2, int splits,
-                        const EpiParams& p_, hipStream_t s, float* split_ws, size_t split_ws_bytes) {
-  if (N1 == 0 || N2 == 0) return hipSuccess;
-  if ((lda % 8) || (ldb % 8)) return hipErrorInvalidValue;
-  if ((size_t)Mred * lda * 2 >= (1ull << 32) || (size_t)Mred * ldb * 2 >= (1ull << 32)) return hipErrorInvalidValue;
-  if (!g_attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, G_LDS);
-    if (e != hipSuccess) return e;
-    g_attr_done = true;
-  }
+// Split the token reduction of a TN GEMM into `splits` ranges of m_per rows (m_per a multiple of G_BK) and run
+// launch(m_per, splits, params).  With a workspace that holds every split's slab the splits store private slabs and
+// reduce_splits() sums them in a fixed order (deterministic, and ~4x cheaper than the atomic epilogue); otherwise they
+// add into the zeroed (or accumulated-into) output with fp32 atomics.
+template <typename Launch>
+static hipError_t tn_split_k(int Mred, int N1, int N2, int splits, const EpiParams& p_, hipStream_t s, float* split_ws,
+                             size_t split_ws_bytes, Launch&& launch) {
   EpiParams p = p_;
   float* out = reinterpret_cast<float*>(p.out);
-  if (Mred <= 0) {
-    if (!p.accumulate)
-      return hipMemset2DAsync(out, (size_t)p.ldo * sizeof(float), 0, (size_t)N2 * sizeof(float), N1, s);
-    return hipSuccess;
-  }
-  if (gemm_generation() != 1 && N1 >= 512 && N2 >= 512 && Mred >= 2048) {
-    // 256x256 tiles, one workgroup per CU: split the token reduction until ~256 workgroups exist
-    // 256x256 tiles, one workgroup per CU (128 KiB LDS): keep tiles*splits <= 256 (a single full round)
-    const int tiles = ((N1 + 255) / 256) * ((N2 + 255) / 256);
-    int sp = 256 / tiles;
-    if (sp < 1) sp = 1;
-    const int max_sp = Mred / 1024 > 0 ? Mred / 1024 : 1;
-    if (sp > max_sp) sp = max_sp;
-    int mp = (Mred + sp - 1) / sp;
-    mp = ((mp + G_BK - 1) / G_BK) * G_BK;
-    sp = (Mred + mp - 1) / mp;
-    if (sp > 1) {
-      const size_t slab = (size_t)N1 * N2;
-      if (split_ws && (size_t)sp * slab * sizeof(float) <= split_ws_bytes && p.alpha == 1.0f && !p.bias &&
-          (N2 % 4 == 0) && (p.ldo % 4 == 0) && ((((uintptr_t)out) | ((uintptr_t)split_ws)) & 15) == 0) {
-        // deterministic split-K: private slabs + a fixed-order reduction (also ~4x cheaper than the atomic epilogue)
-        EpiParams q = p;
-        q.out = split_ws;
-        q.ldo = N2;
-        q.accumulate = 0;
-        q.atomic = 0;
-        q.split_stride = slab;
-        hipError_t e = gemm_tn2_bf16(A_, lda, B_, ldb, Mred, N1, N2, mp, sp, q, s);
-        if (e != hipSuccess) return e;
-        return reduce_splits(split_ws, sp, slab, N1, N2, out, p.ldo, p.accumulate, s);
-      }
-      if (!p.accumulate) {
-        hipError_t e = hipMemset2DAsync(out, (size_t)p.ldo * sizeof(float), 0, (size_t)N2 * sizeof(float), N1, s);
-        if (e != hipSuccess) return e;
-      }
-      p.atomic = 1;
-    }
-    return gemm_tn2_bf16(A_, lda, B_, ldb, Mred, N1, N2, mp, sp, p, s);
-  }
   if (splits < 1) splits = 1;
   int m_per = (Mred + splits - 1) / splits;
   m_per = ((m_per + G_BK - 1) / G_BK) * G_BK;
   splits = (Mred + m_per - 1) / m_per;
-  const int tiles = ((N1 + G_BM - 1) / G_BM) * ((N2 + G_BN - 1) / G_BN);
   if (splits > 1) {
     const size_t slab = (size_t)N1 * N2;
     if (split_ws && (size_t)splits * slab * sizeof(float) <= split_ws_bytes && p.alpha == 1.0f && !p.bias &&
         (N2 % 4 == 0) && (p.ldo % 4 == 0) && ((((uintptr_t)out) | ((uintptr_t)split_ws)) & 15) == 0) {
-      EpiParams q = p;  // deterministic split-K, as in the 256x256 path above
+      EpiParams q = p;
       q.out = split_ws;
       q.ldo = N2;
       q.accumulate = 0;
       q.atomic = 0;
       q.split_stride = slab;
-      hipLaunchKernelGGL(gemm_tn_kernel, dim3(tiles, splits), dim3(256), G_LDS, s, (const bf16*)A_, lda,
-                         (const bf16*)B_, ldb, Mred, N1, N2, m_per, q);
-      hipError_t e = hipGetLastError();
+      const hipError_t e = launch(m_per, splits, q);
       if (e != hipSuccess) return e;
       return reduce_splits(split_ws, splits, slab, N1, N2, out, p.ldo, p.accumulate, s);
     }
     if (!p.accumulate) {
-      hipError_t e = hipMemset2DAsync(out, (size_t)p.ldo * sizeof(float), 0, (size_t)N2 * sizeof(float), N1, s);
+      const hipError_t e = hipMemset2DAsync(out, (size_t)p.ldo * sizeof(float), 0, (size_t)N2 * sizeof(float), N1, s);
       if (e != hipSuccess) return e;
     }
     p.atomic = 1;
   }
-  hipLaunchKernelGGL(gemm_tn_kernel, dim3(tiles, splits), dim3(256), G_LDS, s, (const bf16*)A_, lda, (const bf16*)B_,
-                     ldb, Mred, N1, N2, m_per, p);
-  return hipGetLastError();
+  return launch(m_per, splits, p);
+}
+
+hipError_t gemm_tn_bf16(const void* A, int lda, const void* B, int ldb, int Mred, int N1, int N2, int splits,
+                        const EpiParams& p, hipStream_t s, float* split_ws, size_t split_ws_bytes) {
+  if (N1 == 0 || N2 == 0) return hipSuccess;
+  if ((lda % 8) || (ldb % 8)) return hipErrorInvalidValue;
+  if ((size_t)Mred * lda * 2 >= (1ull << 32) || (size_t)Mred * ldb * 2 >= (1ull << 32)) return hipErrorInvalidValue;
+  if (Mred <= 0) {
+    if (!p.accumulate)
+      return hipMemset2DAsync(p.out, (size_t)p.ldo * sizeof(float), 0, (size_t)N2 * sizeof(float), N1, s);
+    return hipSuccess;
+  }
+  if (N1 >= 512 && N2 >= 512 && Mred >= 2048) {
+    // 256x256 tiles, one workgroup per CU (128 KiB LDS): split the token reduction so that tiles*splits <= 256 (a single
+    // full round), but keep at least 1024 tokens per split
+    const int tiles = ((N1 + 255) / 256) * ((N2 + 255) / 256);
+    int sp = 256 / tiles;
+    if (sp < 1) sp = 1;
+    const int max_sp = Mred / 1024 > 0 ? Mred / 1024 : 1;
+    if (sp > max_sp) sp = max_sp;
+    return tn_split_k(Mred, N1, N2, sp, p, s, split_ws, split_ws_bytes, [&](int m_per, int nsplit, const EpiParams& q) {
+      return gemm_tn256_bf16(A, lda, B, ldb, Mred, N1, N2, m_per, nsplit, q, s);
+    });
+  }
+  return tn_split_k(Mred, N1, N2, splits, p, s, split_ws, split_ws_bytes, [&](int m_per, int nsplit, const EpiParams& q) {
+    const hipError_t e = set_max_dynamic_lds_once<&gemm_tn_kernel>(G_LDS);
+    if (e != hipSuccess) return e;
+    const int tiles = ((N1 + G_BM - 1) / G_BM) * ((N2 + G_BN - 1) / G_BN);
+    hipLaunchKernelGGL(gemm_tn_kernel, dim3(tiles, nsplit), dim3(256), G_LDS, s, (const bf16*)A, lda, (const bf16*)B,
+                       ldb, Mred, N1, N2, m_per, q);
+    return hipGetLastError();
+  });
 }
 
 }  // namespace sgl

@@ -1,9 +1,9 @@
 // bf16 MFMA GEMMs for gfx950 on a 256x256 output tile, K-step 64, 512 threads = 8 waves, operands streamed
 // global -> LDS by LDS-DMA (buffer_load_dwordx4 ... lds, 1 KiB per wave instruction, no VGPR staging), two LDS stages
-// (2 x 64 KiB).  Main loops (they share the images, tile order and epilogues):
-//   nt6 / tn6: anti-phase wave groups, four barrier-separated slots per K-step (see the comment above them)
-//   nt2 / tn2: developer A/B build only (make AB=1, SGL_GEMM_GEN=2): one barrier per K-step, the DMA for step t+1 is
-//              issued right after the barrier that retires step t's DMA and runs under step t's 64 MFMAs per wave
+// (2 x 64 KiB).  The main loops gemm_nt6_kernel / gemm_tn6_kernel run anti-phase wave groups, four barrier-separated
+// slots per K-step (see the comment above them), and share the LDS images, tile order and epilogue below.
+// gemm_nt_bf16 / gemm_tn_bf16 (gemm_bf16.hip) send the shapes that fill the chip here, through gemm_nt256_bf16 /
+// gemm_tn256_bf16 at the end of this file.
 //
 //   nt : C[M,N]   = A[M,K] · B[N,K]ᵀ           (forward projections, dX with transposed weight shadows)
 //   tn : C[N1,N2] (+)= Σ_m A[m,N1] · B[m,N2]    (dW; token index is the MFMA k index via ds_read_b64_tr_b16)
@@ -13,10 +13,12 @@
 //
 // LDS-DMA writes lane-linear (wave-uniform base + lane*16), so the bank-conflict swizzles are applied to each
 // lane's SOURCE address and again on the fragment reads (same involution on both sides):
-//   nt2 image [256 rows][64 k]   128-B rows: slot s of row r holds source chunk s ^ (r & 7)
-//   tn2 image [64 m][256 n]      512-B rows: slot s of row m holds source chunk s ^ (2*(m&3) + 8*((m>>3)&1))
-// Wave w -> (wr, wc) = ((w>>1)&1, (w&1) + 2*(w>>2)) so that the two waves sharing a SIMD (w, w+4) sit in different
-// column halves: a half-empty last column tile (N = 1152 = 4.5 tiles) then costs half a tile, not a whole one.
+//   NT image [256 rows][64 k]   128-B rows: slot s of row r holds source chunk s ^ (r & 7)
+//   TN image [64 m][256 n]      512-B rows: slot s of row m holds source chunk s ^ (2*(m&3) + 8*((m>>3)&1))
+// Wave w -> (wr, wc) = ((w>>1)&1, (w&1) + 2*(w>>2)): the two waves sharing a SIMD (w, w+4) sit in different column
+// halves.  In a half-empty last column tile (N = 1152 = 4.5 tiles) the waves of the empty half skip their
+// instructions (`active`) but still take part in every barrier, so the workgroup holds its CU for the whole K loop:
+// that tile takes as long as a full one (the skipped work saves power, not time).
 // blockIdx -> tile is XCD-aware (unit_of_block / tile_of_unit below): each XCD works through a contiguous chunk of
 // a grouped tile order, so its concurrent workgroups share A and B panels in its private L2.  Measured with
 // rocprofv3 FETCH_SIZE on the fc1 shape: the earlier "row panel per XCD" map fetched 6x the algorithmic bytes
@@ -39,9 +41,6 @@ constexpr int T_STAGE = 2 * T_OP;         // 64 KiB
 constexpr int T_LDS = 2 * T_STAGE;        // 128 KiB
 constexpr int T_CT_LD = 260;              // fp32 epilogue staging stride (64 rows x 260 floats = 66,560 B)
 
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t r, char* lds, uint32_t voff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (SGL_LDS void*)lds, 16, voff, 0, 0, 0);
-}
 __device__ __forceinline__ bf16x4 lds_tr16v2(const char* p) {
   return __builtin_amdgcn_ds_read_tr16_b64_v4bf16((SGL_LDS bf16x4*)(p));
 }
@@ -245,26 +244,6 @@ __device__ __forceinline__ void store_tile256(char* smem, f32x4 (&acc)[8][4], in
   }
 }
 
-#ifdef SGL_AB   // generation 2 (developer A/B build only: make AB=1)
-// Compile-time interleave for one K-step: READS LDS reads per fragment (1 = ds_read_b128, 2 = two ds_read_b64_tr_b16).
-// prologue 7 fragments (4 B + 3 A), then 16 x {4 MFMA, prefetch of A[f+3] (+ one B fragment of the 2nd k-half at f=3..6)}
-template <int READS, int F>
-__device__ __forceinline__ void sched_step() {
-  __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
-  if constexpr (F <= 12) __builtin_amdgcn_sched_group_barrier(0x100, READS, 0);
-  if constexpr (F >= 3 && F < 7) __builtin_amdgcn_sched_group_barrier(0x100, READS, 0);
-}
-template <int READS>
-__device__ __forceinline__ void sched_pipeline() {
-  __builtin_amdgcn_sched_group_barrier(0x100, 7 * READS, 0);
-  sched_step<READS, 0>();  sched_step<READS, 1>();  sched_step<READS, 2>();  sched_step<READS, 3>();
-  sched_step<READS, 4>();  sched_step<READS, 5>();  sched_step<READS, 6>();  sched_step<READS, 7>();
-  sched_step<READS, 8>();  sched_step<READS, 9>();  sched_step<READS, 10>(); sched_step<READS, 11>();
-  sched_step<READS, 12>(); sched_step<READS, 13>(); sched_step<READS, 14>(); sched_step<READS, 15>();
-}
-
-#endif  // SGL_AB
-
 // blockIdx -> work unit.  Workgroups are dealt round-robin to the 8 XCDs (blockIdx % 8 labels the XCD group), each
 // with a private 4 MiB L2.  XCD x takes the CONTIGUOUS chunk [x*per, (x+1)*per) of a locality-ordered unit list, so
 // the ~32 workgroups it runs at any moment are neighbours in that list.  Speed only; any placement is correct.
@@ -298,105 +277,13 @@ __device__ __forceinline__ bool tile_of_local(int xcd, int v, int tiles_m, int t
   return true;
 }
 
-#ifdef SGL_AB
 // ------------------------------------------------------------------------------------------------------
-template <int EPI, typename TOut>
-__global__ __launch_bounds__(512, 2) void gemm_nt2_kernel(const bf16* __restrict__ A, int lda,
-                                                          const bf16* __restrict__ B, int ldb, int M, int N, int K,
-                                                          int tiles_m, int tiles_n, EpiParams p) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int ntiles = tiles_m * tiles_n;
-  const int unit = unit_of_block(blockIdx.x, (ntiles + 7) >> 3);
-  if (unit >= ntiles) return;  // whole block exits together
-  int tile_m, tile_n;
-  tile_of_unit(unit, tiles_m, tiles_n, tile_m, tile_n);
-  const int t = threadIdx.x, lane = t & 63;
-  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int wr = (w >> 1) & 1, wc = (w & 1) + 2 * (w >> 2);
-  const int m0 = tile_m * T_BM, n0 = tile_n * T_BN;
-  const int rows_a = (M - m0 < T_BM) ? M - m0 : T_BM;
-  const int rows_b = (N - n0 < T_BN) ? N - n0 : T_BN;
-  const __amdgpu_buffer_rsrc_t ra = make_rsrc(A + (size_t)m0 * lda, (uint32_t)(((size_t)(rows_a - 1) * lda + K) * 2));
-  const __amdgpu_buffer_rsrc_t rb = make_rsrc(B + (size_t)n0 * ldb, (uint32_t)(((size_t)(rows_b - 1) * ldb + K) * 2));
-
-  // DMA assignment: wave w moves rows [w*32, w*32+32) of each operand, 8 rows (1 KiB) per instruction
-  const int drow = lane >> 3;
-  const int dchunk = (lane & 7) ^ drow;
-  uint32_t a_off[4], b_off[4];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int row = w * 32 + q * 8 + drow;
-    a_off[q] = (row < rows_a) ? (uint32_t)(row * lda + dchunk * 8) * 2u : SGL_OOB;
-    b_off[q] = (row < rows_b) ? (uint32_t)(row * ldb + dchunk * 8) * 2u : SGL_OOB;
-  }
-  auto issue = [&](int kt, int stage) {
-    const int k0 = kt * T_BK;
-    const bool kok = (k0 + dchunk * 8) < K;
-    char* base = smem + stage * T_STAGE + (w * 32) * 128;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      dma16(ra, base + q * 1024, (kok && a_off[q] != SGL_OOB) ? a_off[q] + (uint32_t)k0 * 2u : SGL_OOB);
-      dma16(rb, base + T_OP + q * 1024, (kok && b_off[q] != SGL_OOB) ? b_off[q] + (uint32_t)k0 * 2u : SGL_OOB);
-    }
-  };
-
-  const int frow = lane & 15, fg = lane >> 4, fsw = frow & 7;
-  const uint32_t fa_base = (uint32_t)((wr * 128 + frow) * 128);
-  const uint32_t fb_base = (uint32_t)(T_OP + (wc * 64 + frow) * 128);
-  const bool active = (n0 + wc * 64 < N) && (m0 + wr * 128 < M);
-
-  f32x4 acc[8][4];
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  const int nk = (K + T_BK - 1) / T_BK;
-  issue(0, 0);
-  for (int kt = 0; kt < nk; ++kt) {
-    __syncthreads();  // drains this wave's DMA (vmcnt(0)) and orders every wave past step kt-1
-    if (kt + 1 < nk) issue(kt + 1, (kt + 1) & 1);
-    if (active) {
-      // 16 fragment steps per K-step: step f = (k-half f>>3, 16-row tile f&7) feeds 4 MFMAs.  A fragments are read
-      // three steps ahead, the second k-half's B fragments during steps 3..6, and sched_group_barrier pins the
-      // ds_read/MFMA interleave so the LDS latency hides under the MFMAs of the same wave.
-      const char* base = smem + (kt & 1) * T_STAGE;
-      const char* pa = base + fa_base;
-      const char* pb = base + fb_base;
-      const uint32_t c0 = (uint32_t)(((0 + fg) ^ fsw) << 4), c1 = (uint32_t)(((4 + fg) ^ fsw) << 4);
-      bf16x8 a[16], b[2][4];
-#define SGL_LDA(f) (*reinterpret_cast<const bf16x8*>(pa + ((f) & 7) * 2048 + (((f) >> 3) ? c1 : c0)))
-#define SGL_LDB(s_, j) (*reinterpret_cast<const bf16x8*>(pb + (j) * 2048 + ((s_) ? c1 : c0)))
-#pragma unroll
-      for (int j = 0; j < 4; ++j) b[0][j] = SGL_LDB(0, j);
-      a[0] = SGL_LDA(0);
-      a[1] = SGL_LDA(1);
-      a[2] = SGL_LDA(2);
-#pragma unroll
-      for (int f = 0; f < 16; ++f) {
-        if (f + 3 < 16) a[f + 3] = SGL_LDA(f + 3);
-        if (f >= 3 && f < 7) b[1][f - 3] = SGL_LDB(1, f - 3);
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          acc[f & 7][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[f], b[f >> 3][j], acc[f & 7][j], 0, 0, 0);
-      }
-#undef SGL_LDA
-#undef SGL_LDB
-      sched_pipeline<1>();
-    }
-  }
-  store_tile256<EPI, TOut>(smem, acc, wr, wc, lane, t, m0, n0, M, N, p);
-}
-
-#endif  // SGL_AB
-
-// ------------------------------------------------------------------------------------------------------
-// Anti-phase ("ping-pong") main loops, generation 6 (default).  The two wave groups of the workgroup (G0 = waves
+// Anti-phase ("ping-pong") main loops, generation 6.  The two wave groups of the workgroup (G0 = waves
 // 0-3, G1 = waves 4-7; every SIMD holds one wave of each) alternate: time is cut into slots separated by workgroup
 // barriers, and in every slot one group issues the LDS reads of its next half K-step (plus its share of the
 // global->LDS DMA stream) while the other group issues 32 MFMAs, so each SIMD's matrix pipe always has exactly one
 // wave feeding it and nobody's LDS latency is exposed.  G1 simply starts one barrier late.  Measured against the
-// generation-2 loop (one barrier per K-step, rolling fragment prefetch) in the same process: +8..14 % on the
+// generation-2 loop (one barrier per K-step, rolling fragment prefetch; since removed) in the same process: +8..14 % on the
 // encoder's NT shapes, 1.29 -> 1.45 PFLOP/s at 8192^3.  Variants tried and dropped: 8 slots of 16 MFMAs (+4 %; the
 // barrier hand-off costs about as much per slot regardless of slot length), 2 slots of 64 MFMAs (needs all DMA
 // issued one slot before use: the prefetch distance is too short, -12 %).
@@ -612,7 +499,7 @@ __global__ __launch_bounds__(512, 2) void gemm_tn6_kernel(const bf16* __restrict
   const uint32_t lds0 = (uint32_t)(size_t)((SGL_LDS char*)smem);
 
   // DMA plan: unit u = 2*khalf + operand; wave w moves image rows 32*khalf + 4w + {0..3}, 2 rows (1 KiB) per
-  // instruction; slot s of row m holds source chunk s ^ (2*(m&3) + 8*((m>>3)&1)) (same image as tn2)
+  // instruction; slot s of row m holds source chunk s ^ (2*(m&3) + 8*((m>>3)&1)) (the image of the header comment)
   const int dr2 = lane >> 5, dslot = lane & 31;
   uint32_t voff[4][2], ldst[4][2];
 #pragma unroll
@@ -674,22 +561,10 @@ __global__ __launch_bounds__(512, 2) void gemm_tn6_kernel(const bf16* __restrict
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       if (active) {
-#if !defined(SGL_TN_ABLATE) || SGL_TN_ABLATE != 1
 #pragma unroll
         for (int j = 0; j < 4; ++j) fb[j] = SGL_TR6(base + T_OP + h * 32 * 512 + (fb_col ^ (uint32_t)(j * 32)));
-#else
-        if (kt == 0)   // ablation (wrong results): B fragments read once -> read slots carry A only
-#pragma unroll
-          for (int j = 0; j < 4; ++j) fb[j] = SGL_TR6(base + T_OP + h * 32 * 512 + (fb_col ^ (uint32_t)(j * 32)));
-#endif
-#if !defined(SGL_TN_ABLATE) || SGL_TN_ABLATE != 2
 #pragma unroll
         for (int i = 0; i < 8; ++i) fa[i] = SGL_TR6(base + h * 32 * 512 + (fa_col ^ (uint32_t)(i * 32)));
-#else
-        if (kt == 0)   // ablation (wrong results): A fragments read once -> read slots carry B only
-#pragma unroll
-          for (int i = 0; i < 8; ++i) fa[i] = SGL_TR6(base + h * 32 * 512 + (fa_col ^ (uint32_t)(i * 32)));
-#endif
       }
       if (h == 0) { issue(2, kt + 1); issue(3, kt + 1); }
       else { issue(0, kt + 2); issue(1, kt + 2); }
@@ -735,217 +610,63 @@ __global__ __launch_bounds__(512, 2) void gemm_tn6_kernel(const bf16* __restrict
   store_tile256<EPI_F32, float>(smem, acc, wr, wc, lane, t, n1_0, n2_0, N1, N2, pq);
 }
 
-#ifdef SGL_AB
 // ------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(512, 2) void gemm_tn2_kernel(const bf16* __restrict__ A, int lda,
-                                                          const bf16* __restrict__ B, int ldb, int Mred, int N1, int N2,
-                                                          int m_per_split, int nsplits, int tiles_1, int tiles_2,
-                                                          EpiParams p) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  // units ordered (split, tile1, tile2): an XCD's contiguous chunk shares one token range and neighbouring panels
-  const int ntiles = tiles_1 * tiles_2;
-  const int nunits = ntiles * nsplits;
-  const int unit = unit_of_block(blockIdx.x, (nunits + 7) >> 3);
-  if (unit >= nunits) return;
-  const int split = unit / ntiles, trem = unit - split * ntiles;
-  const int tile1 = trem / tiles_2, tile2 = trem - tile1 * tiles_2;
-  const int t = threadIdx.x, lane = t & 63;
-  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int wr = (w >> 1) & 1, wc = (w & 1) + 2 * (w >> 2);
-  const int n1_0 = tile1 * T_BM, n2_0 = tile2 * T_BN;
-  const int m_begin = split * m_per_split;
-  const int m_end = (m_begin + m_per_split < Mred) ? m_begin + m_per_split : Mred;
-  const int rows = m_end - m_begin;
-  const __amdgpu_buffer_rsrc_t ra = make_rsrc(A + (size_t)m_begin * lda, (uint32_t)((size_t)rows * lda * 2));
-  const __amdgpu_buffer_rsrc_t rb = make_rsrc(B + (size_t)m_begin * ldb, (uint32_t)((size_t)rows * ldb * 2));
-
-  // DMA: image [64 m][256 n] with 512-B rows; wave w moves rows [w*8, w*8+8), 2 rows (1 KiB) per instruction
-  const int dr2 = lane >> 5, dslot = lane & 31;
-  uint32_t a_off[4], b_off[4];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int row = w * 8 + q * 2 + dr2;
-    const int chunk = dslot ^ (2 * (row & 3) + 8 * ((row >> 3) & 1));
-    const int ca = n1_0 + chunk * 8, cb = n2_0 + chunk * 8;
-    a_off[q] = (ca < N1) ? (uint32_t)(row * lda + ca) * 2u : SGL_OOB;
-    b_off[q] = (cb < N2) ? (uint32_t)(row * ldb + cb) * 2u : SGL_OOB;
-  }
-  auto issue = [&](int kt, int stage) {
-    const uint32_t r0 = (uint32_t)kt * T_BK;
-    char* base = smem + stage * T_STAGE + (w * 8) * 512;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      dma16(ra, base + q * 1024, a_off[q] == SGL_OOB ? SGL_OOB : a_off[q] + r0 * (uint32_t)lda * 2u);
-      dma16(rb, base + T_OP + q * 1024, b_off[q] == SGL_OOB ? SGL_OOB : b_off[q] + r0 * (uint32_t)ldb * 2u);
-    }
-  };
-
-  const int fg = lane >> 4, fq = (lane >> 2) & 3, fp = lane & 3;
-  const uint32_t swz = (uint32_t)(32 * fq + 128 * (fg & 1));
-  const uint32_t frow = (uint32_t)((8 * fg + fq) * 512);
-  const uint32_t fa_col = ((uint32_t)(wr * 256 + 8 * fp)) ^ swz;   // + i*32 bytes per 16-column tile (bits 5.. stay XOR-safe)
-  const uint32_t fb_col = ((uint32_t)(wc * 128 + 8 * fp)) ^ swz;
-  const bool active = (n2_0 + wc * 64 < N2) && (n1_0 + wr * 128 < N1);
-
-  f32x4 acc[8][4];
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  const int nk = (rows + T_BK - 1) / T_BK;
-  issue(0, 0);
-  for (int kt = 0; kt < nk; ++kt) {
-    __syncthreads();
-    if (kt + 1 < nk) issue(kt + 1, (kt + 1) & 1);
-    if (active) {
-      // same 16-step pipeline as nt2; every fragment is two transposed 8-byte reads
-      const char* base = smem + (kt & 1) * T_STAGE + frow;
-      bf16x8 a[16], b[2][4];
-#define SGL_TR(ptr) __builtin_shufflevector(lds_tr16v2(ptr), lds_tr16v2((ptr) + 4 * 512), 0, 1, 2, 3, 4, 5, 6, 7)
-#define SGL_LDA(f) SGL_TR(base + ((f) >> 3) * 32 * 512 + (fa_col ^ (uint32_t)(((f) & 7) * 32)))
-#define SGL_LDB(s_, j) SGL_TR(base + T_OP + (s_) * 32 * 512 + (fb_col ^ (uint32_t)((j) * 32)))
-#pragma unroll
-      for (int j = 0; j < 4; ++j) b[0][j] = SGL_LDB(0, j);
-      a[0] = SGL_LDA(0);
-      a[1] = SGL_LDA(1);
-      a[2] = SGL_LDA(2);
-#pragma unroll
-      for (int f = 0; f < 16; ++f) {
-        if (f + 3 < 16) a[f + 3] = SGL_LDA(f + 3);
-        if (f >= 3 && f < 7) b[1][f - 3] = SGL_LDB(1, f - 3);
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          acc[f & 7][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[f], b[f >> 3][j], acc[f & 7][j], 0, 0, 0);
-      }
-#undef SGL_LDA
-#undef SGL_LDB
-#undef SGL_TR
-      sched_pipeline<2>();
-    }
-  }
-  EpiParams pq = p;
-  if (p.split_stride) pq.out = reinterpret_cast<float*>(p.out) + (size_t)split * p.split_stride;  // private slab of this split
-  store_tile256<EPI_F32, float>(smem, acc, wr, wc, lane, t, n1_0, n2_0, N1, N2, pq);
-}
-
-#endif  // SGL_AB
-
+// launchers
 // ------------------------------------------------------------------------------------------------------
 template <int EPI, typename TOut>
-static hipError_t launch_nt2(const bf16* A, int lda, const bf16* B, int ldb, int M, int N, int K, const EpiParams& p,
-                             hipStream_t s) {
+static hipError_t launch_nt256(const bf16* A, int lda, const bf16* B, int ldb, int M, int N, int K, const EpiParams& p,
+                               hipStream_t s) {
+  const hipError_t e = set_max_dynamic_lds_once<&gemm_nt6_kernel<EPI, TOut>>(T_LDS);
+  if (e != hipSuccess) return e;
   const int tiles_m = (M + T_BM - 1) / T_BM, tiles_n = (N + T_BN - 1) / T_BN;
-  const int grid = ((tiles_m * tiles_n + 7) / 8) * 8;
-#ifdef SGL_AB
-  static const int gen = getenv("SGL_GEMM_GEN") ? atoi(getenv("SGL_GEMM_GEN")) : 6;
-  if (gen == 2) {
-    static bool attr = false;
-    if (!attr) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt2_kernel<EPI, TOut>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, T_LDS);
-      if (e != hipSuccess) return e;
-      attr = true;
-    }
-    hipLaunchKernelGGL((gemm_nt2_kernel<EPI, TOut>), dim3(grid), dim3(512), T_LDS, s, A, lda, B, ldb, M, N, K, tiles_m,
-                       tiles_n, p);
-    return hipGetLastError();
-  }
-#endif
-  {
-    static bool attr6 = false;
-    if (!attr6) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt6_kernel<EPI, TOut>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, T_LDS);
-      if (e != hipSuccess) return e;
-      attr6 = true;
-    }
-    // band height of the grouped tile order: 8 row-tiles for wide outputs, 4 when there are few column tiles (measured
-    // on one box: qkv N=3456 +3 %, fc2 N=1152 +1.5 % with 4; fc1 N=4352 best with 8).  SGL_BAND overrides.
-    // Tile order.  Default (round 2): B-stationary with column groups of 8 — same speed as the round-1 grouped bands
-    // (+-1 % over the encoder's eight shapes) but 35 % fewer bytes leave the XCD L2s at the bench batch (rocprofv3
-    // FETCH_SIZE: 2.42 -> 1.56 GB per fc1 launch at B = 128, profiles/r02_pmc_traffic.json).  SGL_BAND > 0 selects the
-    // grouped bands of that height (8 / 4 were the round-1 choices), SGL_BAND < 0 another column-group width.
-    static const int band_env = getenv("SGL_BAND") ? atoi(getenv("SGL_BAND")) : 0;
-    const int band_h = band_env != 0 ? band_env : -8;
-    int grid6 = grid;
-    if (band_h < 0) grid6 = 8 * (((tiles_m + 7) / 8) * tiles_n);   // 8 XCDs x the largest per-XCD tile count
-    EpiParams pp = p;
+  // band height of the grouped tile order: 8 row-tiles for wide outputs, 4 when there are few column tiles (measured
+  // on one box: qkv N=3456 +3 %, fc2 N=1152 +1.5 % with 4; fc1 N=4352 best with 8).  SGL_BAND overrides.
+  // Tile order.  Default (round 2): B-stationary with column groups of 8 — same speed as the round-1 grouped bands
+  // (+-1 % over the encoder's eight shapes) but 35 % fewer bytes leave the XCD L2s at the bench batch (rocprofv3
+  // FETCH_SIZE: 2.42 -> 1.56 GB per fc1 launch at B = 128, profiles/r02_pmc_traffic.json).  SGL_BAND > 0 selects the
+  // grouped bands of that height (8 / 4 were the round-1 choices), SGL_BAND < 0 another column-group width.
+  static const int band_env = getenv("SGL_BAND") ? atoi(getenv("SGL_BAND")) : 0;
+  const int band_h = band_env != 0 ? band_env : -8;
+  const int grid = band_h < 0 ? 8 * (((tiles_m + 7) / 8) * tiles_n)     // 8 XCDs x the largest per-XCD tile count
+                              : ((tiles_m * tiles_n + 7) / 8) * 8;      // one workgroup per tile, whole XCD rounds
+  EpiParams pp = p;
 #ifdef SGL_TIMELINE   // measurement builds only (make TIMELINE=1): the product library never skips an epilogue
-    static const bool skip_epi = getenv("SGL_NT6_SKIP_EPI") != nullptr;
-    if (skip_epi && EPI != EPI_F32) pp.atomic = 77;
+  static const bool skip_epi = getenv("SGL_NT6_SKIP_EPI") != nullptr;
+  if (skip_epi && EPI != EPI_F32) pp.atomic = 77;
 #endif
-    hipLaunchKernelGGL((gemm_nt6_kernel<EPI, TOut>), dim3(grid6), dim3(512), T_LDS, s, A, lda, B, ldb, M, N, K,
-                       tiles_m, tiles_n, band_h, pp);
+  hipLaunchKernelGGL((gemm_nt6_kernel<EPI, TOut>), dim3(grid), dim3(512), T_LDS, s, A, lda, B, ldb, M, N, K, tiles_m,
+                     tiles_n, band_h, pp);
 #ifdef SGL_TIMELINE
-    if (getenv("SGL_TIMELINE")) {   // synchronises: measurement builds only
-      unsigned long long h[4];
-      (void)hipStreamSynchronize(s);
-      (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_nt6_tl), sizeof(h));
-      if (h[2])
-        fprintf(stderr, "[timeline] gemm_nt6 EPI %d M=%d N=%d K=%d: %llu tiles, main loop %.0f, epilogue %.0f cycles per tile\n", EPI, M,
-                N, K, h[2], (double)h[0] / h[2], (double)h[1] / h[2]);
-      memset(h, 0, sizeof(h));
-      (void)hipMemcpyToSymbol(HIP_SYMBOL(g_nt6_tl), h, sizeof(h));
-    }
+  if (getenv("SGL_TIMELINE")) {   // synchronises: measurement builds only
+    unsigned long long h[4];
+    (void)hipStreamSynchronize(s);
+    (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_nt6_tl), sizeof(h));
+    if (h[2])
+      fprintf(stderr, "[timeline] gemm_nt6 EPI %d M=%d N=%d K=%d: %llu tiles, main loop %.0f, epilogue %.0f cycles per tile\n", EPI, M,
+              N, K, h[2], (double)h[0] / h[2], (double)h[1] / h[2]);
+    memset(h, 0, sizeof(h));
+    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_nt6_tl), h, sizeof(h));
+  }
 #endif
-    return hipGetLastError();
-  }
+  return hipGetLastError();
 }
 
-hipError_t gemm_nt2_bf16(const void* A_, int lda, const void* B_, int ldb, int M, int N, int K, int epi, int out_dtype,
-                         const EpiParams& p, hipStream_t s) {
-  const bf16* A = (const bf16*)A_;
-  const bf16* B = (const bf16*)B_;
-  switch (epi) {
-    case EPI_STORE:
-      return out_dtype == DT_BF16 ? launch_nt2<EPI_STORE, bf16>(A, lda, B, ldb, M, N, K, p, s)
-                                  : launch_nt2<EPI_STORE, float>(A, lda, B, ldb, M, N, K, p, s);
-    case EPI_BIAS_GELU:
-      return out_dtype == DT_BF16 ? launch_nt2<EPI_BIAS_GELU, bf16>(A, lda, B, ldb, M, N, K, p, s)
-                                  : launch_nt2<EPI_BIAS_GELU, float>(A, lda, B, ldb, M, N, K, p, s);   // bf16x3 strict mode
-    case EPI_QKV:
-      return out_dtype == DT_BF16 ? launch_nt2<EPI_QKV, bf16>(A, lda, B, ldb, M, N, K, p, s)
-                                  : launch_nt2<EPI_QKV, float>(A, lda, B, ldb, M, N, K, p, s);   // bf16x3 strict mode
-    case EPI_GELU_BWD:
-      return out_dtype == DT_BF16 ? launch_nt2<EPI_GELU_BWD, bf16>(A, lda, B, ldb, M, N, K, p, s)
-                                  : launch_nt2<EPI_GELU_BWD, float>(A, lda, B, ldb, M, N, K, p, s);   // bf16x3 strict mode
-    case EPI_RES_F32: return launch_nt2<EPI_RES_F32, float>(A, lda, B, ldb, M, N, K, p, s);
-    case EPI_POS_F32: return launch_nt2<EPI_POS_F32, float>(A, lda, B, ldb, M, N, K, p, s);
-    case EPI_F32: return launch_nt2<EPI_F32, float>(A, lda, B, ldb, M, N, K, p, s);
-  }
-  return hipErrorInvalidValue;
+hipError_t gemm_nt256_bf16(const void* A, int lda, const void* B, int ldb, int M, int N, int K, int epi, int out_dtype,
+                           const EpiParams& p, hipStream_t s) {
+  return dispatch_epilogue(epi, out_dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return launch_nt256<T::epi, typename T::out>((const bf16*)A, lda, (const bf16*)B, ldb, M, N, K, p, s);
+  });
 }
 
-hipError_t gemm_tn2_bf16(const void* A_, int lda, const void* B_, int ldb, int Mred, int N1, int N2, int m_per,
-                         int splits, const EpiParams& p, hipStream_t s) {
+hipError_t gemm_tn256_bf16(const void* A, int lda, const void* B, int ldb, int Mred, int N1, int N2, int m_per,
+                           int splits, const EpiParams& p, hipStream_t s) {
+  const hipError_t e = set_max_dynamic_lds_once<&gemm_tn6_kernel>(T_LDS);
+  if (e != hipSuccess) return e;
   const int tiles_1 = (N1 + T_BM - 1) / T_BM, tiles_2 = (N2 + T_BN - 1) / T_BN;
   const int grid = ((tiles_1 * tiles_2 * splits + 7) / 8) * 8;
-#ifdef SGL_AB
-  static const int gen = getenv("SGL_GEMM_GEN") ? atoi(getenv("SGL_GEMM_GEN")) : 6;
-  static const int tngen = getenv("SGL_TN_GEN") ? atoi(getenv("SGL_TN_GEN")) : gen;
-  if (tngen == 2) {
-    static bool attr = false;
-    if (!attr) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn2_kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, T_LDS);
-      if (e != hipSuccess) return e;
-      attr = true;
-    }
-    hipLaunchKernelGGL(gemm_tn2_kernel, dim3(grid), dim3(512), T_LDS, s, (const bf16*)A_, lda, (const bf16*)B_, ldb,
-                       Mred, N1, N2, m_per, splits, tiles_1, tiles_2, p);
-    return hipGetLastError();
-  }
-#endif
-  static bool attr6 = false;
-  if (!attr6) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn6_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, T_LDS);
-    if (e != hipSuccess) return e;
-    attr6 = true;
-  }
-  hipLaunchKernelGGL(gemm_tn6_kernel, dim3(grid), dim3(512), T_LDS, s, (const bf16*)A_, lda, (const bf16*)B_, ldb,
-                     Mred, N1, N2, m_per, splits, tiles_1, tiles_2, p);
+  hipLaunchKernelGGL(gemm_tn6_kernel, dim3(grid), dim3(512), T_LDS, s, (const bf16*)A, lda, (const bf16*)B, ldb, Mred,
+                     N1, N2, m_per, splits, tiles_1, tiles_2, p);
 #ifdef SGL_TIMELINE
   if (getenv("SGL_TIMELINE")) {   // synchronises: measurement builds only
     unsigned long long h[12];

@@ -70,21 +70,10 @@ hipError_t gemm_f32_generic(const float* A, long sam, long sak, const float* B, 
                             int K, int epi, int out_dtype, const EpiParams& p, hipStream_t s) {
   if (M == 0 || N == 0) return hipSuccess;
   if (epi != EPI_F32 && (N % 4)) return hipErrorInvalidValue;
-#define SGL_CASE(E)                                                                               \
-  case E:                                                                                         \
-    return out_dtype == DT_BF16 ? launch_f32<E, bf16>(A, sam, sak, B, sbn, sbk, M, N, K, p, s)    \
-                                : launch_f32<E, float>(A, sam, sak, B, sbn, sbk, M, N, K, p, s);
-  switch (epi) {
-    SGL_CASE(EPI_STORE)
-    SGL_CASE(EPI_BIAS_GELU)
-    SGL_CASE(EPI_QKV)
-    SGL_CASE(EPI_GELU_BWD)
-    case EPI_RES_F32: return launch_f32<EPI_RES_F32, float>(A, sam, sak, B, sbn, sbk, M, N, K, p, s);
-    case EPI_POS_F32: return launch_f32<EPI_POS_F32, float>(A, sam, sak, B, sbn, sbk, M, N, K, p, s);
-    case EPI_F32: return launch_f32<EPI_F32, float>(A, sam, sak, B, sbn, sbk, M, N, K, p, s);
-  }
-#undef SGL_CASE
-  return hipErrorInvalidValue;
+  return dispatch_epilogue(epi, out_dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return launch_f32<T::epi, typename T::out>(A, sam, sak, B, sbn, sbk, M, N, K, p, s);
+  });
 }
 
 }  // namespace sgl

@@ -10,6 +10,17 @@ namespace sgl {
 enum DType : int { DT_F32 = 0, DT_BF16 = 1, DT_F32_MFMA = 2 /* attention only: fp32 operands on v_mfma_f32_32x32x2_f32 */ };
 static inline size_t dtype_size(int dt) { return dt == DT_BF16 ? 2 : 4; }
 
+// Raises Kernel's dynamic-LDS limit to `bytes` on the first call that succeeds (once per kernel instantiation).
+template <auto Kernel>
+hipError_t set_max_dynamic_lds_once(int bytes) {
+  static bool done = false;
+  if (done) return hipSuccess;
+  const hipError_t e =
+      hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  done = e == hipSuccess;
+  return e;
+}
+
 // ---- GEMM epilogues (shared by the MFMA kernels and the strict-fp32 generic kernel) ----------------
 enum Epi : int {
   EPI_STORE = 0,      // out[T]   = alpha*acc (+bias)

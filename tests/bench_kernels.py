@@ -49,7 +49,7 @@ def nt_epi(Mm, N, K, epi):
                                   None, 1, 1, 1, 8, 8, 1, st.cuda_stream) == 0
     t = timeit(f); return t, 2.0 * Mm * N * K / t / 1e12
 
-print(f"gen={os.environ.get('SGL_GEMM_GEN','2')} B={B} M={M}")
+print(f"B={B} M={M}")
 for name, (Mm, N, K, epi) in {"fc1+gelu": (M, Ip, D, 1), "gelu_bwd": (M, Ip, D, 4), "out+res": (M, D, D, 2), "fc2+res": (M, D, Ip, 2)}.items():
     t, tf = nt_epi(Mm, N, K, epi); print(f"NT {name:8s} M={Mm:6d} N={N:5d} K={K:5d}  {t*1e3:8.3f} ms  {tf:7.1f} TF/s")
 for name, (Mm, N, K) in {"qkv": (M, 3*D, D), "out": (M, D, D), "fc1": (M, Ip, D), "fc2": (M, D, Ip), "dX_qkv": (M, D, 3*D),

@@ -1,6 +1,6 @@
 """Developer tool: the encoder's eight NT GEMM launches per block (4 forward, 4 dX) at one batch size, each checked
-against torch and timed.  A/B the generations in separate processes:
-   python tests/bench_nt.py [B]            SGL_GEMM_GEN=6 python tests/bench_nt.py [B]"""
+against torch and timed.
+   python tests/bench_nt.py [B] [nocheck]"""
 import math, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -64,4 +64,4 @@ for name, N, K, epi, Na, Ka in shapes:
     fl = 2.0 * M * Na * Ka
     tot_t += t; tot_f += fl
     print(f"{name:16s} M={M} N={N} K={K}: {t*1e6:8.1f} us  {fl/t/1e12:7.1f} TF/s{err}", flush=True)
-print(f"sum: {tot_t*1e3:.3f} ms  {tot_f/tot_t/1e12:.1f} TF/s  (gen {os.environ.get('SGL_GEMM_GEN', '6')})")
+print(f"sum: {tot_t*1e3:.3f} ms  {tot_f/tot_t/1e12:.1f} TF/s")
