@@ -7,10 +7,11 @@ exchange pattern here is designed for the MI355X node: images a
 collective is the sum of parameter gradients.
 
 * **Few, large messages.**  The encoder's backward produces one flat fp32 gradient bucket per transformer block
-  (61 MB for so400m); consecutive blocks share one allocation (``SiglipVisionModelHIP._grad_buckets`` carves a *chunk* of
-  ``ceil(groups / max_buckets)`` blocks out of one tensor), and the chunk is handed to ``reduce_bucket`` the moment its
-  last block is complete: 8 collectives of ≈0.2 GB per step for so400m instead of 29 of 61 MB.  xGMI is point-to-point
-  (7 links × ≈153 GB/s per GPU), so a ring step is bound by one link: big messages amortise the per-step latency.
+  (61 MB for so400m); consecutive blocks share one allocation (``SiglipVisionModelHIP._bucket_layout`` cuts the blocks
+  into at most ``max_buckets`` *chunks*, each one tensor), and the chunk is handed to ``reduce_bucket`` the moment its
+  last block is complete: 8 collectives of up to ≈0.37 GB per step for so400m instead of 29 of 61 MB.  xGMI is
+  point-to-point (7 links × ≈153 GB/s per GPU), so a ring step is bound by one link: big messages amortise the per-step
+  latency.
 * **Wire format.**  ``wire="fp32"`` (default): one in-place sum all-reduce per chunk, exact.  ``wire="bf16"``: the
   full-mesh form of SURVEY.md §8e — every rank sends shard *j* of its bf16-rounded gradients straight to rank *j*
   (``all_to_all_single``: 7 peers, 7 different links), sums the ``world`` shards it received **in fp32**, and the reduced
@@ -21,9 +22,11 @@ collective is the sum of parameter gradients.
   folds it into the clip coefficient it already multiplies every gradient by (no extra pass over the gradients).
 * ``no_sync()`` suppresses the exchange for gradient-accumulation micro-steps (the reference accumulates:
   Siglip2sidafrozen.py:1390 ``loss / current_grad_accum``).  The micro-step that leaves the context must exchange the
-  ACCUMULATED gradient, not just its own contribution: when a trainable encoder parameter already carries a ``.grad`` the
-  in-backward hand-off is skipped and ``reduce_accumulated`` runs from an autograd-engine callback after every
-  ``AccumulateGrad`` of the pass has fired, one collective per chunk over the memory ``.grad`` lives in.
+  ACCUMULATED gradient, not just its own contribution.  ``backward_node`` decides once per autograd pass, at the pass's
+  first encoder node: when a trainable encoder parameter already carries a ``.grad`` the in-backward hand-off is skipped
+  and ONE autograd-engine callback runs ``reduce_accumulated`` after every ``AccumulateGrad`` of the pass has fired, one
+  collective per chunk over the memory ``.grad`` lives in, however many times the encoder ran in that pass.  The rule
+  looks at ``.grad`` only, so ``torch.autograd.grad`` on a model whose ``.grad`` is still set also exchanges ``.grad``.
 * ``reduce_grads`` (everything outside the encoder: decoder, heads) is asynchronous and completed by ``finish()`` as well.
 * Chunk sizes taper (``SiglipVisionModelHIP._bucket_layout``): the chunk that completes last holds one block (+ the
   embeddings), so the exchange that cannot overlap anything is 67 MB, not 244 MB.
@@ -60,12 +63,12 @@ class GradBucketReducer:
         self.collectives_issued = 0       # statistics for tests / bench
         self.time_exposed = False         # bench: HIP events around finish()'s waits = communication nothing overlapped
         self._exposed: list = []
+        self._pass = None                 # (graph task id, accumulating, chunks) of the autograd pass in progress
 
     # ---- wiring ------------------------------------------------------------------------------------------
     def attach(self, encoder_module) -> "GradBucketReducer":
         """Make ``encoder_module`` (a ``SiglipVisionModelHIP``) call back into this reducer per gradient chunk."""
-        encoder_module._grad_reducer = self
-        encoder_module._bucket_cache = {}
+        encoder_module.set_grad_reducer(self)
         return self
 
     def world_size(self) -> int:
@@ -100,6 +103,29 @@ class GradBucketReducer:
         return out
 
     # ---- called from the encoder's backward -----------------------------------------------------------------
+    def backward_node(self, chunks) -> bool:
+        """Called by every encoder backward node, before its first chunk is complete, with its chunk layout
+        ``[(total_elems, [(param, offset, numel)])]``.  Returns whether the node hands its chunks to ``reduce_bucket``
+        as they complete and calls ``finish`` at its end.  The first node of an autograd pass decides for the whole pass:
+        if a parameter it differentiates already carries a ``.grad`` (micro-steps under ``no_sync()`` came before), the
+        pass accumulates, no node hands anything over, and one engine callback exchanges the union of the pass's layouts
+        (``reduce_accumulated``) once autograd has summed the pass into ``.grad``."""
+        task = torch._C._current_graph_task_id()
+        if self._pass is None or self._pass[0] != task:
+            state = (task, any(p.grad is not None for _, entries in chunks for p, _, _ in entries), [])
+            self._pass = state
+            torch.autograd.Variable._execution_engine.queue_callback(lambda: self._end_pass(state))
+        _, accumulating, work = self._pass
+        if accumulating:
+            work.extend(chunks)
+        return not accumulating
+
+    def _end_pass(self, state) -> None:
+        if self._pass is state:
+            self._pass = None
+        if state[1]:
+            self.reduce_accumulated(state[2])
+
     def reduce_bucket(self, flat: torch.Tensor) -> None:
         """Start the exchange of one flat fp32 gradient chunk (asynchronous; completed by ``finish``)."""
         world = self.world_size()
@@ -167,14 +193,18 @@ class GradBucketReducer:
         accumulated this pass into ``.grad``.  When a chunk's gradients still sit at their offsets inside one allocation
         (the flat tensor an earlier micro-step's backward wrote: ``AccumulateGrad`` adopts the views and later adds in
         place) that memory is exchanged directly, one collective per chunk as in the overlapped case; otherwise the chunk
-        goes through a packed copy.  Completed (and averaged) by the ``finish()`` at the end."""
+        goes through a packed copy.  A parameter listed in more than one chunk is exchanged once.  Completed (and
+        averaged) by the ``finish()`` at the end."""
         if not self.syncing():
             return
+        seen = set()
         for total, entries in chunks:
-            entries = [(p, off, n) for p, off, n in entries if p.grad is not None]
+            with_grad = [(p, off, n) for p, off, n in entries if p.grad is not None]
+            entries = [e for e in with_grad if id(e[0]) not in seen]
             if not entries:
                 continue
-            flat = _common_flat(entries, total)
+            seen.update(id(p) for p, _, _ in entries)
+            flat = _common_flat(entries, total) if len(entries) == len(with_grad) else None
             if flat is not None:
                 self.reduce_bucket(flat)
             else:

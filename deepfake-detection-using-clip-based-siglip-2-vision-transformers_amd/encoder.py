@@ -291,25 +291,22 @@ def encoder_bwd(grads: Sequence[Optional[torch.Tensor]], taps: Sequence[torch.Te
         chunks, groups = mod._bucket_layout(needs)
         flats = mod._alloc_buckets(chunks, dev)
         grads_out = [None] * len(params)
-        chunk_of, last_of = {}, {}
-        for ci, (total, members, entries) in enumerate(chunks):
+        for flat, (_, _, entries) in zip(flats, chunks):
             for i, off, n in entries:
-                grads_out[i] = flats[ci][off:off + n]
-            for grp in members:
-                chunk_of[grp] = ci
-            last_of[ci] = members[-1]
+                grads_out[i] = flat[off:off + n]
         if d_pooled is None and "head" in groups:     # the C side skips the pooling head (and post-LN when d_last is None too)
             for i in groups["head"]:
                 grads_out[i].zero_()
         reducer = mod._grad_reducer
-        # gradient accumulation (micro-steps under reducer.no_sync() came before): what must be exchanged is the SUM in
-        # .grad, which autograd forms after this op returns, so nothing is handed over from here (see _encoder_backward)
-        overlapped = reducer is not None and not mod._accumulating(needs)
+        # the reducer decides, once per autograd pass, whether chunks are handed over from here (ddp.py)
+        overlapped = reducer is not None and reducer.backward_node(
+            [(total, [(params[i], off, n) for i, off, n in entries]) for total, _, entries in chunks])
+        ready = {members[-1]: flat for flat, (_, members, _) in zip(flats, chunks)} if overlapped else {}
 
         def group_done(grp):
             """Hand a chunk to the reducer once its last group (in completion order) is complete."""
-            if overlapped and grp in chunk_of and last_of[chunk_of[grp]] == grp:
-                reducer.reduce_bucket(flats[chunk_of[grp]])
+            if grp in ready:
+                reducer.reduce_bucket(ready[grp])
 
         gl = (_lib.SglLayerPtrs * max(L, 1))()
         g = _lib.SglGrads()
@@ -383,14 +380,6 @@ def _encoder_backward(ctx, grads):
     taps, saved, hs_rest, params = list(saved_t[:nt]), saved_t[nt], saved_t[nt + 1], list(saved_t[nt + 2:])
     needs = [bool(n) for n in ctx.needs_input_grad[1]] if isinstance(ctx.needs_input_grad[1], (list, tuple)) \
         else [p.requires_grad for p in params]
-    mod = _module_of(ctx.handle)
-    if mod._grad_reducer is not None and mod._grad_reducer.syncing() and mod._accumulating(needs):
-        # the exchange of the accumulated gradients runs when the whole autograd pass (every AccumulateGrad) is over
-        layout, _ = mod._bucket_layout(needs)
-        plist = mod._flat_params()
-        work = [(total, [(plist[i], off, n) for i, off, n in entries]) for total, _, entries in layout]
-        reducer = mod._grad_reducer
-        torch.autograd.Variable._execution_engine.queue_callback(lambda: reducer.reduce_accumulated(work))
     flats = torch.ops.siglip_hip.encoder_bwd(list(grads[:2 + nt]), taps, saved, hs_rest, params, ctx.handle, ctx.image_hw,
                                              ctx.interp, ctx.want_pooled, ctx.tap_ids, needs)
     chunks, _ = _module_of(ctx.handle)._bucket_layout(needs)
@@ -593,6 +582,7 @@ class SiglipVisionModelHIP(nn.Module):
         self._weights_key = None
         self._size_cache = {}
         self._ws_cache = None
+        self._layout_cache = {}
         self._bucket_cache = {}
         self._pending_fwd = {}
         self._fwd_count = 0
@@ -633,14 +623,25 @@ class SiglipVisionModelHIP(nn.Module):
                 "SiglipVisionModelHIP: parameters changed between this forward and its backward (optimizer step, EMA "
                 "swap or load_state_dict in between re-cast the bf16 weight shadows); run backward before touching them")
 
+    def set_grad_reducer(self, reducer) -> None:
+        """Hand this module's gradient chunks to ``reducer`` (a ``ddp.GradBucketReducer``; its ``max_buckets`` sets the
+        chunk plan) from the next backward on; None detaches.  Flat buffers cached for the previous plan are dropped."""
+        self._grad_reducer = reducer
+        self._bucket_cache = {}
+
     def _bucket_layout(self, needs):
-        """Pure function of (which parameters need gradients): the gradient memory plan.
+        """Pure function of (which parameters need gradients, chunk count): the gradient memory plan, memoized, so the op,
+        its fake implementation and the autograd formula of one backward share one result.
 
         Groups (embeddings, each block, post-LN + head) are listed in the order the backward completes them (head, block
         L-1 ... first trainable block, embeddings) and cut into at most ``max_buckets`` chunks of consecutive groups; every
         chunk is ONE flat fp32 tensor (= one DDP collective, ddp.py) holding its groups' per-parameter gradients, each
         16-byte aligned.  Returns (chunks, groups): chunks = [(total_elems, [group names], [(param index, offset, numel)])],
         groups = {group name: [param indices]}."""
+        max_buckets = self._grad_reducer.max_buckets if self._grad_reducer is not None else 8
+        key = (tuple(map(bool, needs)), max_buckets)
+        if key in self._layout_cache:
+            return self._layout_cache[key]
         names = self._flat_names
         params = self._flat_params()
         groups: dict[str, list[int]] = {}
@@ -649,7 +650,6 @@ class SiglipVisionModelHIP(nn.Module):
                 groups.setdefault(grp, []).append(idx)
         L = self.config.num_hidden_layers
         order = [g_ for g_ in (["head"] + [f"layer{l}" for l in range(L - 1, -1, -1)] + ["emb"]) if g_ in groups]
-        max_buckets = getattr(self._grad_reducer, "max_buckets", 8) if self._grad_reducer is not None else 8
         # q/k/v weight (and bias) gradients back to back: the C side then runs them as one dW GEMM / one column sum
         rank = {"q_w": 0, "k_w": 1, "v_w": 2, "q_b": 3, "k_b": 4, "v_b": 5}
         chunks = []
@@ -662,11 +662,8 @@ class SiglipVisionModelHIP(nn.Module):
                     entries.append((i, off, n))
                     off += (n + 3) // 4 * 4
             chunks.append((off, members, entries))
+        self._layout_cache[key] = chunks, groups
         return chunks, groups
-
-    def _accumulating(self, needs) -> bool:
-        """Does a parameter this backward differentiates already carry a gradient (accumulation micro-steps)?"""
-        return any(n and p.grad is not None for n, p in zip(needs, self._flat_params()))
 
     def _alloc_buckets(self, chunks, dev):
         """The flat tensors of ``_bucket_layout``.  The C side overwrites every element, so they are reused from step to

@@ -1,6 +1,7 @@
 """CPU, world_size 2 over gloo: the data-parallel gradient exchange (bucket all-reduce + 1/world averaging,
 parameter broadcast, batch sharding).  The encoder kernels are not involved: the reducer is exercised with the
 same flat fp32 buckets the encoder's backward hands to it."""
+import contextlib
 import os
 import socket
 
@@ -138,6 +139,125 @@ def test_shard_batch_covers_everything():
             assert max(sizes) - min(sizes) <= 1
 
 
+class _EncoderNode(torch.autograd.Function):
+    """Stands in for one encoder backward node (encoder.py ``encoder_bwd``): its backward writes ``x * [1..n]`` into fresh
+    flat chunks of ``layout``, asks the reducer whether to hand them over, and returns per-parameter views of the chunks."""
+
+    @staticmethod
+    def forward(ctx, x, red, layout, *params):
+        ctx.x, ctx.red, ctx.layout = float(x), red, layout
+        return x.clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        flats = [torch.zeros(total) for total, _ in ctx.layout]
+        for flat, (_, entries) in zip(flats, ctx.layout):
+            for p, off, n in entries:
+                flat[off:off + n] = g * ctx.x * torch.arange(1, n + 1, dtype=torch.float32)
+        if ctx.red.backward_node(ctx.layout):
+            for flat in flats:
+                ctx.red.reduce_bucket(flat)
+            ctx.red.finish()
+        views = [flat[off:off + n] for flat, (_, entries) in zip(flats, ctx.layout) for _, off, n in entries]
+        return (None, None, None, *views)
+
+
+def _policy_worker(rank, world, port, q):
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import __graft_entry__ as g
+    pkg = g.load_package()
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        red = pkg.GradBucketReducer(average="defer")
+        pa, pb, pc = (torch.nn.Parameter(torch.zeros(n)) for n in (10, 7, 20))
+        layout = [(24, [(pa, 0, 10), (pb, 12, 7)]), (20, [(pc, 0, 20)])]
+        params = [p for _, entries in layout for p, _, _ in entries]
+
+        def x_of(r, m, c):            # what call c of micro-step m on rank r contributes (times [1..n])
+            return 1.0 + r + 2 * m + 4 * c
+
+        def step(micro_steps):
+            """Zeroed .grad, then one backward per micro-step, each over a loss that calls the stand-in TWICE; returns
+            the collectives each micro-step issued and whether .grad * grad_scale is the single-process mean."""
+            for p in params:
+                p.grad = None
+            issued = []
+            for m, quiet in enumerate(micro_steps):
+                before = red.collectives_issued
+                with red.no_sync() if quiet else contextlib.nullcontext():
+                    sum(_EncoderNode.apply(torch.tensor(x_of(rank, m, c)), red, layout, *params)
+                        for c in range(2)).backward()
+                issued.append(red.collectives_issued - before)
+            want = sum(x_of(r, m, c) for r in range(world) for m in range(len(micro_steps)) for c in range(2)) / world
+            ok = all(torch.allclose(p.grad * red.grad_scale, want * torch.arange(1, p.numel() + 1, dtype=torch.float32))
+                     for p in params)
+            return issued, ok, red._pass is None
+
+        # accumulation, twice: nothing under no_sync(); the syncing pass exchanges each chunk ONCE although two nodes
+        # ran in it; then a plain pass, where each node hands its own chunks over from inside the backward
+        q.put((rank, [step([True, False]), step([True, False]), step([False])]))
+    finally:
+        dist.destroy_process_group()
+
+
+def test_encoder_nodes_of_one_pass_share_one_exchange_world2_gloo():
+    world = 2
+    port = _free_port()
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    procs = [ctx.Process(target=_policy_worker, args=(r, world, port, q)) for r in range(world)]
+    for p in procs:
+        p.start()
+    res = sorted(q.get(timeout=180) for _ in range(world))
+    for p in procs:
+        p.join(60)
+        assert p.exitcode == 0
+    for rank, steps in res:
+        assert steps == [([0, 2], True, True), ([0, 2], True, True), ([4], True, True)], (rank, steps)
+
+
+def test_chunk_plan_tapers_and_keeps_qkv_adjacent():
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import __graft_entry__ as g
+    pkg = g.load_package()
+    order = ["head"] + [f"layer{l}" for l in range(26, -1, -1)] + ["emb"]
+    runs = pkg.encoder._taper(order, 8)
+    assert [len(r) for r in runs] == [6, 6, 4, 4, 3, 3, 1, 2] and runs[-1] == ["layer0", "emb"]
+    assert sum(runs, []) == order
+    for name, sizes in (("tiny", [1, 1, 1, 2]), ("so400m-patch14-384", [6, 6, 4, 4, 3, 3, 1, 2])):
+        with torch.device("meta"):                  # the plan needs parameter shapes only
+            model = pkg.SiglipVisionModelHIP(pkg.get_config(name), compute_dtype="fp32")
+        params, names = model._flat_params(), model._flat_names
+        needs = [True] * len(params)
+        chunks, groups = model._bucket_layout(needs)
+        assert model._bucket_layout(needs) == (chunks, groups) and model._bucket_layout(needs)[0] is chunks
+        assert [len(members) for _, members, _ in chunks] == sizes
+        assert chunks[0][1][0] == "head" and chunks[-1][1] == ["layer0", "emb"]
+        assert sorted(i for _, _, entries in chunks for i, _, _ in entries) == list(range(len(params)))
+        for total, members, entries in chunks:
+            assert sorted(i for grp in members for i in groups[grp]) == sorted(i for i, _, _ in entries)
+            end = 0
+            for i, off, n in entries:
+                assert off % 4 == 0 and off >= end and n == params[i].numel()
+                end = off + n
+            assert total == (end + 3) // 4 * 4
+            fields = [names[i][1] for i, _, _ in entries]
+            for grp in members:
+                if grp.startswith("layer"):
+                    at = fields.index("q_w")
+                    assert fields[at:at + 6] == ["q_w", "k_w", "v_w", "q_b", "k_b", "v_b"]
+                    assert all(names[i][0] == grp for i, _, _ in entries[at:at + 6])
+                    fields[at:at + 6] = [None] * 6
+        model.set_grad_reducer(pkg.GradBucketReducer(max_buckets=2))
+        assert [len(members) for _, members, _ in model._bucket_layout(needs)[0]] == ([3, 2] if name == "tiny"
+                                                                                     else [19, 10])
+
+
 # ---------------------------------------------------------------------------------------------------------
 # GPU: the encoder's backward really calls the reducer per bucket; two ranks share the one GPU of the test box and
 # exchange over gloo (RCCL refuses two ranks on one device), which exercises exactly the hook plumbing bench.py uses.
@@ -166,7 +286,7 @@ def _gpu_worker(rank, world, port, q):
         torch.cuda.synchronize()
         got = {n: p.grad.detach().cpu().clone() for n, p in model.named_parameters()}
         # single-process reference: mean over the two ranks' losses
-        model._grad_reducer = None
+        model.set_grad_reducer(None)
         for p in model.parameters():
             p.grad = None
         total = 0
@@ -340,7 +460,7 @@ def _accum_worker(rank, world, port, q):
         flat = torch.cat([v.reshape(-1) for v in got.values()])
         both = [torch.zeros_like(flat) for _ in range(world)]
         dist.all_gather(both, flat)
-        model._grad_reducer = None
+        model.set_grad_reducer(None)
         for p in list(model.parameters()) + list(head.parameters()):
             p.grad = None
         total = 0
@@ -375,3 +495,78 @@ def test_gradient_accumulation_with_no_sync_exchanges_the_accumulated_sum():
         assert same, "ranks hold different gradients after the syncing micro-step"
         assert worst < 2e-5, f"rank {rank}: accumulated + averaged gradients differ from the joined batch by {worst}"
         assert n_coll == 3, n_coll         # 2 encoder chunks (in place, from the engine callback) + the head message
+
+
+def _twice_worker(rank, world, port, q):
+    """Siamese use: every loss calls the encoder TWICE, micro-step 1 under no_sync(), micro-step 2 syncing, sums left in
+    .grad (average='defer').  The syncing pass must exchange the accumulated .grad once, however many encoder nodes it
+    ran: .grad * grad_scale equals one single-process pass over all micro-batches."""
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import __graft_entry__ as g
+    pkg = g.load_package()
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        cfg = pkg.get_config("hostile")
+        model = pkg.SiglipVisionModelHIP(cfg, compute_dtype="fp32")
+        model.load_state_dict(pkg.weights.seeded_state_dict(cfg, 4))
+        model = model.to("cuda")
+        red = pkg.GradBucketReducer(average="defer", max_buckets=2).attach(model)
+        xs = [[[pkg.weights.seeded_pixels(2, 42, 42, seed=110 + 10 * r + 2 * m + c).cuda() for c in range(2)]
+               for m in range(2)] for r in range(world)]
+
+        def loss_of(pair):
+            total = 0
+            for x in pair:
+                out = model(pixel_values=x, output_hidden_states=True, interpolate_pos_encoding=True)
+                total = total + out.pooler_output.square().sum() + out.hidden_states[1].mean()
+            return total / 2                                        # / accumulation steps
+
+        n_coll = []
+        for step in range(2):
+            for p in model.parameters():
+                p.grad = None
+            with red.no_sync():
+                loss_of(xs[rank][0]).backward()
+            issued = red.collectives_issued
+            loss_of(xs[rank][1]).backward()
+            n_coll.append(red.collectives_issued - issued)
+        torch.cuda.synchronize()
+        got = {n: (p.grad * red.grad_scale).detach().cpu() for n, p in model.named_parameters()}
+        model.set_grad_reducer(None)
+        for p in model.parameters():
+            p.grad = None
+        total = 0
+        for r in range(world):
+            for m in range(2):
+                total = total + loss_of(xs[r][m]) / world
+        total.backward()
+        torch.cuda.synchronize()
+        worst = 0.0
+        for n, p in model.named_parameters():
+            ref = p.grad.detach().cpu()
+            worst = max(worst, ((got[n] - ref).abs().max() / (ref.abs().max() + 1e-12)).item())
+        q.put((rank, worst, n_coll))
+    finally:
+        dist.destroy_process_group()
+
+
+@pytest.mark.gpu
+def test_two_encoder_calls_per_loss_exchange_the_accumulated_sum_once():
+    world = 2
+    port = _free_port()
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    procs = [ctx.Process(target=_twice_worker, args=(r, world, port, q)) for r in range(world)]
+    for p in procs:
+        p.start()
+    res = sorted(q.get(timeout=300) for _ in range(world))
+    for p in procs:
+        p.join(60)
+        assert p.exitcode == 0
+    for rank, worst, n_coll in res:
+        assert worst < 2e-5, f"rank {rank}: .grad * grad_scale differs from the joined batch by {worst}"
+        assert n_coll == [2, 2], n_coll        # 2 encoder chunks (max_buckets=2) per syncing micro-step, once
