@@ -1,4 +1,5 @@
-// bf16 flash attention for gfx950: softmax(QKᵀ/√dh)·V, non-causal, no mask, dropout 0
+// bf16 flash attention for gfx950: softmax(QKᵀ/√dh)·V, non-causal, no mask, dropout 0.  The kernels take the 16-bit
+// operand type as a template parameter: fp16 (DT_F16) runs the same tiles and schedule on v_mfma_f32_32x32x16_f16.
 // (SiglipAttention, TF:models/siglip/modeling_siglip.py:273-306; softmax in fp32 as in :241).
 // v_mfma_f32_32x32x16_bf16 throughout, 64-lane wavefronts, 4 waves per workgroup, each wave owns 32 rows.
 //
@@ -48,24 +49,29 @@ struct AttnCfg {
 __device__ __forceinline__ u32x4 a_ldg(__amdgpu_buffer_rsrc_t r, uint32_t off) {
   return __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0);
 }
-__device__ __forceinline__ bf16x8 as_bf16x8(u32x4 v) { return __builtin_bit_cast(bf16x8, v); }
-__device__ __forceinline__ bf16x8 lds_row8(const char* p) { return *reinterpret_cast<const bf16x8*>(p); }
-__device__ __forceinline__ bf16x4 lds_tr4(const char* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4bf16((SGL_LDS bf16x4*)(p));
-}
+// T = bf16 or f16 (DT_F16): the operand type of every 16-bit fragment below
+template <typename T>
+__device__ __forceinline__ lo_x8<T> as_x8(u32x4 v) { return __builtin_bit_cast(lo_x8<T>, v); }
+template <typename T>
+__device__ __forceinline__ lo_x8<T> lds_row8(const char* p) { return *reinterpret_cast<const lo_x8<T>*>(p); }
+template <typename T>
+__device__ __forceinline__ lo_x4<T> lds_tr4(const char* p) { return lds_read_tr16<T>(p); }
 // A-operand fragment of Xᵀ for a 32x32x16 MFMA whose B operand is an accumulator tile: element j of lane half h
 // is row 16*kk + 8*(j>>2) + 4*h + (j&3) of the row-major LDS image, column = d0 + (lane & 31).
-__device__ __forceinline__ bf16x8 lds_trfrag(const char* img, int stride, int kk, int dcol0, int lane) {
+template <typename T>
+__device__ __forceinline__ lo_x8<T> lds_trfrag(const char* img, int stride, int kk, int dcol0, int lane) {
   const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
   const char* a = img + (16 * kk + 4 * (g >> 1) + q) * stride + (dcol0 + 16 * (g & 1) + 4 * p) * 2;
-  const bf16x4 lo = lds_tr4(a);
-  const bf16x4 hi = lds_tr4(a + 8 * stride);
+  const lo_x4<T> lo = lds_tr4<T>(a);
+  const lo_x4<T> hi = lds_tr4<T>(a + 8 * stride);
   return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
 }
-__device__ __forceinline__ bf16x8 pack8(const f32x16& s, int base) {
-  bf16x8 r;
+// round-to-nearest-even conversion of P / dS to the MFMA operand type (fp16: overflow -> inf, denormals kept)
+template <typename T>
+__device__ __forceinline__ lo_x8<T> pack8(const f32x16& s, int base) {
+  lo_x8<T> r;
 #pragma unroll
-  for (int j = 0; j < 8; ++j) r[j] = (bf16)s[base + j];
+  for (int j = 0; j < 8; ++j) r[j] = (T)s[base + j];
   return r;
 }
 __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
@@ -105,7 +111,7 @@ __device__ __forceinline__ HeadSrc head_src(int ld, int b, int hd, int H, int N,
   return r;
 }
 
-#define MFMA32(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16((a), (b), (c), 0, 0, 0)
+#define MFMA32(a, b, c) mfma_32x32x16((a), (b), (c))
 
 // ======================================================================================================
 // tile staging
@@ -147,9 +153,9 @@ __device__ __forceinline__ uint32_t att_chunk_off(int cidx, int rows, int SC, in
 // ======================================================================================================
 // forward
 // ======================================================================================================
-template <int DP, bool TOK>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void attn_fwd_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ K,
-                                                          const bf16* __restrict__ V, bf16* __restrict__ out,
+template <typename T, int DP, bool TOK>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void attn_fwd_kernel(const T* __restrict__ Q, const T* __restrict__ K,
+                                                          const T* __restrict__ V, T* __restrict__ out,
                                                           float* __restrict__ lse, int B, int H, int N, int dh, int ld,
                                                           float c, float scale) {
   using C = AttnCfg<DP>;
@@ -177,11 +183,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
   const uint32_t lds0 = (uint32_t)(size_t)((SGL_LDS char*)smem);
 
   const int qi = lane & 31, hh = lane >> 5;
-  bf16x8 qf[C::KS];
+  lo_x8<T> qf[C::KS];
 #pragma unroll
   for (int ks = 0; ks < C::KS; ++ks) {
     const uint32_t ch = (uint32_t)(2 * ks + hh);
-    qf[ks] = as_bf16x8(a_ldg(rq, (q0 + qi < N && ch < src.nc) ? (uint32_t)(q0 + qi) * src.rowbytes + ch * 16u : SGL_OOB));
+    qf[ks] = as_x8<T>(a_ldg(rq, (q0 + qi < N && ch < src.nc) ? (uint32_t)(q0 + qi) * src.rowbytes + ch * 16u : SGL_OOB));
   }
 
   // K/V tiles: global -> LDS by DMA (see the dK/dV kernel), two stages (three workgroups per CU leave no room for a third):
@@ -229,8 +235,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     for (int r = 0; r < 16; ++r) { s0[r] = 0.f; s1[r] = 0.f; }
 #pragma unroll
     for (int ks = 0; ks < C::KS; ++ks) {
-      const bf16x8 k0 = lds_row8(kb + qi * C::RSTR + (16 * ks + 8 * hh) * 2);
-      const bf16x8 k1 = lds_row8(kb + (qi + 32) * C::RSTR + (16 * ks + 8 * hh) * 2);
+      const lo_x8<T> k0 = lds_row8<T>(kb + qi * C::RSTR + (16 * ks + 8 * hh) * 2);
+      const lo_x8<T> k1 = lds_row8<T>(kb + (qi + 32) * C::RSTR + (16 * ks + 8 * hh) * 2);
       s0 = MFMA32(k0, qf[ks], s0);
       s1 = MFMA32(k1, qf[ks], s1);
     }
@@ -267,31 +273,31 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 #pragma unroll
         for (int r = 0; r < 16; ++r) o[dt][r] *= alpha;
     }
-    bf16x8 pb[4];
-    pb[0] = pack8(s0, 0);
-    pb[1] = pack8(s0, 8);
-    pb[2] = pack8(s1, 0);
-    pb[3] = pack8(s1, 8);
+    lo_x8<T> pb[4];
+    pb[0] = pack8<T>(s0, 0);
+    pb[1] = pack8<T>(s0, 8);
+    pb[2] = pack8<T>(s1, 0);
+    pb[3] = pack8<T>(s1, 8);
 #pragma unroll
     for (int dt = 0; dt < C::DT; ++dt)
 #pragma unroll
-      for (int kk = 0; kk < 4; ++kk) o[dt] = MFMA32(lds_trfrag(vb, C::TSTR, kk, dt * 32, lane), pb[kk], o[dt]);
+      for (int kk = 0; kk < 4; ++kk) o[dt] = MFMA32(lds_trfrag<T>(vb, C::TSTR, kk, dt * 32, lane), pb[kk], o[dt]);
   }
   const float l = l_run + __shfl_xor(l_run, 32, 64);
   const float inv = 1.0f / l;
   const int q = q0 + qi;
   if (q < N) {
-    bf16* orow = out + ((size_t)b * N + q) * ((size_t)H * dh) + hd * dh;
+    T* orow = out + ((size_t)b * N + q) * ((size_t)H * dh) + hd * dh;
 #pragma unroll
     for (int dt = 0; dt < C::DT; ++dt)
 #pragma unroll
       for (int g4 = 0; g4 < 4; ++g4) {
         const int d = dt * 32 + 8 * g4 + 4 * hh;
         if (d < dh) {
-          bf16x4 v4;
+          lo_x4<T> v4;
 #pragma unroll
-          for (int r = 0; r < 4; ++r) v4[r] = (bf16)(o[dt][4 * g4 + r] * inv);
-          *reinterpret_cast<bf16x4*>(orow + d) = v4;
+          for (int r = 0; r < 4; ++r) v4[r] = (T)(o[dt][4 * g4 + r] * inv);
+          *reinterpret_cast<lo_x4<T>*>(orow + d) = v4;
         }
       }
     if (hh == 0) lse[(size_t)bh * N + q] = m_run * scale + __logf(l);
@@ -301,10 +307,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 // ======================================================================================================
 // backward: dK, dV   (wave owns 32 keys; sweeps 32-query tiles staged in LDS)
 // ======================================================================================================
-template <int DP, bool TOK>
-__global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ K,
-                                                             const bf16* __restrict__ V, const bf16* __restrict__ dO,
-                                                             const float* __restrict__ aux, bf16* __restrict__ dqkv,
+template <typename T, int DP, bool TOK>
+__global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(const T* __restrict__ Q, const T* __restrict__ K,
+                                                             const T* __restrict__ V, const T* __restrict__ dO,
+                                                             const float* __restrict__ aux, T* __restrict__ dqkv,
                                                              int B, int H, int N, int dh, int ld, float c, float scale) {
   using C = AttnCfg<DP>;
   constexpr int QT = 32;
@@ -329,20 +335,20 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(const bf16* __restr
   }
   const __amdgpu_buffer_rsrc_t rk = make_rsrc(K + src.base, src.bytes);
   const __amdgpu_buffer_rsrc_t rv = make_rsrc(V + src.base, src.bytes);
-  const bf16* dOb = dO + (size_t)b * N * D + hd * dh;
+  const T* dOb = dO + (size_t)b * N * D + hd * dh;
   const u32x4 dq_ = att_desc(Q + src.base, src.bytes);
   const u32x4 ddo = att_desc(dOb, (uint32_t)(((size_t)(N - 1) * D + dh) * 2));
   const u32x4 dax = att_desc(aux + (size_t)bh * N * 2, (uint32_t)((size_t)N * 8));
   const uint32_t lds0 = (uint32_t)(size_t)((SGL_LDS char*)smem);
 
   const int li = lane & 31, hh = lane >> 5;
-  bf16x8 kfr[C::KS], vfr[C::KS];
+  lo_x8<T> kfr[C::KS], vfr[C::KS];
 #pragma unroll
   for (int ks = 0; ks < C::KS; ++ks) {
     const uint32_t ch = (uint32_t)(2 * ks + hh);
     const uint32_t off = (key0 + li < N && ch < src.nc) ? (uint32_t)(key0 + li) * src.rowbytes + ch * 16u : SGL_OOB;
-    kfr[ks] = as_bf16x8(a_ldg(rk, off));
-    vfr[ks] = as_bf16x8(a_ldg(rv, off));
+    kfr[ks] = as_x8<T>(a_ldg(rk, off));
+    vfr[ks] = as_x8<T>(a_ldg(rv, off));
   }
 
   // this wave's DMA slots: sl = w + 4j.  sl < NIS: Q image, sl < 2*NIS: dO image, sl == 2*NIS: the 32 {lse, delta} pairs.
@@ -412,11 +418,11 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(const bf16* __restr
     // ---- phase A: S = Q·Kᵀ, dP = dO·Vᵀ.  All row fragments are requested up front and the schedule is pinned
     // (sched_group_barrier): left alone, hipcc issued two LDS reads and waited for them in front of EVERY MFMA, so the
     // matrix pipe idled for an LDS round trip 22 times per tile (PMC: waves parked 43 % of the time).
-    bf16x8 qa[C::KS], da[C::KS];
+    lo_x8<T> qa[C::KS], da[C::KS];
 #pragma unroll
     for (int ks = 0; ks < C::KS; ++ks) {
-      qa[ks] = lds_row8(qimg + li * C::DSTR + (16 * ks + 8 * hh) * 2);
-      da[ks] = lds_row8(dimg + li * C::DSTR + (16 * ks + 8 * hh) * 2);
+      qa[ks] = lds_row8<T>(qimg + li * C::DSTR + (16 * ks + 8 * hh) * 2);
+      da[ks] = lds_row8<T>(dimg + li * C::DSTR + (16 * ks + 8 * hh) * 2);
     }
 #pragma unroll
     for (int ks = 0; ks < C::KS; ++ks) {
@@ -436,10 +442,10 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(const bf16* __restr
     // ---- the first two transposed fragments of phase B depend only on the staged tile: their latency runs under the
     // softmax arithmetic.  Fragment order: (dv, dk) for (dt, kk) = (0,0) (0,1) (1,0) ...
     constexpr int NF = 2 * 2 * C::DT;
-    bf16x8 fr[NF];
+    lo_x8<T> fr[NF];
     auto frag = [&](int i) {
       const int which = i & 1, kk = (i >> 1) & 1, dt = i >> 2;
-      return lds_trfrag(which ? qimg : dimg, C::DSTR, kk, dt * 32, lane);
+      return lds_trfrag<T>(which ? qimg : dimg, C::DSTR, kk, dt * 32, lane);
     };
     constexpr int PRE = NF < 2 ? NF : 2;
 #pragma unroll
@@ -461,11 +467,11 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(const bf16* __restr
         dP[r] = p * fmaf(dP[r], scale, D4[r3]);
       }
     }
-    bf16x8 pb[2], dsb[2];
-    pb[0] = pack8(S, 0);
-    pb[1] = pack8(S, 8);
-    dsb[0] = pack8(dP, 0);
-    dsb[1] = pack8(dP, 8);
+    lo_x8<T> pb[2], dsb[2];
+    pb[0] = pack8<T>(S, 0);
+    pb[1] = pack8<T>(S, 8);
+    dsb[0] = pack8<T>(dP, 0);
+    dsb[1] = pack8<T>(dP, 8);
     __builtin_amdgcn_sched_barrier(0);
     // ---- phase B: dVᵀ += dOᵀ·P, dKᵀ += Qᵀ·dS, two fragments ahead of the MFMA that consumes them
 #pragma unroll
@@ -487,22 +493,22 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(const bf16* __restr
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // trailing out-of-range requests
   const int key = key0 + li;
   if (key < N) {
-    bf16* krow = dqkv + ((size_t)b * N + key) * (3 * (size_t)D) + D + hd * dh;
-    bf16* vrow = krow + D;
+    T* krow = dqkv + ((size_t)b * N + key) * (3 * (size_t)D) + D + hd * dh;
+    T* vrow = krow + D;
 #pragma unroll
     for (int dt = 0; dt < C::DT; ++dt)
 #pragma unroll
       for (int g4 = 0; g4 < 4; ++g4) {
         const int d = dt * 32 + 8 * g4 + 4 * hh;
         if (d < dh) {
-          bf16x4 a, g;
+          lo_x4<T> a, g;
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            a[r] = (bf16)dk[dt][4 * g4 + r];
-            g[r] = (bf16)dv[dt][4 * g4 + r];
+            a[r] = (T)dk[dt][4 * g4 + r];
+            g[r] = (T)dv[dt][4 * g4 + r];
           }
-          *reinterpret_cast<bf16x4*>(krow + d) = a;
-          *reinterpret_cast<bf16x4*>(vrow + d) = g;
+          *reinterpret_cast<lo_x4<T>*>(krow + d) = a;
+          *reinterpret_cast<lo_x4<T>*>(vrow + d) = g;
         }
       }
   }
@@ -511,11 +517,11 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(const bf16* __restr
 // ======================================================================================================
 // backward: dQ   (wave owns 32 queries; sweeps 32-key tiles staged in LDS)
 // ======================================================================================================
-template <int DP, bool TOK>
-__global__ __launch_bounds__(256, 2) void attn_bwd_q_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ K,
-                                                            const bf16* __restrict__ V, const bf16* __restrict__ O,
-                                                            const bf16* __restrict__ dO, const float* __restrict__ lse,
-                                                            float* __restrict__ aux, bf16* __restrict__ dqkv,
+template <typename T, int DP, bool TOK>
+__global__ __launch_bounds__(256, 2) void attn_bwd_q_kernel(const T* __restrict__ Q, const T* __restrict__ K,
+                                                            const T* __restrict__ V, const T* __restrict__ O,
+                                                            const T* __restrict__ dO, const float* __restrict__ lse,
+                                                            float* __restrict__ aux, T* __restrict__ dqkv,
                                                             int B, int H, int N, int dh, int ld, float c, float scale) {
   using C = AttnCfg<DP>;
   constexpr int KT = 32;
@@ -539,7 +545,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_q_kernel(const bf16* __restri
     src.nc = (uint32_t)DP / 8u;
   }
   const __amdgpu_buffer_rsrc_t rq = make_rsrc(Q + src.base, src.bytes);
-  const bf16* dOb = dO + (size_t)b * N * D + hd * dh;
+  const T* dOb = dO + (size_t)b * N * D + hd * dh;
   const __amdgpu_buffer_rsrc_t rdo = make_rsrc(dOb, (uint32_t)(((size_t)(N - 1) * D + dh) * 2));
   const u32x4 dk_ = att_desc(K + src.base, src.bytes);
   const u32x4 dv_ = att_desc(V + src.base, src.bytes);
@@ -547,13 +553,13 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_q_kernel(const bf16* __restri
 
   const int li = lane & 31, hh = lane >> 5;
   const int q = q0 + li;
-  bf16x8 qf[C::KS], dof[C::KS];
+  lo_x8<T> qf[C::KS], dof[C::KS];
 #pragma unroll
   for (int ks = 0; ks < C::KS; ++ks) {
     const int col = 16 * ks + 8 * hh;
-    qf[ks] = as_bf16x8(a_ldg(rq, (q < N && (uint32_t)(col >> 3) < src.nc) ? (uint32_t)q * src.rowbytes + (uint32_t)col * 2u
+    qf[ks] = as_x8<T>(a_ldg(rq, (q < N && (uint32_t)(col >> 3) < src.nc) ? (uint32_t)q * src.rowbytes + (uint32_t)col * 2u
                                                                            : SGL_OOB));
-    dof[ks] = as_bf16x8(a_ldg(rdo, (q < N && col < dh) ? (uint32_t)(((size_t)q * D + col) * 2) : SGL_OOB));
+    dof[ks] = as_x8<T>(a_ldg(rdo, (q < N && col < dh) ? (uint32_t)(((size_t)q * D + col) * 2) : SGL_OOB));
   }
   // delta = rowsum(dO ∘ O) of this lane's query, computed here (each lane holds half of its row of dO; O's half is loaded
   // once) instead of in a pre-pass over O and dO; the pair {-lse*log2e, -delta*scale} is what both backward kernels add
@@ -564,7 +570,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_q_kernel(const bf16* __restri
 #pragma unroll
     for (int ks = 0; ks < C::KS; ++ks) {
       const int col = 16 * ks + 8 * hh;
-      const bf16x8 of = as_bf16x8(a_ldg(ro, (q < N && col < dh) ? (uint32_t)(((size_t)q * D + col) * 2) : SGL_OOB));
+      const lo_x8<T> of = as_x8<T>(a_ldg(ro, (q < N && col < dh) ? (uint32_t)(((size_t)q * D + col) * 2) : SGL_OOB));
 #pragma unroll
       for (int j = 0; j < 8; ++j) dl = fmaf((float)of[j], (float)dof[ks][j], dl);
     }
@@ -629,11 +635,11 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_q_kernel(const bf16* __restri
 #pragma unroll
     for (int r = 0; r < 16; ++r) { S[r] = 0.f; dP[r] = 0.f; }
     // phase A: Sᵀ = K·Qᵀ, dPᵀ = V·dOᵀ with the row fragments requested up front and the schedule pinned (see the kv kernel)
-    bf16x8 ka[C::KS], va[C::KS];
+    lo_x8<T> ka[C::KS], va[C::KS];
 #pragma unroll
     for (int ks = 0; ks < C::KS; ++ks) {
-      ka[ks] = lds_row8(kimg + li * C::DSTR + (16 * ks + 8 * hh) * 2);
-      va[ks] = lds_row8(vimg + li * C::RSTR + (16 * ks + 8 * hh) * 2);
+      ka[ks] = lds_row8<T>(kimg + li * C::DSTR + (16 * ks + 8 * hh) * 2);
+      va[ks] = lds_row8<T>(vimg + li * C::RSTR + (16 * ks + 8 * hh) * 2);
     }
 #pragma unroll
     for (int ks = 0; ks < C::KS; ++ks) {
@@ -653,11 +659,11 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_q_kernel(const bf16* __restri
     // S[r], dP[r]: key row (r&3) + 8*(r>>2) + 4*hh of the tile, query = lane & 31
     // the transposed K fragments of the dQ product depend only on the staged tile: request them now, so that their LDS
     // latency runs under the softmax arithmetic below instead of in front of every MFMA
-    bf16x8 kt_frag[C::DT][2];
+    lo_x8<T> kt_frag[C::DT][2];
 #pragma unroll
     for (int dt = 0; dt < C::DT; ++dt)
 #pragma unroll
-      for (int kk = 0; kk < 2; ++kk) kt_frag[dt][kk] = lds_trfrag(kimg, C::DSTR, kk, dt * 32, lane);
+      for (int kk = 0; kk < 2; ++kk) kt_frag[dt][kk] = lds_trfrag<T>(kimg, C::DSTR, kk, dt * 32, lane);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
@@ -671,9 +677,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_q_kernel(const bf16* __restri
         if (key >= N) dP[r] = 0.f;
       }
     }
-    bf16x8 dsb[2];
-    dsb[0] = pack8(dP, 0);
-    dsb[1] = pack8(dP, 8);
+    lo_x8<T> dsb[2];
+    dsb[0] = pack8<T>(dP, 0);
+    dsb[1] = pack8<T>(dP, 8);
     // dQᵀ += Kᵀ·dSᵀ, with the request for tile kt+2 spread behind the MFMAs (see the dK/dV kernel)
 #pragma unroll
     for (int i = 0; i < 2 * C::DT; ++i) {
@@ -686,17 +692,17 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_q_kernel(const bf16* __restri
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // trailing out-of-range requests
   if (q < N) {
-    bf16* qrow = dqkv + ((size_t)b * N + q) * (3 * (size_t)D) + hd * dh;
+    T* qrow = dqkv + ((size_t)b * N + q) * (3 * (size_t)D) + hd * dh;
 #pragma unroll
     for (int dt = 0; dt < C::DT; ++dt)
 #pragma unroll
       for (int g4 = 0; g4 < 4; ++g4) {
         const int d = dt * 32 + 8 * g4 + 4 * hh;
         if (d < dh) {
-          bf16x4 a;
+          lo_x4<T> a;
 #pragma unroll
-          for (int r = 0; r < 4; ++r) a[r] = (bf16)dq[dt][4 * g4 + r];
-          *reinterpret_cast<bf16x4*>(qrow + d) = a;
+          for (int r = 0; r < 4; ++r) a[r] = (T)dq[dt][4 * g4 + r];
+          *reinterpret_cast<lo_x4<T>*>(qrow + d) = a;
         }
       }
   }
@@ -705,24 +711,24 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_q_kernel(const bf16* __restri
 // ======================================================================================================
 // launchers
 // ======================================================================================================
-template <int DP>
-static hipError_t fwd_launch(const bf16* q, const bf16* k, const bf16* v, bf16* out, float* lse, int B, int H, int N,
+template <typename T, int DP>
+static hipError_t fwd_launch(const T* q, const T* k, const T* v, T* out, float* lse, int B, int H, int N,
                              int dh, int ld, hipStream_t s) {
   using C = AttnCfg<DP>;
   constexpr int smem = 2 * (64 * C::RSTR + 64 * C::TSTR);
   const float scale = 1.0f / sqrtf((float)dh);
   if (ld > 0)
-    hipLaunchKernelGGL((attn_fwd_kernel<DP, true>), head_grid((N + 127) / 128, B * H), dim3(256), smem, s, q, k, v, out, lse,
+    hipLaunchKernelGGL((attn_fwd_kernel<T, DP, true>), head_grid((N + 127) / 128, B * H), dim3(256), smem, s, q, k, v, out, lse,
                        B, H, N, dh, ld, scale * 1.4426950408889634f, scale);
   else
-    hipLaunchKernelGGL((attn_fwd_kernel<DP, false>), head_grid((N + 127) / 128, B * H), dim3(256), smem, s, q, k, v, out,
+    hipLaunchKernelGGL((attn_fwd_kernel<T, DP, false>), head_grid((N + 127) / 128, B * H), dim3(256), smem, s, q, k, v, out,
                        lse, B, H, N, dh, 0, scale * 1.4426950408889634f, scale);
   return hipGetLastError();
 }
 
-template <int DP>
-static hipError_t bwd_launch(const bf16* q, const bf16* k, const bf16* v, const bf16* out, const bf16* dout,
-                             const float* lse, bf16* dqkv, float* delta, int B, int H, int N, int dh, int ld,
+template <typename T, int DP>
+static hipError_t bwd_launch(const T* q, const T* k, const T* v, const T* out, const T* dout,
+                             const float* lse, T* dqkv, float* delta, int B, int H, int N, int dh, int ld,
                              hipStream_t s) {
   using C = AttnCfg<DP>;
   const float scale = 1.0f / sqrtf((float)dh);
@@ -732,18 +738,18 @@ static hipError_t bwd_launch(const bf16* q, const bf16* k, const bf16* v, const 
   constexpr int smem_q = 3 * (((32 * (C::DSTR / 16) + 63) / 64) + ((32 * (C::RSTR / 16) + 63) / 64)) * 1024;
   const dim3 grid = head_grid((N + 127) / 128, B * H), block(256);
   if (ld > 0)
-    hipLaunchKernelGGL((attn_bwd_q_kernel<DP, true>), grid, block, smem_q, s, q, k, v, out, dout, lse, delta, dqkv, B, H, N,
+    hipLaunchKernelGGL((attn_bwd_q_kernel<T, DP, true>), grid, block, smem_q, s, q, k, v, out, dout, lse, delta, dqkv, B, H, N,
                        dh, ld, c, scale);
   else
-    hipLaunchKernelGGL((attn_bwd_q_kernel<DP, false>), grid, block, smem_q, s, q, k, v, out, dout, lse, delta, dqkv, B, H, N,
+    hipLaunchKernelGGL((attn_bwd_q_kernel<T, DP, false>), grid, block, smem_q, s, q, k, v, out, dout, lse, delta, dqkv, B, H, N,
                        dh, 0, c, scale);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   if (ld > 0)
-    hipLaunchKernelGGL((attn_bwd_kv_kernel<DP, true>), grid, block, smem_kv, s, q, k, v, dout, delta, dqkv, B, H, N, dh, ld, c,
+    hipLaunchKernelGGL((attn_bwd_kv_kernel<T, DP, true>), grid, block, smem_kv, s, q, k, v, dout, delta, dqkv, B, H, N, dh, ld, c,
                        scale);
   else
-    hipLaunchKernelGGL((attn_bwd_kv_kernel<DP, false>), grid, block, smem_kv, s, q, k, v, dout, delta, dqkv, B, H, N, dh, 0,
+    hipLaunchKernelGGL((attn_bwd_kv_kernel<T, DP, false>), grid, block, smem_kv, s, q, k, v, dout, delta, dqkv, B, H, N, dh, 0,
                        c, scale);
   return hipGetLastError();
 }
@@ -766,10 +772,16 @@ hipError_t attn_fwd(const void* q, const void* k, const void* v, int dtype, void
     return attn_f32_fwd((const float*)q, (const float*)k, (const float*)v, (float*)out, lse, B, H, N, dh, DP, ld, s);
   if (!attn_shape_ok(N, dh, DP, H, ld)) return hipErrorInvalidValue;
   if ((((uintptr_t)q) | ((uintptr_t)k) | ((uintptr_t)v)) & 15) return hipErrorInvalidValue;
-#define SGL_F(DPV) \
-  case DPV: return fwd_launch<DPV>((const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)out, lse, B, H, N, dh, ld, s);
+#define SGL_F(T, DPV) \
+  case DPV: return fwd_launch<T, DPV>((const T*)q, (const T*)k, (const T*)v, (T*)out, lse, B, H, N, dh, ld, s);
+  if (dtype == DT_F16) {
+    switch (DP) {
+      SGL_F(f16, 16) SGL_F(f16, 32) SGL_F(f16, 48) SGL_F(f16, 64) SGL_F(f16, 80) SGL_F(f16, 96)
+    }
+    return hipErrorInvalidValue;
+  }
   switch (DP) {
-    SGL_F(16) SGL_F(32) SGL_F(48) SGL_F(64) SGL_F(80) SGL_F(96)
+    SGL_F(bf16, 16) SGL_F(bf16, 32) SGL_F(bf16, 48) SGL_F(bf16, 64) SGL_F(bf16, 80) SGL_F(bf16, 96)
   }
 #undef SGL_F
   return hipErrorInvalidValue;
@@ -787,12 +799,18 @@ hipError_t attn_bwd(const void* q, const void* k, const void* v, const void* out
                         (float*)dqkv, delta, B, H, N, dh, DP, ld, s);
   if (!attn_shape_ok(N, dh, DP, H, ld)) return hipErrorInvalidValue;
   if ((((uintptr_t)q) | ((uintptr_t)k) | ((uintptr_t)v)) & 15) return hipErrorInvalidValue;
-#define SGL_B(DPV)                                                                                             \
-  case DPV:                                                                                                    \
-    return bwd_launch<DPV>((const bf16*)q, (const bf16*)k, (const bf16*)v, (const bf16*)out, (const bf16*)dout, \
-                           lse, (bf16*)dqkv, delta, B, H, N, dh, ld, s);
+#define SGL_B(T, DPV)                                                                                  \
+  case DPV:                                                                                            \
+    return bwd_launch<T, DPV>((const T*)q, (const T*)k, (const T*)v, (const T*)out, (const T*)dout, lse, \
+                              (T*)dqkv, delta, B, H, N, dh, ld, s);
+  if (dtype == DT_F16) {
+    switch (DP) {
+      SGL_B(f16, 16) SGL_B(f16, 32) SGL_B(f16, 48) SGL_B(f16, 64) SGL_B(f16, 80) SGL_B(f16, 96)
+    }
+    return hipErrorInvalidValue;
+  }
   switch (DP) {
-    SGL_B(16) SGL_B(32) SGL_B(48) SGL_B(64) SGL_B(80) SGL_B(96)
+    SGL_B(bf16, 16) SGL_B(bf16, 32) SGL_B(bf16, 48) SGL_B(bf16, 64) SGL_B(bf16, 80) SGL_B(bf16, 96)
   }
 #undef SGL_B
   return hipErrorInvalidValue;

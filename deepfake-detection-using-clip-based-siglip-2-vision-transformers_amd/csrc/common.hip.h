@@ -10,6 +10,9 @@ typedef __bf16 bf16;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
+typedef _Float16 f16;
+typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
+typedef __attribute__((ext_vector_type(4))) _Float16 f16x4;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(2))) float f32x2;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
@@ -43,6 +46,11 @@ template <> struct Elem<float> {
 template <> struct Elem<bf16> {
   static __device__ __forceinline__ float ld(const bf16* p) { return (float)*p; }
   static __device__ __forceinline__ void st(bf16* p, float v) { *p = (bf16)v; }
+};
+// fp16: plain conversions round to nearest even and overflow to +-inf (never v_cvt_pkrtz, which rounds toward zero)
+template <> struct Elem<f16> {
+  static __device__ __forceinline__ float ld(const f16* p) { return (float)*p; }
+  static __device__ __forceinline__ void st(f16* p, float v) { *p = (f16)v; }
 };
 
 // load / store NV (4 or 8) consecutive elements as float; pointers must be NV*sizeof(T)-aligned
@@ -117,6 +125,74 @@ template <> struct Vec<bf16, 8> {
     __builtin_nontemporal_store(t, reinterpret_cast<bf16x8*>(p));
   }
 };
+template <> struct Vec<f16, 4> {
+  static __device__ __forceinline__ void ld(const f16* p, float* v) {
+    f16x4 t = *reinterpret_cast<const f16x4*>(p);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) v[i] = (float)t[i];
+  }
+  static __device__ __forceinline__ void st(f16* p, const float* v) {
+    f16x4 t;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) t[i] = (f16)v[i];
+    *reinterpret_cast<f16x4*>(p) = t;
+  }
+  static __device__ __forceinline__ void st_nt(f16* p, const float* v) {
+    f16x4 t;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) t[i] = (f16)v[i];
+    __builtin_nontemporal_store(t, reinterpret_cast<f16x4*>(p));
+  }
+};
+template <> struct Vec<f16, 8> {
+  static __device__ __forceinline__ void ld(const f16* p, float* v) {
+    f16x8 t = *reinterpret_cast<const f16x8*>(p);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) v[i] = (float)t[i];
+  }
+  static __device__ __forceinline__ void st(f16* p, const float* v) {
+    f16x8 t;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) t[i] = (f16)v[i];
+    *reinterpret_cast<f16x8*>(p) = t;
+  }
+  static __device__ __forceinline__ void st_nt(f16* p, const float* v) {
+    f16x8 t;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) t[i] = (f16)v[i];
+    __builtin_nontemporal_store(t, reinterpret_cast<f16x8*>(p));
+  }
+};
+
+// ---- 16-bit MFMA operand types: bf16 (DT_BF16) and fp16 (DT_F16) share fragment layouts and issue rates on gfx950, so the
+// MFMA kernels take the operand type as a template parameter and reach the type-specific builtins through these overloads
+template <typename T> struct LoVec;
+template <> struct LoVec<bf16> { typedef bf16x4 x4; typedef bf16x8 x8; };
+template <> struct LoVec<f16> { typedef f16x4 x4; typedef f16x8 x8; };
+template <typename T> using lo_x4 = typename LoVec<T>::x4;
+template <typename T> using lo_x8 = typename LoVec<T>::x8;
+
+__device__ __forceinline__ f32x4 mfma_16x16x32(bf16x8 a, bf16x8 b, f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+}
+__device__ __forceinline__ f32x4 mfma_16x16x32(f16x8 a, f16x8 b, f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
+}
+__device__ __forceinline__ f32x16 mfma_32x32x16(bf16x8 a, bf16x8 b, f32x16 c) {
+  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+}
+__device__ __forceinline__ f32x16 mfma_32x32x16(f16x8 a, f16x8 b, f32x16 c) {
+  return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
+}
+// ds_read_b64_tr_b16: 4 rows x 16 columns of 16-bit elements -> lane i gets column i
+template <typename T> __device__ __forceinline__ lo_x4<T> lds_read_tr16(const char* p);
+template <> __device__ __forceinline__ bf16x4 lds_read_tr16<bf16>(const char* p) {
+  return __builtin_amdgcn_ds_read_tr16_b64_v4bf16((SGL_LDS bf16x4*)(p));
+}
+typedef __fp16 fp16x4_builtin __attribute__((vector_size(8)));   // the fp16 form's declared operand type
+template <> __device__ __forceinline__ f16x4 lds_read_tr16<f16>(const char* p) {
+  return __builtin_bit_cast(f16x4, __builtin_amdgcn_ds_read_tr16_b64_v4f16((SGL_LDS fp16x4_builtin*)(p)));
+}
 
 // ---- GELU (tanh form, 'gelu_pytorch_tanh') and its derivative ---------------------------------------
 // 0.5 x (1 + tanh(z)) == x * sigmoid(2z),  z = c (x + a x^3).  Written with one v_exp_f32 and one v_rcp_f32 (both

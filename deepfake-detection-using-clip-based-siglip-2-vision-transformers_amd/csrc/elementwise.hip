@@ -42,6 +42,9 @@ hipError_t im2col(const float* pix, int channels_last, void* out, int out_dtype,
   if (out_dtype == DT_BF16)
     hipLaunchKernelGGL(im2col_kernel<bf16>, dim3(blocks), dim3(256), 0, s, pix, channels_last, (bf16*)out, B, H, W, P,
                        gh, gw, Kp);
+  else if (out_dtype == DT_F16)
+    hipLaunchKernelGGL(im2col_kernel<f16>, dim3(blocks), dim3(256), 0, s, pix, channels_last, (f16*)out, B, H, W, P,
+                       gh, gw, Kp);
   else
     hipLaunchKernelGGL(im2col_kernel<float>, dim3(blocks), dim3(256), 0, s, pix, channels_last, (float*)out, B, H, W,
                        P, gh, gw, Kp);
@@ -68,6 +71,8 @@ hipError_t cast_pad(const float* src, int R, int C, int ld, void* dst, int dst_d
   int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
   if (dst_dtype == DT_BF16)
     hipLaunchKernelGGL(cast_pad_kernel<bf16>, dim3(blocks), dim3(256), 0, s, src, R, C, ld, (bf16*)dst, Rp, Cp, ldd);
+  else if (dst_dtype == DT_F16)
+    hipLaunchKernelGGL(cast_pad_kernel<f16>, dim3(blocks), dim3(256), 0, s, src, R, C, ld, (f16*)dst, Rp, Cp, ldd);
   else
     hipLaunchKernelGGL(cast_pad_kernel<float>, dim3(blocks), dim3(256), 0, s, src, R, C, ld, (float*)dst, Rp, Cp, ldd);
   return hipGetLastError();
@@ -191,6 +196,8 @@ hipError_t cast_transpose_pad(const float* src, int R, int C, int ld, void* dst,
   dim3 grid((Cp + 31) / 32, (Rp + 31) / 32), block(256);
   if (dst_dtype == DT_BF16)
     hipLaunchKernelGGL(cast_transpose_kernel<bf16>, grid, block, 0, s, src, R, C, ld, (bf16*)dst, Cp, Rp, ldd);
+  else if (dst_dtype == DT_F16)
+    hipLaunchKernelGGL(cast_transpose_kernel<f16>, grid, block, 0, s, src, R, C, ld, (f16*)dst, Cp, Rp, ldd);
   else
     hipLaunchKernelGGL(cast_transpose_kernel<float>, grid, block, 0, s, src, R, C, ld, (float*)dst, Cp, Rp, ldd);
   return hipGetLastError();
@@ -205,6 +212,7 @@ hipError_t cast_transpose_pad(const float* src, int R, int C, int ld, void* dst,
 template <typename T> __device__ __forceinline__ T cj_cvt(float x);
 template <> __device__ __forceinline__ float cj_cvt<float>(float x) { return x; }
 template <> __device__ __forceinline__ bf16 cj_cvt<bf16>(float x) { return (bf16)x; }
+template <> __device__ __forceinline__ f16 cj_cvt<f16>(float x) { return (f16)x; }
 
 template <typename T>
 __global__ __launch_bounds__(256) void cast_job_kernel(CastJob job) {
@@ -308,6 +316,8 @@ hipError_t cast_job_run(const CastJob& job, int dst_dtype, hipStream_t s) {
   const dim3 grid((unsigned)(job.ntiles + (job.nvec ? 1 : 0)));
   if (dst_dtype == DT_BF16)
     hipLaunchKernelGGL(cast_job_kernel<bf16>, grid, dim3(256), 0, s, job);
+  else if (dst_dtype == DT_F16)
+    hipLaunchKernelGGL(cast_job_kernel<f16>, grid, dim3(256), 0, s, job);
   else
     hipLaunchKernelGGL(cast_job_kernel<float>, grid, dim3(256), 0, s, job);
   return hipGetLastError();
@@ -357,6 +367,8 @@ hipError_t colsum(const void* in, int dtype, int ld, int M, int N, int n_out, fl
   dim3 grid((N + 255) / 256, chunks), block(256);
   if (dtype == DT_BF16)
     hipLaunchKernelGGL(colsum_kernel<bf16>, grid, block, 0, s, (const bf16*)in, ld, M, N, rows_per, partial);
+  else if (dtype == DT_F16)
+    hipLaunchKernelGGL(colsum_kernel<f16>, grid, block, 0, s, (const f16*)in, ld, M, N, rows_per, partial);
   else
     hipLaunchKernelGGL(colsum_kernel<float>, grid, block, 0, s, (const float*)in, ld, M, N, rows_per, partial);
   hipError_t e = hipGetLastError();
@@ -553,6 +565,8 @@ hipError_t cast_f32(const float* src, void* dst, int dst_dtype, size_t n, hipStr
   if (blocks > 4096) blocks = 4096;
   if (dst_dtype == DT_BF16)
     hipLaunchKernelGGL(cast_f32_kernel<bf16>, dim3((unsigned)blocks), dim3(256), 0, s, src, (bf16*)dst, n);
+  else if (dst_dtype == DT_F16)
+    hipLaunchKernelGGL(cast_f32_kernel<f16>, dim3((unsigned)blocks), dim3(256), 0, s, src, (f16*)dst, n);
   else
     hipLaunchKernelGGL(cast_f32_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, s, src, (float*)dst, n);
   return hipGetLastError();
@@ -659,6 +673,9 @@ hipError_t pool_attn_fwd(const float* q, const void* K, const void* V, int dtype
   if (dtype == DT_BF16)
     hipLaunchKernelGGL(pool_attn_fwd_kernel<bf16>, dim3(B * H), dim3(256), smem, s, q, (const bf16*)K, (const bf16*)V,
                        (bf16*)out, probs, H, N, dh, DP);
+  else if (dtype == DT_F16)
+    hipLaunchKernelGGL(pool_attn_fwd_kernel<f16>, dim3(B * H), dim3(256), smem, s, q, (const f16*)K, (const f16*)V,
+                       (f16*)out, probs, H, N, dh, DP);
   else
     hipLaunchKernelGGL(pool_attn_fwd_kernel<float>, dim3(B * H), dim3(256), smem, s, q, (const float*)K,
                        (const float*)V, (float*)out, probs, H, N, dh, DP);
@@ -764,6 +781,9 @@ hipError_t pool_attn_bwd(const float* q, const void* K, const void* V, int dtype
   if (dtype == DT_BF16)
     hipLaunchKernelGGL(pool_attn_bwd_kernel<bf16>, dim3(B * H), dim3(256), smem, s, q, (const bf16*)K, (const bf16*)V,
                        probs, dout, (bf16*)dkv, dq_partial, H, N, dh, DP);
+  else if (dtype == DT_F16)
+    hipLaunchKernelGGL(pool_attn_bwd_kernel<f16>, dim3(B * H), dim3(256), smem, s, q, (const f16*)K, (const f16*)V,
+                       probs, dout, (f16*)dkv, dq_partial, H, N, dh, DP);
   else
     hipLaunchKernelGGL(pool_attn_bwd_kernel<float>, dim3(B * H), dim3(256), smem, s, q, (const float*)K,
                        (const float*)V, probs, dout, (float*)dkv, dq_partial, H, N, dh, DP);

@@ -3,8 +3,8 @@
 //   embeddings   TF:models/siglip/modeling_siglip.py:175-185      (im2col + GEMM, bias + position fused)
 //   27x block    TF:...:335-356   x += out_proj(attn(qkv(LN1 x)));  x += fc2(gelu_tanh(fc1(LN2 x)))
 //   post LN      TF:...:612        pooling head  TF:...:633-643
-// The residual stream, LayerNorm statistics and softmax run in fp32 in both compute modes; GEMM / attention
-// operands are bf16 (MFMA) or fp32 (strict).  The ctx owns no device memory: every buffer is the caller's.
+// The residual stream, LayerNorm statistics and softmax run in fp32 in every compute mode; GEMM / attention
+// operands are bf16 or fp16 (MFMA) or fp32 (strict).  The ctx owns no device memory: every buffer is the caller's.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -19,6 +19,8 @@ using namespace sgl;
 namespace {
 
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+// 16-bit MFMA compute modes (bf16, fp16): the same kernels and buffer layouts, only the operand type differs
+inline bool mfma16(int dt) { return dt == DT_BF16 || dt == DT_F16; }
 inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
 struct Bump {
@@ -184,6 +186,7 @@ inline const char* at(const void* base, size_t off) { return reinterpret_cast<co
 hipError_t gemm_nt(const sgl_ctx* c, const void* A, int lda, const void* B, int ldb, int M, int N, int K, int epi,
                    int out_dt, const EpiParams& p, hipStream_t s) {
   if (c->dt == DT_BF16) return gemm_nt_bf16(A, lda, B, ldb, M, N, K, epi, out_dt, p, s);
+  if (c->dt == DT_F16) return gemm_nt_f16(A, lda, B, ldb, M, N, K, epi, out_dt, p, s);
   if (c->split && M > 0 && N > 0) {   // bf16x3: one MFMA GEMM over [hi|hi|lo] x [hi|lo|hi], three times the reduction length
     const int Ks = round_up(K, 8);
     hipError_t e = split3_rows((const float*)A, M, K, lda, c->sp_a, Ks, 0, s);
@@ -203,12 +206,14 @@ hipError_t gemm_tn(const sgl_ctx* c, const void* A, int lda, const void* B, int 
   p.out = out;
   p.ldo = ldo;
   p.accumulate = accumulate;
-  if (c->dt == DT_BF16) {
+  if (mfma16(c->dt)) {
     const int tiles = ((N1 + 127) / 128) * ((N2 + 127) / 128);
     int splits = (512 + tiles - 1) / tiles;
     const int max_splits = Mred / 512 > 0 ? Mred / 512 : 1;
     if (splits > max_splits) splits = max_splits;
     if (splits > 16) splits = 16;
+    if (c->dt == DT_F16)
+      return gemm_tn_f16(A, lda, B, ldb, Mred, N1, N2, splits, p, s, reinterpret_cast<float*>(split_ws), split_ws_bytes);
     return gemm_tn_bf16(A, lda, B, ldb, Mred, N1, N2, splits, p, s, reinterpret_cast<float*>(split_ws), split_ws_bytes);
   }
   if (c->split && Mred > 0 && N1 > 0 && N2 > 0) {   // bf16x3: [hi;hi;lo]^T x [hi;lo;hi], reduction over 3*Mred rows
@@ -264,7 +269,7 @@ sgl_ctx* sgl_create(const sgl_config* cfg) {
       cfg->native_grid <= 0)
     return nullptr;
   if (cfg->compute_dtype != SGL_DTYPE_F32 && cfg->compute_dtype != SGL_DTYPE_BF16 &&
-      cfg->compute_dtype != SGL_DTYPE_BF16X3)
+      cfg->compute_dtype != SGL_DTYPE_BF16X3 && cfg->compute_dtype != SGL_DTYPE_F16)
     return nullptr;
   sgl_ctx* c = new (std::nothrow) sgl_ctx();
   if (!c) return nullptr;
@@ -281,7 +286,7 @@ sgl_ctx* sgl_create(const sgl_config* cfg) {
   c->Kp = round_up(c->K0, 64);
   c->g0 = cfg->native_grid;
   c->split = cfg->compute_dtype == SGL_DTYPE_BF16X3;
-  c->dt = c->split ? DT_F32 : cfg->compute_dtype;
+  c->dt = c->split ? DT_F32 : cfg->compute_dtype == SGL_DTYPE_F16 ? DT_F16 : cfg->compute_dtype;
   c->es = dtype_size(c->dt);
   const size_t es = c->es, D = c->D, Ip = c->Ip;
   Bump b;
@@ -562,7 +567,7 @@ int sgl_forward_slots(sgl_ctx* ctx, const sgl_weights* w, const void* shadow, co
     {
       EpiParams p;
       p.out = (train && l >= first_trainable_block) ? lb + lay.r_u : nullptr;
-      p.gelu_grad_form = (dt == DT_BF16);   // r_u holds gelu'(u) in bf16 mode (the backward only ever needs that)
+      p.gelu_grad_form = mfma16(dt);   // r_u holds gelu'(u) in bf16 / fp16 mode (the backward only ever needs that)
       p.ldo = Ip;
       p.out2 = lb + lay.r_a;
       p.ldo2 = Ip;
@@ -858,14 +863,14 @@ int sgl_backward_layer_p(sgl_ctx* ctx, const sgl_weights* w, const void* shadow,
   // ---- MLP: x_out = xmid + fc2(gelu(fc1(LN2 xmid)))          gbuf = lowp(d x_out)
   float* gsum = reinterpret_cast<float*>(at(ws, lay.w_gsum));   // column sums of dx, left by the producer of dx
   float* csum = reinterpret_cast<float*>(at(ws, lay.w_csum));
-  const bool fuse_cs = (dt == DT_BF16) && lg.fc1_b;  // MFMA epilogue adds colsum(du); strict mode uses colsum()
+  const bool fuse_cs = mfma16(dt) && lg.fc1_b;  // MFMA epilogue adds colsum(du); strict mode uses colsum()
   {
     EpiParams p;
     p.out = du;
     p.ldo = Ip;
     p.aux = lb + lay.r_u;
     p.ldaux = Ip;
-    p.gelu_grad_form = (dt == DT_BF16);
+    p.gelu_grad_form = mfma16(dt);
     if (fuse_cs) {  // deterministic: one row of partial sums per 128-row tile, folded in order below
       CK(hipMemsetAsync(csum, 0, (size_t)((M + 127) / 128) * Ip * 4, s));
       p.colsum = csum;
@@ -1036,6 +1041,8 @@ int sgl_op_gemm_nt(int dtype, const void* A, int lda, const void* B, int ldb, in
   const int out_dt = f32_out ? DT_F32 : dtype;
   if (dtype == DT_BF16)
     CKV(gemm_nt_bf16(A, lda, B, ldb, M, N, K, epi, out_dt, p, (hipStream_t)stream));
+  else if (dtype == DT_F16)
+    CKV(gemm_nt_f16(A, lda, B, ldb, M, N, K, epi, out_dt, p, (hipStream_t)stream));
   else
     CKV(gemm_f32_generic((const float*)A, lda, 1, (const float*)B, ldb, 1, M, N, K, epi, out_dt, p,
                          (hipStream_t)stream));
@@ -1053,6 +1060,8 @@ int sgl_op_gemm_tn_ws(int dtype, const void* A, int lda, const void* B, int ldb,
   p.out = out; p.ldo = ldo; p.accumulate = accumulate;
   if (dtype == DT_BF16)
     CKV(gemm_tn_bf16(A, lda, B, ldb, Mred, N1, N2, splits, p, (hipStream_t)stream, scratch, scratch_bytes));
+  else if (dtype == DT_F16)
+    CKV(gemm_tn_f16(A, lda, B, ldb, Mred, N1, N2, splits, p, (hipStream_t)stream, scratch, scratch_bytes));
   else
     CKV(gemm_f32_generic((const float*)A, 1, lda, (const float*)B, 1, ldb, N1, N2, Mred, EPI_F32, DT_F32, p,
                          (hipStream_t)stream));

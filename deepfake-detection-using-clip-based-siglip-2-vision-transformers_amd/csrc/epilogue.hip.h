@@ -8,6 +8,8 @@
 //   EPI_BIAS_GELU fc1 bias + gelu_pytorch_tanh                              :319-320
 //   EPI_POS_F32   patch conv bias + position embedding add                  :178-184
 #pragma once
+#include <type_traits>
+
 #include "common.hip.h"
 #include "kernels.h"
 
@@ -110,21 +112,23 @@ __device__ __forceinline__ void epi_apply(const EpiParams& p, int row, int col, 
 }
 
 // Host side: calls launch(EpiTag<EPI, TOut>{}) for a runtime (epilogue, output dtype) pair, so that every GEMM family
-// instantiates the same table: bf16 or fp32 outputs for the first four epilogues (fp32 = bf16x3 strict mode on the MFMA
+// instantiates the same table: bf16 (fp16) or fp32 outputs for the first four epilogues (fp32 = bf16x3 strict mode on the MFMA
 // kernels), fp32 for the others.
 template <int EPI, typename TOut>
 struct EpiTag {
   static constexpr int epi = EPI;
   using out = TOut;
 };
-template <typename Launch>
+// TLo is the 16-bit output type of the family being dispatched (bf16, or fp16 for the DT_F16 kernels): out_dtype selects
+// it or fp32.
+template <typename TLo = bf16, typename Launch>
 hipError_t dispatch_epilogue(int epi, int out_dtype, Launch&& launch) {
-  const bool b16 = out_dtype == DT_BF16;
+  const bool b16 = out_dtype == (std::is_same<TLo, f16>::value ? DT_F16 : DT_BF16);
   switch (epi) {
-    case EPI_STORE: return b16 ? launch(EpiTag<EPI_STORE, bf16>{}) : launch(EpiTag<EPI_STORE, float>{});
-    case EPI_BIAS_GELU: return b16 ? launch(EpiTag<EPI_BIAS_GELU, bf16>{}) : launch(EpiTag<EPI_BIAS_GELU, float>{});
-    case EPI_QKV: return b16 ? launch(EpiTag<EPI_QKV, bf16>{}) : launch(EpiTag<EPI_QKV, float>{});
-    case EPI_GELU_BWD: return b16 ? launch(EpiTag<EPI_GELU_BWD, bf16>{}) : launch(EpiTag<EPI_GELU_BWD, float>{});
+    case EPI_STORE: return b16 ? launch(EpiTag<EPI_STORE, TLo>{}) : launch(EpiTag<EPI_STORE, float>{});
+    case EPI_BIAS_GELU: return b16 ? launch(EpiTag<EPI_BIAS_GELU, TLo>{}) : launch(EpiTag<EPI_BIAS_GELU, float>{});
+    case EPI_QKV: return b16 ? launch(EpiTag<EPI_QKV, TLo>{}) : launch(EpiTag<EPI_QKV, float>{});
+    case EPI_GELU_BWD: return b16 ? launch(EpiTag<EPI_GELU_BWD, TLo>{}) : launch(EpiTag<EPI_GELU_BWD, float>{});
     case EPI_RES_F32: return launch(EpiTag<EPI_RES_F32, float>{});
     case EPI_POS_F32: return launch(EpiTag<EPI_POS_F32, float>{});
     case EPI_F32: return launch(EpiTag<EPI_F32, float>{});

@@ -1,4 +1,5 @@
-// bf16 MFMA GEMMs for gfx950 (v_mfma_f32_16x16x32_bf16, fp32 accumulate), 64-lane wavefronts.
+// bf16 MFMA GEMMs for gfx950 (v_mfma_f32_16x16x32_bf16, fp32 accumulate), 64-lane wavefronts.  The same kernels take
+// fp16 operands (DT_F16: v_mfma_f32_16x16x32_f16, same fragment layouts) through their operand-type template parameter.
 //
 //   gemm_nt : C[M,N]  = A[M,K] · B[N,K]ᵀ      forward projections and dX (with pre-transposed weight shadows)
 //   gemm_tn : C[N1,N2] (+)= Σ_m A[m,N1]·B[m,N2]   weight gradients dW = dYᵀ·X, reduction over tokens
@@ -113,9 +114,9 @@ __device__ __forceinline__ void store_tile(char* smem, f32x4 (&acc)[4][4], int w
 // ------------------------------------------------------------------------------------------------------
 // NT
 // ------------------------------------------------------------------------------------------------------
-template <int EPI, typename TOut>
-__global__ __launch_bounds__(256, 2) void gemm_nt_kernel(const bf16* __restrict__ A, int lda,
-                                                         const bf16* __restrict__ B, int ldb, int M, int N, int K,
+template <int EPI, typename TOut, typename TIn>
+__global__ __launch_bounds__(256, 2) void gemm_nt_kernel(const TIn* __restrict__ A, int lda,
+                                                         const TIn* __restrict__ B, int ldb, int M, int N, int K,
                                                          EpiParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -184,17 +185,17 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(const bf16* __restrict_
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
       const uint32_t coff = (uint32_t)(((4 * s + fg) ^ fsw) << 4);
-      bf16x8 af[4], bfr[4];
+      lo_x8<TIn> af[4], bfr[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        af[i] = *reinterpret_cast<const bf16x8*>(base + fa_row[i] + coff);
-        bfr[i] = *reinterpret_cast<const bf16x8*>(base + fb_row[i] + coff);
+        af[i] = *reinterpret_cast<const lo_x8<TIn>*>(base + fa_row[i] + coff);
+        bfr[i] = *reinterpret_cast<const lo_x8<TIn>*>(base + fb_row[i] + coff);
       }
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
+          acc[i][j] = mfma_16x16x32(af[i], bfr[j], acc[i][j]);
     }
     if (kt + 1 < nk) store_stage(cur ^ 1);
     __syncthreads();
@@ -205,12 +206,9 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(const bf16* __restrict_
 // ------------------------------------------------------------------------------------------------------
 // TN
 // ------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ bf16x4 lds_tr16(const char* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4bf16((SGL_LDS bf16x4*)(p));
-}
-
-__global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const bf16* __restrict__ A, int lda,
-                                                         const bf16* __restrict__ B, int ldb, int Mred, int N1, int N2,
+template <typename TIn>
+__global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const TIn* __restrict__ A, int lda,
+                                                         const TIn* __restrict__ B, int ldb, int Mred, int N1, int N2,
                                                          int m_per_split, EpiParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -284,13 +282,13 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const bf16* __restrict_
     for (int s = 0; s < 2; ++s) {
       const char* ba = base + s * 32 * 256 + frow;
       const char* bb = ba + OPB;
-      bf16x8 af[4], bfr[4];
+      lo_x8<TIn> af[4], bfr[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const bf16x4 alo = lds_tr16(ba + fa_col[i]);
-        const bf16x4 ahi = lds_tr16(ba + 4 * 256 + fa_col[i]);
-        const bf16x4 blo = lds_tr16(bb + fb_col[i]);
-        const bf16x4 bhi = lds_tr16(bb + 4 * 256 + fb_col[i]);
+        const lo_x4<TIn> alo = lds_read_tr16<TIn>(ba + fa_col[i]);
+        const lo_x4<TIn> ahi = lds_read_tr16<TIn>(ba + 4 * 256 + fa_col[i]);
+        const lo_x4<TIn> blo = lds_read_tr16<TIn>(bb + fb_col[i]);
+        const lo_x4<TIn> bhi = lds_read_tr16<TIn>(bb + 4 * 256 + fb_col[i]);
         af[i] = __builtin_shufflevector(alo, ahi, 0, 1, 2, 3, 4, 5, 6, 7);
         bfr[i] = __builtin_shufflevector(blo, bhi, 0, 1, 2, 3, 4, 5, 6, 7);
       }
@@ -298,7 +296,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const bf16* __restrict_
       for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
+          acc[i][j] = mfma_16x16x32(af[i], bfr[j], acc[i][j]);
     }
     if (kt + 1 < nk) store_stage(cur ^ 1);
     __syncthreads();
@@ -316,28 +314,43 @@ hipError_t gemm_nt256_bf16(const void* A, int lda, const void* B, int ldb, int M
                            const EpiParams& p, hipStream_t s);
 hipError_t gemm_tn256_bf16(const void* A, int lda, const void* B, int ldb, int Mred, int N1, int N2, int m_per,
                            int splits, const EpiParams& p, hipStream_t s);
+hipError_t gemm_nt256_f16(const void* A, int lda, const void* B, int ldb, int M, int N, int K, int epi, int out_dtype,
+                          const EpiParams& p, hipStream_t s);
+hipError_t gemm_tn256_f16(const void* A, int lda, const void* B, int ldb, int Mred, int N1, int N2, int m_per,
+                          int splits, const EpiParams& p, hipStream_t s);
 
-template <int EPI, typename TOut>
-static hipError_t launch_nt(const bf16* A, int lda, const bf16* B, int ldb, int M, int N, int K, const EpiParams& p,
+template <int EPI, typename TOut, typename TIn>
+static hipError_t launch_nt(const TIn* A, int lda, const TIn* B, int ldb, int M, int N, int K, const EpiParams& p,
                             hipStream_t s) {
-  const hipError_t e = set_max_dynamic_lds_once<&gemm_nt_kernel<EPI, TOut>>(G_LDS);
+  const hipError_t e = set_max_dynamic_lds_once<&gemm_nt_kernel<EPI, TOut, TIn>>(G_LDS);
   if (e != hipSuccess) return e;
   const int tiles = ((M + G_BM - 1) / G_BM) * ((N + G_BN - 1) / G_BN);
-  hipLaunchKernelGGL((gemm_nt_kernel<EPI, TOut>), dim3(tiles), dim3(256), G_LDS, s, A, lda, B, ldb, M, N, K, p);
+  hipLaunchKernelGGL((gemm_nt_kernel<EPI, TOut, TIn>), dim3(tiles), dim3(256), G_LDS, s, A, lda, B, ldb, M, N, K, p);
   return hipGetLastError();
 }
 
-hipError_t gemm_nt_bf16(const void* A, int lda, const void* B, int ldb, int M, int N, int K, int epi, int out_dtype,
-                        const EpiParams& p, hipStream_t s) {
+template <typename TIn>
+static hipError_t gemm_nt_mfma(const void* A, int lda, const void* B, int ldb, int M, int N, int K, int epi,
+                               int out_dtype, const EpiParams& p, hipStream_t s) {
   if (M == 0 || N == 0) return hipSuccess;
   if ((lda % 8) || (ldb % 8) || (K % 8) || K <= 0) return hipErrorInvalidValue;
   if (epi != EPI_F32 && (N % 8)) return hipErrorInvalidValue;
   if ((size_t)M * lda * 2 >= (1ull << 32) || (size_t)N * ldb * 2 >= (1ull << 32)) return hipErrorInvalidValue;
-  if (M >= 2048 && N >= 256) return gemm_nt256_bf16(A, lda, B, ldb, M, N, K, epi, out_dtype, p, s);
-  return dispatch_epilogue(epi, out_dtype, [&](auto tag) {
+  if (M >= 2048 && N >= 256)
+    return std::is_same<TIn, f16>::value ? gemm_nt256_f16(A, lda, B, ldb, M, N, K, epi, out_dtype, p, s)
+                                         : gemm_nt256_bf16(A, lda, B, ldb, M, N, K, epi, out_dtype, p, s);
+  return dispatch_epilogue<TIn>(epi, out_dtype, [&](auto tag) {
     using T = decltype(tag);
-    return launch_nt<T::epi, typename T::out>((const bf16*)A, lda, (const bf16*)B, ldb, M, N, K, p, s);
+    return launch_nt<T::epi, typename T::out, TIn>((const TIn*)A, lda, (const TIn*)B, ldb, M, N, K, p, s);
   });
+}
+hipError_t gemm_nt_bf16(const void* A, int lda, const void* B, int ldb, int M, int N, int K, int epi, int out_dtype,
+                        const EpiParams& p, hipStream_t s) {
+  return gemm_nt_mfma<bf16>(A, lda, B, ldb, M, N, K, epi, out_dtype, p, s);
+}
+hipError_t gemm_nt_f16(const void* A, int lda, const void* B, int ldb, int M, int N, int K, int epi, int out_dtype,
+                       const EpiParams& p, hipStream_t s) {
+  return gemm_nt_mfma<f16>(A, lda, B, ldb, M, N, K, epi, out_dtype, p, s);
 }
 
 // Split the token reduction of a TN GEMM into `splits` ranges of m_per rows (m_per a multiple of G_BK) and run
@@ -376,8 +389,9 @@ static hipError_t tn_split_k(int Mred, int N1, int N2, int splits, const EpiPara
   return launch(m_per, splits, p);
 }
 
-hipError_t gemm_tn_bf16(const void* A, int lda, const void* B, int ldb, int Mred, int N1, int N2, int splits,
-                        const EpiParams& p, hipStream_t s, float* split_ws, size_t split_ws_bytes) {
+template <typename TIn>
+static hipError_t gemm_tn_mfma(const void* A, int lda, const void* B, int ldb, int Mred, int N1, int N2, int splits,
+                               const EpiParams& p, hipStream_t s, float* split_ws, size_t split_ws_bytes) {
   if (N1 == 0 || N2 == 0) return hipSuccess;
   if ((lda % 8) || (ldb % 8)) return hipErrorInvalidValue;
   if ((size_t)Mred * lda * 2 >= (1ull << 32) || (size_t)Mred * ldb * 2 >= (1ull << 32)) return hipErrorInvalidValue;
@@ -395,17 +409,26 @@ hipError_t gemm_tn_bf16(const void* A, int lda, const void* B, int ldb, int Mred
     const int max_sp = Mred / 1024 > 0 ? Mred / 1024 : 1;
     if (sp > max_sp) sp = max_sp;
     return tn_split_k(Mred, N1, N2, sp, p, s, split_ws, split_ws_bytes, [&](int m_per, int nsplit, const EpiParams& q) {
-      return gemm_tn256_bf16(A, lda, B, ldb, Mred, N1, N2, m_per, nsplit, q, s);
+      return std::is_same<TIn, f16>::value ? gemm_tn256_f16(A, lda, B, ldb, Mred, N1, N2, m_per, nsplit, q, s)
+                                           : gemm_tn256_bf16(A, lda, B, ldb, Mred, N1, N2, m_per, nsplit, q, s);
     });
   }
   return tn_split_k(Mred, N1, N2, splits, p, s, split_ws, split_ws_bytes, [&](int m_per, int nsplit, const EpiParams& q) {
-    const hipError_t e = set_max_dynamic_lds_once<&gemm_tn_kernel>(G_LDS);
+    const hipError_t e = set_max_dynamic_lds_once<&gemm_tn_kernel<TIn>>(G_LDS);
     if (e != hipSuccess) return e;
     const int tiles = ((N1 + G_BM - 1) / G_BM) * ((N2 + G_BN - 1) / G_BN);
-    hipLaunchKernelGGL(gemm_tn_kernel, dim3(tiles, nsplit), dim3(256), G_LDS, s, (const bf16*)A, lda, (const bf16*)B,
+    hipLaunchKernelGGL(gemm_tn_kernel<TIn>, dim3(tiles, nsplit), dim3(256), G_LDS, s, (const TIn*)A, lda, (const TIn*)B,
                        ldb, Mred, N1, N2, m_per, q);
     return hipGetLastError();
   });
+}
+hipError_t gemm_tn_bf16(const void* A, int lda, const void* B, int ldb, int Mred, int N1, int N2, int splits,
+                        const EpiParams& p, hipStream_t s, float* split_ws, size_t split_ws_bytes) {
+  return gemm_tn_mfma<bf16>(A, lda, B, ldb, Mred, N1, N2, splits, p, s, split_ws, split_ws_bytes);
+}
+hipError_t gemm_tn_f16(const void* A, int lda, const void* B, int ldb, int Mred, int N1, int N2, int splits,
+                       const EpiParams& p, hipStream_t s, float* split_ws, size_t split_ws_bytes) {
+  return gemm_tn_mfma<f16>(A, lda, B, ldb, Mred, N1, N2, splits, p, s, split_ws, split_ws_bytes);
 }
 
 }  // namespace sgl

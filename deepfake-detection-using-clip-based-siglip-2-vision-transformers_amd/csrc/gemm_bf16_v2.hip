@@ -1,4 +1,4 @@
-// bf16 MFMA GEMMs for gfx950 on a 256x256 output tile, K-step 64, 512 threads = 8 waves, operands streamed
+// bf16 / fp16 MFMA GEMMs for gfx950 on a 256x256 output tile, K-step 64, 512 threads = 8 waves, operands streamed
 // global -> LDS by LDS-DMA (buffer_load_dwordx4 ... lds, 1 KiB per wave instruction, no VGPR staging), two LDS stages
 // (2 x 64 KiB).  The main loops gemm_nt6_kernel / gemm_tn6_kernel run anti-phase wave groups, four barrier-separated
 // slots per K-step (see the comment above them), and share the LDS images, tile order and epilogue below.
@@ -41,9 +41,6 @@ constexpr int T_STAGE = 2 * T_OP;         // 64 KiB
 constexpr int T_LDS = 2 * T_STAGE;        // 128 KiB
 constexpr int T_CT_LD = 260;              // fp32 epilogue staging stride (64 rows x 260 floats = 66,560 B)
 
-__device__ __forceinline__ bf16x4 lds_tr16v2(const char* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4bf16((SGL_LDS bf16x4*)(p));
-}
 
 // accumulators -> LDS (64 rows at a time) -> row-contiguous chunks -> fused epilogue
 template <int EPI, typename TOut>
@@ -96,7 +93,7 @@ __device__ __forceinline__ void store_tile256(char* smem, f32x4 (&acc)[8][4], in
     qkv_c0 = ((size_t)which * p.batch * p.heads + h) * (size_t)p.tokens * p.head_dim_pad + d;
     qkv_pad = (d + NV == p.head_dim) ? (p.head_dim_pad - p.head_dim) / NV : 0;
   }
-  using PreT = u32x4;                       // one raw 16-byte chunk: 4 fp32 residuals / 8 bf16 pre-activations
+  using PreT = u32x4;                       // one raw 16-byte chunk: 4 fp32 residuals / 8 bf16 (fp16) pre-activations
   constexpr bool HAS_PRE = (EPI == EPI_RES_F32 || EPI == EPI_GELU_BWD);
   PreT pre[2][QN];
   auto load_pre = [&](int pass, PreT (&dst)[QN]) {
@@ -197,7 +194,7 @@ __device__ __forceinline__ void store_tile256(char* smem, f32x4 (&acc)[8][4], in
         } else if constexpr (EPI == EPI_GELU_BWD) {
           float u[NV];
           if constexpr (NV == 8) {
-            const bf16x8 ub = __builtin_bit_cast(bf16x8, pre[pass & 1][q]);
+            const lo_x8<TOut> ub = __builtin_bit_cast(lo_x8<TOut>, pre[pass & 1][q]);
 #pragma unroll
             for (int j = 0; j < NV; ++j) u[j] = (float)ub[j];
           } else {
@@ -336,9 +333,9 @@ __device__ unsigned long long g_tn6_tl[12];   // [group][phase 0..4, slot-pair c
 #else
 #define SGL_TL_STAMP(v)
 #endif
-template <int EPI, typename TOut>
-__global__ __launch_bounds__(512, 2) void gemm_nt6_kernel(const bf16* __restrict__ A, int lda,
-                                                          const bf16* __restrict__ B, int ldb, int M, int N, int K,
+template <int EPI, typename TOut, typename TIn>
+__global__ __launch_bounds__(512, 2) void gemm_nt6_kernel(const TIn* __restrict__ A, int lda,
+                                                          const TIn* __restrict__ B, int ldb, int M, int N, int K,
                                                           int tiles_m, int tiles_n, int band_h, EpiParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   SGL_TL_STAMP(tl0);
@@ -407,7 +404,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt6_kernel(const bf16* __restrict
   SGL_PP_END_READ8();                // Aq02(0), BX(0), BY(0) of every wave have landed
   if (grp == 1) SGL_PP_END_MFMA();   // G1 runs one slot behind G0 from here on
 
-  bf16x8 fa[8], fb[8];
+  lo_x8<TIn> fa[8], fb[8];
   for (int kt = 0; kt < nk; ++kt) {
     const char* base = smem + (kt & 1) * T_STAGE;
     const char* pa = base + fa_base;
@@ -415,9 +412,9 @@ __global__ __launch_bounds__(512, 2) void gemm_nt6_kernel(const bf16* __restrict
     // ---- R1: A0 (row tiles 0-3), B (column tiles 0-3), both k-halves
     if (active) {
 #pragma unroll
-      for (int f = 0; f < 8; ++f) fb[f] = *reinterpret_cast<const bf16x8*>(pb + (f & 3) * 2048 + ((f >> 2) ? c1 : c0));
+      for (int f = 0; f < 8; ++f) fb[f] = *reinterpret_cast<const lo_x8<TIn>*>(pb + (f & 3) * 2048 + ((f >> 2) ? c1 : c0));
 #pragma unroll
-      for (int f = 0; f < 8; ++f) fa[f] = *reinterpret_cast<const bf16x8*>(pa + (f & 3) * 2048 + ((f >> 2) ? c1 : c0));
+      for (int f = 0; f < 8; ++f) fa[f] = *reinterpret_cast<const lo_x8<TIn>*>(pa + (f & 3) * 2048 + ((f >> 2) ? c1 : c0));
     }
     issue(3, kt + 1);
     SGL_PP_END_READ8();
@@ -429,14 +426,14 @@ __global__ __launch_bounds__(512, 2) void gemm_nt6_kernel(const bf16* __restrict
         for (int i = 0; i < 4; ++i)
 #pragma unroll
           for (int j = 0; j < 4; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[4 * h + i], fb[4 * h + j], acc[i][j], 0, 0, 0);
+            acc[i][j] = mfma_16x16x32(fa[4 * h + i], fb[4 * h + j], acc[i][j]);
       __builtin_amdgcn_s_setprio(0);
     }
     SGL_PP_END_MFMA();
     // ---- R2: A1 (row tiles 4-7)
     if (active) {
 #pragma unroll
-      for (int f = 0; f < 8; ++f) fa[f] = *reinterpret_cast<const bf16x8*>(pa + (4 + (f & 3)) * 2048 + ((f >> 2) ? c1 : c0));
+      for (int f = 0; f < 8; ++f) fa[f] = *reinterpret_cast<const lo_x8<TIn>*>(pa + (4 + (f & 3)) * 2048 + ((f >> 2) ? c1 : c0));
     }
     issue(0, kt + 2); issue(1, kt + 2); issue(2, kt + 2);
     SGL_PP_END_READ8();
@@ -448,7 +445,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt6_kernel(const bf16* __restrict
         for (int i = 0; i < 4; ++i)
 #pragma unroll
           for (int j = 0; j < 4; ++j)
-            acc[4 + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[4 * h + i], fb[4 * h + j], acc[4 + i][j], 0, 0, 0);
+            acc[4 + i][j] = mfma_16x16x32(fa[4 * h + i], fb[4 * h + j], acc[4 + i][j]);
       __builtin_amdgcn_s_setprio(0);
     }
     SGL_PP_END_MFMA();
@@ -476,8 +473,9 @@ __global__ __launch_bounds__(512, 2) void gemm_nt6_kernel(const bf16* __restrict
 //     R1(t): k-half 0 fragments (8 A + 4 B, two transposed reads each) + DMA units U2(t+1), U3(t+1)
 //     M1(t): 32 MFMAs      R2(t): k-half 1 fragments + DMA units U0(t+2), U1(t+2)      M2(t): 32 MFMAs
 // units: U0 = A image rows 0-31, U1 = B rows 0-31, U2 = A rows 32-63, U3 = B rows 32-63 (16 KiB each).
-__global__ __launch_bounds__(512, 2) void gemm_tn6_kernel(const bf16* __restrict__ A, int lda,
-                                                          const bf16* __restrict__ B, int ldb, int Mred, int N1, int N2,
+template <typename TIn>
+__global__ __launch_bounds__(512, 2) void gemm_tn6_kernel(const TIn* __restrict__ A, int lda,
+                                                          const TIn* __restrict__ B, int ldb, int Mred, int N1, int N2,
                                                           int m_per_split, int nsplits, int tiles_1, int tiles_2,
                                                           EpiParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -545,8 +543,9 @@ __global__ __launch_bounds__(512, 2) void gemm_tn6_kernel(const bf16* __restrict
   SGL_PP_END_READ8();                // U0(0), U1(0) of every wave have landed
   if (grp == 1) SGL_PP_END_MFMA();   // G1 runs one slot behind G0 from here on
 
-#define SGL_TR6(ptr) __builtin_shufflevector(lds_tr16v2(ptr), lds_tr16v2((ptr) + 4 * 512), 0, 1, 2, 3, 4, 5, 6, 7)
-  bf16x8 fa[8], fb[4];
+#define SGL_TR6(ptr) \
+  __builtin_shufflevector(lds_read_tr16<TIn>(ptr), lds_read_tr16<TIn>((ptr) + 4 * 512), 0, 1, 2, 3, 4, 5, 6, 7)
+  lo_x8<TIn> fa[8], fb[4];
 #ifdef SGL_TIMELINE
   // per-phase cycle sums of this wave over the main loop: [0] issue fragment reads + DMA, [1] wait for them (lgkmcnt/vmcnt),
   // [2] barrier after the read slot, [3] 32 MFMAs, [4] barrier after the MFMA slot
@@ -585,7 +584,7 @@ __global__ __launch_bounds__(512, 2) void gemm_tn6_kernel(const bf16* __restrict
         for (int i = 0; i < 8; ++i)
 #pragma unroll
           for (int j = 0; j < 4; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
+            acc[i][j] = mfma_16x16x32(fa[i], fb[j], acc[i][j]);
         __builtin_amdgcn_s_setprio(0);
       }
 #ifdef SGL_TIMELINE
@@ -613,10 +612,10 @@ __global__ __launch_bounds__(512, 2) void gemm_tn6_kernel(const bf16* __restrict
 // ------------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------------
-template <int EPI, typename TOut>
-static hipError_t launch_nt256(const bf16* A, int lda, const bf16* B, int ldb, int M, int N, int K, const EpiParams& p,
+template <int EPI, typename TOut, typename TIn>
+static hipError_t launch_nt256(const TIn* A, int lda, const TIn* B, int ldb, int M, int N, int K, const EpiParams& p,
                                hipStream_t s) {
-  const hipError_t e = set_max_dynamic_lds_once<&gemm_nt6_kernel<EPI, TOut>>(T_LDS);
+  const hipError_t e = set_max_dynamic_lds_once<&gemm_nt6_kernel<EPI, TOut, TIn>>(T_LDS);
   if (e != hipSuccess) return e;
   const int tiles_m = (M + T_BM - 1) / T_BM, tiles_n = (N + T_BN - 1) / T_BN;
   // band height of the grouped tile order: 8 row-tiles for wide outputs, 4 when there are few column tiles (measured
@@ -634,7 +633,7 @@ static hipError_t launch_nt256(const bf16* A, int lda, const bf16* B, int ldb, i
   static const bool skip_epi = getenv("SGL_NT6_SKIP_EPI") != nullptr;
   if (skip_epi && EPI != EPI_F32) pp.atomic = 77;
 #endif
-  hipLaunchKernelGGL((gemm_nt6_kernel<EPI, TOut>), dim3(grid), dim3(512), T_LDS, s, A, lda, B, ldb, M, N, K, tiles_m,
+  hipLaunchKernelGGL((gemm_nt6_kernel<EPI, TOut, TIn>), dim3(grid), dim3(512), T_LDS, s, A, lda, B, ldb, M, N, K, tiles_m,
                      tiles_n, band_h, pp);
 #ifdef SGL_TIMELINE
   if (getenv("SGL_TIMELINE")) {   // synchronises: measurement builds only
@@ -651,21 +650,31 @@ static hipError_t launch_nt256(const bf16* A, int lda, const bf16* B, int ldb, i
   return hipGetLastError();
 }
 
-hipError_t gemm_nt256_bf16(const void* A, int lda, const void* B, int ldb, int M, int N, int K, int epi, int out_dtype,
-                           const EpiParams& p, hipStream_t s) {
-  return dispatch_epilogue(epi, out_dtype, [&](auto tag) {
+template <typename TIn>
+static hipError_t gemm_nt256(const void* A, int lda, const void* B, int ldb, int M, int N, int K, int epi, int out_dtype,
+                             const EpiParams& p, hipStream_t s) {
+  return dispatch_epilogue<TIn>(epi, out_dtype, [&](auto tag) {
     using T = decltype(tag);
-    return launch_nt256<T::epi, typename T::out>((const bf16*)A, lda, (const bf16*)B, ldb, M, N, K, p, s);
+    return launch_nt256<T::epi, typename T::out, TIn>((const TIn*)A, lda, (const TIn*)B, ldb, M, N, K, p, s);
   });
 }
+hipError_t gemm_nt256_bf16(const void* A, int lda, const void* B, int ldb, int M, int N, int K, int epi, int out_dtype,
+                           const EpiParams& p, hipStream_t s) {
+  return gemm_nt256<bf16>(A, lda, B, ldb, M, N, K, epi, out_dtype, p, s);
+}
+hipError_t gemm_nt256_f16(const void* A, int lda, const void* B, int ldb, int M, int N, int K, int epi, int out_dtype,
+                          const EpiParams& p, hipStream_t s) {
+  return gemm_nt256<f16>(A, lda, B, ldb, M, N, K, epi, out_dtype, p, s);
+}
 
-hipError_t gemm_tn256_bf16(const void* A, int lda, const void* B, int ldb, int Mred, int N1, int N2, int m_per,
-                           int splits, const EpiParams& p, hipStream_t s) {
-  const hipError_t e = set_max_dynamic_lds_once<&gemm_tn6_kernel>(T_LDS);
+template <typename TIn>
+static hipError_t gemm_tn256(const void* A, int lda, const void* B, int ldb, int Mred, int N1, int N2, int m_per,
+                             int splits, const EpiParams& p, hipStream_t s) {
+  const hipError_t e = set_max_dynamic_lds_once<&gemm_tn6_kernel<TIn>>(T_LDS);
   if (e != hipSuccess) return e;
   const int tiles_1 = (N1 + T_BM - 1) / T_BM, tiles_2 = (N2 + T_BN - 1) / T_BN;
   const int grid = ((tiles_1 * tiles_2 * splits + 7) / 8) * 8;
-  hipLaunchKernelGGL(gemm_tn6_kernel, dim3(grid), dim3(512), T_LDS, s, (const bf16*)A, lda, (const bf16*)B, ldb, Mred,
+  hipLaunchKernelGGL(gemm_tn6_kernel<TIn>, dim3(grid), dim3(512), T_LDS, s, (const TIn*)A, lda, (const TIn*)B, ldb, Mred,
                      N1, N2, m_per, splits, tiles_1, tiles_2, p);
 #ifdef SGL_TIMELINE
   if (getenv("SGL_TIMELINE")) {   // synchronises: measurement builds only
@@ -683,6 +692,15 @@ hipError_t gemm_tn256_bf16(const void* A, int lda, const void* B, int ldb, int M
   }
 #endif
   return hipGetLastError();
+}
+
+hipError_t gemm_tn256_bf16(const void* A, int lda, const void* B, int ldb, int Mred, int N1, int N2, int m_per,
+                           int splits, const EpiParams& p, hipStream_t s) {
+  return gemm_tn256<bf16>(A, lda, B, ldb, Mred, N1, N2, m_per, splits, p, s);
+}
+hipError_t gemm_tn256_f16(const void* A, int lda, const void* B, int ldb, int Mred, int N1, int N2, int m_per,
+                          int splits, const EpiParams& p, hipStream_t s) {
+  return gemm_tn256<f16>(A, lda, B, ldb, Mred, N1, N2, m_per, splits, p, s);
 }
 
 }  // namespace sgl

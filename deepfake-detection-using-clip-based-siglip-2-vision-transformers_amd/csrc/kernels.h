@@ -7,8 +7,13 @@
 
 namespace sgl {
 
-enum DType : int { DT_F32 = 0, DT_BF16 = 1, DT_F32_MFMA = 2 /* attention only: fp32 operands on v_mfma_f32_32x32x2_f32 */ };
-static inline size_t dtype_size(int dt) { return dt == DT_BF16 ? 2 : 4; }
+enum DType : int {
+  DT_F32 = 0,
+  DT_BF16 = 1,
+  DT_F32_MFMA = 2,   // attention only: fp32 operands on v_mfma_f32_32x32x2_f32
+  DT_F16 = 3,        // fp16 operands on the same MFMA kernels as bf16 (fp32 accumulation)
+};
+static inline size_t dtype_size(int dt) { return (dt == DT_BF16 || dt == DT_F16) ? 2 : 4; }
 
 // Raises Kernel's dynamic-LDS limit to `bytes` on the first call that succeeds (once per kernel instantiation).
 template <auto Kernel>
@@ -141,6 +146,11 @@ hipError_t reduce_splits(const float* ws, int splits, size_t stride, int N1, int
 // slabs and reduce_splits() sums them (bitwise reproducible); otherwise they add into `out` with fp32 atomics.
 hipError_t gemm_tn_bf16(const void* A, int lda, const void* B, int ldb, int Mred, int N1, int N2, int splits,
                         const EpiParams& p, hipStream_t s, float* split_ws = nullptr, size_t split_ws_bytes = 0);
+// fp16-operand forms of the two (DT_F16): same kernels, tiles and dispatch; 16-bit outputs are fp16 (out_dtype DT_F16)
+hipError_t gemm_nt_f16(const void* A, int lda, const void* B, int ldb, int M, int N, int K, int epi, int out_dtype,
+                       const EpiParams& p, hipStream_t s);
+hipError_t gemm_tn_f16(const void* A, int lda, const void* B, int ldb, int Mred, int N1, int N2, int splits,
+                       const EpiParams& p, hipStream_t s, float* split_ws = nullptr, size_t split_ws_bytes = 0);
 
 // ---- attention.hip -------------------------------------------------------------------------------------
 // q,k,v: ld_qkv > 0: token-major [B*N][ld_qkv] column blocks (head h of row r at r*ld_qkv + h*dh; the QKV projection's

@@ -104,6 +104,7 @@ hipError_t layernorm_fwd(const float* x, const float* gamma, const float* beta, 
   if (D % 4 || D > 64 * 4 * LN_MAXV_MAX || ldy % 4) return hipErrorInvalidValue;
   if (M == 0) return hipSuccess;
   if (y_dtype == DT_BF16) return ln_fwd_launch<bf16>(x, gamma, beta, (bf16*)y, ldy, mean, rstd, M, D, eps, s);
+  if (y_dtype == DT_F16) return ln_fwd_launch<f16>(x, gamma, beta, (f16*)y, ldy, mean, rstd, M, D, eps, s);
   return ln_fwd_launch<float>(x, gamma, beta, (float*)y, ldy, mean, rstd, M, D, eps, s);
 }
 
@@ -244,6 +245,8 @@ static hipError_t ln_bwd_launch(const void* dy, int lddy, const float* x, const 
                                 float* partial, int nblk, int M, int D, hipStream_t s) {
   if (lp_dtype == DT_BF16)
     return ln_bwd_launch2<TDy, bf16>(dy, lddy, x, mean, rstd, gamma, dres, dx, dx_lp, partial, nblk, M, D, s);
+  if (lp_dtype == DT_F16)
+    return ln_bwd_launch2<TDy, f16>(dy, lddy, x, mean, rstd, gamma, dres, dx, dx_lp, partial, nblk, M, D, s);
   return ln_bwd_launch2<TDy, float>(dy, lddy, x, mean, rstd, gamma, dres, dx, dx_lp, partial, nblk, M, D, s);
 }
 
@@ -254,6 +257,8 @@ hipError_t layernorm_bwd(const void* dy, int dy_dtype, int lddy, const float* x,
   if (M == 0) return hipSuccess;
   if (dy_dtype == DT_BF16)
     return ln_bwd_launch<bf16>(dy, lddy, x, mean, rstd, gamma, dres, dx, dx_lp, lp_dtype, partial, nblk, M, D, s);
+  if (dy_dtype == DT_F16)
+    return ln_bwd_launch<f16>(dy, lddy, x, mean, rstd, gamma, dres, dx, dx_lp, lp_dtype, partial, nblk, M, D, s);
   return ln_bwd_launch<float>(dy, lddy, x, mean, rstd, gamma, dres, dx, dx_lp, lp_dtype, partial, nblk, M, D, s);
 }
 

@@ -172,6 +172,7 @@ struct GroupHyper {
 template <typename T> __device__ __forceinline__ T cvt_out(float x);
 template <> __device__ __forceinline__ float cvt_out<float>(float x) { return x; }
 template <> __device__ __forceinline__ bf16 cvt_out<bf16>(float x) { return (bf16)x; }
+template <> __device__ __forceinline__ f16 cvt_out<f16>(float x) { return (f16)x; }
 
 template <typename T>
 __device__ __forceinline__ void adamw_tile(const sgl_adamw_tensor& t, const sgl_adamw_aux& a, int tile, float lr,
@@ -291,6 +292,8 @@ __global__ __launch_bounds__(256) void adamw_ex_kernel(const sgl_adamw_tensor* _
   if (a.dst || a.dst_t) {  // tiled matrix with shadow copies
     if (a.dtype == SGL_DTYPE_BF16)
       adamw_tile<bf16>(t, a, ch, lr, wd, gs, c, ema_decay, reinterpret_cast<bf16*>(lds_tile));
+    else if (a.dtype == SGL_DTYPE_F16)
+      adamw_tile<f16>(t, a, ch, lr, wd, gs, c, ema_decay, reinterpret_cast<f16*>(lds_tile));
     else
       adamw_tile<float>(t, a, ch, lr, wd, gs, c, ema_decay, lds_tile);
     return;

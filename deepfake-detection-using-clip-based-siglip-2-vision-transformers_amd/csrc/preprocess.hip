@@ -302,7 +302,7 @@ int sgl_op_preprocess(const void* src, int src_is_u8_nhwc, int B, int Hs, int Ws
   if (!src || !out) return SGL_ERR_NULL;
   if (B <= 0 || Hs <= 0 || Ws <= 0 || S <= 0 || std == 0.f) return SGL_ERR_BAD_SHAPE;
   if (patch_major && (P <= 0 || S < P || Kp < 3 * P * P)) return SGL_ERR_BAD_SHAPE;
-  if (out_dtype != SGL_DTYPE_BF16 && out_dtype != SGL_DTYPE_F32) return SGL_ERR_UNSUPPORTED;
+  if (out_dtype != SGL_DTYPE_BF16 && out_dtype != SGL_DTYPE_F16 && out_dtype != SGL_DTYPE_F32) return SGL_ERR_UNSUPPORTED;
   if ((float)Hs / (float)S > 16.f || (float)Ws / (float)S > 16.f) return SGL_ERR_UNSUPPORTED;  // tap loops stay short
   const int g = patch_major ? S / P : 0;
   const size_t total = patch_major ? (size_t)B * g * g * Kp : (size_t)B * 3 * S * S;
@@ -313,9 +313,13 @@ int sgl_op_preprocess(const void* src, int src_is_u8_nhwc, int B, int Hs, int Ws
   hipLaunchKernelGGL((sgl::preprocess_kernel<U8, T>), dim3(blocks), dim3(256), 0, s, src, (T*)out, B, Hs, Ws, S, P, Kp, \
                      patch_major, mean, inv_std, mix_index, lam)
   if (src_is_u8_nhwc) {
-    if (out_dtype == SGL_DTYPE_BF16) SGL_PP(true, sgl::bf16); else SGL_PP(true, float);
+    if (out_dtype == SGL_DTYPE_BF16) SGL_PP(true, sgl::bf16);
+    else if (out_dtype == SGL_DTYPE_F16) SGL_PP(true, sgl::f16);
+    else SGL_PP(true, float);
   } else {
-    if (out_dtype == SGL_DTYPE_BF16) SGL_PP(false, sgl::bf16); else SGL_PP(false, float);
+    if (out_dtype == SGL_DTYPE_BF16) SGL_PP(false, sgl::bf16);
+    else if (out_dtype == SGL_DTYPE_F16) SGL_PP(false, sgl::f16);
+    else SGL_PP(false, float);
   }
 #undef SGL_PP
   return hipGetLastError() == hipSuccess ? SGL_OK : SGL_ERR_HIP;
@@ -328,7 +332,7 @@ int sgl_op_preprocess_aug(const void* src, int src_is_u8_nhwc, int B, int Hs, in
   if (!src || !out || !aug || !grey_mean) return SGL_ERR_NULL;
   if (B <= 0 || Hs <= 0 || Ws <= 0 || S <= 0 || std == 0.f) return SGL_ERR_BAD_SHAPE;
   if (patch_major && (P <= 0 || S < P || Kp < 3 * P * P)) return SGL_ERR_BAD_SHAPE;
-  if (out_dtype != SGL_DTYPE_BF16 && out_dtype != SGL_DTYPE_F32) return SGL_ERR_UNSUPPORTED;
+  if (out_dtype != SGL_DTYPE_BF16 && out_dtype != SGL_DTYPE_F16 && out_dtype != SGL_DTYPE_F32) return SGL_ERR_UNSUPPORTED;
   if ((float)Hs / (float)S > 16.f || (float)Ws / (float)S > 16.f) return SGL_ERR_UNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
   const sgl::AugSample* tab = reinterpret_cast<const sgl::AugSample*>(aug);
@@ -350,9 +354,13 @@ int sgl_op_preprocess_aug(const void* src, int src_is_u8_nhwc, int B, int Hs, in
                        Kp, patch_major, mean, inv_std, tab, grey_mean);                                                 \
   } while (0)
   if (src_is_u8_nhwc) {
-    if (out_dtype == SGL_DTYPE_BF16) SGL_PA(true, sgl::bf16); else SGL_PA(true, float);
+    if (out_dtype == SGL_DTYPE_BF16) SGL_PA(true, sgl::bf16);
+    else if (out_dtype == SGL_DTYPE_F16) SGL_PA(true, sgl::f16);
+    else SGL_PA(true, float);
   } else {
-    if (out_dtype == SGL_DTYPE_BF16) SGL_PA(false, sgl::bf16); else SGL_PA(false, float);
+    if (out_dtype == SGL_DTYPE_BF16) SGL_PA(false, sgl::bf16);
+    else if (out_dtype == SGL_DTYPE_F16) SGL_PA(false, sgl::f16);
+    else SGL_PA(false, float);
   }
 #undef SGL_PA
   return hipGetLastError() == hipSuccess ? SGL_OK : SGL_ERR_HIP;

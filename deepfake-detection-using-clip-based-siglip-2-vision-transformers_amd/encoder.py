@@ -167,6 +167,12 @@ def _taper(order, max_chunks):
     return runs
 
 
+# compute_dtype -> sgl_config.compute_dtype, and the dtype of the patch-GEMM operand (``patches=``) each mode reads
+COMPUTE_DTYPES = {"bf16": _lib.SGL_DTYPE_BF16, "fp32": _lib.SGL_DTYPE_F32, "bf16x3": _lib.SGL_DTYPE_BF16X3,
+                  "fp16": _lib.SGL_DTYPE_F16}
+OPERAND_DTYPE = {"bf16": torch.bfloat16, "fp32": torch.float32, "bf16x3": torch.float32, "fp16": torch.float16}
+
+
 @torch.library.custom_op("siglip_hip::encoder_fwd", mutates_args=())
 def encoder_fwd(pixel_values: torch.Tensor, params: Sequence[torch.Tensor], handle: int, train: bool, interp: bool,
                 want_pooled: bool, tap_ids: Sequence[int], first_trainable: int, layout: int, img_h: int,
@@ -181,7 +187,7 @@ def encoder_fwd(pixel_values: torch.Tensor, params: Sequence[torch.Tensor], hand
     px = pixel_values
     channels_last = 0
     if layout == 2:
-        want = torch.bfloat16 if mod.compute_dtype == "bf16" else torch.float32
+        want = OPERAND_DTYPE[mod.compute_dtype]
         if px.dtype != want or not px.is_contiguous():
             raise ValueError(f"patch operand must be contiguous {want} (the encoder's compute dtype)")
         channels_last = 2
@@ -428,9 +434,11 @@ class SiglipVisionModelHIP(nn.Module):
         # "bf16": the benchmarked mode (bf16 MFMA operands, fp32 accumulate / residual stream / statistics);
         # "fp32": strict reference arithmetic (plain fp32 FMAs, no matrix cores): tightest parity, slow;
         # "bf16x3": strict mode on the matrix cores (every GEMM as one bf16 MFMA GEMM over hi/lo-split operands, fp32
-        #           accumulate; ~2^-17 relative per product): the north-star "logits within 1e-3" at MFMA speed
-        if compute_dtype not in ("bf16", "fp32", "bf16x3"):
-            raise ValueError("compute_dtype must be 'bf16', 'fp32' or 'bf16x3'")
+        #           accumulate; ~2^-17 relative per product): the north-star "logits within 1e-3" at MFMA speed;
+        # "fp16": "bf16" with fp16 operands and weight shadows (fp16 MFMA, same kernels and speed, 3 more mantissa bits):
+        #         the arithmetic of a torch.autocast(float16) run; operand overflow gives inf (GradScaler sees it)
+        if compute_dtype not in COMPUTE_DTYPES:
+            raise ValueError("compute_dtype must be 'bf16', 'fp32', 'bf16x3' or 'fp16'")
         self.compute_dtype = compute_dtype
         cfg = self.config
         self.embeddings = _EmbeddingParams(cfg)
@@ -698,8 +706,7 @@ class SiglipVisionModelHIP(nn.Module):
             cfg = self.config
             c = _lib.SglConfig(cfg.hidden_size, cfg.intermediate_size, cfg.num_hidden_layers, cfg.num_attention_heads,
                                cfg.patch_size, cfg.native_grid, cfg.layer_norm_eps,
-                               {"bf16": _lib.SGL_DTYPE_BF16, "fp32": _lib.SGL_DTYPE_F32,
-                                "bf16x3": _lib.SGL_DTYPE_BF16X3}[self.compute_dtype],
+                               COMPUTE_DTYPES[self.compute_dtype],
                                1 if self.use_head else 0)
             ctx = lib.sgl_create(C.byref(c))
             if not ctx:
@@ -725,7 +732,7 @@ class SiglipVisionModelHIP(nn.Module):
             strided_ok = field == "patch_w" and p.dim() == 4 and p.is_contiguous(memory_format=torch.channels_last)
             if p.dtype != torch.float32 or not (p.is_contiguous() or strided_ok):
                 raise RuntimeError("encoder master parameters must be contiguous fp32 (the HIP path keeps its own "
-                                   "bf16 shadows); do not call .half()/.bfloat16() on the encoder")
+                                   "16-bit shadows); do not call .half()/.bfloat16() on the encoder")
         layers = (_lib.SglLayerPtrs * max(L, 1))()
         w = _lib.SglWeights()
         w.layers = C.cast(layers, C.POINTER(_lib.SglLayerPtrs))

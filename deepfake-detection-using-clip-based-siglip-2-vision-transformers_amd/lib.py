@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SGL_LIB_PATH") or os.path.join(_HERE, "libsiglip_hip.so")  # override: developer builds (make TIMELINE=1)
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "siglip_hip.h")
 
-SGL_DTYPE_F32, SGL_DTYPE_BF16, SGL_DTYPE_BF16X3 = 0, 1, 2
+SGL_DTYPE_F32, SGL_DTYPE_BF16, SGL_DTYPE_BF16X3, SGL_DTYPE_F16 = 0, 1, 2, 3
 EPI_STORE, EPI_BIAS_GELU, EPI_RES_F32, EPI_QKV, EPI_GELU_BWD, EPI_POS_F32, EPI_F32 = range(7)
 STATUS = {0: "ok", -1: "bad shape", -2: "unsupported configuration", -3: "buffer too small", -4: "HIP error",
           -5: "null pointer"}

@@ -31,8 +31,8 @@ class FusedAdamW(torch.optim.Optimizer):
 
     In the same pass over each parameter the kernel can also write what the update invalidates (kernel work-list k11):
 
-    * ``attach_encoder(enc)``: the bf16 (or strict-fp32) weight shadows of a ``SiglipVisionModelHIP`` and their
-      transposes, so the next forward does no re-cast (the reference's autocast casts every weight every step,
+    * ``attach_encoder(enc)``: the weight shadows of a ``SiglipVisionModelHIP`` (bf16 / fp16 / strict-fp32: the encoder's
+      compute dtype) and their transposes, so the next forward does no re-cast (the reference's autocast casts every weight every step,
       Siglip2sidafrozen.py:1375);
     * ``attach_ema(ema)``: ``ExponentialMovingAverage.update()`` (cifake_binary_classifier.py:222-225);
     * ``grad_scale``: gradients are rank SUMS and this is 1/world (``GradBucketReducer(average="defer")``): folded into

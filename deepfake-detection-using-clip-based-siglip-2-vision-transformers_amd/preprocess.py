@@ -57,6 +57,20 @@ def _mix(mix_index, B, dev):
     return idx
 
 
+_DTYPE_CODES = {torch.float32: _lib.SGL_DTYPE_F32, torch.bfloat16: _lib.SGL_DTYPE_BF16, torch.float16: _lib.SGL_DTYPE_F16}
+
+
+def _dtype_code(dtype: torch.dtype) -> int:
+    if dtype not in _DTYPE_CODES:
+        raise ValueError(f"output dtype must be float32, bfloat16 or float16, not {dtype}")
+    return _DTYPE_CODES[dtype]
+
+
+def _operand_dtype(compute_dtype: str) -> torch.dtype:
+    """dtype of the patch-GEMM operand of an encoder in ``compute_dtype`` (strict modes read fp32)."""
+    return {"bf16": torch.bfloat16, "fp16": torch.float16}.get(compute_dtype, torch.float32)
+
+
 def resize_normalize(images: torch.Tensor, size: int, mean: float = 0.5, std: float = 0.5,
                      mix_index: Optional[torch.Tensor] = None, lam: float = 1.0,
                      dtype: torch.dtype = torch.float32) -> torch.Tensor:
@@ -65,7 +79,7 @@ def resize_normalize(images: torch.Tensor, size: int, mean: float = 0.5, std: fl
     lib = _lib.load()
     src, is_u8, B, Hs, Ws = _source(images)
     out = torch.empty((B, 3, size, size), device=src.device, dtype=dtype)
-    code = _lib.SGL_DTYPE_BF16 if dtype == torch.bfloat16 else _lib.SGL_DTYPE_F32
+    code = _dtype_code(dtype)
     idx = _mix(mix_index, B, src.device)
     with torch.cuda.device(src.device):
         _lib.check(lib.sgl_op_preprocess(src.data_ptr(), is_u8, B, Hs, Ws, out.data_ptr(), code, size, 1, 3, 0, float(mean),
@@ -86,9 +100,9 @@ def to_patch_operand(images: torch.Tensor, config, size: Optional[int] = None, c
     g = S // P
     Kp = (3 * P * P + 63) // 64 * 64
     src, is_u8, B, Hs, Ws = _source(images)
-    dt = torch.bfloat16 if compute_dtype == "bf16" else torch.float32
+    dt = _operand_dtype(compute_dtype)
     out = torch.empty((B * g * g, Kp), device=src.device, dtype=dt)
-    code = _lib.SGL_DTYPE_BF16 if dt == torch.bfloat16 else _lib.SGL_DTYPE_F32
+    code = _dtype_code(dt)
     idx = _mix(mix_index, B, src.device)
     with torch.cuda.device(src.device):
         _lib.check(lib.sgl_op_preprocess(src.data_ptr(), is_u8, B, Hs, Ws, out.data_ptr(), code, S, P, Kp, 1, float(mean),
@@ -144,7 +158,7 @@ def augment_resize_normalize(images: torch.Tensor, size: int, params: list, mean
     if len(params) != B:
         raise ValueError("one augmentation record per image")
     out = torch.empty((B, 3, size, size), device=src.device, dtype=dtype)
-    code = _lib.SGL_DTYPE_BF16 if dtype == torch.bfloat16 else _lib.SGL_DTYPE_F32
+    code = _dtype_code(dtype)
     tab = augment_table(params, src.device)
     gm = torch.empty(B, device=src.device, dtype=torch.float32)
     with torch.cuda.device(src.device):
@@ -166,9 +180,9 @@ def augment_to_patch_operand(images: torch.Tensor, config, params: list, size: O
     src, is_u8, B, Hs, Ws = _source(images)
     if len(params) != B:
         raise ValueError("one augmentation record per image")
-    dt = torch.bfloat16 if compute_dtype == "bf16" else torch.float32
+    dt = _operand_dtype(compute_dtype)
     out = torch.empty((B * g * g, Kp), device=src.device, dtype=dt)
-    code = _lib.SGL_DTYPE_BF16 if dt == torch.bfloat16 else _lib.SGL_DTYPE_F32
+    code = _dtype_code(dt)
     tab = augment_table(params, src.device)
     gm = torch.empty(B, device=src.device, dtype=torch.float32)
     with torch.cuda.device(src.device):

@@ -29,7 +29,7 @@ extern "C" {
 typedef struct sgl_ctx sgl_ctx;
 typedef void* sgl_stream; /* hipStream_t */
 
-enum { SGL_DTYPE_F32 = 0, SGL_DTYPE_BF16 = 1, SGL_DTYPE_BF16X3 = 2 };
+enum { SGL_DTYPE_F32 = 0, SGL_DTYPE_BF16 = 1, SGL_DTYPE_BF16X3 = 2, SGL_DTYPE_F16 = 3 };
 
 typedef enum {
   SGL_OK = 0,
@@ -54,7 +54,10 @@ typedef struct {
                              SGL_DTYPE_BF16X3: strict mode ON the matrix cores: activations, weights and buffers exactly as
                                 in SGL_DTYPE_F32, but every GEMM runs as one bf16 MFMA GEMM over split operands
                                 (x = hi + lo; hi*hi + hi*lo + lo*hi, fp32 accumulate: ~2^-17 relative per product) and
-                                attention as fp32 MFMA; meets "logits within 1e-3" at a fraction of SGL_DTYPE_F32's cost */
+                                attention as fp32 MFMA; meets "logits within 1e-3" at a fraction of SGL_DTYPE_F32's cost;
+                             SGL_DTYPE_F16 : SGL_DTYPE_BF16 with fp16 operands (fp16 MFMA, fp32 accumulate / residual stream /
+                                statistics / softmax, fp16 weight shadows): the arithmetic of an fp16-autocast run, 3 more
+                                mantissa bits than bf16 at the same MFMA rate; overflow of an fp16 operand gives +-inf */
   int use_head;           /* attention-pool head present (vision_use_head) */
 } sgl_config;
 
@@ -191,7 +194,8 @@ int sgl_op_layernorm_bwd(const void* dy, int dy_dtype, const float* x, const flo
 /* epilogue selectors for sgl_op_gemm_nt */
 enum { SGL_EPI_STORE = 0, SGL_EPI_BIAS_GELU = 1, SGL_EPI_RES_F32 = 2, SGL_EPI_QKV = 3, SGL_EPI_GELU_BWD = 4,
        SGL_EPI_POS_F32 = 5, SGL_EPI_F32 = 6 };
-/* C[M,N] = A[M,K] * B[N,K]^T with a fused epilogue; dtype is the operand dtype (bf16 -> MFMA kernel). */
+/* C[M,N] = A[M,K] * B[N,K]^T with a fused epilogue; dtype is the operand dtype (bf16 / fp16 -> MFMA kernel; the 16-bit
+ * outputs of EPI_STORE / BIAS_GELU / QKV / GELU_BWD are in the operand dtype). */
 int sgl_op_gemm_nt(int dtype, const void* A, int lda, const void* B, int ldb, int M, int N, int K, int epi, void* out,
                    int ldo, void* out2, int ldo2, const float* bias, const float* res, int ldr, const void* aux,
                    int ldaux, const float* pos, int pos_rows, int tokens, int heads, int head_dim, int head_dim_pad,
@@ -205,7 +209,8 @@ int sgl_op_gemm_tn_ws(int dtype, const void* A, int lda, const void* B, int ldb,
                       float* out, int ldo, int accumulate, float* scratch, size_t scratch_bytes, sgl_stream stream);
 /* Scaled-dot-product attention of one block (TF:modeling_siglip.py:227-247,288-301), all heads and images in one launch.
  * dtype: SGL_DTYPE_BF16 (bf16 operands, bf16 MFMA, fp32 softmax), SGL_DTYPE_F32 (fp32 operands, plain FMAs: the reference
- *   kernels) or SGL_DTYPE_BF16X3 (fp32 operands on v_mfma_f32_32x32x2_f32: what the strict MFMA mode uses).
+ *   kernels), SGL_DTYPE_BF16X3 (fp32 operands on v_mfma_f32_32x32x2_f32: what the strict MFMA mode uses) or
+ *   SGL_DTYPE_F16 (the bf16 kernels on fp16 operands, fp16 MFMA, fp32 softmax).
  * ld_qkv > 0 (what the encoder uses since ABI 3): q, k, v point at the three column blocks of the QKV projection's
  *   token-major output [B*N][ld_qkv]; head h of token row r is the head_dim elements at r*ld_qkv + h*head_dim (16-byte
  *   aligned: head_dim % 8 == 0, ld_qkv % 8 == 0, pointers 16-byte aligned).  Nothing is padded in memory.
