@@ -4,7 +4,9 @@
 //   27x block    TF:...:335-356   x += out_proj(attn(qkv(LN1 x)));  x += fc2(gelu_tanh(fc1(LN2 x)))
 //   post LN      TF:...:612        pooling head  TF:...:633-643
 // The residual stream, LayerNorm statistics and softmax run in fp32 in every compute mode; GEMM / attention
-// operands are bf16 or fp16 (MFMA) or fp32 (strict).  The ctx owns no device memory: every buffer is the caller's.
+// operands are bf16 or fp16 (MFMA) or fp32 (strict); the MX-fp8 inference mode (SGL_DTYPE_MXFP8) is the bf16 mode with the
+// four projection GEMMs of every block on MX-fp8 operands (mx.hip).  The ctx owns no device memory: every buffer is the
+// caller's.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -34,6 +36,7 @@ struct Bump {
 
 struct ShadowLayer {
   size_t wqkv, wqkv_t, wo, wo_t, w1, w1_t, w2, w2_t, bqkv, b1;
+  size_t wqkv_s, wo_s, w1_s, w2_s;   // MX mode: E8M0 scales of the MX matrices at wqkv / wo / w1 / w2 (no transposes)
 };
 
 }  // namespace
@@ -43,6 +46,8 @@ struct sgl_ctx {
   int D, I, Ip, L, H, dh, DP, P, K0, Kp, g0, dt;
   size_t es;  // element size of the compute dtype
   int split = 0;   // SGL_DTYPE_BF16X3: dt == DT_F32 everywhere, GEMMs through the bf16x3 operand split
+  int mx = 0;      // SGL_DTYPE_MXFP8: dt == DT_BF16 everywhere except the block GEMMs, which read MX-fp8 operands
+  int Dp = 0;      // MX mode: K padding of the D-wide operands, round_up(D, 128) (the MX GEMM's K-step)
   // scratch for the split operands of the GEMM being launched: set by every entry point from the CALLER's buffers (the ctx
   // owns no memory); calls on one ctx are stream-ordered (siglip_hip.h), so one pair per ctx suffices
   void* sp_a = nullptr;
@@ -70,7 +75,7 @@ struct Layout {
   // activation region ("saved" when training, a slice of ws otherwise)
   size_t a_im2col, a_pos;
   size_t a_layer0, a_layer_stride;
-  size_t r_stats1, r_h1, r_qkv, r_attn, r_lse, r_xmid, r_stats2, r_h2, r_u, r_a;  // relative to a layer base
+  size_t r_stats1, r_h1, r_qkv, r_attn, r_lse, r_xmid, r_stats2, r_h2, r_u, r_a, r_attq;  // relative to a layer base
   size_t a_pstats, a_lastlp, a_kvh, a_qp, a_probs, a_ao, a_h0, a_hstats, a_hl, a_hu, a_ha;
   size_t a_spa = 0, a_spb = 0, w_spa = 0, w_spb = 0;   // bf16x3 split operands (forward: in act; backward: in ws)
   size_t act_total;
@@ -92,16 +97,21 @@ struct Layout {
     a_im2col = a.take(Mz * c->Kp * es);
     a_pos = a.take((size_t)N * D * 4);
     Bump r;
+    // MX mode (inference only): r_h1 / r_h2 / r_a hold MX operands (bytes, then their scales), r_attq the quantized
+    // attention output; r_u is never written
+    const size_t Dp = c->Dp;
+    const bool mx = c->mx;
     r_stats1 = r.take(Mz * 2 * 4);
-    r_h1 = r.take(Mz * D * es);
+    r_h1 = r.take(mx ? Mz * Dp + Mz * Dp / 32 : Mz * D * es);
     r_qkv = r.take((size_t)3 * B * c->H * N * c->DP * es);
     r_attn = r.take(Mz * D * es);
     r_lse = r.take((size_t)B * c->H * N * 4);
     r_xmid = r.take(Mz * D * 4);
     r_stats2 = r.take(Mz * 2 * 4);
-    r_h2 = r.take(Mz * D * es);
-    r_u = r.take(Mz * Ip * es);
-    r_a = r.take(Mz * Ip * es);
+    r_h2 = r.take(mx ? Mz * Dp + Mz * Dp / 32 : Mz * D * es);
+    r_u = r.take(mx ? 0 : Mz * Ip * es);
+    r_a = r.take(mx ? Mz * Ip + Mz * Ip / 32 : Mz * Ip * es);
+    r_attq = r.take(mx ? Mz * Dp + Mz * Dp / 32 : 0);
     a_layer_stride = train ? r.off : 0;
     a_layer0 = a.take(train ? r.off * (size_t)c->L : r.off);
     a_pstats = a.take(Mz * 2 * 4);
@@ -233,6 +243,75 @@ hipError_t gemm_tn(const sgl_ctx* c, const void* A, int lda, const void* B, int 
   return gemm_f32_generic((const float*)A, 1, lda, (const float*)B, 1, ldb, N1, N2, Mred, EPI_F32, DT_F32, p, s);
 }
 
+#define RET(expr)                 \
+  do {                            \
+    int r_ = (expr);              \
+    if (r_ != SGL_OK) return r_;  \
+  } while (0)
+
+// One encoder block of the MX-fp8 mode: x -> xo through xmid, with the four projection GEMMs on MX operands.
+//   LN1 -> MX (r_h1) ; QKV GEMM -> bf16 head-major (r_qkv) ; bf16 attention -> r_attn ; quantize -> MX (r_attq) ;
+//   out_proj + bias + x -> xmid ; LN2 -> MX (r_h2) ; fc1 + bias, GELU, quantized in the epilogue -> MX (r_a) ;
+//   fc2 + bias + xmid -> xo
+int mx_block(sgl_ctx* ctx, const Layout& lay, const sgl_layer_weights& lw, const ShadowLayer& sl, const void* shadow,
+             char* lb, const float* x, float* xo, float* xmid, int B, hipStream_t s) {
+  const int D = ctx->D, Ip = ctx->Ip, Dp = ctx->Dp, M = lay.M, N = lay.N, Hh = ctx->H, dh = ctx->dh, DP = ctx->DP;
+  const float eps = ctx->cfg.layer_norm_eps;
+  const size_t Mz = (size_t)M;
+  char* h1 = lb + lay.r_h1;
+  char* aq = lb + lay.r_attq;
+  char* h2 = lb + lay.r_h2;
+  char* ua = lb + lay.r_a;
+  CK(layernorm_fwd_mx(x, lw.ln1_w, lw.ln1_b, h1, h1 + Mz * Dp, M, D, Dp, eps, s));
+  {
+    EpiParams p;
+    p.out = lb + lay.r_qkv;
+    p.bias = reinterpret_cast<const float*>(at(shadow, sl.bqkv));
+    p.tokens = N;
+    p.heads = Hh;
+    p.head_dim = dh;
+    p.head_dim_pad = DP;
+    p.batch = B;
+    CK(gemm_nt_mx(h1, h1 + Mz * Dp, at(shadow, sl.wqkv), at(shadow, sl.wqkv_s), M, 3 * D, Dp, EPI_QKV, p, nullptr, s));
+  }
+  {
+    const size_t hsz = (size_t)B * Hh * N * DP * ctx->es;
+    char* q = lb + lay.r_qkv;
+    CK(attn_fwd(q, q + hsz, q + 2 * hsz, DT_BF16, lb + lay.r_attn, reinterpret_cast<float*>(lb + lay.r_lse), B, Hh, N, dh,
+                DP, 0, s));
+  }
+  // a 32-block of the attention output straddles heads when head_dim = 72: a pass of its own, not an attention epilogue
+  CK(quantize_mx(lb + lay.r_attn, DT_BF16, D, M, D, Dp, aq, aq + Mz * Dp, s));
+  {
+    EpiParams p;
+    p.out = xmid;
+    p.ldo = D;
+    p.bias = lw.o_b;
+    p.res = x;
+    p.ldr = D;
+    CK(gemm_nt_mx(aq, aq + Mz * Dp, at(shadow, sl.wo), at(shadow, sl.wo_s), M, D, Dp, EPI_RES_F32, p, nullptr, s));
+  }
+  CK(layernorm_fwd_mx(xmid, lw.ln2_w, lw.ln2_b, h2, h2 + Mz * Dp, M, D, Dp, eps, s));
+  {
+    EpiParams p;
+    p.out = ua;
+    p.ldo = Ip;
+    p.bias = reinterpret_cast<const float*>(at(shadow, sl.b1));
+    CK(gemm_nt_mx(h2, h2 + Mz * Dp, at(shadow, sl.w1), at(shadow, sl.w1_s), M, Ip, Dp, EPI_BIAS_GELU, p,
+                  ua + Mz * Ip, s));
+  }
+  {
+    EpiParams p;
+    p.out = xo;
+    p.ldo = D;
+    p.bias = lw.fc2_b;
+    p.res = xmid;
+    p.ldr = D;
+    CK(gemm_nt_mx(ua, ua + Mz * Ip, at(shadow, sl.w2), at(shadow, sl.w2_s), M, D, Ip, EPI_RES_F32, p, nullptr, s));
+  }
+  return SGL_OK;
+}
+
 bool shape_ok(const sgl_ctx* c, int B, int H, int W) {
   if (B <= 0 || H <= 0 || W <= 0) return false;
   if (H < c->P || W < c->P) return false;  // 'valid' conv: trailing pixels beyond gh*P are ignored
@@ -269,7 +348,8 @@ sgl_ctx* sgl_create(const sgl_config* cfg) {
       cfg->native_grid <= 0)
     return nullptr;
   if (cfg->compute_dtype != SGL_DTYPE_F32 && cfg->compute_dtype != SGL_DTYPE_BF16 &&
-      cfg->compute_dtype != SGL_DTYPE_BF16X3 && cfg->compute_dtype != SGL_DTYPE_F16)
+      cfg->compute_dtype != SGL_DTYPE_BF16X3 && cfg->compute_dtype != SGL_DTYPE_F16 &&
+      cfg->compute_dtype != SGL_DTYPE_MXFP8)
     return nullptr;
   sgl_ctx* c = new (std::nothrow) sgl_ctx();
   if (!c) return nullptr;
@@ -286,14 +366,30 @@ sgl_ctx* sgl_create(const sgl_config* cfg) {
   c->Kp = round_up(c->K0, 64);
   c->g0 = cfg->native_grid;
   c->split = cfg->compute_dtype == SGL_DTYPE_BF16X3;
-  c->dt = c->split ? DT_F32 : cfg->compute_dtype == SGL_DTYPE_F16 ? DT_F16 : cfg->compute_dtype;
+  c->mx = cfg->compute_dtype == SGL_DTYPE_MXFP8;
+  c->dt = c->split ? DT_F32 : cfg->compute_dtype == SGL_DTYPE_F16 ? DT_F16 : c->mx ? DT_BF16 : cfg->compute_dtype;
   c->es = dtype_size(c->dt);
-  const size_t es = c->es, D = c->D, Ip = c->Ip;
+  c->Dp = round_up(c->D, 128);
+  const size_t es = c->es, D = c->D, Ip = c->Ip, Dp = c->Dp;
   Bump b;
   c->sh_wpatch = b.take(D * c->Kp * es);
   c->sh_layers.resize(c->L);
   for (int l = 0; l < c->L; ++l) {
     ShadowLayer& s = c->sh_layers[l];
+    if (c->mx) {   // row-major MX blocks only (no backward, so no transposes); fp32 biases as in the other modes
+      s = ShadowLayer{};
+      s.wqkv = b.take(3 * D * Dp);
+      s.wqkv_s = b.take(3 * D * Dp / 32);
+      s.wo = b.take(D * Dp);
+      s.wo_s = b.take(D * Dp / 32);
+      s.w1 = b.take(Ip * Dp);
+      s.w1_s = b.take(Ip * Dp / 32);
+      s.w2 = b.take(D * Ip);
+      s.w2_s = b.take(D * Ip / 32);
+      s.bqkv = b.take(3 * D * 4);
+      s.b1 = b.take(Ip * 4);
+      continue;
+    }
     s.wqkv = b.take(3 * D * D * es);
     s.wqkv_t = b.take(3 * D * D * es);
     s.wo = b.take(D * D * es);
@@ -328,6 +424,7 @@ int sgl_query_sizes(const sgl_ctx* ctx, int B, int H, int W, int train, size_t* 
                     size_t* ws_bytes) {
   if (!ctx) return SGL_ERR_NULL;
   if (!shape_ok(ctx, B, H, W)) return SGL_ERR_BAD_SHAPE;
+  if (ctx->mx && train) return SGL_ERR_UNSUPPORTED;   // the MX-fp8 mode has no backward
   Layout lay(ctx, B, H, W, train != 0);
   if (shadow_bytes) *shadow_bytes = ctx->sh_total;
   if (saved_bytes) *saved_bytes = lay.saved_total;
@@ -353,6 +450,25 @@ int sgl_prepare_weights_dirty(sgl_ctx* ctx, const sgl_weights* w, void* shadow, 
     const ShadowLayer& sl = ctx->sh_layers[l];
     const float* qkv_w[3] = {lw.q_w, lw.k_w, lw.v_w};
     const float* qkv_b[3] = {lw.q_b, lw.k_b, lw.v_b};
+    if (ctx->mx) {   // each weight row quantized along its input dim, exactly as the activations are
+      const size_t Dp = ctx->Dp;
+      for (int j = 0; j < 3; ++j)
+        CK(quantize_mx(qkv_w[j], DT_F32, D, D, D, (int)Dp, at(shadow, sl.wqkv + (size_t)j * D * Dp),
+                       at(shadow, sl.wqkv_s + (size_t)j * D * Dp / 32), s));
+      CK(quantize_mx(lw.o_w, DT_F32, D, D, D, (int)Dp, at(shadow, sl.wo), at(shadow, sl.wo_s), s));
+      CK(quantize_mx(lw.fc1_w, DT_F32, D, I, D, (int)Dp, at(shadow, sl.w1), at(shadow, sl.w1_s), s));
+      if (Ip > I) {   // fc1 rows I..Ip: zero bytes and zero scales (their GELU outputs are the zero K-padding of fc2)
+        CK(hipMemsetAsync(at(shadow, sl.w1 + (size_t)I * Dp), 0, (size_t)(Ip - I) * Dp, s));
+        CK(hipMemsetAsync(at(shadow, sl.w1_s + (size_t)I * Dp / 32), 0, (size_t)(Ip - I) * Dp / 32, s));
+      }
+      CK(quantize_mx(lw.fc2_w, DT_F32, I, D, I, Ip, at(shadow, sl.w2), at(shadow, sl.w2_s), s));
+      CastJob job;
+      for (int j = 0; j < 3; ++j)
+        cast_job_add_vec(job, qkv_b[j], D, reinterpret_cast<float*>(at(shadow, sl.bqkv)) + (size_t)j * D, D);
+      cast_job_add_vec(job, lw.fc1_b, I, reinterpret_cast<float*>(at(shadow, sl.b1)), Ip);
+      CK(cast_job_run(job, dt, s));
+      continue;
+    }
     // one launch per block (elementwise.hip, cast_job_kernel): every matrix read once, written row-major and transposed
     CastJob job;
     for (int j = 0; j < 3; ++j) {
@@ -389,6 +505,7 @@ int sgl_prepare_weights(sgl_ctx* ctx, const sgl_weights* w, void* shadow, size_t
 int sgl_adamw_bind_shadows(const sgl_ctx* ctx, const sgl_weights* w, void* shadow, const sgl_adamw_tensor* table,
                            sgl_adamw_aux* aux, int ntensors) {
   if (!ctx || !w || !shadow || !table || !aux) return SGL_ERR_NULL;
+  if (ctx->mx) return 0;   // MX shadows are re-quantized by sgl_prepare_weights_dirty (the mode does not train)
   const int D = ctx->D, I = ctx->I, Ip = ctx->Ip;
   const size_t es = ctx->es;
   int bound = 0;
@@ -481,6 +598,7 @@ int sgl_forward_slots(sgl_ctx* ctx, const sgl_weights* w, const void* shadow, co
   for (int l = 0; l <= ctx->L; ++l)
     if (!hs_slots[l]) return SGL_ERR_NULL;
   const bool train = saved != nullptr;
+  if (train && ctx->mx) return SGL_ERR_UNSUPPORTED;   // the MX-fp8 mode has no backward
   if (train)   // backward reads every hidden state: the slots must be distinct buffers
     for (int l = 0; l < ctx->L; ++l)
       for (int k = l + 1; k <= ctx->L; ++k)
@@ -531,6 +649,10 @@ int sgl_forward_slots(sgl_ctx* ctx, const sgl_weights* w, const void* shadow, co
     float* st1 = reinterpret_cast<float*>(lb + lay.r_stats1);
     float* st2 = reinterpret_cast<float*>(lb + lay.r_stats2);
     float* xmid = reinterpret_cast<float*>(lb + lay.r_xmid);
+    if (ctx->mx) {
+      RET(mx_block(ctx, lay, lw, sl, shadow, lb, x, xo, xmid, B, s));
+      continue;
+    }
     CK(layernorm_fwd(x, lw.ln1_w, lw.ln1_b, lb + lay.r_h1, dt, D, st1, st1 + M, M, D, ctx->cfg.layer_norm_eps, s));
     {
       // head-major scatter [3][B][H][N][DP] in the GEMM epilogue (EPI_QKV).  Round 3 measured the alternative the kernels
@@ -673,14 +795,9 @@ int ln_backward(sgl_ctx* ctx, const Layout& lay, void* ws, const void* dy, int d
   return SGL_OK;
 }
 
-#define RET(expr)                 \
-  do {                            \
-    int r_ = (expr);              \
-    if (r_ != SGL_OK) return r_;  \
-  } while (0)
-
 int check_bwd_args(const sgl_ctx* ctx, const Layout& lay, const void* saved, size_t saved_bytes, void* ws,
                    size_t ws_bytes) {
+  if (ctx->mx) return SGL_ERR_UNSUPPORTED;
   if (!saved || !ws) return SGL_ERR_NULL;
   if (saved_bytes < lay.saved_total || ws_bytes < lay.ws_total) return SGL_ERR_WORKSPACE;
   return SGL_OK;
@@ -1013,6 +1130,32 @@ int sgl_backward(sgl_ctx* ctx, const sgl_weights* w, const void* shadow, const s
 int sgl_op_layernorm_fwd(const float* x, const float* gamma, const float* beta, void* y, int y_dtype, float* mean,
                          float* rstd, int M, int D, float eps, sgl_stream stream) {
   CKV(layernorm_fwd(x, gamma, beta, y, y_dtype, D, mean, rstd, M, D, eps, (hipStream_t)stream));
+  return SGL_OK;
+}
+
+int sgl_op_quantize_mxfp8(const void* x, int x_dtype, int ldx, int M, int K, int Kp, void* q, void* scales,
+                          sgl_stream stream) {
+  if (!x || !q || !scales) return SGL_ERR_NULL;
+  CKV(quantize_mx(x, x_dtype, ldx, M, K, Kp, q, scales, (hipStream_t)stream));
+  return SGL_OK;
+}
+
+int sgl_op_layernorm_fwd_mx(const float* x, const float* gamma, const float* beta, void* q, void* scales, int M, int D,
+                            int Kp, float eps, sgl_stream stream) {
+  if (!x || !gamma || !beta || !q || !scales) return SGL_ERR_NULL;
+  CKV(layernorm_fwd_mx(x, gamma, beta, q, scales, M, D, Kp, eps, (hipStream_t)stream));
+  return SGL_OK;
+}
+
+int sgl_op_gemm_nt_mx(const void* A, const void* As, const void* B, const void* Bs, int M, int N, int Kp, int epi,
+                      void* out, int ldo, void* out_scales, const float* bias, const float* res, int ldr, int tokens,
+                      int heads, int head_dim, int head_dim_pad, int batch, sgl_stream stream) {
+  if (!A || !As || !B || !Bs || !out || !bias) return SGL_ERR_NULL;
+  EpiParams p;
+  p.out = out; p.ldo = ldo; p.bias = bias; p.res = res; p.ldr = ldr;
+  p.tokens = tokens > 0 ? tokens : 1; p.heads = heads > 0 ? heads : 1; p.head_dim = head_dim > 0 ? head_dim : 8;
+  p.head_dim_pad = head_dim_pad > 0 ? head_dim_pad : 8; p.batch = batch > 0 ? batch : 1;
+  CKV(gemm_nt_mx(A, As, B, Bs, M, N, Kp, epi, p, out_scales, (hipStream_t)stream));
   return SGL_OK;
 }
 

@@ -64,6 +64,18 @@ struct EpiParams {
   size_t split_stride = 0;
 };
 
+// ---- mx.hip: MX-fp8 (e4m3fn elements, E8M0 scale per 32 K-elements) inference kernels -------------------------------
+// An MX operand [rows][Kp] is Kp e4m3 bytes per row (Kp % 128 == 0, zero-padded) plus scales [rows][Kp / 32].
+// x [M][K] (ldx elements, DT_F32 or DT_BF16) -> q [M][Kp] + sc [M][Kp/32]
+hipError_t quantize_mx(const void* x, int x_dtype, int ldx, int M, int K, int Kp, void* q, void* sc, hipStream_t s);
+// LayerNorm (fp32 statistics) of x [M][D] straight into an MX operand [M][Kp] (Kp <= 2048)
+hipError_t layernorm_fwd_mx(const float* x, const float* gamma, const float* beta, void* q, void* sc, int M, int D, int Kp,
+                            float eps, hipStream_t s);
+// C = A . B^T on MX operands (A [M][Kp], B [N][Kp]) with epilogue EPI_RES_F32, EPI_QKV (bf16 output) or EPI_BIAS_GELU
+// (MX output: p.out [M][p.ldo] bytes, out_sc [M][p.ldo / 32], N % 32 == 0, p.ldo % 128 == 0; p.out2 unused)
+hipError_t gemm_nt_mx(const void* A, const void* As, const void* B, const void* Bs, int M, int N, int Kp, int epi,
+                      const EpiParams& p, void* out_sc, hipStream_t s);
+
 // ---- layernorm.hip -----------------------------------------------------------------------------------
 hipError_t layernorm_fwd(const float* x, const float* gamma, const float* beta, void* y, int y_dtype, int ldy,
                          float* mean, float* rstd, int M, int D, float eps, hipStream_t s);

@@ -169,8 +169,12 @@ def _taper(order, max_chunks):
 
 # compute_dtype -> sgl_config.compute_dtype, and the dtype of the patch-GEMM operand (``patches=``) each mode reads
 COMPUTE_DTYPES = {"bf16": _lib.SGL_DTYPE_BF16, "fp32": _lib.SGL_DTYPE_F32, "bf16x3": _lib.SGL_DTYPE_BF16X3,
-                  "fp16": _lib.SGL_DTYPE_F16}
-OPERAND_DTYPE = {"bf16": torch.bfloat16, "fp32": torch.float32, "bf16x3": torch.float32, "fp16": torch.float16}
+                  "fp16": _lib.SGL_DTYPE_F16, "mxfp8": _lib.SGL_DTYPE_MXFP8}
+# mxfp8 keeps the patch embedding in bf16 (only the four block GEMMs read MX-fp8 operands)
+OPERAND_DTYPE = {"bf16": torch.bfloat16, "fp32": torch.float32, "bf16x3": torch.float32, "fp16": torch.float16,
+                 "mxfp8": torch.bfloat16}
+# modes without a backward: a forward that would have to save activations for one is refused
+INFERENCE_ONLY = {"mxfp8"}
 
 
 @torch.library.custom_op("siglip_hip::encoder_fwd", mutates_args=())
@@ -436,9 +440,12 @@ class SiglipVisionModelHIP(nn.Module):
         # "bf16x3": strict mode on the matrix cores (every GEMM as one bf16 MFMA GEMM over hi/lo-split operands, fp32
         #           accumulate; ~2^-17 relative per product): the north-star "logits within 1e-3" at MFMA speed;
         # "fp16": "bf16" with fp16 operands and weight shadows (fp16 MFMA, same kernels and speed, 3 more mantissa bits):
-        #         the arithmetic of a torch.autocast(float16) run; operand overflow gives inf (GradScaler sees it)
+        #         the arithmetic of a torch.autocast(float16) run; operand overflow gives inf (GradScaler sees it);
+        # "mxfp8": INFERENCE ONLY: "bf16" with the four projection GEMMs of every block on MX-fp8 operands (e4m3 with one
+        #          power-of-two scale per 32 inputs, twice the bf16 MFMA rate); for inference and frozen-backbone training
+        #          (heads train on its detached features); a forward that would differentiate the encoder raises
         if compute_dtype not in COMPUTE_DTYPES:
-            raise ValueError("compute_dtype must be 'bf16', 'fp32', 'bf16x3' or 'fp16'")
+            raise ValueError("compute_dtype must be 'bf16', 'fp32', 'bf16x3', 'fp16' or 'mxfp8'")
         self.compute_dtype = compute_dtype
         cfg = self.config
         self.embeddings = _EmbeddingParams(cfg)
@@ -538,6 +545,10 @@ class SiglipVisionModelHIP(nn.Module):
         uniq = sorted(set(tap_ids))
         params = self._flat_params()
         train = torch.is_grad_enabled() and any(p.requires_grad for p in params)
+        if train and self.compute_dtype in INFERENCE_ONLY:
+            raise RuntimeError(f"compute_dtype={self.compute_dtype!r} is inference-only and cannot differentiate the "
+                               "encoder: freeze it (encoder.requires_grad_(False); heads on top still train), run under "
+                               "torch.no_grad(), or use compute_dtype='bf16' to train it")
         # first block that can receive a gradient (frozen prefix, Siglip2sidafrozen.py:757-768); 0 when the embeddings train
         first = 0
         if train and not any(p.requires_grad for p in params[:3]):

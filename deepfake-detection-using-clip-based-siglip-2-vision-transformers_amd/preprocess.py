@@ -68,7 +68,7 @@ def _dtype_code(dtype: torch.dtype) -> int:
 
 def _operand_dtype(compute_dtype: str) -> torch.dtype:
     """dtype of the patch-GEMM operand of an encoder in ``compute_dtype`` (strict modes read fp32)."""
-    return {"bf16": torch.bfloat16, "fp16": torch.float16}.get(compute_dtype, torch.float32)
+    return {"bf16": torch.bfloat16, "fp16": torch.float16, "mxfp8": torch.bfloat16}.get(compute_dtype, torch.float32)
 
 
 def resize_normalize(images: torch.Tensor, size: int, mean: float = 0.5, std: float = 0.5,

@@ -29,7 +29,8 @@ extern "C" {
 typedef struct sgl_ctx sgl_ctx;
 typedef void* sgl_stream; /* hipStream_t */
 
-enum { SGL_DTYPE_F32 = 0, SGL_DTYPE_BF16 = 1, SGL_DTYPE_BF16X3 = 2, SGL_DTYPE_F16 = 3 };
+enum { SGL_DTYPE_F32 = 0, SGL_DTYPE_BF16 = 1, SGL_DTYPE_BF16X3 = 2, SGL_DTYPE_F16 = 3, SGL_DTYPE_MXFP8 = 5 };
+/* code 4 is not assigned: sgl_create rejects it like every other unknown code */
 
 typedef enum {
   SGL_OK = 0,
@@ -57,7 +58,14 @@ typedef struct {
                                 attention as fp32 MFMA; meets "logits within 1e-3" at a fraction of SGL_DTYPE_F32's cost;
                              SGL_DTYPE_F16 : SGL_DTYPE_BF16 with fp16 operands (fp16 MFMA, fp32 accumulate / residual stream /
                                 statistics / softmax, fp16 weight shadows): the arithmetic of an fp16-autocast run, 3 more
-                                mantissa bits than bf16 at the same MFMA rate; overflow of an fp16 operand gives +-inf */
+                                mantissa bits than bf16 at the same MFMA rate; overflow of an fp16 operand gives +-inf;
+                             SGL_DTYPE_MXFP8: INFERENCE ONLY.  The four projection GEMMs of every block (QKV, out_proj,
+                                fc1, fc2) run on MX-fp8 operands (OCP e4m3fn elements, one E8M0 scale per 32 K-elements,
+                                v_mfma_scale_f32_16x16x128_f8f6f4, fp32 accumulate); everything else as SGL_DTYPE_BF16
+                                (fp32 residual stream and statistics, bf16 attention, patch embedding and pooling head).
+                                The weight shadows are MX blocks (re-quantized by sgl_prepare_weights*).  Training is
+                                refused: sgl_query_sizes(train=1) and sgl_forward* with saved != NULL return
+                                SGL_ERR_UNSUPPORTED, and sgl_adamw_bind_shadows binds nothing */
   int use_head;           /* attention-pool head present (vision_use_head) */
 } sgl_config;
 
@@ -200,6 +208,24 @@ int sgl_op_gemm_nt(int dtype, const void* A, int lda, const void* B, int ldb, in
                    int ldo, void* out2, int ldo2, const float* bias, const float* res, int ldr, const void* aux,
                    int ldaux, const float* pos, int pos_rows, int tokens, int heads, int head_dim, int head_dim_pad,
                    int batch, sgl_stream stream);
+/* MX-fp8 single-kernel entry points (the SGL_DTYPE_MXFP8 mode's kernels).  An MX operand [rows][Kp] is Kp e4m3fn bytes per
+ * row plus E8M0 scale bytes [rows][Kp/32] (value = e4m3 * 2^(scale - 127)); Kp % 128 == 0, padding bytes and scales are 0.
+ * Quantizer, per 32-block with amax = max|x|: e = the smallest integer with amax <= 448 * 2^e, clamped to [-127, 127];
+ * scale byte e + 127; elements x * 2^-e rounded to nearest even (subnormals kept); an all-zero block has scale byte 0; a
+ * block holding an inf or NaN gets scale byte 0xFF and NaN elements (0x7F).
+ * sgl_op_quantize_mxfp8: x [M][K] (ldx elements, x_dtype SGL_DTYPE_F32 or SGL_DTYPE_BF16) -> q [M][Kp] + scales. */
+int sgl_op_quantize_mxfp8(const void* x, int x_dtype, int ldx, int M, int K, int Kp, void* q, void* scales,
+                          sgl_stream stream);
+/* LayerNorm of x [M][D] (fp32 statistics, as sgl_op_layernorm_fwd) written as an MX operand [M][Kp] (D <= Kp <= 2048). */
+int sgl_op_layernorm_fwd_mx(const float* x, const float* gamma, const float* beta, void* q, void* scales, int M, int D,
+                            int Kp, float eps, sgl_stream stream);
+/* C[M,N] = A[M,Kp] * B[N,Kp]^T on MX operands (A with scales As, B with scales Bs), fp32 accumulate, fused epilogue:
+ * SGL_EPI_RES_F32 (fp32 out = res + acc + bias), SGL_EPI_QKV (bf16 head-major scatter, as sgl_op_gemm_nt) or
+ * SGL_EPI_BIAS_GELU (gelu_tanh(acc + bias) quantized to an MX operand: out [M][ldo] bytes, out_scales [M][ldo/32];
+ * N % 32 == 0, ldo % 128 == 0, columns N..ldo untouched).  bias is required. */
+int sgl_op_gemm_nt_mx(const void* A, const void* As, const void* B, const void* Bs, int M, int N, int Kp, int epi,
+                      void* out, int ldo, void* out_scales, const float* bias, const float* res, int ldr, int tokens,
+                      int heads, int head_dim, int head_dim_pad, int batch, sgl_stream stream);
 /* C[N1,N2] (+)= sum_m A[m,N1] * B[m,N2]  (fp32 output). */
 int sgl_op_gemm_tn(int dtype, const void* A, int lda, const void* B, int ldb, int Mred, int N1, int N2, int splits,
                    float* out, int ldo, int accumulate, sgl_stream stream);
