@@ -21,6 +21,8 @@ using namespace sgl;
 namespace {
 
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+inline char* at(void* base, size_t off) { return reinterpret_cast<char*>(base) + off; }
+inline const char* at(const void* base, size_t off) { return reinterpret_cast<const char*>(base) + off; }
 // 16-bit MFMA compute modes (bf16, fp16): the same kernels and buffer layouts, only the operand type differs
 inline bool mfma16(int dt) { return dt == DT_BF16 || dt == DT_F16; }
 inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
@@ -48,6 +50,7 @@ struct sgl_ctx {
   int split = 0;   // SGL_DTYPE_BF16X3: dt == DT_F32 everywhere, GEMMs through the bf16x3 operand split
   int mx = 0;      // SGL_DTYPE_MXFP8: dt == DT_BF16 everywhere except the block GEMMs, which read MX-fp8 operands
   int Dp = 0;      // MX mode: K padding of the D-wide operands, round_up(D, 128) (the MX GEMM's K-step)
+  int recompute = 0;   // SGL_RECOMPUTE_BLOCKS: training keeps no per-block activations; sgl_backward_layer* recomputes them
   // scratch for the split operands of the GEMM being launched: set by every entry point from the CALLER's buffers (the ctx
   // owns no memory); calls on one ctx are stream-ordered (siglip_hip.h), so one pair per ctx suffices
   void* sp_a = nullptr;
@@ -84,10 +87,15 @@ struct Layout {
   size_t w_hg, w_hdu, w_hdh, w_hdao, w_hdqpart, w_hdqp, w_hdh0;
   size_t ws_bwd_total;
   size_t saved_total, ws_total, ws_act_off;
+  // recompute context, training: ONE block region in ws (w_blk) that the forward and every backward block reuse; no
+  // per-block region in `saved`, and the forward's bf16x3 split scratch is the backward's (w_spa / w_spb)
+  bool rc;
+  size_t w_blk = 0;
 
   Layout(const sgl_ctx* c, int B_, int Himg, int Wimg, bool train_) {
     B = B_;
     train = train_;
+    rc = train && c->recompute;
     gh = Himg / c->P;
     gw = Wimg / c->P;
     N = gh * gw;
@@ -112,8 +120,8 @@ struct Layout {
     r_u = r.take(mx ? 0 : Mz * Ip * es);
     r_a = r.take(mx ? Mz * Ip + Mz * Ip / 32 : Mz * Ip * es);
     r_attq = r.take(mx ? Mz * Dp + Mz * Dp / 32 : 0);
-    a_layer_stride = train ? r.off : 0;
-    a_layer0 = a.take(train ? r.off * (size_t)c->L : r.off);
+    a_layer_stride = (train && !rc) ? r.off : 0;
+    a_layer0 = a.take(rc ? 0 : train ? r.off * (size_t)c->L : r.off);
     a_pstats = a.take(Mz * 2 * 4);
     a_lastlp = a.take(Mz * D * es);
     a_kvh = a.take((size_t)2 * B * c->H * N * c->DP * es);
@@ -130,7 +138,7 @@ struct Layout {
     const size_t sp_act = 3 * (Mz > (size_t)B ? Mz : (size_t)B) * Wd * 2;
     const size_t sp_wgt = 3 * Wd * (size_t)round_up((int)D > c->Kp ? (int)D : c->Kp, 8) * 2;
     const size_t sp_bytes = sp_act > sp_wgt ? sp_act : sp_wgt;
-    if (c->split) {
+    if (c->split && !rc) {
       a_spa = a.take(sp_bytes);
       a_spb = a.take(sp_bytes);
     }
@@ -162,6 +170,7 @@ struct Layout {
         w_spa = w.take(sp_bytes);
         w_spb = w.take(sp_bytes);
       }
+      if (rc) w_blk = w.take(r.off);
     } else {
       w_dx = w_g = w_du = w_dh = w_dqkv = w_delta = w_splitws = w_lnpart = w_cspart = w_dlast = w_gsum = w_csum = 0;
       w_hg = w_hdu = w_hdh = w_hdao = w_hdqpart = w_hdqp = w_hdh0 = 0;
@@ -179,6 +188,8 @@ struct Layout {
     if (ws_total == 0) ws_total = 256;
   }
   size_t layer_base(int l) const { return a_layer0 + a_layer_stride * (size_t)l; }
+  // block l's activation region: in the activation arena, or (recompute, training) the one region in ws
+  char* block(char* act, void* ws, int l) const { return rc ? at(ws, w_blk) : act + layer_base(l); }
 };
 
 #define CK(expr)                        \
@@ -189,9 +200,6 @@ struct Layout {
       return SGL_ERR_HIP;               \
     }                                   \
   } while (0)
-
-inline char* at(void* base, size_t off) { return reinterpret_cast<char*>(base) + off; }
-inline const char* at(const void* base, size_t off) { return reinterpret_cast<const char*>(base) + off; }
 
 hipError_t gemm_nt(const sgl_ctx* c, const void* A, int lda, const void* B, int ldb, int M, int N, int K, int epi,
                    int out_dt, const EpiParams& p, hipStream_t s) {
@@ -312,12 +320,87 @@ int mx_block(sgl_ctx* ctx, const Layout& lay, const sgl_layer_weights& lw, const
   return SGL_OK;
 }
 
+// One encoder block of the 16-bit / strict modes up to the MLP's hidden activation: LN1 -> QKV (head-major) -> attention
+// -> out_proj + bias + x = xmid -> LN2 -> fc1 + bias, GELU into the block region lb (u = the pre-activation, or gelu'(u)
+// in bf16 / fp16 mode, only when want_u).  The training forward and the recompute of sgl_backward_layer* share it, so
+// both launch the same kernels on the same shapes and produce the same bits.
+int block_to_fc1(sgl_ctx* ctx, const Layout& lay, const sgl_layer_weights& lw, const ShadowLayer& sl, const void* shadow,
+                 char* lb, const float* x, int B, bool want_u, hipStream_t s) {
+  const int D = ctx->D, Ip = ctx->Ip, M = lay.M, N = lay.N, dt = ctx->dt, Hh = ctx->H, dh = ctx->dh, DP = ctx->DP;
+  float* st1 = reinterpret_cast<float*>(lb + lay.r_stats1);
+  float* st2 = reinterpret_cast<float*>(lb + lay.r_stats2);
+  float* xmid = reinterpret_cast<float*>(lb + lay.r_xmid);
+  CK(layernorm_fwd(x, lw.ln1_w, lw.ln1_b, lb + lay.r_h1, dt, D, st1, st1 + M, M, D, ctx->cfg.layer_norm_eps, s));
+  {
+    // head-major scatter [3][B][H][N][DP] in the GEMM epilogue (EPI_QKV).  Round 3 measured the alternative the kernels
+    // also support (ld_qkv > 0: plain token-major [M][3D] store, attention gathers each head's 144-byte row segments):
+    // QKV GEMM 853 -> 754 us per launch at B = 128, but attention forward +5.8 % and backward +5.9 % (every DMA instruction
+    // touches 14 cache lines instead of 8, and K/V are re-read by six workgroups per head and three kernels): +0.75 ms
+    // per step net, so the 144-byte granularity is paid once, on the write side.
+    EpiParams p;
+    p.out = lb + lay.r_qkv;
+    p.bias = reinterpret_cast<const float*>(at(shadow, sl.bqkv));
+    p.tokens = N;
+    p.heads = Hh;
+    p.head_dim = dh;
+    p.head_dim_pad = DP;
+    p.batch = B;
+    CK(gemm_nt(ctx, lb + lay.r_h1, D, at(shadow, sl.wqkv), D, M, 3 * D, D, EPI_QKV, dt, p, s));
+  }
+  {
+    const size_t hsz = (size_t)B * Hh * N * DP * ctx->es;
+    char* q = lb + lay.r_qkv;
+    CK(attn_fwd(q, q + hsz, q + 2 * hsz, ctx->split ? DT_F32_MFMA : dt, lb + lay.r_attn,
+                reinterpret_cast<float*>(lb + lay.r_lse), B, Hh, N, dh, DP, 0, s));
+  }
+  {
+    EpiParams p;
+    p.out = xmid;
+    p.ldo = D;
+    p.bias = lw.o_b;
+    p.res = x;
+    p.ldr = D;
+    CK(gemm_nt(ctx, lb + lay.r_attn, D, at(shadow, sl.wo), D, M, D, D, EPI_RES_F32, DT_F32, p, s));
+  }
+  CK(layernorm_fwd(xmid, lw.ln2_w, lw.ln2_b, lb + lay.r_h2, dt, D, st2, st2 + M, M, D, ctx->cfg.layer_norm_eps, s));
+  {
+    EpiParams p;
+    p.out = want_u ? lb + lay.r_u : nullptr;
+    p.gelu_grad_form = mfma16(dt);   // r_u holds gelu'(u) in bf16 / fp16 mode (the backward only ever needs that)
+    p.ldo = Ip;
+    p.out2 = lb + lay.r_a;
+    p.ldo2 = Ip;
+    p.bias = reinterpret_cast<const float*>(at(shadow, sl.b1));
+    CK(gemm_nt(ctx, lb + lay.r_h2, D, at(shadow, sl.w1), D, M, Ip, D, EPI_BIAS_GELU, dt, p, s));
+  }
+  return SGL_OK;
+}
+
+// Largest token count M = B * grid a recompute context trains on (size audit).  The MFMA GEMM
+// dispatchers refuse any operand of 2^32 bytes or more (32-bit buffer-descriptor ranges): the widest operand with M rows
+// on the training path is [M][max(Ip, 3D, Kp)] (u / a / du, dqkv, im2col), three times as wide after the bf16x3 split,
+// 4-byte in strict fp32.  The EPI_QKV row division is exact for rows < 2^22.
+long rc_max_tokens(const sgl_ctx* c) {
+  long w = c->Ip;
+  if (3l * c->D > w) w = 3l * c->D;
+  if ((long)c->Kp > w) w = c->Kp;
+  const long row_bytes = c->split ? 3 * (long)round_up((int)w, 8) * 2 : w * (long)c->es;
+  const long m = ((1l << 32) - 1) / row_bytes;
+  return m < (1l << 22) - 1 ? m : (1l << 22) - 1;
+}
+
 bool shape_ok(const sgl_ctx* c, int B, int H, int W) {
   if (B <= 0 || H <= 0 || W <= 0) return false;
   if (H < c->P || W < c->P) return false;  // 'valid' conv: trailing pixels beyond gh*P are ignored
   const long N = (long)(H / c->P) * (W / c->P);
   if ((long)B * N > (1l << 24)) return false;
   return true;
+}
+
+// shape_ok plus, on a recompute context, the training token limit
+bool train_shape_ok(const sgl_ctx* c, int B, int H, int W) {
+  if (!shape_ok(c, B, H, W)) return false;
+  return !c->recompute || (long)B * (H / c->P) * (W / c->P) <= rc_max_tokens(c);
 }
 
 }  // namespace
@@ -339,8 +422,12 @@ const char* sgl_status_string(int status) {
   return "unknown";
 }
 
-sgl_ctx* sgl_create(const sgl_config* cfg) {
+sgl_ctx* sgl_create(const sgl_config* cfg) { return sgl_create_ex(cfg, SGL_RECOMPUTE_NONE); }
+
+sgl_ctx* sgl_create_ex(const sgl_config* cfg, int recompute) {
   if (!cfg) return nullptr;
+  if (recompute != SGL_RECOMPUTE_NONE && recompute != SGL_RECOMPUTE_BLOCKS) return nullptr;
+  if (recompute && cfg->compute_dtype == SGL_DTYPE_MXFP8) return nullptr;   // the MX-fp8 mode never trains
   if (cfg->hidden_size <= 0 || cfg->num_heads <= 0 || cfg->hidden_size % cfg->num_heads) return nullptr;
   const int dh = cfg->hidden_size / cfg->num_heads;
   if (dh % 8 || dh > 96 || cfg->hidden_size % 8 || cfg->hidden_size > 2048) return nullptr;
@@ -370,6 +457,7 @@ sgl_ctx* sgl_create(const sgl_config* cfg) {
   c->dt = c->split ? DT_F32 : cfg->compute_dtype == SGL_DTYPE_F16 ? DT_F16 : c->mx ? DT_BF16 : cfg->compute_dtype;
   c->es = dtype_size(c->dt);
   c->Dp = round_up(c->D, 128);
+  c->recompute = recompute;
   const size_t es = c->es, D = c->D, Ip = c->Ip, Dp = c->Dp;
   Bump b;
   c->sh_wpatch = b.take(D * c->Kp * es);
@@ -423,7 +511,7 @@ int sgl_last_hip_error(const sgl_ctx* ctx) { return ctx ? ctx->last_hip : 0; }
 int sgl_query_sizes(const sgl_ctx* ctx, int B, int H, int W, int train, size_t* shadow_bytes, size_t* saved_bytes,
                     size_t* ws_bytes) {
   if (!ctx) return SGL_ERR_NULL;
-  if (!shape_ok(ctx, B, H, W)) return SGL_ERR_BAD_SHAPE;
+  if (!(train ? train_shape_ok(ctx, B, H, W) : shape_ok(ctx, B, H, W))) return SGL_ERR_BAD_SHAPE;
   if (ctx->mx && train) return SGL_ERR_UNSUPPORTED;   // the MX-fp8 mode has no backward
   Layout lay(ctx, B, H, W, train != 0);
   if (shadow_bytes) *shadow_bytes = ctx->sh_total;
@@ -603,18 +691,20 @@ int sgl_forward_slots(sgl_ctx* ctx, const sgl_weights* w, const void* shadow, co
     for (int l = 0; l < ctx->L; ++l)
       for (int k = l + 1; k <= ctx->L; ++k)
         if (hs_slots[l] == hs_slots[k]) return SGL_ERR_BAD_SHAPE;
+  if (train && !train_shape_ok(ctx, B, H, W)) return SGL_ERR_BAD_SHAPE;
   Layout lay(ctx, B, H, W, train);
   if (train && saved_bytes < lay.saved_total) return SGL_ERR_WORKSPACE;
-  // training forward keeps everything in `saved`; the workspace is only touched by inference and backward
-  if (!train && (!ws || ws_bytes < lay.ws_total)) return SGL_ERR_WORKSPACE;
+  // a plain training forward keeps everything in `saved` and leaves the workspace alone; inference and a recompute
+  // context's training forward (its block region) use it
+  if ((!train || lay.rc) && (!ws || ws_bytes < lay.ws_total)) return SGL_ERR_WORKSPACE;
   if (!(lay.gh == ctx->g0 && lay.gw == ctx->g0) && !interpolate_pos) return SGL_ERR_BAD_SHAPE;
   hipStream_t s = (hipStream_t)stream;
   const int D = ctx->D, Ip = ctx->Ip, M = lay.M, N = lay.N, dt = ctx->dt, Hh = ctx->H, dh = ctx->dh, DP = ctx->DP;
   char* act = train ? reinterpret_cast<char*>(saved) : at(ws, lay.ws_act_off);
   auto hs = [&](int l) { return hs_slots[l]; };
   if (ctx->split) {
-    ctx->sp_a = act + lay.a_spa;
-    ctx->sp_b = act + lay.a_spb;
+    ctx->sp_a = lay.rc ? at(ws, lay.w_spa) : act + lay.a_spa;
+    ctx->sp_b = lay.rc ? at(ws, lay.w_spb) : act + lay.a_spb;
   }
 
   // ---- embeddings
@@ -643,59 +733,16 @@ int sgl_forward_slots(sgl_ctx* ctx, const sgl_weights* w, const void* shadow, co
   for (int l = 0; l < ctx->L; ++l) {
     const sgl_layer_weights& lw = w->layers[l];
     const ShadowLayer& sl = ctx->sh_layers[l];
-    char* lb = act + lay.layer_base(l);
+    char* lb = lay.block(act, ws, l);
     float* x = hs(l);
     float* xo = hs(l + 1);
-    float* st1 = reinterpret_cast<float*>(lb + lay.r_stats1);
-    float* st2 = reinterpret_cast<float*>(lb + lay.r_stats2);
     float* xmid = reinterpret_cast<float*>(lb + lay.r_xmid);
     if (ctx->mx) {
       RET(mx_block(ctx, lay, lw, sl, shadow, lb, x, xo, xmid, B, s));
       continue;
     }
-    CK(layernorm_fwd(x, lw.ln1_w, lw.ln1_b, lb + lay.r_h1, dt, D, st1, st1 + M, M, D, ctx->cfg.layer_norm_eps, s));
-    {
-      // head-major scatter [3][B][H][N][DP] in the GEMM epilogue (EPI_QKV).  Round 3 measured the alternative the kernels
-      // also support (ld_qkv > 0: plain token-major [M][3D] store, attention gathers each head's 144-byte row segments):
-      // QKV GEMM 853 -> 754 us per launch at B = 128, but attention forward +5.8 % and backward +5.9 % (every DMA instruction
-      // touches 14 cache lines instead of 8, and K/V are re-read by six workgroups per head and three kernels): +0.75 ms
-      // per step net, so the 144-byte granularity is paid once, on the write side.
-      EpiParams p;
-      p.out = lb + lay.r_qkv;
-      p.bias = reinterpret_cast<const float*>(at(shadow, sl.bqkv));
-      p.tokens = N;
-      p.heads = Hh;
-      p.head_dim = dh;
-      p.head_dim_pad = DP;
-      p.batch = B;
-      CK(gemm_nt(ctx, lb + lay.r_h1, D, at(shadow, sl.wqkv), D, M, 3 * D, D, EPI_QKV, dt, p, s));
-    }
-    {
-      const size_t hsz = (size_t)B * Hh * N * DP * ctx->es;
-      char* q = lb + lay.r_qkv;
-      CK(attn_fwd(q, q + hsz, q + 2 * hsz, ctx->split ? DT_F32_MFMA : dt, lb + lay.r_attn,
-                  reinterpret_cast<float*>(lb + lay.r_lse), B, Hh, N, dh, DP, 0, s));
-    }
-    {
-      EpiParams p;
-      p.out = xmid;
-      p.ldo = D;
-      p.bias = lw.o_b;
-      p.res = x;
-      p.ldr = D;
-      CK(gemm_nt(ctx, lb + lay.r_attn, D, at(shadow, sl.wo), D, M, D, D, EPI_RES_F32, DT_F32, p, s));
-    }
-    CK(layernorm_fwd(xmid, lw.ln2_w, lw.ln2_b, lb + lay.r_h2, dt, D, st2, st2 + M, M, D, ctx->cfg.layer_norm_eps, s));
-    {
-      EpiParams p;
-      p.out = (train && l >= first_trainable_block) ? lb + lay.r_u : nullptr;
-      p.gelu_grad_form = mfma16(dt);   // r_u holds gelu'(u) in bf16 / fp16 mode (the backward only ever needs that)
-      p.ldo = Ip;
-      p.out2 = lb + lay.r_a;
-      p.ldo2 = Ip;
-      p.bias = reinterpret_cast<const float*>(at(shadow, sl.b1));
-      CK(gemm_nt(ctx, lb + lay.r_h2, D, at(shadow, sl.w1), D, M, Ip, D, EPI_BIAS_GELU, dt, p, s));
-    }
+    // u is kept for the blocks the backward will differentiate, unless it recomputes them
+    RET(block_to_fc1(ctx, lay, lw, sl, shadow, lb, x, B, train && !lay.rc && l >= first_trainable_block, s));
     {
       EpiParams p;
       p.out = xo;
@@ -810,7 +857,7 @@ int sgl_backward_begin(sgl_ctx* ctx, const sgl_weights* w, const void* shadow, c
                        const float* d_tap_last, const void* saved, size_t saved_bytes, void* ws, size_t ws_bytes,
                        sgl_stream stream) {
   if (!ctx || !hidden_states) return SGL_ERR_NULL;
-  if (!shape_ok(ctx, B, H, W)) return SGL_ERR_BAD_SHAPE;
+  if (!train_shape_ok(ctx, B, H, W)) return SGL_ERR_BAD_SHAPE;
   const size_t stride = (size_t)B * (H / ctx->P) * (W / ctx->P) * ctx->D;
   return sgl_backward_begin_p(ctx, w, shadow, g, B, H, W, hidden_states + (size_t)ctx->L * stride, d_last_hidden, d_pooled,
                               d_tap_last, saved, saved_bytes, ws, ws_bytes, stream);
@@ -821,7 +868,7 @@ int sgl_backward_begin_p(sgl_ctx* ctx, const sgl_weights* w, const void* shadow,
                          const float* d_tap_last, const void* saved, size_t saved_bytes, void* ws, size_t ws_bytes,
                          sgl_stream stream) {
   if (!ctx || !w || !shadow || !g || !hs_last) return SGL_ERR_NULL;
-  if (!shape_ok(ctx, B, H, W)) return SGL_ERR_BAD_SHAPE;
+  if (!train_shape_ok(ctx, B, H, W)) return SGL_ERR_BAD_SHAPE;
   Layout lay(ctx, B, H, W, true);
   RET(check_bwd_args(ctx, lay, saved, saved_bytes, ws, ws_bytes));
   if (ctx->split) {
@@ -942,7 +989,7 @@ int sgl_backward_layer(sgl_ctx* ctx, const sgl_weights* w, const void* shadow, c
                        int H, int W, const float* hidden_states, const float* d_tap, int need_dx, const void* saved,
                        size_t saved_bytes, void* ws, size_t ws_bytes, sgl_stream stream) {
   if (!ctx || !hidden_states) return SGL_ERR_NULL;
-  if (layer < 0 || layer >= ctx->L || !shape_ok(ctx, B, H, W)) return SGL_ERR_BAD_SHAPE;
+  if (layer < 0 || layer >= ctx->L || !train_shape_ok(ctx, B, H, W)) return SGL_ERR_BAD_SHAPE;
   const size_t stride = (size_t)B * (H / ctx->P) * (W / ctx->P) * ctx->D;
   return sgl_backward_layer_p(ctx, w, shadow, g, layer, B, H, W, hidden_states + (size_t)layer * stride, d_tap, need_dx,
                               saved, saved_bytes, ws, ws_bytes, stream);
@@ -953,7 +1000,7 @@ int sgl_backward_layer_p(sgl_ctx* ctx, const sgl_weights* w, const void* shadow,
                          size_t saved_bytes, void* ws, size_t ws_bytes, sgl_stream stream) {
   if (!ctx || !w || !shadow || !g || !hs_in || !g->layers) return SGL_ERR_NULL;
   if (layer < 0 || layer >= ctx->L) return SGL_ERR_BAD_SHAPE;
-  if (!shape_ok(ctx, B, H, W)) return SGL_ERR_BAD_SHAPE;
+  if (!train_shape_ok(ctx, B, H, W)) return SGL_ERR_BAD_SHAPE;
   Layout lay(ctx, B, H, W, true);
   RET(check_bwd_args(ctx, lay, saved, saved_bytes, ws, ws_bytes));
   if (ctx->split) {
@@ -967,7 +1014,14 @@ int sgl_backward_layer_p(sgl_ctx* ctx, const sgl_weights* w, const void* shadow,
   const sgl_layer_weights& lw = w->layers[layer];
   const sgl_layer_grads& lg = g->layers[layer];
   const ShadowLayer& sl = ctx->sh_layers[layer];
+  // recompute context: rebuild the block's activations from its input into the shared region first (everything but fc2:
+  // hidden_states[layer + 1] is saved); the region is disjoint from the gradient this call carries in ws
   const char* lb = reinterpret_cast<const char*>(saved) + lay.layer_base(layer);
+  if (lay.rc) {
+    char* rb = at(ws, lay.w_blk);
+    RET(block_to_fc1(ctx, lay, lw, sl, shadow, rb, hs_in, B, true, s));
+    lb = rb;
+  }
   const float* x_in = hs_in;
   const float* xmid = reinterpret_cast<const float*>(lb + lay.r_xmid);
   float* dx = reinterpret_cast<float*>(at(ws, lay.w_dx));
@@ -1066,7 +1120,7 @@ int sgl_backward_layer_p(sgl_ctx* ctx, const sgl_weights* w, const void* shadow,
 int sgl_backward_embed(sgl_ctx* ctx, const sgl_weights* w, const sgl_grads* g, int B, int H, int W, int interpolate_pos,
                        const void* saved, size_t saved_bytes, void* ws, size_t ws_bytes, sgl_stream stream) {
   if (!ctx || !w || !g) return SGL_ERR_NULL;
-  if (!shape_ok(ctx, B, H, W)) return SGL_ERR_BAD_SHAPE;
+  if (!train_shape_ok(ctx, B, H, W)) return SGL_ERR_BAD_SHAPE;
   Layout lay(ctx, B, H, W, true);
   RET(check_bwd_args(ctx, lay, saved, saved_bytes, ws, ws_bytes));
   if (ctx->split) {

@@ -180,10 +180,11 @@ INFERENCE_ONLY = {"mxfp8"}
 @torch.library.custom_op("siglip_hip::encoder_fwd", mutates_args=())
 def encoder_fwd(pixel_values: torch.Tensor, params: Sequence[torch.Tensor], handle: int, train: bool, interp: bool,
                 want_pooled: bool, tap_ids: Sequence[int], first_trainable: int, layout: int, img_h: int,
-                img_w: int) -> List[torch.Tensor]:
+                img_w: int, recompute: bool = False) -> List[torch.Tensor]:
     """sgl_forward_slots.  Returns [pooled (B,D) or empty, last_hidden_state (B,N,D), one (B,N,D) tensor per entry of
     tap_ids (distinct, ascending), saved (uint8 activation arena, empty when not training), hs_rest (the hidden-state
-    slots nobody asked for: [n, B*N, D])].  No output aliases another."""
+    slots nobody asked for: [n, B*N, D])].  No output aliases another.  recompute (training only): run on the module's
+    recompute context, which saves no per-block activations (its backward recomputes them)."""
     mod = _module_of(handle)
     cfg = mod.config
     L, D = cfg.num_hidden_layers, cfg.hidden_size
@@ -208,9 +209,10 @@ def encoder_fwd(pixel_values: torch.Tensor, params: Sequence[torch.Tensor], hand
         raise ValueError(f"Input image size ({H}*{W}) doesn't match model native "
                          f"({cfg.image_size}*{cfg.image_size}); pass interpolate_pos_encoding=True")
     dev = px.device
+    recompute = bool(recompute) and train     # inference ignores the policy
     with torch.cuda.device(dev):
         shadow, weights = mod._prepared(dev)
-        sizes = mod._sizes(B, H, W, train)
+        sizes = mod._sizes(B, H, W, train, recompute)
         taps = [torch.empty((B, N, D), dtype=torch.float32, device=dev) for _ in tap_ids]
         tapset = {int(t): i for i, t in enumerate(tap_ids)}
         n_rest = (L + 1 - len(tapset)) if train else min(2, L + 1 - len(tapset))
@@ -228,20 +230,23 @@ def encoder_fwd(pixel_values: torch.Tensor, params: Sequence[torch.Tensor], hand
         last = torch.empty((B, N, D), dtype=torch.float32, device=dev)
         pooled = torch.empty((B, D) if want_pooled else (0,), dtype=torch.float32, device=dev)
         saved = torch.empty(sizes[1] if train else 0, dtype=torch.uint8, device=dev)
-        ws = None if train else mod._workspace(sizes[2], dev)
-        st = lib.sgl_forward_slots(mod._ctx, C.byref(weights), shadow.data_ptr(), px.data_ptr(), channels_last, B, H, W,
+        # a plain training forward leaves the workspace alone; a recompute one writes its block region there
+        ws = mod._workspace(sizes[2], dev) if (recompute or not train) else None
+        ctx = mod._ensure_ctx(recompute)
+        st = lib.sgl_forward_slots(ctx, C.byref(weights), shadow.data_ptr(), px.data_ptr(), channels_last, B, H, W,
                                    1 if interp else 0, slots, last.data_ptr(),
                                    pooled.data_ptr() if want_pooled else None, saved.data_ptr() if train else None,
-                                   sizes[1] if train else 0, _lib.ptr(ws), 0 if train else sizes[2],
+                                   sizes[1] if train else 0, _lib.ptr(ws), 0 if ws is None else sizes[2],
                                    int(first_trainable), _lib.current_stream_handle())
-        _lib.check(st, "sgl_forward_slots", mod._ctx)
+        _lib.check(st, "sgl_forward_slots", ctx)
     if train:
         mod._note_forward(saved)
     return [pooled, last, *taps, saved, hs_rest]
 
 
 @encoder_fwd.register_fake
-def _(pixel_values, params, handle, train, interp, want_pooled, tap_ids, first_trainable, layout, img_h, img_w):
+def _(pixel_values, params, handle, train, interp, want_pooled, tap_ids, first_trainable, layout, img_h, img_w,
+      recompute=False):
     mod = _module_of(handle)
     cfg = mod.config
     L, D = cfg.num_hidden_layers, cfg.hidden_size
@@ -250,7 +255,7 @@ def _(pixel_values, params, handle, train, interp, want_pooled, tap_ids, first_t
         raise RuntimeError("siglip_hip::encoder_fwd needs static image shapes under torch.compile (dynamic=False)")
     new = pixel_values.new_empty
     n_rest = (L + 1 - len(tap_ids)) if train else min(2, L + 1 - len(tap_ids))
-    saved_bytes = mod._sizes(B, H, W, True)[1] if train else 0
+    saved_bytes = mod._sizes(B, H, W, True, bool(recompute))[1] if train else 0
     return [new((B, D) if want_pooled else (0,), dtype=torch.float32), new((B, N, D), dtype=torch.float32),
             *[new((B, N, D), dtype=torch.float32) for _ in tap_ids], new((saved_bytes,), dtype=torch.uint8),
             new((n_rest, M, D), dtype=torch.float32)]
@@ -259,8 +264,10 @@ def _(pixel_values, params, handle, train, interp, want_pooled, tap_ids, first_t
 @torch.library.custom_op("siglip_hip::encoder_bwd", mutates_args=())
 def encoder_bwd(grads: Sequence[Optional[torch.Tensor]], taps: Sequence[torch.Tensor], saved: torch.Tensor,
                 hs_rest: torch.Tensor, params: Sequence[torch.Tensor], handle: int, image_hw: Sequence[int],
-                interp: bool, want_pooled: bool, tap_ids: Sequence[int], needs: Sequence[bool]) -> List[torch.Tensor]:
-    """sgl_backward_begin_p -> sgl_backward_layer_p (L-1 ... first trainable block) -> sgl_backward_embed.
+                interp: bool, want_pooled: bool, tap_ids: Sequence[int], needs: Sequence[bool],
+                recompute: bool = False) -> List[torch.Tensor]:
+    """sgl_backward_begin_p -> sgl_backward_layer_p (L-1 ... first trainable block) -> sgl_backward_embed, on the context
+    of the policy the forward ran with (recompute: each sgl_backward_layer_p recomputes its block first).
     grads = [d pooled, d last_hidden_state, d tap...] (None = no gradient).  Returns the flat fp32 gradient chunks of
     ``SiglipVisionModelHIP._bucket_layout(needs)`` (the DDP all-reduce units); the autograd formula slices the
     per-parameter views out of them outside the op, so no output of the op aliases another."""
@@ -333,26 +340,28 @@ def encoder_bwd(grads: Sequence[Optional[torch.Tensor]], taps: Sequence[torch.Te
         layer_ids = sorted(int(k_[5:]) for k_ in groups if k_.startswith("layer"))
         first = layer_ids[0] if layer_ids else L
         stop = 0 if train_emb else first
-        sizes = mod._sizes(B, H, W, True)
+        recompute = bool(recompute)
+        sizes = mod._sizes(B, H, W, True, recompute)
         ws = mod._workspace(sizes[2], dev)
         stream = _lib.current_stream_handle()
         shadow, wts = mod._shadow, mod._weights_struct
-        st = lib.sgl_backward_begin_p(mod._ctx, C.byref(wts), shadow.data_ptr(), C.byref(g), B, H, W, hs_ptr[L],
+        cx = mod._ensure_ctx(recompute)
+        st = lib.sgl_backward_begin_p(cx, C.byref(wts), shadow.data_ptr(), C.byref(g), B, H, W, hs_ptr[L],
                                       _lib.ptr(d_last), _lib.ptr(d_pooled), _lib.ptr(tap_grads[L]),
                                       saved.data_ptr(), sizes[1], ws.data_ptr(), sizes[2], stream)
-        _lib.check(st, "sgl_backward_begin_p", mod._ctx)
+        _lib.check(st, "sgl_backward_begin_p", cx)
         group_done("head")
         for l in range(L - 1, stop - 1, -1):
             need_dx = 1 if (l > stop or train_emb) else 0
-            st = lib.sgl_backward_layer_p(mod._ctx, C.byref(wts), shadow.data_ptr(), C.byref(g), l, B, H, W, hs_ptr[l],
+            st = lib.sgl_backward_layer_p(cx, C.byref(wts), shadow.data_ptr(), C.byref(g), l, B, H, W, hs_ptr[l],
                                           _lib.ptr(tap_grads[l]), need_dx, saved.data_ptr(), sizes[1], ws.data_ptr(),
                                           sizes[2], stream)
-            _lib.check(st, f"sgl_backward_layer_p[{l}]", mod._ctx)
+            _lib.check(st, f"sgl_backward_layer_p[{l}]", cx)
             group_done(f"layer{l}")
         if train_emb:
-            st = lib.sgl_backward_embed(mod._ctx, C.byref(wts), C.byref(g), B, H, W, 1 if interp else 0,
+            st = lib.sgl_backward_embed(cx, C.byref(wts), C.byref(g), B, H, W, 1 if interp else 0,
                                         saved.data_ptr(), sizes[1], ws.data_ptr(), sizes[2], stream)
-            _lib.check(st, "sgl_backward_embed", mod._ctx)
+            _lib.check(st, "sgl_backward_embed", cx)
             group_done("emb")
         if overlapped:
             reducer.finish()
@@ -360,14 +369,16 @@ def encoder_bwd(grads: Sequence[Optional[torch.Tensor]], taps: Sequence[torch.Te
 
 
 @encoder_bwd.register_fake
-def _(grads, taps, saved, hs_rest, params, handle, image_hw, interp, want_pooled, tap_ids, needs):
+def _(grads, taps, saved, hs_rest, params, handle, image_hw, interp, want_pooled, tap_ids, needs, recompute=False):
     chunks, _ = _module_of(handle)._bucket_layout(needs)
     return [saved.new_empty((total,), dtype=torch.float32) for total, _, _ in chunks]
 
 
 def _encoder_setup_context(ctx, inputs, output):
-    pixel_values, params, handle, train, interp, want_pooled, tap_ids, first_trainable, layout, img_h, img_w = inputs
+    pixel_values, params, handle, train, interp, want_pooled, tap_ids, first_trainable, layout, img_h, img_w = inputs[:11]
     ctx.set_materialize_grads(False)
+    # the backward runs with the policy its forward ran with, whatever model.recompute says by then
+    ctx.recompute = bool(inputs[11])
     ctx.handle, ctx.interp, ctx.want_pooled, ctx.tap_ids = handle, interp, want_pooled, list(tap_ids)
     ctx.image_hw = [int(img_h), int(img_w)] if layout == 2 else [int(pixel_values.shape[2]), int(pixel_values.shape[3])]
     ctx.ntaps, ctx.nparams, ctx.train = len(tap_ids), len(params), train
@@ -391,14 +402,16 @@ def _encoder_backward(ctx, grads):
     needs = [bool(n) for n in ctx.needs_input_grad[1]] if isinstance(ctx.needs_input_grad[1], (list, tuple)) \
         else [p.requires_grad for p in params]
     flats = torch.ops.siglip_hip.encoder_bwd(list(grads[:2 + nt]), taps, saved, hs_rest, params, ctx.handle, ctx.image_hw,
-                                             ctx.interp, ctx.want_pooled, ctx.tap_ids, needs)
+                                             ctx.interp, ctx.want_pooled, ctx.tap_ids, needs, ctx.recompute)
     chunks, _ = _module_of(ctx.handle)._bucket_layout(needs)
     pgrads: List[Optional[torch.Tensor]] = [None] * len(params)
     for flat, (_, _, entries) in zip(flats, chunks):
         for i, off, n in entries:
             pgrads[i] = flat[off:off + n].view(params[i].shape)
     # pytree structure of the inputs: an EMPTY int list is a list node, a non-empty one a leaf (torch/_library/autograd.py)
-    return None, pgrads, None, None, None, None, ([] if len(ctx.tap_ids) == 0 else None), None, None, None, None
+    # one entry per argument the caller passed (needs_input_grad has that structure): 11, or 12 with recompute
+    return (None, pgrads, None, None, None, None, ([] if len(ctx.tap_ids) == 0 else None), None, None, None, None) + \
+        (None,) * (len(ctx.needs_input_grad) - 11)
 
 
 encoder_fwd.register_autograd(_encoder_backward, setup_context=_encoder_setup_context)
@@ -432,7 +445,7 @@ def vision_tower_only(state_dict: dict) -> dict:
 class SiglipVisionModelHIP(nn.Module):
     """Drop-in for ``transformers.SiglipVisionModel`` on the reference's path (see module docstring)."""
 
-    def __init__(self, config, compute_dtype: str = "bf16"):
+    def __init__(self, config, compute_dtype: str = "bf16", recompute: bool = False):
         super().__init__()
         self.config = get_config(config)
         # "bf16": the benchmarked mode (bf16 MFMA operands, fp32 accumulate / residual stream / statistics);
@@ -444,9 +457,12 @@ class SiglipVisionModelHIP(nn.Module):
         # "mxfp8": INFERENCE ONLY: "bf16" with the four projection GEMMs of every block on MX-fp8 operands (e4m3 with one
         #          power-of-two scale per 32 inputs, twice the bf16 MFMA rate); for inference and frozen-backbone training
         #          (heads train on its detached features); a forward that would differentiate the encoder raises
+        # recompute=True: gradient checkpointing (see the ``recompute`` property)
         if compute_dtype not in COMPUTE_DTYPES:
             raise ValueError("compute_dtype must be 'bf16', 'fp32', 'bf16x3', 'fp16' or 'mxfp8'")
         self.compute_dtype = compute_dtype
+        self._recompute = False
+        self.recompute = recompute
         cfg = self.config
         self.embeddings = _EmbeddingParams(cfg)
         self.encoder = _EncoderParams(cfg)
@@ -469,9 +485,26 @@ class SiglipVisionModelHIP(nn.Module):
         (``Siglip2sidafrozen.py:757,762``): ``encoder.vision_model.embeddings`` / ``.encoder.layers``."""
         return self
 
+    @property
+    def recompute(self) -> bool:
+        """Activation policy of training forwards (gradient checkpointing).  False (default): every block's activations are
+        kept until the backward.  True: only the hidden states are kept and the backward recomputes each block from its
+        input (one extra LN1 .. fc1 per block, about a fifth of the step; bitwise the same gradients), so activation
+        memory drops to about a sixth.  Applies from the next forward; a backward always uses its forward's policy.
+        Inference forwards ignore it."""
+        return self._recompute
+
+    @recompute.setter
+    def recompute(self, value: bool) -> None:
+        if not isinstance(value, bool):
+            raise TypeError(f"recompute must be a bool, got {type(value).__name__}")
+        if value and self.compute_dtype in INFERENCE_ONLY:
+            raise ValueError(f"compute_dtype={self.compute_dtype!r} is inference-only: there is no backward to recompute for")
+        self._recompute = value
+
     @classmethod
     def from_pretrained(cls, name_or_path: str, compute_dtype: str = "bf16", seed: int = 0,
-                        allow_random_init: bool = False):
+                        allow_random_init: bool = False, recompute: bool = False):
         """Local directory (``config.json`` + ``model.safetensors``) or a known config name.  A published
         google/siglip(2) checkpoint is the FULL SiglipModel (``vision_model.*``, ``text_model.*``, ``logit_scale``,
         ``logit_bias``): like ``SiglipVisionModel.from_pretrained`` (Siglip2sidafrozen.py:753) only the vision tower is
@@ -483,7 +516,7 @@ class SiglipVisionModelHIP(nn.Module):
             raw = raw.get("vision_config", raw)
             fields = SiglipVisionConfig.__dataclass_fields__
             cfg = SiglipVisionConfig(**{k: v for k, v in raw.items() if k in fields})
-            model = cls(cfg, compute_dtype)
+            model = cls(cfg, compute_dtype, recompute)
             from safetensors.torch import load_file
             model.load_state_dict(vision_tower_only(load_file(os.path.join(name_or_path, "model.safetensors"))))
             return model
@@ -496,20 +529,29 @@ class SiglipVisionModelHIP(nn.Module):
             warnings.warn(f"SiglipVisionModelHIP.from_pretrained('{name_or_path}'): no checkpoint — using seeded RANDOM "
                           "weights (allow_random_init=True); outputs are not those of the pretrained model",
                           stacklevel=2)
-            model = cls(get_config(name_or_path), compute_dtype)
+            model = cls(get_config(name_or_path), compute_dtype, recompute)
             model.load_state_dict(seeded_state_dict(model.config, seed))
             return model
         raise OSError(f"{name_or_path} is neither a local checkpoint directory nor a known config name "
                       f"(no network access); known: {sorted(NAMED_CONFIGS)}")
 
-    def gradient_checkpointing_enable(self, **_):
-        """Accepted for interface parity (``Siglip2sidafrozen.py:1195-1196``) but does nothing, and says so once:
-        activations of a 128-image so400m batch (87 GB) fit the 288 GB of HBM3E, so nothing is recomputed."""
+    def gradient_checkpointing_enable(self, recompute: bool = False, **_):
+        """``recompute=True`` turns block recompute on (``self.recompute = True``).  The bare call, as the reference makes
+        it (``Siglip2sidafrozen.py:1195-1196``, on a frozen-prefix config where recompute only costs time), is accepted for
+        interface parity but does nothing, and says so once: activations of a 128-image so400m batch fit the 288 GB of
+        HBM3E, so nothing is recomputed unless asked for."""
+        if recompute:
+            self.recompute = True
+            return
         if not self._gradient_checkpointing:
             warnings.warn("SiglipVisionModelHIP.gradient_checkpointing_enable(): no-op — the HIP encoder keeps all "
-                          "activations (0.68 GB per so400m@384 image; 288 GB HBM3E) and never recomputes",
-                          stacklevel=2)
+                          "activations (0.82 GB per so400m@384 image; 288 GB HBM3E) and does not recompute; pass "
+                          "recompute=True (or set model.recompute = True) to trade compute for memory", stacklevel=2)
         self._gradient_checkpointing = True
+
+    def gradient_checkpointing_disable(self):
+        """Turn block recompute off (``self.recompute = False``)."""
+        self.recompute = False
 
     def load_state_dict(self, state_dict, strict: bool = True, **kw):
         """Accepts HF names with or without the ``vision_model.`` prefix, or an open_clip/timm vision tower
@@ -559,7 +601,7 @@ class SiglipVisionModelHIP(nn.Module):
                     break
         outs = torch.ops.siglip_hip.encoder_fwd(pixel_values, params, self._handle, train,
                                                 bool(interpolate_pos_encoding), self.use_head, uniq, first, layout, img_h,
-                                                img_w)
+                                                img_w, train and self._recompute)
         pooled = outs[0] if self.use_head else None
         hs = tuple(outs[2 + uniq.index(i)] for i in tap_ids) if tap_ids else None
         return VisionModelOutput(last_hidden_state=outs[1], pooler_output=pooled, hidden_states=hs)
@@ -593,6 +635,7 @@ class SiglipVisionModelHIP(nn.Module):
     def _reset_runtime_state(self):
         """Everything that belongs to THIS Python object (not to its parameters): C context, op handle, caches."""
         self._ctx = None
+        self._ctx_rc = None       # recompute context, created on first use (the shadows stay on _ctx)
         self._shadow = None
         self._shadow_key = None
         self._shadow_serial = 0
@@ -612,7 +655,7 @@ class SiglipVisionModelHIP(nn.Module):
 
     def __deepcopy__(self, memo):
         """copy.deepcopy (EMA / SWA wrappers): a fresh module with copied parameters and its own C context."""
-        new = type(self)(self.config, self.compute_dtype)
+        new = type(self)(self.config, self.compute_dtype, self.recompute)
         new.load_state_dict(self.state_dict())
         new.to(next(self.parameters()).device)
         for a, b in zip(new.parameters(), self.parameters()):
@@ -709,29 +752,43 @@ class SiglipVisionModelHIP(nn.Module):
             flats.append(flat)
         return flats
 
-    def _ensure_ctx(self):
+    def _ensure_ctx(self, recompute: bool = False):
+        """The C context of an activation policy: one per policy in use.  The shadow arena's layout does not depend on the
+        policy, so the shadows (and FusedAdamW's binding of them) live on the plain context."""
         if self._owner != id(self):      # object was copied field by field (copy.copy): do not share the original's state
             self._reset_runtime_state()
-        if self._ctx is None:
+        if self._ctx is None or (recompute and self._ctx_rc is None):
             lib = _lib.load()
             cfg = self.config
             c = _lib.SglConfig(cfg.hidden_size, cfg.intermediate_size, cfg.num_hidden_layers, cfg.num_attention_heads,
                                cfg.patch_size, cfg.native_grid, cfg.layer_norm_eps,
                                COMPUTE_DTYPES[self.compute_dtype],
                                1 if self.use_head else 0)
-            ctx = lib.sgl_create(C.byref(c))
-            if not ctx:
-                raise _lib.SglError(f"sgl_create: unsupported configuration {cfg}")
-            self._ctx = ctx
-        return self._ctx
+            if self._ctx is None:
+                ctx = lib.sgl_create(C.byref(c))
+                if not ctx:
+                    raise _lib.SglError(f"sgl_create: unsupported configuration {cfg}")
+                self._ctx = ctx
+            if recompute and self._ctx_rc is None:
+                ctx = lib.sgl_create_ex(C.byref(c), _lib.SGL_RECOMPUTE_BLOCKS)
+                if not ctx:
+                    raise _lib.SglError(f"sgl_create_ex: recompute unsupported for {cfg} ({self.compute_dtype})")
+                self._ctx_rc = ctx
+                P = cfg.patch_size
+                sh = [C.c_size_t(), C.c_size_t()]
+                for cx, out in zip((self._ctx, ctx), sh):
+                    _lib.check(lib.sgl_query_sizes(cx, 1, P, P, 0, C.byref(out), None, None), "sgl_query_sizes", cx)
+                assert sh[0].value == sh[1].value, "shadow arena layout must not depend on the recompute policy"
+        return self._ctx_rc if recompute else self._ctx
 
-    def _sizes(self, B, H, W, train):
-        key = (B, H, W, bool(train))
+    def _sizes(self, B, H, W, train, recompute=False):
+        key = (B, H, W, bool(train), bool(recompute))
         if key not in self._size_cache:
             lib = _lib.load()
+            ctx = self._ensure_ctx(bool(recompute))
             a, b, c = C.c_size_t(), C.c_size_t(), C.c_size_t()
-            st = lib.sgl_query_sizes(self._ensure_ctx(), B, H, W, 1 if train else 0, C.byref(a), C.byref(b), C.byref(c))
-            _lib.check(st, "sgl_query_sizes", self._ctx)
+            st = lib.sgl_query_sizes(ctx, B, H, W, 1 if train else 0, C.byref(a), C.byref(b), C.byref(c))
+            _lib.check(st, "sgl_query_sizes", ctx)
             self._size_cache[key] = (a.value, b.value, c.value)
         return self._size_cache[key]
 
@@ -846,8 +903,9 @@ class SiglipVisionModelHIP(nn.Module):
 
     def __del__(self):
         try:
-            if self._ctx is not None and _lib._lib is not None:
-                _lib._lib.sgl_destroy(self._ctx)
+            for ctx in (self._ctx, self._ctx_rc):
+                if ctx is not None and _lib._lib is not None:
+                    _lib._lib.sgl_destroy(ctx)
         except Exception:
             pass
 
@@ -917,6 +975,10 @@ class OpenClipStyleEncoder(nn.Module):
                     tail = tail.replace(a, b)
                 name = root + tail
             yield name, p
+
+    def set_grad_checkpointing(self, enable: bool = True):
+        """open_clip's name for gradient checkpointing: sets ``visual.recompute``."""
+        self.visual.recompute = bool(enable)
 
     def encode_image(self, x=None, normalize: bool = False, patches=None):
         out = self.visual(pixel_values=x, interpolate_pos_encoding=False, patches=patches)

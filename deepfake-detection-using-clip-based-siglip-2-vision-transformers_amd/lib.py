@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("SGL_LIB_PATH") or os.path.join(_HERE, "libsiglip_hip.
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "siglip_hip.h")
 
 SGL_DTYPE_F32, SGL_DTYPE_BF16, SGL_DTYPE_BF16X3, SGL_DTYPE_F16, SGL_DTYPE_MXFP8 = 0, 1, 2, 3, 5   # 4 is unassigned
+SGL_RECOMPUTE_NONE, SGL_RECOMPUTE_BLOCKS = 0, 1   # sgl_create_ex activation policies
 EPI_STORE, EPI_BIAS_GELU, EPI_RES_F32, EPI_QKV, EPI_GELU_BWD, EPI_POS_F32, EPI_F32 = range(7)
 STATUS = {0: "ok", -1: "bad shape", -2: "unsupported configuration", -3: "buffer too small", -4: "HIP error",
           -5: "null pointer"}
@@ -94,6 +95,7 @@ def load():
     _sig(lib, "sgl_abi_version", i, [])
     _sig(lib, "sgl_status_string", C.c_char_p, [i])
     _sig(lib, "sgl_create", C.c_void_p, [C.POINTER(SglConfig)])
+    _sig(lib, "sgl_create_ex", C.c_void_p, [C.POINTER(SglConfig), i])
     _sig(lib, "sgl_destroy", None, [C.c_void_p])
     _sig(lib, "sgl_last_hip_error", i, [C.c_void_p])
     _sig(lib, "sgl_query_sizes", i, [C.c_void_p, i, i, i, i, psz, psz, psz])

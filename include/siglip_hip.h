@@ -110,6 +110,13 @@ typedef struct {
 
 /* ---- lifetime ------------------------------------------------------------------------------------- */
 sgl_ctx* sgl_create(const sgl_config* cfg); /* NULL if the config is unsupported */
+/* Activation policy of a context (gradient checkpointing).  SGL_RECOMPUTE_NONE: a training forward keeps every block's
+ * activations in `saved` until the backward.  SGL_RECOMPUTE_BLOCKS: it keeps only each block's input (the hidden states)
+ * and sgl_backward_layer* recomputes the block; see "recompute context" below. */
+enum { SGL_RECOMPUTE_NONE = 0, SGL_RECOMPUTE_BLOCKS = 1 };
+/* sgl_create with an activation policy; sgl_create_ex(cfg, SGL_RECOMPUTE_NONE) is sgl_create(cfg).  NULL for any other
+ * policy value, and for SGL_DTYPE_MXFP8 with SGL_RECOMPUTE_BLOCKS (that mode never trains). */
+sgl_ctx* sgl_create_ex(const sgl_config* cfg, int recompute);
 void sgl_destroy(sgl_ctx* ctx);
 int sgl_last_hip_error(const sgl_ctx* ctx);
 const char* sgl_status_string(int status);
@@ -118,7 +125,22 @@ int sgl_abi_version(void);
 /* ---- sizes (bytes) for caller-allocated buffers ----------------------------------------------------- */
 /* shadow: compute-dtype copies of the weight matrices (padded, plus pre-transposed forms for dX GEMMs);
  * saved:  activations kept from forward for backward (0 when train == 0);
- * ws:     scratch; must stay untouched between sgl_backward_begin and the last sgl_backward_* call. */
+ * ws:     scratch; must stay untouched between sgl_backward_begin and the last sgl_backward_* call.
+ * Recompute context (sgl_create_ex(cfg, SGL_RECOMPUTE_BLOCKS)); every entry point keeps its signature and obeys it:
+ *   - train == 1: `saved` holds no per-block region (it keeps the patch operand, the resized position table, the
+ *     post-LayerNorm statistics and the pooling-head activations); `ws` is larger by ONE block region, which the training
+ *     forward and every sgl_backward_layer* call reuse.  train == 0 sizes and the shadow size are those of a plain context;
+ *   - a training forward (saved != NULL) also needs `ws` (ws_bytes of train == 1): it writes each block's activations into
+ *     the shared region (the GELU pre-activation nowhere) and every hidden-state slot as on a plain context; nothing in
+ *     `ws` has to survive from the forward to the backward;
+ *   - sgl_backward_layer*(layer) first recomputes block `layer` from its input hidden state into the shared region (LN1,
+ *     QKV, attention, out_proj + residual, LN2, fc1 + GELU; not fc2), then runs the plain backward of the block.  The call
+ *     sequence and the gradient carried in `ws` between calls are unchanged;
+ *   - training token limit: B * grid must not exceed floor((2^32 - 1) / R), R = the bytes of one row of the widest GEMM
+ *     operand, max(round_up(I, 128), 3 * hidden_size, round_up(3 * p^2, 64)) elements of the compute dtype (two bytes in
+ *     bf16 / fp16, four in fp32, 6 * round_up(that, 8) for the bf16x3 split operand), and not 2^22 - 1: the GEMMs refuse an
+ *     operand of 2^32 bytes.  Larger training shapes return SGL_ERR_BAD_SHAPE from sgl_query_sizes(train = 1),
+ *     sgl_forward* with saved != NULL and sgl_backward_*.  so400m in bf16: 493 447 tokens (B = 676 at 384 px). */
 int sgl_query_sizes(const sgl_ctx* ctx, int B, int H, int W, int train, size_t* shadow_bytes, size_t* saved_bytes,
                     size_t* ws_bytes);
 
