@@ -681,7 +681,8 @@ int sgl_forward_slots(sgl_ctx* ctx, const sgl_weights* w, const void* shadow, co
                       int B, int H, int W, int interpolate_pos, float* const* hs_slots, float* last_hidden,
                       float* pooled, void* saved, size_t saved_bytes, void* ws, size_t ws_bytes,
                       int first_trainable_block, sgl_stream stream) {
-  if (!ctx || !w || !shadow || !pixels || !hs_slots || !last_hidden) return SGL_ERR_NULL;
+  if (!ctx || !w || !shadow || !pixels || !hs_slots || !last_hidden || (ctx->L > 0 && !w->layers))
+    return SGL_ERR_NULL;
   if (!shape_ok(ctx, B, H, W)) return SGL_ERR_BAD_SHAPE;
   for (int l = 0; l <= ctx->L; ++l)
     if (!hs_slots[l]) return SGL_ERR_NULL;
@@ -696,7 +697,8 @@ int sgl_forward_slots(sgl_ctx* ctx, const sgl_weights* w, const void* shadow, co
   if (train && saved_bytes < lay.saved_total) return SGL_ERR_WORKSPACE;
   // a plain training forward keeps everything in `saved` and leaves the workspace alone; inference and a recompute
   // context's training forward (its block region) use it
-  if ((!train || lay.rc) && (!ws || ws_bytes < lay.ws_total)) return SGL_ERR_WORKSPACE;
+  if ((!train || lay.rc) && !ws) return SGL_ERR_NULL;
+  if ((!train || lay.rc) && ws_bytes < lay.ws_total) return SGL_ERR_WORKSPACE;
   if (!(lay.gh == ctx->g0 && lay.gw == ctx->g0) && !interpolate_pos) return SGL_ERR_BAD_SHAPE;
   hipStream_t s = (hipStream_t)stream;
   const int D = ctx->D, Ip = ctx->Ip, M = lay.M, N = lay.N, dt = ctx->dt, Hh = ctx->H, dh = ctx->dh, DP = ctx->DP;
@@ -969,6 +971,30 @@ int sgl_backward_begin_p(sgl_ctx* ctx, const sgl_weights* w, const void* shadow,
     dlast = dlast_buf;
   }
 
+  // A destination whose gradient is identically zero (no d_pooled: the pooling head; neither d_pooled nor d_last_hidden:
+  // post_layernorm) is written as zeros when overwriting, like every other destination, and left alone when accumulating.
+  if (!acc) {
+    auto zero = [&](float* p, size_t n) { return p ? hipMemsetAsync(p, 0, n * 4, s) : hipSuccess; };
+    const size_t Dz = (size_t)D, Iz = (size_t)I;
+    if (ctx->cfg.use_head && !d_pooled) {
+      CK(zero(g->probe, Dz));
+      CK(zero(g->in_proj_w, 3 * Dz * Dz));
+      CK(zero(g->in_proj_b, 3 * Dz));
+      CK(zero(g->out_proj_w, Dz * Dz));
+      CK(zero(g->out_proj_b, Dz));
+      CK(zero(g->head_ln_w, Dz));
+      CK(zero(g->head_ln_b, Dz));
+      CK(zero(g->head_fc1_w, Iz * Dz));
+      CK(zero(g->head_fc1_b, Iz));
+      CK(zero(g->head_fc2_w, Dz * Iz));
+      CK(zero(g->head_fc2_b, Dz));
+    }
+    if (!dlast) {
+      CK(zero(g->post_ln_w, Dz));
+      CK(zero(g->post_ln_b, Dz));
+    }
+  }
+
   // post_layernorm backward -> dx (fp32) and its low-precision copy (A operand of the last block's GEMMs)
   if (dlast) {
     RET(ln_backward(ctx, lay, ws, dlast, DT_F32, hsL, reinterpret_cast<const float*>(act + lay.a_pstats), M,
@@ -998,7 +1024,7 @@ int sgl_backward_layer(sgl_ctx* ctx, const sgl_weights* w, const void* shadow, c
 int sgl_backward_layer_p(sgl_ctx* ctx, const sgl_weights* w, const void* shadow, const sgl_grads* g, int layer, int B,
                          int H, int W, const float* hs_in, const float* d_tap, int need_dx, const void* saved,
                          size_t saved_bytes, void* ws, size_t ws_bytes, sgl_stream stream) {
-  if (!ctx || !w || !shadow || !g || !hs_in || !g->layers) return SGL_ERR_NULL;
+  if (!ctx || !w || !shadow || !g || !hs_in || !g->layers || !w->layers) return SGL_ERR_NULL;
   if (layer < 0 || layer >= ctx->L) return SGL_ERR_BAD_SHAPE;
   if (!train_shape_ok(ctx, B, H, W)) return SGL_ERR_BAD_SHAPE;
   Layout lay(ctx, B, H, W, true);
@@ -1157,10 +1183,12 @@ int sgl_backward(sgl_ctx* ctx, const sgl_weights* w, const void* shadow, const s
                  const void* saved, size_t saved_bytes, void* ws, size_t ws_bytes, sgl_stream stream) {
   if (!ctx) return SGL_ERR_NULL;
   const int L = ctx->L;
-  RET(sgl_backward_begin(ctx, w, shadow, g, B, H, W, hidden_states, d_last_hidden, d_pooled,
-                         d_taps ? d_taps[L] : nullptr, saved, saved_bytes, ws, ws_bytes, stream));
   int stop = train_embeddings ? 0 : first_trainable_block;
   if (stop < 0) stop = 0;
+  // what only the per-block step checks is checked here, before sgl_backward_begin enqueues anything
+  if (stop < L && w && g && (!w->layers || !g->layers)) return SGL_ERR_NULL;
+  RET(sgl_backward_begin(ctx, w, shadow, g, B, H, W, hidden_states, d_last_hidden, d_pooled,
+                         d_taps ? d_taps[L] : nullptr, saved, saved_bytes, ws, ws_bytes, stream));
   for (int l = L - 1; l >= stop; --l) {
     const int need_dx = (l > stop) || train_embeddings;
     RET(sgl_backward_layer(ctx, w, shadow, g, l, B, H, W, hidden_states, d_taps ? d_taps[l] : nullptr, need_dx, saved,

@@ -11,6 +11,8 @@
  * stub.  Rules common to every call:
  *   - returns 0 (SGL_OK) or a negative sgl_status; never throws, aborts, prints, allocates device memory or
  *     synchronises the device; sgl_last_hip_error(ctx) holds the hipError_t behind SGL_ERR_HIP;
+ *   - argument errors (SGL_ERR_NULL / BAD_SHAPE / UNSUPPORTED / WORKSPACE) are reported before any work is enqueued and
+ *     before any buffer is touched (tests/test_abi_contract_host.py makes every such call on a machine without a device);
  *   - all pointers are device pointers on the current device unless stated; work is enqueued on `stream`;
  *   - re-entrant per ctx as long as the calls on one ctx are stream-ordered; no thread-local state (PyTorch runs
  *     backward on an autograd worker thread);
@@ -34,11 +36,14 @@ enum { SGL_DTYPE_F32 = 0, SGL_DTYPE_BF16 = 1, SGL_DTYPE_BF16X3 = 2, SGL_DTYPE_F1
 
 typedef enum {
   SGL_OK = 0,
-  SGL_ERR_BAD_SHAPE = -1,   /* image not divisible into patches, non-square grid, dims not supported */
+  SGL_ERR_BAD_SHAPE = -1,   /* B <= 0, image smaller than one patch, too many tokens, a non-native grid without
+                               interpolate_pos, hs_slots / layer out of range.  Rectangular grids (H / p, W / p) and
+                               trailing pixels beyond the last whole patch are supported */
   SGL_ERR_UNSUPPORTED = -2, /* dtype / config outside what the kernels implement */
   SGL_ERR_WORKSPACE = -3,   /* saved / workspace / shadow buffer smaller than sgl_query_sizes reports */
   SGL_ERR_HIP = -4,         /* a HIP call failed: see sgl_last_hip_error */
-  SGL_ERR_NULL = -5         /* a required pointer is NULL */
+  SGL_ERR_NULL = -5         /* a required pointer is NULL (the layers tables of sgl_weights / sgl_grads and a workspace the
+                               call needs included) */
 } sgl_status;
 
 /* Immutable model description (HF SiglipVisionConfig fields; TF:models/siglip/configuration_siglip.py:90-99). */
@@ -91,7 +96,9 @@ typedef struct {
 } sgl_weights;
 
 /* Gradient destinations, same layouts as sgl_weights.  A NULL pointer means "frozen: do not compute".
- * accumulate != 0 adds into the buffers (gradient accumulation), otherwise they are overwritten. */
+ * accumulate != 0 adds into the buffers (gradient accumulation), otherwise they are overwritten: every non-NULL
+ * destination of a step that runs is written in full, with zeros where the gradient is identically zero (k_b always;
+ * the pooling head without d_pooled; post_layernorm with neither d_pooled nor d_last_hidden). */
 typedef struct {
   float *ln1_w, *ln1_b;
   float *q_w, *q_b, *k_w, *k_b, *v_w, *v_b, *o_w, *o_b;

@@ -6,7 +6,8 @@ small .npz outputs).  For every case it instantiates ``transformers.SiglipVision
 seeded weights, runs forward (+ backward of a fixed scalar loss) in fp32 on CPU, and stores inputs' seeds
 and expected outputs (full tensors when small, checksums + strided samples when large).
 
-    python oracle/gen_golden.py
+    python oracle/gen_golden.py                  every case of CASES and RECT_CASES
+    python oracle/gen_golden.py --only NAME      one case (adding a fixture leaves the committed ones byte-identical)
 """
 from __future__ import annotations
 
@@ -64,6 +65,26 @@ GRAD_NAMES = [
     "head.attention.out_proj.weight", "head.layernorm.bias", "head.mlp.fc1.weight", "head.mlp.fc2.bias",
 ]
 
+# rectangular images (res_h x res_w instead of res; tests/golden_util.RECT_CASES): the bf16 / fp16 yardsticks of the
+# rectangular position-table resize.  Their fixtures carry meta.res_h / meta.res_w instead of meta.res.
+RECT_CASES = [
+    dict(name="tiny_32x48_interp", config="tiny", seed=10, batch=2, res_h=32, res_w=48, interp=True, taps=(1, 3)),
+    dict(name="hostile_42x70_interp", config="hostile", seed=11, batch=2, res_h=42, res_w=70, interp=True, taps=(0, 2)),
+]
+
+
+def case_hw(case):
+    """(height, width) of a case: square cases give `res`, rectangular ones `res_h` / `res_w`."""
+    return (case["res"], case["res"]) if "res" in case else (case["res_h"], case["res_w"])
+
+
+def select_cases(cases, argv):
+    if "--only" in argv:
+        name = argv[argv.index("--only") + 1]
+        cases = [c for c in cases if c["name"] == name]
+    return cases
+
+
 FULL_LIMIT = 1 << 16
 NSAMP = 256
 
@@ -101,7 +122,7 @@ def main():
     oracle = _oracle()
     os.makedirs(os.path.join(ROOT, "tests", "golden"), exist_ok=True)
     torch.set_num_threads(8)
-    for case in CASES:
+    for case in select_cases(CASES + RECT_CASES, sys.argv):
         cfg = config.get_config(case["config"])
         sd = weights.seeded_state_dict(cfg, seed=case["seed"])
         hf = SiglipVisionModel(HFConfig(
@@ -110,7 +131,7 @@ def main():
             image_size=cfg.image_size, patch_size=cfg.patch_size, attn_implementation="eager"))
         hf.load_state_dict(sd, strict=True)
         hf.train()  # dropout is 0.0; train() so that gradient flow is the training path
-        x = weights.seeded_pixels(case["batch"], case["res"], case["res"], seed=case["seed"] + 1000)
+        x = weights.seeded_pixels(case["batch"], *case_hw(case), seed=case["seed"] + 1000)
         o = hf(pixel_values=x, output_hidden_states=True, interpolate_pos_encoding=case["interp"])
         out = {"pooler_output": o.pooler_output, "last_hidden_state": o.last_hidden_state,
                "hidden_states": o.hidden_states}
@@ -120,7 +141,10 @@ def main():
         rec["meta.config"] = np.asarray(case["config"])
         rec["meta.seed"] = np.int64(case["seed"])
         rec["meta.batch"] = np.int64(case["batch"])
-        rec["meta.res"] = np.int64(case["res"])
+        if "res" in case:
+            rec["meta.res"] = np.int64(case["res"])
+        else:
+            rec["meta.res_h"], rec["meta.res_w"] = np.int64(case["res_h"]), np.int64(case["res_w"])
         rec["meta.interp"] = np.int64(int(case["interp"]))
         rec["meta.taps"] = np.asarray(case["taps"], dtype=np.int64)
         rec["meta.transformers_version"] = np.asarray(__import__("transformers").__version__)

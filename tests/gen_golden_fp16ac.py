@@ -10,6 +10,7 @@ It also writes ``so400m27_384.npz``: so400m-patch14-384, all 27 blocks, B=1, tap
 outputs, the taps and a handful of gradients, plus ``fp16ac.*`` and ``bf16ac.*`` statistics on them.
 
 Run once in a CPU container that has ``transformers``:  python tests/gen_golden_fp16ac.py
+``--only NAME`` writes one case only (and skips the full-depth file unless NAME is so400m27_384).
 """
 from __future__ import annotations
 
@@ -85,11 +86,11 @@ def _errs(tag, rec, tensors, named, grads, out):
 
 def golden_cases():
     config, weights = gg._light_package()
-    for case in gg.CASES:
+    for case in gg.select_cases(gg.CASES + gg.RECT_CASES, sys.argv):
         rec = dict(np.load(os.path.join(ROOT, "tests", "golden", case["name"] + ".npz")))
         cfg = config.get_config(case["config"])
         hf = _hf_model(cfg, weights.seeded_state_dict(cfg, seed=case["seed"]))
-        x = weights.seeded_pixels(case["batch"], case["res"], case["res"], seed=case["seed"] + 1000)
+        x = weights.seeded_pixels(case["batch"], *gg.case_hw(case), seed=case["seed"] + 1000)
         tensors, loss = _run(hf, x, case, torch.float16)
         out = {k: rec[k] for k in rec if k.startswith("meta.")}
         _errs("fp16ac.", rec, tensors, dict(hf.named_parameters()), gg.GRAD_NAMES, out)
@@ -133,5 +134,5 @@ if __name__ == "__main__":
     os.makedirs(OUT_DIR, exist_ok=True)
     torch.set_num_threads(8)
     golden_cases()
-    if "--no-full" not in sys.argv:
+    if "--no-full" not in sys.argv and gg.select_cases([FULL_CASE], sys.argv):
         full_depth()

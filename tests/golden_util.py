@@ -8,6 +8,8 @@ GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 CASES = ["tiny_32", "tiny_48_interp", "hostile_42", "hostile_98_interp", "so400m1_384", "so400m1_224_interp",
          "base1_224"]
 SMALL_CASES = CASES[:4]
+# rectangular images (meta.res_h / meta.res_w): the bf16 / fp16 autocast yardsticks of the rectangular position resize
+RECT_CASES = ["tiny_32x48_interp", "hostile_42x70_interp"]
 
 
 def load(case):
@@ -15,9 +17,14 @@ def load(case):
 
 
 def meta(rec):
-    return dict(config=str(rec["meta.config"]), seed=int(rec["meta.seed"]), batch=int(rec["meta.batch"]),
-                res=int(rec["meta.res"]), interp=bool(int(rec["meta.interp"])),
-                taps=tuple(int(t) for t in rec["meta.taps"]))
+    """res_h / res_w are always there; res only for the square fixtures that store it."""
+    m = dict(config=str(rec["meta.config"]), seed=int(rec["meta.seed"]), batch=int(rec["meta.batch"]),
+             interp=bool(int(rec["meta.interp"])), taps=tuple(int(t) for t in rec["meta.taps"]))
+    if "meta.res" in rec:
+        m["res"] = m["res_h"] = m["res_w"] = int(rec["meta.res"])
+    else:
+        m["res_h"], m["res_w"] = int(rec["meta.res_h"]), int(rec["meta.res_w"])
+    return m
 
 
 def compare(rec, prefix, tensor, atol, rtol):

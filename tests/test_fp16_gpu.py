@@ -257,7 +257,7 @@ def _probe_loss(out, tap_ids):
 def _run_case(pkg, m, mode, hidden_state_ids=None):
     cfg = pkg.get_config(m["config"])
     model = _build(pkg, cfg, m["seed"], mode)
-    x = pkg.weights.seeded_pixels(m["batch"], m["res"], m["res"], seed=m["seed"] + 1000).cuda()
+    x = pkg.weights.seeded_pixels(m["batch"], m["res_h"], m["res_w"], seed=m["seed"] + 1000).cuda()
     if hidden_state_ids is None:
         out = model(pixel_values=x, output_hidden_states=True, interpolate_pos_encoding=m["interp"])
         hs = dict(enumerate(out.hidden_states))
@@ -304,6 +304,16 @@ def _check_against_fp16ac(rec, ac, tensors, named, label, bf16_bar=()):
 def test_fp16_error_within_2x_of_hf_fp16_autocast(case, pkg, hiplib):
     """|HIP_fp16 - fp32 golden| <= 2x (rel-L2) / 3x (max) |HF_fp16_autocast - fp32 golden| for pooled, last, every tap and
     every recorded gradient; and HIP-fp16's pooled / last errors <= 0.3x HIP-bf16's on the same inputs."""
+    _check_fp16_case(case, pkg)
+
+
+@pytest.mark.parametrize("case", gu.RECT_CASES)
+def test_fp16_rectangular_error_within_2x_of_hf_fp16_autocast(case, pkg, hiplib):
+    """The same yardstick and bars on rectangular images (rectangular position-table resize and its gradient)."""
+    _check_fp16_case(case, pkg)
+
+
+def _check_fp16_case(case, pkg):
     rec = gu.load(case)
     ac = dict(np.load(os.path.join(FP16_DIR, case + ".npz")))
     m = gu.meta(rec)

@@ -6,7 +6,7 @@ import torch
 import golden_util as gu
 
 
-@pytest.mark.parametrize("case", gu.CASES)
+@pytest.mark.parametrize("case", gu.CASES + gu.RECT_CASES)
 def test_oracle_matches_hf_golden(case, pkg, oracle):
     rec = gu.load(case)
     m = gu.meta(rec)
@@ -14,7 +14,7 @@ def test_oracle_matches_hf_golden(case, pkg, oracle):
     cfg = pkg.get_config(m["config"])
     sd = pkg.weights.seeded_state_dict(cfg, seed=m["seed"])
     sd = {k: v.clone().requires_grad_(True) for k, v in sd.items()}
-    x = pkg.weights.seeded_pixels(m["batch"], m["res"], m["res"], seed=m["seed"] + 1000)
+    x = pkg.weights.seeded_pixels(m["batch"], m["res_h"], m["res_w"], seed=m["seed"] + 1000)
     torch.set_num_threads(8)
     out = oracle.vision_forward(x, sd, cfg, True, m["interp"])
     atol, rtol = (2e-5, 2e-5) if not big else (5e-5, 5e-5)

@@ -49,10 +49,20 @@ def rel_l2(got, ref):
 @pytest.mark.parametrize("case", gu.CASES)
 def test_bf16_error_within_2x_of_hf_bf16_autocast(case, pkg, hiplib):
     """|HIP_bf16 - fp32 golden| <= 2 x |HF_bf16_autocast - fp32 golden| for pooled, last, every tap and 22 gradients."""
+    _check_bf16_case(case, pkg)
+
+
+@pytest.mark.parametrize("case", gu.RECT_CASES)
+def test_bf16_rectangular_error_within_2x_of_hf_bf16_autocast(case, pkg, hiplib):
+    """The same yardstick and bars on rectangular images (rectangular position-table resize and its gradient)."""
+    _check_bf16_case(case, pkg)
+
+
+def _check_bf16_case(case, pkg):
     rec = gu.load(case)
     m = gu.meta(rec)
     model = build(pkg, m["config"], m["seed"], "bf16")
-    x = pkg.weights.seeded_pixels(m["batch"], m["res"], m["res"], seed=m["seed"] + 1000).cuda()
+    x = pkg.weights.seeded_pixels(m["batch"], m["res_h"], m["res_w"], seed=m["seed"] + 1000).cuda()
     out = model(pixel_values=x, output_hidden_states=True, interpolate_pos_encoding=m["interp"])
     tensors = {"pooler_output": out.pooler_output, "last_hidden_state": out.last_hidden_state}
     for i, h in enumerate(out.hidden_states):
