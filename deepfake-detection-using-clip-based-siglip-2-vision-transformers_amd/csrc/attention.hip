@@ -816,7 +816,4 @@ hipError_t attn_bwd(const void* q, const void* k, const void* v, const void* out
   return hipErrorInvalidValue;
 }
 
-// delta_scratch of attn_bwd: {-lse*log2e, -delta*scale} PAIRS per (batch, head, query) = 2*B*H*N floats (since round 2)
-size_t attn_bwd_scratch_bytes(int, int B, int H, int N, int, int) { return (size_t)2 * B * H * N * sizeof(float); }
-
 }  // namespace sgl

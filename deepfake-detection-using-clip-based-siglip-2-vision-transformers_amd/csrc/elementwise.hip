@@ -170,39 +170,6 @@ hipError_t split3_stack(const float* src, int R, int C, int ld, void* dst, int C
   return hipGetLastError();
 }
 
-// dst[c][r] = src[r][c]; dst is [Cp][Rp] zero padded.  32x32 LDS tile so both sides stay coalesced.
-template <typename T>
-__global__ __launch_bounds__(256) void cast_transpose_kernel(const float* __restrict__ src, int R, int C, int ld,
-                                                             T* __restrict__ dst, int Cp, int Rp, int ldd) {
-  __shared__ float tile[32][33];
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8
-  const int r0 = blockIdx.y * 32, c0 = blockIdx.x * 32;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int r = r0 + ty + i * 8, c = c0 + tx;
-    tile[ty + i * 8][tx] = (r < R && c < C) ? src[(size_t)r * ld + c] : 0.f;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int c = c0 + ty + i * 8, r = r0 + tx;
-    if (c < Cp && r < Rp) Elem<T>::st(dst + (size_t)c * ldd + r, tile[tx][ty + i * 8]);
-  }
-}
-
-hipError_t cast_transpose_pad(const float* src, int R, int C, int ld, void* dst, int dst_dtype, int Cp, int Rp,
-                              int ldd, hipStream_t s) {
-  if ((size_t)Rp * Cp == 0) return hipSuccess;
-  dim3 grid((Cp + 31) / 32, (Rp + 31) / 32), block(256);
-  if (dst_dtype == DT_BF16)
-    hipLaunchKernelGGL(cast_transpose_kernel<bf16>, grid, block, 0, s, src, R, C, ld, (bf16*)dst, Cp, Rp, ldd);
-  else if (dst_dtype == DT_F16)
-    hipLaunchKernelGGL(cast_transpose_kernel<f16>, grid, block, 0, s, src, R, C, ld, (f16*)dst, Cp, Rp, ldd);
-  else
-    hipLaunchKernelGGL(cast_transpose_kernel<float>, grid, block, 0, s, src, R, C, ld, (float*)dst, Cp, Rp, ldd);
-  return hipGetLastError();
-}
-
 // ---- all weight shadows of one transformer block (or of the pooling head) in ONE launch -----------------------------------
 // The per-step refresh of the compute-dtype weight copies (what autocast re-does every step in the reference,
 // Siglip2sidafrozen.py:1375) used to be 13 launches per block (cast_pad + cast_transpose_pad per matrix, copy_f32 per bias):

@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <string.h>
 
+#include <algorithm>
 #include <new>
 #include <vector>
 
@@ -51,11 +52,7 @@ struct sgl_ctx {
   int mx = 0;      // SGL_DTYPE_MXFP8: dt == DT_BF16 everywhere except the block GEMMs, which read MX-fp8 operands
   int Dp = 0;      // MX mode: K padding of the D-wide operands, round_up(D, 128) (the MX GEMM's K-step)
   int recompute = 0;   // SGL_RECOMPUTE_BLOCKS: training keeps no per-block activations; sgl_backward_layer* recomputes them
-  // scratch for the split operands of the GEMM being launched: set by every entry point from the CALLER's buffers (the ctx
-  // owns no memory); calls on one ctx are stream-ordered (siglip_hip.h), so one pair per ctx suffices
-  void* sp_a = nullptr;
-  void* sp_b = nullptr;
-  int last_hip = 0;
+  int last_hip = 0;   // the only member written after sgl_create_ex
   // shadow arena layout (config-only)
   size_t sh_wpatch = 0;
   std::vector<ShadowLayer> sh_layers;
@@ -71,27 +68,34 @@ constexpr int kMaxLayers = 128;
 // splits * N1 * N2 * 4 bytes with tiles*splits <= 256 workgroups of 256x256 outputs: never more than 64 MiB
 constexpr size_t kSplitWsBytes = (size_t)256 * 256 * 256 * 4;
 
+// one of q / k / v of a whole batch, head-major [B][H][N][DP]
+inline size_t head_bytes(const sgl_ctx* c, int B, int N) { return (size_t)B * c->H * N * c->DP * c->es; }
+
 // Per-call activation / workspace layout (pure function of ctx, B, grid, train).
 struct Layout {
-  int B, gh, gw, N, M;
-  bool train;
+  int B = 0, gh = 0, gw = 0, N = 0, M = 0;
+  bool train = false;
   // activation region ("saved" when training, a slice of ws otherwise)
-  size_t a_im2col, a_pos;
-  size_t a_layer0, a_layer_stride;
-  size_t r_stats1, r_h1, r_qkv, r_attn, r_lse, r_xmid, r_stats2, r_h2, r_u, r_a, r_attq;  // relative to a layer base
-  size_t a_pstats, a_lastlp, a_kvh, a_qp, a_probs, a_ao, a_h0, a_hstats, a_hl, a_hu, a_ha;
+  size_t a_im2col = 0, a_pos = 0;
+  size_t a_layer0 = 0, a_layer_stride = 0;
+  size_t r_stats1 = 0, r_h1 = 0, r_qkv = 0, r_attn = 0, r_lse = 0, r_xmid = 0, r_stats2 = 0, r_h2 = 0, r_u = 0, r_a = 0,
+         r_attq = 0;  // relative to a layer base
+  size_t a_pstats = 0, a_lastlp = 0, a_kvh = 0, a_qp = 0, a_probs = 0, a_ao = 0, a_h0 = 0, a_hstats = 0, a_hl = 0, a_hu = 0,
+         a_ha = 0;
   size_t a_spa = 0, a_spb = 0, w_spa = 0, w_spb = 0;   // bf16x3 split operands (forward: in act; backward: in ws)
-  size_t act_total;
-  // backward scratch (ws)
-  size_t w_dx, w_g, w_du, w_dh, w_dqkv, w_delta, w_splitws, w_lnpart, w_cspart, w_dlast, w_gsum, w_csum;
-  size_t w_hg, w_hdu, w_hdh, w_hdao, w_hdqpart, w_hdqp, w_hdh0;
-  size_t ws_bwd_total;
-  size_t saved_total, ws_total, ws_act_off;
+  size_t act_total = 0;
+  // backward scratch (ws): all zero unless training
+  size_t w_dx = 0, w_g = 0, w_du = 0, w_dh = 0, w_dqkv = 0, w_delta = 0, w_splitws = 0, w_lnpart = 0, w_cspart = 0,
+         w_dlast = 0, w_gsum = 0, w_csum = 0;
+  size_t w_hg = 0, w_hdu = 0, w_hdh = 0, w_hdao = 0, w_hdqpart = 0, w_hdqp = 0, w_hdh0 = 0;
+  size_t ws_bwd_total = 0;
+  size_t saved_total = 0, ws_total = 0, ws_act_off = 0;
   // recompute context, training: ONE block region in ws (w_blk) that the forward and every backward block reuse; no
   // per-block region in `saved`, and the forward's bf16x3 split scratch is the backward's (w_spa / w_spb)
-  bool rc;
+  bool rc = false;
   size_t w_blk = 0;
 
+  Layout() = default;
   Layout(const sgl_ctx* c, int B_, int Himg, int Wimg, bool train_) {
     B = B_;
     train = train_;
@@ -111,7 +115,7 @@ struct Layout {
     const bool mx = c->mx;
     r_stats1 = r.take(Mz * 2 * 4);
     r_h1 = r.take(mx ? Mz * Dp + Mz * Dp / 32 : Mz * D * es);
-    r_qkv = r.take((size_t)3 * B * c->H * N * c->DP * es);
+    r_qkv = r.take(3 * head_bytes(c, B, N));
     r_attn = r.take(Mz * D * es);
     r_lse = r.take((size_t)B * c->H * N * 4);
     r_xmid = r.take(Mz * D * 4);
@@ -124,7 +128,7 @@ struct Layout {
     a_layer0 = a.take(rc ? 0 : train ? r.off * (size_t)c->L : r.off);
     a_pstats = a.take(Mz * 2 * 4);
     a_lastlp = a.take(Mz * D * es);
-    a_kvh = a.take((size_t)2 * B * c->H * N * c->DP * es);
+    a_kvh = a.take(2 * head_bytes(c, B, N));
     a_qp = a.take(D * 4);
     a_probs = a.take((size_t)B * c->H * N * 4);
     a_ao = a.take((size_t)B * D * es);
@@ -134,10 +138,11 @@ struct Layout {
     a_hu = a.take((size_t)B * Ip * es);
     a_ha = a.take((size_t)B * Ip * es);
     // widest GEMM operand: [rows, W] with rows <= max(M, W) on the activation side, [W, max(D, Kp)] on the weight side
-    const size_t Wd = (size_t)round_up((int)(Ip > 3 * D ? Ip : 3 * D) > c->Kp ? (int)(Ip > 3 * D ? Ip : 3 * D) : c->Kp, 8);
-    const size_t sp_act = 3 * (Mz > (size_t)B ? Mz : (size_t)B) * Wd * 2;
-    const size_t sp_wgt = 3 * Wd * (size_t)round_up((int)D > c->Kp ? (int)D : c->Kp, 8) * 2;
-    const size_t sp_bytes = sp_act > sp_wgt ? sp_act : sp_wgt;
+    const size_t widest = std::max(Ip, 3 * D), Kp = (size_t)c->Kp;
+    const size_t Wd = (size_t)round_up((int)std::max(widest, Kp), 8);
+    const size_t sp_act = 3 * std::max(Mz, (size_t)B) * Wd * 2;
+    const size_t sp_wgt = 3 * Wd * (size_t)round_up((int)std::max(D, Kp), 8) * 2;
+    const size_t sp_bytes = std::max(sp_act, sp_wgt);
     if (c->split && !rc) {
       a_spa = a.take(sp_bytes);
       a_spb = a.take(sp_bytes);
@@ -146,7 +151,6 @@ struct Layout {
 
     Bump w;
     if (train) {
-      const size_t widest = (size_t)(Ip > 3 * D ? Ip : 3 * D);
       w_dx = w.take(Mz * D * 4);
       w_g = w.take(Mz * D * es);
       w_du = w.take(Mz * Ip * es);
@@ -157,7 +161,7 @@ struct Layout {
       w_lnpart = w.take((size_t)layernorm_bwd_blocks(M) * 3 * D * 4);
       w_gsum = w.take(D * 4);        // column sums of the current d hidden_states (bias grad of the GEMM below)
       w_csum = w.take((size_t)((M + 127) / 128) * widest * 4);   // per-row-tile column sums out of a GEMM epilogue
-      w_cspart = w.take((size_t)(colsum_chunks(M) > 16 ? colsum_chunks(M) : 16) * widest * 4);   // also vecmat_f32's 16 row chunks
+      w_cspart = w.take((size_t)std::max(colsum_chunks(M), 16) * widest * 4);   // also vecmat_f32's 16 row chunks
       w_dlast = w.take(Mz * D * 4);
       w_hg = w.take((size_t)B * D * es);
       w_hdu = w.take((size_t)B * Ip * es);
@@ -171,9 +175,6 @@ struct Layout {
         w_spb = w.take(sp_bytes);
       }
       if (rc) w_blk = w.take(r.off);
-    } else {
-      w_dx = w_g = w_du = w_dh = w_dqkv = w_delta = w_splitws = w_lnpart = w_cspart = w_dlast = w_gsum = w_csum = 0;
-      w_hg = w_hdu = w_hdh = w_hdao = w_hdqpart = w_hdqp = w_hdh0 = 0;
     }
     ws_bwd_total = w.off;
     if (train) {
@@ -188,8 +189,6 @@ struct Layout {
     if (ws_total == 0) ws_total = 256;
   }
   size_t layer_base(int l) const { return a_layer0 + a_layer_stride * (size_t)l; }
-  // block l's activation region: in the activation arena, or (recompute, training) the one region in ws
-  char* block(char* act, void* ws, int l) const { return rc ? at(ws, w_blk) : act + layer_base(l); }
 };
 
 #define CK(expr)                        \
@@ -201,122 +200,225 @@ struct Layout {
     }                                   \
   } while (0)
 
-hipError_t gemm_nt(const sgl_ctx* c, const void* A, int lda, const void* B, int ldb, int M, int N, int K, int epi,
-                   int out_dt, const EpiParams& p, hipStream_t s) {
-  if (c->dt == DT_BF16) return gemm_nt_bf16(A, lda, B, ldb, M, N, K, epi, out_dt, p, s);
-  if (c->dt == DT_F16) return gemm_nt_f16(A, lda, B, ldb, M, N, K, epi, out_dt, p, s);
-  if (c->split && M > 0 && N > 0) {   // bf16x3: one MFMA GEMM over [hi|hi|lo] x [hi|lo|hi], three times the reduction length
-    const int Ks = round_up(K, 8);
-    hipError_t e = split3_rows((const float*)A, M, K, lda, c->sp_a, Ks, 0, s);
-    if (e != hipSuccess) return e;
-    e = split3_rows((const float*)B, N, K, ldb, c->sp_b, Ks, 1, s);
-    if (e != hipSuccess) return e;
-    return gemm_nt_bf16(c->sp_a, 3 * Ks, c->sp_b, 3 * Ks, M, N, 3 * Ks, epi, out_dt, p, s);
-  }
-  return gemm_f32_generic((const float*)A, lda, 1, (const float*)B, ldb, 1, M, N, K, epi, out_dt, p, s);
-}
-
-// dW[N1,N2] (+)= A[:, :N1]^T · B[:, :N2]   (reduction over the Mred rows)
-hipError_t gemm_tn(const sgl_ctx* c, const void* A, int lda, const void* B, int ldb, int Mred, int N1, int N2,
-                   float* out, int ldo, int accumulate, hipStream_t s, void* split_ws = nullptr,
-                   size_t split_ws_bytes = 0) {
-  EpiParams p;
-  p.out = out;
-  p.ldo = ldo;
-  p.accumulate = accumulate;
-  if (mfma16(c->dt)) {
-    const int tiles = ((N1 + 127) / 128) * ((N2 + 127) / 128);
-    int splits = (512 + tiles - 1) / tiles;
-    const int max_splits = Mred / 512 > 0 ? Mred / 512 : 1;
-    if (splits > max_splits) splits = max_splits;
-    if (splits > 16) splits = 16;
-    if (c->dt == DT_F16)
-      return gemm_tn_f16(A, lda, B, ldb, Mred, N1, N2, splits, p, s, reinterpret_cast<float*>(split_ws), split_ws_bytes);
-    return gemm_tn_bf16(A, lda, B, ldb, Mred, N1, N2, splits, p, s, reinterpret_cast<float*>(split_ws), split_ws_bytes);
-  }
-  if (c->split && Mred > 0 && N1 > 0 && N2 > 0) {   // bf16x3: [hi;hi;lo]^T x [hi;lo;hi], reduction over 3*Mred rows
-    const int l1 = round_up(N1, 8), l2 = round_up(N2, 8);
-    hipError_t e = split3_stack((const float*)A, Mred, N1, lda, c->sp_a, l1, 0, s);
-    if (e != hipSuccess) return e;
-    e = split3_stack((const float*)B, Mred, N2, ldb, c->sp_b, l2, 1, s);
-    if (e != hipSuccess) return e;
-    const int tiles = ((N1 + 127) / 128) * ((N2 + 127) / 128);
-    int splits = (512 + tiles - 1) / tiles;
-    const int max_splits = (3 * Mred) / 512 > 0 ? (3 * Mred) / 512 : 1;
-    if (splits > max_splits) splits = max_splits;
-    if (splits > 16) splits = 16;
-    return gemm_tn_bf16(c->sp_a, l1, c->sp_b, l2, 3 * Mred, N1, N2, splits, p, s, reinterpret_cast<float*>(split_ws),
-                        split_ws_bytes);
-  }
-  return gemm_f32_generic((const float*)A, 1, lda, (const float*)B, 1, ldb, N1, N2, Mred, EPI_F32, DT_F32, p, s);
-}
-
 #define RET(expr)                 \
   do {                            \
     int r_ = (expr);              \
     if (r_ != SGL_OK) return r_;  \
   } while (0)
 
+// ---- epilogue constructors: one per epilogue the encoder uses; whatever one does not set keeps EpiParams' default -----
+// EPI_STORE: out[T] = acc
+EpiParams epi_store(void* out, int ldo) {
+  EpiParams p;
+  p.out = out;
+  p.ldo = ldo;
+  return p;
+}
+// EPI_F32: out[f32] = acc (+ bias)
+EpiParams epi_f32(float* out, int ldo, const float* bias = nullptr) {
+  EpiParams p;
+  p.out = out;
+  p.ldo = ldo;
+  p.bias = bias;
+  return p;
+}
+// EPI_F32: out[f32] (+)= acc
+EpiParams epi_f32_acc(float* out, int ldo, int accumulate) {
+  EpiParams p;
+  p.out = out;
+  p.ldo = ldo;
+  p.accumulate = accumulate;
+  return p;
+}
+// EPI_RES_F32: out[f32] = res + acc + bias (out and res share the row stride ld)
+EpiParams epi_res_f32(float* out, const float* bias, const float* res, int ld) {
+  EpiParams p;
+  p.out = out;
+  p.ldo = ld;
+  p.bias = bias;
+  p.res = res;
+  p.ldr = ld;
+  return p;
+}
+// EPI_POS_F32: out[f32] = acc + bias + pos[row % pos_rows]
+EpiParams epi_pos_f32(float* out, int ldo, const float* bias, const float* pos, int pos_rows) {
+  EpiParams p;
+  p.out = out;
+  p.ldo = ldo;
+  p.bias = bias;
+  p.pos = pos;
+  p.pos_rows = pos_rows;
+  return p;
+}
+// EPI_BIAS_GELU: a = gelu(acc + bias); u (nullable: not stored) = the pre-activation, or gelu'(u) when grad_form (the
+// EPI_GELU_BWD launch that reads it must agree)
+EpiParams epi_bias_gelu(void* u, void* a, int ld, const float* bias, int grad_form) {
+  EpiParams p;
+  p.out = u;
+  p.gelu_grad_form = grad_form;
+  p.ldo = ld;
+  p.out2 = a;
+  p.ldo2 = ld;
+  p.bias = bias;
+  return p;
+}
+// EPI_BIAS_GELU of the MX GEMM: gelu(acc + bias) quantized into the MX operand `out` (its scales are a launch argument)
+EpiParams epi_bias_gelu_mx(void* out, int ldo, const float* bias) {
+  EpiParams p;
+  p.out = out;
+  p.ldo = ldo;
+  p.bias = bias;
+  return p;
+}
+// EPI_GELU_BWD: out = acc * gelu'(u) with u (or gelu'(u) when grad_form) in aux.  colsum (nullable, MFMA kernels only): the
+// deterministic per-128-row-tile column sums of the output, [ceil(M / 128)][ld]; the caller zeroes it first and folds it after
+EpiParams epi_gelu_bwd(void* out, const void* aux, int ld, int grad_form, float* colsum = nullptr) {
+  EpiParams p;
+  p.out = out;
+  p.ldo = ld;
+  p.aux = aux;
+  p.ldaux = ld;
+  p.gelu_grad_form = grad_form;
+  if (colsum) {
+    p.colsum = colsum;
+    p.colsum_ld = ld;
+  }
+  return p;
+}
+
+// the split-K count of a dW GEMM: enough splits for 512 workgroups, each reducing at least 512 rows, 16 at the most
+int tn_splits(int N1, int N2, int rows) {
+  const int tiles = ((N1 + 127) / 128) * ((N2 + 127) / 128);
+  return std::min({(512 + tiles - 1) / tiles, std::max(rows / 512, 1), 16});
+}
+
+// Everything one entry-point call works on, yielded by begin_call() once the arguments have passed their checks and
+// handed to every stage.  The ctx is immutable after sgl_create_ex (but for last_hip) and owns no memory; what belongs to
+// this call, the bf16x3 split scratch included, is here, so a GEMM cannot be launched on another call's buffers.
+struct Call {
+  sgl_ctx* ctx = nullptr;   // non-const only because CK records last_hip through it
+  Layout lay;
+  hipStream_t s = nullptr;
+  const void* shadow = nullptr;
+  char* act = nullptr;   // activation arena: `saved` (written by the forward only), or its slice of ws at inference
+  void* ws = nullptr;
+  void* sp_a = nullptr;   // bf16x3: split operands of the GEMM being launched (calls on one ctx are stream-ordered)
+  void* sp_b = nullptr;
+
+  char* wsp(size_t off) const { return at(ws, off); }
+  float* wsf(size_t off) const { return reinterpret_cast<float*>(at(ws, off)); }
+  float* actf(size_t off) const { return reinterpret_cast<float*>(act + off); }
+  const char* sh(size_t off) const { return at(shadow, off); }
+  const float* shf(size_t off) const { return reinterpret_cast<const float*>(at(shadow, off)); }
+  size_t head_bytes() const { return ::head_bytes(ctx, lay.B, lay.N); }
+  // block l's activation region: in the activation arena, or (recompute, training) the one region in ws
+  char* block(int l) const { return lay.rc ? wsp(lay.w_blk) : act + lay.layer_base(l); }
+
+  // EPI_QKV: head-major scatter of acc + bias into out[which][B][H][N][DP], geometry of this call
+  EpiParams epi_qkv(void* out, const float* bias) const {
+    EpiParams p;
+    p.out = out;
+    p.bias = bias;
+    p.tokens = lay.N;
+    p.heads = ctx->H;
+    p.head_dim = ctx->dh;
+    p.head_dim_pad = ctx->DP;
+    p.batch = lay.B;
+    return p;
+  }
+
+  // C[M,N] = A[M,K] · B[N,K]^T through epilogue epi
+  hipError_t gemm_nt(const void* A, int lda, const void* B, int ldb, int M, int N, int K, int epi, int out_dt,
+                     const EpiParams& p) const {
+    if (ctx->dt == DT_BF16) return gemm_nt_bf16(A, lda, B, ldb, M, N, K, epi, out_dt, p, s);
+    if (ctx->dt == DT_F16) return gemm_nt_f16(A, lda, B, ldb, M, N, K, epi, out_dt, p, s);
+    if (ctx->split && M > 0 && N > 0) {   // bf16x3: one MFMA GEMM over [hi|hi|lo] x [hi|lo|hi], three times the reduction length
+      const int Ks = round_up(K, 8);
+      hipError_t e = split3_rows((const float*)A, M, K, lda, sp_a, Ks, 0, s);
+      if (e != hipSuccess) return e;
+      e = split3_rows((const float*)B, N, K, ldb, sp_b, Ks, 1, s);
+      if (e != hipSuccess) return e;
+      return gemm_nt_bf16(sp_a, 3 * Ks, sp_b, 3 * Ks, M, N, 3 * Ks, epi, out_dt, p, s);
+    }
+    return gemm_f32_generic((const float*)A, lda, 1, (const float*)B, ldb, 1, M, N, K, epi, out_dt, p, s);
+  }
+
+  // dW[N1,N2] (+)= A[:, :N1]^T · B[:, :N2]   (reduction over the Mred rows); split_slabs: the K-splits write the private slabs
+  // of w_splitws and are summed in a fixed order (the GEMMs over all M tokens), instead of adding into out
+  hipError_t gemm_tn(const void* A, int lda, const void* B, int ldb, int Mred, int N1, int N2, float* out, int ldo,
+                     int accumulate, bool split_slabs) const {
+    const EpiParams p = epi_f32_acc(out, ldo, accumulate);
+    float* slabs = split_slabs ? wsf(lay.w_splitws) : nullptr;
+    const size_t slab_bytes = split_slabs ? kSplitWsBytes : 0;
+    if (ctx->dt == DT_F16)
+      return gemm_tn_f16(A, lda, B, ldb, Mred, N1, N2, tn_splits(N1, N2, Mred), p, s, slabs, slab_bytes);
+    if (ctx->dt == DT_BF16)
+      return gemm_tn_bf16(A, lda, B, ldb, Mred, N1, N2, tn_splits(N1, N2, Mred), p, s, slabs, slab_bytes);
+    if (ctx->split && Mred > 0 && N1 > 0 && N2 > 0) {   // bf16x3: [hi;hi;lo]^T x [hi;lo;hi], reduction over 3*Mred rows
+      const int l1 = round_up(N1, 8), l2 = round_up(N2, 8);
+      hipError_t e = split3_stack((const float*)A, Mred, N1, lda, sp_a, l1, 0, s);
+      if (e != hipSuccess) return e;
+      e = split3_stack((const float*)B, Mred, N2, ldb, sp_b, l2, 1, s);
+      if (e != hipSuccess) return e;
+      return gemm_tn_bf16(sp_a, l1, sp_b, l2, 3 * Mred, N1, N2, tn_splits(N1, N2, 3 * Mred), p, s, slabs, slab_bytes);
+    }
+    return gemm_f32_generic((const float*)A, 1, lda, (const float*)B, 1, ldb, N1, N2, Mred, EPI_F32, DT_F32, p, s);
+  }
+
+  // bias gradient: out[0:n_out] (+)= colsum(in[:, 0:N]); a null out is skipped
+  int bias_grad(const void* in, int ld, int M, int N, int n_out, float* out, int accumulate) const {
+    if (!out) return SGL_OK;
+    CK(colsum(in, ctx->dt, ld, M, N, n_out, wsf(lay.w_cspart), out, accumulate, s));
+    return SGL_OK;
+  }
+
+  // LayerNorm backward + dgamma/dbeta reduction.  colsum_out (nullable, [D]) = column sums of the dx written, i.e. the
+  // bias gradient of the Linear whose output gradient dx is.
+  int ln_backward(const void* dy, int dy_dt, const float* x, const float* stats, int rows, const float* gamma,
+                  const float* dres, float* dx, void* dx_lp, float* dgamma, float* dbeta, int accumulate,
+                  float* colsum_out = nullptr) const {
+    const int D = ctx->D;
+    const bool want = dgamma || dbeta || colsum_out;
+    const int nblk = layernorm_bwd_blocks(rows);
+    float* part = wsf(lay.w_lnpart);
+    CK(layernorm_bwd(dy, dy_dt, D, x, stats, stats + rows, gamma, dres, dx, dx_lp, ctx->dt, want ? part : nullptr, nblk,
+                     rows, D, s));
+    CK(reduce_partials3(part, nblk, 3 * D, dgamma, dbeta, colsum_out, D, accumulate, accumulate, 0, s));
+    return SGL_OK;
+  }
+};
+
 // One encoder block of the MX-fp8 mode: x -> xo through xmid, with the four projection GEMMs on MX operands.
 //   LN1 -> MX (r_h1) ; QKV GEMM -> bf16 head-major (r_qkv) ; bf16 attention -> r_attn ; quantize -> MX (r_attq) ;
 //   out_proj + bias + x -> xmid ; LN2 -> MX (r_h2) ; fc1 + bias, GELU, quantized in the epilogue -> MX (r_a) ;
 //   fc2 + bias + xmid -> xo
-int mx_block(sgl_ctx* ctx, const Layout& lay, const sgl_layer_weights& lw, const ShadowLayer& sl, const void* shadow,
-             char* lb, const float* x, float* xo, float* xmid, int B, hipStream_t s) {
-  const int D = ctx->D, Ip = ctx->Ip, Dp = ctx->Dp, M = lay.M, N = lay.N, Hh = ctx->H, dh = ctx->dh, DP = ctx->DP;
+int mx_block(const Call& c, const sgl_layer_weights& lw, const ShadowLayer& sl, char* lb, const float* x, float* xo) {
+  sgl_ctx* ctx = c.ctx;
+  const Layout& lay = c.lay;
+  hipStream_t s = c.s;
+  const int D = ctx->D, Ip = ctx->Ip, Dp = ctx->Dp, M = lay.M;
   const float eps = ctx->cfg.layer_norm_eps;
   const size_t Mz = (size_t)M;
   char* h1 = lb + lay.r_h1;
+  char* q = lb + lay.r_qkv;
   char* aq = lb + lay.r_attq;
+  float* xmid = reinterpret_cast<float*>(lb + lay.r_xmid);
   char* h2 = lb + lay.r_h2;
   char* ua = lb + lay.r_a;
   CK(layernorm_fwd_mx(x, lw.ln1_w, lw.ln1_b, h1, h1 + Mz * Dp, M, D, Dp, eps, s));
-  {
-    EpiParams p;
-    p.out = lb + lay.r_qkv;
-    p.bias = reinterpret_cast<const float*>(at(shadow, sl.bqkv));
-    p.tokens = N;
-    p.heads = Hh;
-    p.head_dim = dh;
-    p.head_dim_pad = DP;
-    p.batch = B;
-    CK(gemm_nt_mx(h1, h1 + Mz * Dp, at(shadow, sl.wqkv), at(shadow, sl.wqkv_s), M, 3 * D, Dp, EPI_QKV, p, nullptr, s));
-  }
-  {
-    const size_t hsz = (size_t)B * Hh * N * DP * ctx->es;
-    char* q = lb + lay.r_qkv;
-    CK(attn_fwd(q, q + hsz, q + 2 * hsz, DT_BF16, lb + lay.r_attn, reinterpret_cast<float*>(lb + lay.r_lse), B, Hh, N, dh,
-                DP, 0, s));
-  }
+  CK(gemm_nt_mx(h1, h1 + Mz * Dp, c.sh(sl.wqkv), c.sh(sl.wqkv_s), M, 3 * D, Dp, EPI_QKV, c.epi_qkv(q, c.shf(sl.bqkv)),
+                nullptr, s));
+  CK(attn_fwd(q, q + c.head_bytes(), q + 2 * c.head_bytes(), DT_BF16, lb + lay.r_attn,
+              reinterpret_cast<float*>(lb + lay.r_lse), lay.B, ctx->H, lay.N, ctx->dh, ctx->DP, 0, s));
   // a 32-block of the attention output straddles heads when head_dim = 72: a pass of its own, not an attention epilogue
   CK(quantize_mx(lb + lay.r_attn, DT_BF16, D, M, D, Dp, aq, aq + Mz * Dp, s));
-  {
-    EpiParams p;
-    p.out = xmid;
-    p.ldo = D;
-    p.bias = lw.o_b;
-    p.res = x;
-    p.ldr = D;
-    CK(gemm_nt_mx(aq, aq + Mz * Dp, at(shadow, sl.wo), at(shadow, sl.wo_s), M, D, Dp, EPI_RES_F32, p, nullptr, s));
-  }
+  CK(gemm_nt_mx(aq, aq + Mz * Dp, c.sh(sl.wo), c.sh(sl.wo_s), M, D, Dp, EPI_RES_F32, epi_res_f32(xmid, lw.o_b, x, D),
+                nullptr, s));
   CK(layernorm_fwd_mx(xmid, lw.ln2_w, lw.ln2_b, h2, h2 + Mz * Dp, M, D, Dp, eps, s));
-  {
-    EpiParams p;
-    p.out = ua;
-    p.ldo = Ip;
-    p.bias = reinterpret_cast<const float*>(at(shadow, sl.b1));
-    CK(gemm_nt_mx(h2, h2 + Mz * Dp, at(shadow, sl.w1), at(shadow, sl.w1_s), M, Ip, Dp, EPI_BIAS_GELU, p,
-                  ua + Mz * Ip, s));
-  }
-  {
-    EpiParams p;
-    p.out = xo;
-    p.ldo = D;
-    p.bias = lw.fc2_b;
-    p.res = xmid;
-    p.ldr = D;
-    CK(gemm_nt_mx(ua, ua + Mz * Ip, at(shadow, sl.w2), at(shadow, sl.w2_s), M, D, Ip, EPI_RES_F32, p, nullptr, s));
-  }
+  CK(gemm_nt_mx(h2, h2 + Mz * Dp, c.sh(sl.w1), c.sh(sl.w1_s), M, Ip, Dp, EPI_BIAS_GELU,
+                epi_bias_gelu_mx(ua, Ip, c.shf(sl.b1)), ua + Mz * Ip, s));
+  CK(gemm_nt_mx(ua, ua + Mz * Ip, c.sh(sl.w2), c.sh(sl.w2_s), M, D, Ip, EPI_RES_F32, epi_res_f32(xo, lw.fc2_b, xmid, D),
+                nullptr, s));
   return SGL_OK;
 }
 
@@ -324,55 +426,79 @@ int mx_block(sgl_ctx* ctx, const Layout& lay, const sgl_layer_weights& lw, const
 // -> out_proj + bias + x = xmid -> LN2 -> fc1 + bias, GELU into the block region lb (u = the pre-activation, or gelu'(u)
 // in bf16 / fp16 mode, only when want_u).  The training forward and the recompute of sgl_backward_layer* share it, so
 // both launch the same kernels on the same shapes and produce the same bits.
-int block_to_fc1(sgl_ctx* ctx, const Layout& lay, const sgl_layer_weights& lw, const ShadowLayer& sl, const void* shadow,
-                 char* lb, const float* x, int B, bool want_u, hipStream_t s) {
-  const int D = ctx->D, Ip = ctx->Ip, M = lay.M, N = lay.N, dt = ctx->dt, Hh = ctx->H, dh = ctx->dh, DP = ctx->DP;
+int block_to_fc1(const Call& c, const sgl_layer_weights& lw, const ShadowLayer& sl, char* lb, const float* x, bool want_u) {
+  sgl_ctx* ctx = c.ctx;
+  const Layout& lay = c.lay;
+  hipStream_t s = c.s;
+  const int D = ctx->D, Ip = ctx->Ip, M = lay.M, dt = ctx->dt;
+  const float eps = ctx->cfg.layer_norm_eps;
   float* st1 = reinterpret_cast<float*>(lb + lay.r_stats1);
   float* st2 = reinterpret_cast<float*>(lb + lay.r_stats2);
+  char* q = lb + lay.r_qkv;
   float* xmid = reinterpret_cast<float*>(lb + lay.r_xmid);
-  CK(layernorm_fwd(x, lw.ln1_w, lw.ln1_b, lb + lay.r_h1, dt, D, st1, st1 + M, M, D, ctx->cfg.layer_norm_eps, s));
-  {
-    // head-major scatter [3][B][H][N][DP] in the GEMM epilogue (EPI_QKV).  Round 3 measured the alternative the kernels
-    // also support (ld_qkv > 0: plain token-major [M][3D] store, attention gathers each head's 144-byte row segments):
-    // QKV GEMM 853 -> 754 us per launch at B = 128, but attention forward +5.8 % and backward +5.9 % (every DMA instruction
-    // touches 14 cache lines instead of 8, and K/V are re-read by six workgroups per head and three kernels): +0.75 ms
-    // per step net, so the 144-byte granularity is paid once, on the write side.
-    EpiParams p;
-    p.out = lb + lay.r_qkv;
-    p.bias = reinterpret_cast<const float*>(at(shadow, sl.bqkv));
-    p.tokens = N;
-    p.heads = Hh;
-    p.head_dim = dh;
-    p.head_dim_pad = DP;
-    p.batch = B;
-    CK(gemm_nt(ctx, lb + lay.r_h1, D, at(shadow, sl.wqkv), D, M, 3 * D, D, EPI_QKV, dt, p, s));
+  CK(layernorm_fwd(x, lw.ln1_w, lw.ln1_b, lb + lay.r_h1, dt, D, st1, st1 + M, M, D, eps, s));
+  // head-major scatter [3][B][H][N][DP] in the GEMM epilogue (EPI_QKV).  Round 3 measured the alternative the kernels
+  // also support (ld_qkv > 0: plain token-major [M][3D] store, attention gathers each head's 144-byte row segments):
+  // QKV GEMM 853 -> 754 us per launch at B = 128, but attention forward +5.8 % and backward +5.9 % (every DMA instruction
+  // touches 14 cache lines instead of 8, and K/V are re-read by six workgroups per head and three kernels): +0.75 ms
+  // per step net, so the 144-byte granularity is paid once, on the write side.
+  CK(c.gemm_nt(lb + lay.r_h1, D, c.sh(sl.wqkv), D, M, 3 * D, D, EPI_QKV, dt, c.epi_qkv(q, c.shf(sl.bqkv))));
+  CK(attn_fwd(q, q + c.head_bytes(), q + 2 * c.head_bytes(), ctx->split ? DT_F32_MFMA : dt, lb + lay.r_attn,
+              reinterpret_cast<float*>(lb + lay.r_lse), lay.B, ctx->H, lay.N, ctx->dh, ctx->DP, 0, s));
+  CK(c.gemm_nt(lb + lay.r_attn, D, c.sh(sl.wo), D, M, D, D, EPI_RES_F32, DT_F32, epi_res_f32(xmid, lw.o_b, x, D)));
+  CK(layernorm_fwd(xmid, lw.ln2_w, lw.ln2_b, lb + lay.r_h2, dt, D, st2, st2 + M, M, D, eps, s));
+  // r_u holds gelu'(u) in bf16 / fp16 mode (the backward only ever needs that)
+  CK(c.gemm_nt(lb + lay.r_h2, D, c.sh(sl.w1), D, M, Ip, D, EPI_BIAS_GELU, dt,
+               epi_bias_gelu(want_u ? lb + lay.r_u : nullptr, lb + lay.r_a, Ip, c.shf(sl.b1), mfma16(dt))));
+  return SGL_OK;
+}
+
+// Patch embedding: pixels -> im2col operand (kept in act for the backward) -> GEMM + bias + position table = out
+int embed_forward(const Call& c, const sgl_weights* w, const float* pixels, int channels_last, int H, int W, float* out) {
+  sgl_ctx* ctx = c.ctx;
+  const Layout& lay = c.lay;
+  hipStream_t s = c.s;
+  const int D = ctx->D, Kp = ctx->Kp, M = lay.M;
+  char* cols = c.act + lay.a_im2col;
+  if (channels_last == 2) {   // ready patch-major operand (sgl_op_preprocess): keep a copy where backward expects it
+    CK(hipMemcpyAsync(cols, pixels, (size_t)M * Kp * ctx->es, hipMemcpyDeviceToDevice, s));
+  } else {
+    CK(im2col(pixels, channels_last, cols, ctx->dt, lay.B, H, W, ctx->P, Kp, s));
   }
-  {
-    const size_t hsz = (size_t)B * Hh * N * DP * ctx->es;
-    char* q = lb + lay.r_qkv;
-    CK(attn_fwd(q, q + hsz, q + 2 * hsz, ctx->split ? DT_F32_MFMA : dt, lb + lay.r_attn,
-                reinterpret_cast<float*>(lb + lay.r_lse), B, Hh, N, dh, DP, 0, s));
+  const float* pos = w->pos;
+  if (!(lay.gh == ctx->g0 && lay.gw == ctx->g0)) {
+    float* pr = c.actf(lay.a_pos);
+    CK(pos_resize(w->pos, ctx->g0, pr, lay.gh, lay.gw, D, s));
+    pos = pr;
   }
-  {
-    EpiParams p;
-    p.out = xmid;
-    p.ldo = D;
-    p.bias = lw.o_b;
-    p.res = x;
-    p.ldr = D;
-    CK(gemm_nt(ctx, lb + lay.r_attn, D, at(shadow, sl.wo), D, M, D, D, EPI_RES_F32, DT_F32, p, s));
-  }
-  CK(layernorm_fwd(xmid, lw.ln2_w, lw.ln2_b, lb + lay.r_h2, dt, D, st2, st2 + M, M, D, ctx->cfg.layer_norm_eps, s));
-  {
-    EpiParams p;
-    p.out = want_u ? lb + lay.r_u : nullptr;
-    p.gelu_grad_form = mfma16(dt);   // r_u holds gelu'(u) in bf16 / fp16 mode (the backward only ever needs that)
-    p.ldo = Ip;
-    p.out2 = lb + lay.r_a;
-    p.ldo2 = Ip;
-    p.bias = reinterpret_cast<const float*>(at(shadow, sl.b1));
-    CK(gemm_nt(ctx, lb + lay.r_h2, D, at(shadow, sl.w1), D, M, Ip, D, EPI_BIAS_GELU, dt, p, s));
-  }
+  CK(c.gemm_nt(cols, Kp, c.sh(ctx->sh_wpatch), Kp, M, D, Kp, EPI_POS_F32, DT_F32,
+               epi_pos_f32(out, D, w->patch_b, pos, lay.N)));
+  return SGL_OK;
+}
+
+// Attention-pool head: pooled = h0 + fc2(gelu(fc1(LN(h0)))), h0 = out_proj(attn(probe · Wq, kv(last_hidden)))
+int head_forward(const Call& c, const sgl_weights* w, const float* last_hidden, float* pooled) {
+  sgl_ctx* ctx = c.ctx;
+  const Layout& lay = c.lay;
+  hipStream_t s = c.s;
+  const int D = ctx->D, Ip = ctx->Ip, M = lay.M, B = lay.B, dt = ctx->dt;
+  char* act = c.act;
+  char* kv = act + lay.a_kvh;
+  float* qp = c.actf(lay.a_qp);
+  float* h0 = c.actf(lay.a_h0);
+  float* hst = c.actf(lay.a_hstats);
+  CK(cast_f32(last_hidden, act + lay.a_lastlp, dt, (size_t)M * D, s));
+  CK(c.gemm_nt(act + lay.a_lastlp, D, c.sh(ctx->sh_hwkv), D, M, 2 * D, D, EPI_QKV, dt, c.epi_qkv(kv, w->in_proj_b + D)));
+  CK(gemm_f32_generic(w->probe, D, 1, w->in_proj_w, D, 1, 1, D, D, EPI_F32, DT_F32, epi_f32(qp, D, w->in_proj_b), s));
+  CK(pool_attn_fwd(qp, kv, kv + c.head_bytes(), dt, act + lay.a_ao, c.actf(lay.a_probs), B, ctx->H, lay.N, ctx->dh,
+                   ctx->DP, s));
+  CK(c.gemm_nt(act + lay.a_ao, D, c.sh(ctx->sh_hwo), D, B, D, D, EPI_F32, DT_F32, epi_f32(h0, D, w->out_proj_b)));
+  CK(layernorm_fwd(h0, w->head_ln_w, w->head_ln_b, act + lay.a_hl, dt, D, hst, hst + B, B, D, ctx->cfg.layer_norm_eps, s));
+  // the head keeps the pre-activation u in every mode (gelu_grad_form = 0), unlike the blocks
+  CK(c.gemm_nt(act + lay.a_hl, D, c.sh(ctx->sh_hw1), D, B, Ip, D, EPI_BIAS_GELU, dt,
+               epi_bias_gelu(act + lay.a_hu, act + lay.a_ha, Ip, c.shf(ctx->sh_hb1), 0)));
+  CK(c.gemm_nt(act + lay.a_ha, Ip, c.sh(ctx->sh_hw2), Ip, B, D, Ip, EPI_RES_F32, DT_F32,
+               epi_res_f32(pooled, w->head_fc2_b, h0, D)));
   return SGL_OK;
 }
 
@@ -401,6 +527,41 @@ bool shape_ok(const sgl_ctx* c, int B, int H, int W) {
 bool train_shape_ok(const sgl_ctx* c, int B, int H, int W) {
   if (!shape_ok(c, B, H, W)) return false;
   return !c->recompute || (long)B * (H / c->P) * (W / c->P) <= rc_max_tokens(c);
+}
+
+// The prologue of every encoder call, after the entry point's own pointer checks (ctx among them) and before anything is
+// enqueued: shape, mode, Layout, arena pointers and sizes, then the Call.  A forward trains iff it is given `saved`; a
+// plain training forward keeps everything there and leaves the workspace alone, inference and a recompute context's
+// training forward (its block region) use ws; a backward needs both arenas.  The order of the checks is the order in
+// which a call invalid in several arguments reports them, and differs between the two families as it always has.
+enum Pass { FORWARD, BACKWARD };
+int begin_call(Call& c, Pass pass, sgl_ctx* ctx, const void* shadow, int B, int H, int W, const void* saved,
+               size_t saved_bytes, void* ws, size_t ws_bytes, sgl_stream stream) {
+  const bool train = pass == BACKWARD || saved != nullptr;
+  if (!(train ? train_shape_ok(ctx, B, H, W) : shape_ok(ctx, B, H, W))) return SGL_ERR_BAD_SHAPE;
+  if (train && ctx->mx) return SGL_ERR_UNSUPPORTED;   // the MX-fp8 mode has no backward
+  c.lay = Layout(ctx, B, H, W, train);
+  const Layout& lay = c.lay;
+  if (pass == BACKWARD) {
+    if (!saved || !ws) return SGL_ERR_NULL;
+    if (saved_bytes < lay.saved_total || ws_bytes < lay.ws_total) return SGL_ERR_WORKSPACE;
+  } else {
+    const bool needs_ws = !train || lay.rc;
+    if (train && saved_bytes < lay.saved_total) return SGL_ERR_WORKSPACE;
+    if (needs_ws && !ws) return SGL_ERR_NULL;
+    if (needs_ws && ws_bytes < lay.ws_total) return SGL_ERR_WORKSPACE;
+  }
+  c.ctx = ctx;
+  c.s = (hipStream_t)stream;
+  c.shadow = shadow;
+  c.ws = ws;
+  c.act = train ? reinterpret_cast<char*>(const_cast<void*>(saved)) : at(ws, lay.ws_act_off);
+  if (ctx->split) {   // forward: in act, or in ws on a recompute context; backward: in ws
+    const bool in_ws = pass == BACKWARD || lay.rc;
+    c.sp_a = in_ws ? at(ws, lay.w_spa) : c.act + lay.a_spa;
+    c.sp_b = in_ws ? at(ws, lay.w_spb) : c.act + lay.a_spb;
+  }
+  return SGL_OK;
 }
 
 }  // namespace
@@ -683,6 +844,7 @@ int sgl_forward_slots(sgl_ctx* ctx, const sgl_weights* w, const void* shadow, co
                       int first_trainable_block, sgl_stream stream) {
   if (!ctx || !w || !shadow || !pixels || !hs_slots || !last_hidden || (ctx->L > 0 && !w->layers))
     return SGL_ERR_NULL;
+  // the slot table's own checks report after a bad shape and around the mode check, both of which begin_call repeats
   if (!shape_ok(ctx, B, H, W)) return SGL_ERR_BAD_SHAPE;
   for (int l = 0; l <= ctx->L; ++l)
     if (!hs_slots[l]) return SGL_ERR_NULL;
@@ -692,127 +854,29 @@ int sgl_forward_slots(sgl_ctx* ctx, const sgl_weights* w, const void* shadow, co
     for (int l = 0; l < ctx->L; ++l)
       for (int k = l + 1; k <= ctx->L; ++k)
         if (hs_slots[l] == hs_slots[k]) return SGL_ERR_BAD_SHAPE;
-  if (train && !train_shape_ok(ctx, B, H, W)) return SGL_ERR_BAD_SHAPE;
-  Layout lay(ctx, B, H, W, train);
-  if (train && saved_bytes < lay.saved_total) return SGL_ERR_WORKSPACE;
-  // a plain training forward keeps everything in `saved` and leaves the workspace alone; inference and a recompute
-  // context's training forward (its block region) use it
-  if ((!train || lay.rc) && !ws) return SGL_ERR_NULL;
-  if ((!train || lay.rc) && ws_bytes < lay.ws_total) return SGL_ERR_WORKSPACE;
+  Call c;
+  RET(begin_call(c, FORWARD, ctx, shadow, B, H, W, saved, saved_bytes, ws, ws_bytes, stream));
+  const Layout& lay = c.lay;
   if (!(lay.gh == ctx->g0 && lay.gw == ctx->g0) && !interpolate_pos) return SGL_ERR_BAD_SHAPE;
-  hipStream_t s = (hipStream_t)stream;
-  const int D = ctx->D, Ip = ctx->Ip, M = lay.M, N = lay.N, dt = ctx->dt, Hh = ctx->H, dh = ctx->dh, DP = ctx->DP;
-  char* act = train ? reinterpret_cast<char*>(saved) : at(ws, lay.ws_act_off);
-  auto hs = [&](int l) { return hs_slots[l]; };
-  if (ctx->split) {
-    ctx->sp_a = lay.rc ? at(ws, lay.w_spa) : act + lay.a_spa;
-    ctx->sp_b = lay.rc ? at(ws, lay.w_spb) : act + lay.a_spb;
-  }
 
-  // ---- embeddings
-  if (channels_last == 2) {   // ready patch-major operand (sgl_op_preprocess): keep a copy where backward expects it
-    CK(hipMemcpyAsync(act + lay.a_im2col, pixels, (size_t)M * ctx->Kp * ctx->es, hipMemcpyDeviceToDevice, s));
-  } else {
-    CK(im2col(pixels, channels_last, act + lay.a_im2col, dt, B, H, W, ctx->P, ctx->Kp, s));
-  }
-  const float* pos = w->pos;
-  if (!(lay.gh == ctx->g0 && lay.gw == ctx->g0)) {
-    float* pr = reinterpret_cast<float*>(act + lay.a_pos);
-    CK(pos_resize(w->pos, ctx->g0, pr, lay.gh, lay.gw, D, s));
-    pos = pr;
-  }
-  {
-    EpiParams p;
-    p.out = hs(0);
-    p.ldo = D;
-    p.bias = w->patch_b;
-    p.pos = pos;
-    p.pos_rows = N;
-    CK(gemm_nt(ctx, act + lay.a_im2col, ctx->Kp, at(shadow, ctx->sh_wpatch), ctx->Kp, M, D, ctx->Kp, EPI_POS_F32,
-               DT_F32, p, s));
-  }
-  // ---- blocks
+  RET(embed_forward(c, w, pixels, channels_last, H, W, hs_slots[0]));
   for (int l = 0; l < ctx->L; ++l) {
     const sgl_layer_weights& lw = w->layers[l];
     const ShadowLayer& sl = ctx->sh_layers[l];
-    char* lb = lay.block(act, ws, l);
-    float* x = hs(l);
-    float* xo = hs(l + 1);
-    float* xmid = reinterpret_cast<float*>(lb + lay.r_xmid);
+    char* lb = c.block(l);
     if (ctx->mx) {
-      RET(mx_block(ctx, lay, lw, sl, shadow, lb, x, xo, xmid, B, s));
+      RET(mx_block(c, lw, sl, lb, hs_slots[l], hs_slots[l + 1]));
       continue;
     }
     // u is kept for the blocks the backward will differentiate, unless it recomputes them
-    RET(block_to_fc1(ctx, lay, lw, sl, shadow, lb, x, B, train && !lay.rc && l >= first_trainable_block, s));
-    {
-      EpiParams p;
-      p.out = xo;
-      p.ldo = D;
-      p.bias = lw.fc2_b;
-      p.res = xmid;
-      p.ldr = D;
-      CK(gemm_nt(ctx, lb + lay.r_a, Ip, at(shadow, sl.w2), Ip, M, D, Ip, EPI_RES_F32, DT_F32, p, s));
-    }
+    RET(block_to_fc1(c, lw, sl, lb, hs_slots[l], train && !lay.rc && l >= first_trainable_block));
+    CK(c.gemm_nt(lb + lay.r_a, ctx->Ip, c.sh(sl.w2), ctx->Ip, lay.M, ctx->D, ctx->Ip, EPI_RES_F32, DT_F32,
+                 epi_res_f32(hs_slots[l + 1], lw.fc2_b, reinterpret_cast<const float*>(lb + lay.r_xmid), ctx->D)));
   }
-  // ---- post layernorm + attention-pool head
-  float* pst = reinterpret_cast<float*>(act + lay.a_pstats);
-  CK(layernorm_fwd(hs(ctx->L), w->post_ln_w, w->post_ln_b, last_hidden, DT_F32, D, pst, pst + M, M, D,
-                   ctx->cfg.layer_norm_eps, s));
-  if (ctx->cfg.use_head && pooled) {
-    CK(cast_f32(last_hidden, act + lay.a_lastlp, dt, (size_t)M * D, s));
-    {
-      EpiParams p;
-      p.out = act + lay.a_kvh;
-      p.bias = w->in_proj_b + D;
-      p.tokens = N;
-      p.heads = Hh;
-      p.head_dim = dh;
-      p.head_dim_pad = DP;
-      p.batch = B;
-      CK(gemm_nt(ctx, act + lay.a_lastlp, D, at(shadow, ctx->sh_hwkv), D, M, 2 * D, D, EPI_QKV, dt, p, s));
-    }
-    float* qp = reinterpret_cast<float*>(act + lay.a_qp);
-    {
-      EpiParams p;
-      p.out = qp;
-      p.ldo = D;
-      p.bias = w->in_proj_b;
-      CK(gemm_f32_generic(w->probe, D, 1, w->in_proj_w, D, 1, 1, D, D, EPI_F32, DT_F32, p, s));
-    }
-    const size_t hsz = (size_t)B * Hh * N * DP * ctx->es;
-    CK(pool_attn_fwd(qp, act + lay.a_kvh, act + lay.a_kvh + hsz, dt, act + lay.a_ao,
-                     reinterpret_cast<float*>(act + lay.a_probs), B, Hh, N, dh, DP, s));
-    float* h0 = reinterpret_cast<float*>(act + lay.a_h0);
-    {
-      EpiParams p;
-      p.out = h0;
-      p.ldo = D;
-      p.bias = w->out_proj_b;
-      CK(gemm_nt(ctx, act + lay.a_ao, D, at(shadow, ctx->sh_hwo), D, B, D, D, EPI_F32, DT_F32, p, s));
-    }
-    float* hst = reinterpret_cast<float*>(act + lay.a_hstats);
-    CK(layernorm_fwd(h0, w->head_ln_w, w->head_ln_b, act + lay.a_hl, dt, D, hst, hst + B, B, D,
-                     ctx->cfg.layer_norm_eps, s));
-    {
-      EpiParams p;
-      p.out = act + lay.a_hu;
-      p.ldo = Ip;
-      p.out2 = act + lay.a_ha;
-      p.ldo2 = Ip;
-      p.bias = reinterpret_cast<const float*>(at(shadow, ctx->sh_hb1));
-      CK(gemm_nt(ctx, act + lay.a_hl, D, at(shadow, ctx->sh_hw1), D, B, Ip, D, EPI_BIAS_GELU, dt, p, s));
-    }
-    {
-      EpiParams p;
-      p.out = pooled;
-      p.ldo = D;
-      p.bias = w->head_fc2_b;
-      p.res = h0;
-      p.ldr = D;
-      CK(gemm_nt(ctx, act + lay.a_ha, Ip, at(shadow, ctx->sh_hw2), Ip, B, D, Ip, EPI_RES_F32, DT_F32, p, s));
-    }
-  }
+  float* pst = c.actf(lay.a_pstats);
+  CK(layernorm_fwd(hs_slots[ctx->L], w->post_ln_w, w->post_ln_b, last_hidden, DT_F32, ctx->D, pst, pst + lay.M, lay.M,
+                   ctx->D, ctx->cfg.layer_norm_eps, c.s));
+  if (ctx->cfg.use_head && pooled) RET(head_forward(c, w, last_hidden, pooled));
   return SGL_OK;
 }
 
@@ -821,34 +885,177 @@ int sgl_forward_slots(sgl_ctx* ctx, const sgl_weights* w, const void* shadow, co
 // -------------------------------------------------------------------------------------------------------
 namespace {
 
-// bias gradient helper: out[0:n_out] (+)= colsum(in[:, 0:N])
-int bias_grad(sgl_ctx* ctx, const Layout& lay, void* ws, const void* in, int ld, int M, int N, int n_out, float* out,
-              int accumulate, hipStream_t s) {
-  if (!out) return SGL_OK;
-  CK(colsum(in, ctx->dt, ld, M, N, n_out, reinterpret_cast<float*>(at(ws, lay.w_cspart)), out, accumulate, s));
+// Pooling head backward from d_pooled: the head's parameter gradients, and dlast [M][D] = the gradient w.r.t. the
+// post_layernorm output, d_last_hidden (nullable) included
+int head_backward(const Call& c, const sgl_weights* w, const sgl_grads* g, const float* d_pooled,
+                  const float* d_last_hidden, float* dlast) {
+  sgl_ctx* ctx = c.ctx;
+  const Layout& lay = c.lay;
+  hipStream_t s = c.s;
+  const int D = ctx->D, I = ctx->I, Ip = ctx->Ip, M = lay.M, B = lay.B, dt = ctx->dt;
+  const int acc = g->accumulate;
+  const char* act = c.act;
+  const char* kv = act + lay.a_kvh;
+  const float* qp = c.actf(lay.a_qp);
+  void* hg = c.wsp(lay.w_hg);
+  void* hdu = c.wsp(lay.w_hdu);
+  void* hdh = c.wsp(lay.w_hdh);
+  float* hdao = c.wsf(lay.w_hdao);
+  // pooled = h0 + fc2(gelu(fc1(LN(h0))))
+  CK(cast_f32(d_pooled, hg, dt, (size_t)B * D, s));
+  CK(c.gemm_nt(hg, D, c.sh(ctx->sh_hw2_t), D, B, Ip, D, EPI_GELU_BWD, dt, epi_gelu_bwd(hdu, act + lay.a_hu, Ip, 0)));
+  if (g->head_fc2_w) CK(c.gemm_tn(hg, D, act + lay.a_ha, Ip, B, D, I, g->head_fc2_w, I, acc, false));
+  RET(c.bias_grad(hg, D, B, D, D, g->head_fc2_b, acc));
+  CK(c.gemm_nt(hdu, Ip, c.sh(ctx->sh_hw1_t), Ip, B, D, Ip, EPI_STORE, dt, epi_store(hdh, D)));
+  if (g->head_fc1_w) CK(c.gemm_tn(hdu, Ip, act + lay.a_hl, D, B, I, D, g->head_fc1_w, D, acc, false));
+  RET(c.bias_grad(hdu, Ip, B, Ip, I, g->head_fc1_b, acc));
+  // LN backward (+ residual d_pooled): dh0, low-precision copy into hg
+  RET(c.ln_backward(hdh, dt, c.actf(lay.a_h0), c.actf(lay.a_hstats), B, w->head_ln_w, d_pooled, c.wsf(lay.w_hdh0), hg,
+                    g->head_ln_w, g->head_ln_b, acc));
+  // h0 = ao · Woᵀ + bo
+  CK(c.gemm_nt(hg, D, c.sh(ctx->sh_hwo_t), D, B, D, D, EPI_F32, DT_F32, epi_f32(hdao, D)));
+  if (g->out_proj_w) CK(c.gemm_tn(hg, D, act + lay.a_ao, D, B, D, D, g->out_proj_w, D, acc, false));
+  RET(c.bias_grad(hg, D, B, D, D, g->out_proj_b, acc));
+  // attention pool backward
+  void* dkv = c.wsp(lay.w_dqkv);  // [M][2D]
+  float* dqpart = c.wsf(lay.w_hdqpart);
+  float* dqp = c.wsf(lay.w_hdqp);
+  CK(pool_attn_bwd(qp, kv, kv + c.head_bytes(), dt, c.actf(lay.a_probs), hdao, dkv, dqpart, B, ctx->H, lay.N, ctx->dh,
+                   ctx->DP, s));
+  if (g->probe || g->in_proj_w || g->in_proj_b) {
+    CK(batch_sum(dqpart, B, (size_t)D, dqp, 0, s));
+    if (g->in_proj_w)   // d Wq[i,j] = dqp[i] * probe[j]
+      CK(gemm_f32_generic(dqp, 1, 1, w->probe, 1, 1, D, D, 1, EPI_F32, DT_F32, epi_f32_acc(g->in_proj_w, D, acc), s));
+    if (g->in_proj_b) CK(batch_sum(dqp, 1, (size_t)D, g->in_proj_b, acc, s));
+    if (g->probe)   // dprobe[j] = sum_i dqp[i] Wq[i,j]
+      CK(gemm_f32_generic(dqp, D, 1, w->in_proj_w, 1, D, 1, D, D, EPI_F32, DT_F32, epi_f32_acc(g->probe, D, acc), s));
+  }
+  // k,v projections: dlast (+)= dkv · Wkv ; dWkv = dkvᵀ · last_lp
+  if (d_last_hidden) CK(copy_f32(d_last_hidden, dlast, (size_t)M * D, s));
+  CK(c.gemm_nt(dkv, 2 * D, c.sh(ctx->sh_hwkv_t), 2 * D, M, D, 2 * D, EPI_F32, DT_F32,
+               epi_f32_acc(dlast, D, d_last_hidden ? 1 : 0)));
+  if (g->in_proj_w)
+    CK(c.gemm_tn(dkv, 2 * D, act + lay.a_lastlp, D, M, 2 * D, D, g->in_proj_w + (size_t)D * D, D, acc, true));
+  if (g->in_proj_b) RET(c.bias_grad(dkv, 2 * D, M, 2 * D, 2 * D, g->in_proj_b + D, acc));
   return SGL_OK;
 }
 
-// LayerNorm backward + dgamma/dbeta reduction.  colsum_out (nullable, [D]) (+)= column sums of the dx written,
-// i.e. the bias gradient of the Linear whose output gradient dx is (col_acc selects add vs overwrite).
-int ln_backward(sgl_ctx* ctx, const Layout& lay, void* ws, const void* dy, int dy_dt, const float* x, const float* stats,
-                int rows, const float* gamma, const float* dres, float* dx, void* dx_lp, float* dgamma, float* dbeta,
-                int accumulate, hipStream_t s, float* colsum_out = nullptr, int col_acc = 0) {
-  const int D = ctx->D;
-  const bool want = dgamma || dbeta || colsum_out;
-  const int nblk = layernorm_bwd_blocks(rows);
-  float* part = reinterpret_cast<float*>(at(ws, lay.w_lnpart));
-  CK(layernorm_bwd(dy, dy_dt, D, x, stats, stats + rows, gamma, dres, dx, dx_lp, ctx->dt, want ? part : nullptr, nblk,
-                   rows, D, s));
-  CK(reduce_partials3(part, nblk, 3 * D, dgamma, dbeta, colsum_out, D, accumulate, accumulate, col_acc, s));
+// A destination whose gradient is identically zero (no_head_grad, i.e. no d_pooled: the pooling head; no_post_ln_grad,
+// i.e. neither d_pooled nor d_last_hidden: post_layernorm) is written as zeros when overwriting, like every other
+// destination, and left alone when accumulating.
+int zero_dead_grads(const Call& c, const sgl_grads* g, bool no_head_grad, bool no_post_ln_grad) {
+  sgl_ctx* ctx = c.ctx;
+  hipStream_t s = c.s;
+  if (g->accumulate) return SGL_OK;
+  auto zero = [&](float* p, size_t n) { return p ? hipMemsetAsync(p, 0, n * 4, s) : hipSuccess; };
+  const size_t Dz = (size_t)ctx->D, Iz = (size_t)ctx->I;
+  if (ctx->cfg.use_head && no_head_grad) {
+    CK(zero(g->probe, Dz));
+    CK(zero(g->in_proj_w, 3 * Dz * Dz));
+    CK(zero(g->in_proj_b, 3 * Dz));
+    CK(zero(g->out_proj_w, Dz * Dz));
+    CK(zero(g->out_proj_b, Dz));
+    CK(zero(g->head_ln_w, Dz));
+    CK(zero(g->head_ln_b, Dz));
+    CK(zero(g->head_fc1_w, Iz * Dz));
+    CK(zero(g->head_fc1_b, Iz));
+    CK(zero(g->head_fc2_w, Dz * Iz));
+    CK(zero(g->head_fc2_b, Dz));
+  }
+  if (no_post_ln_grad) {
+    CK(zero(g->post_ln_w, Dz));
+    CK(zero(g->post_ln_b, Dz));
+  }
   return SGL_OK;
 }
 
-int check_bwd_args(const sgl_ctx* ctx, const Layout& lay, const void* saved, size_t saved_bytes, void* ws,
-                   size_t ws_bytes) {
-  if (ctx->mx) return SGL_ERR_UNSUPPORTED;
-  if (!saved || !ws) return SGL_ERR_NULL;
-  if (saved_bytes < lay.saved_total || ws_bytes < lay.ws_total) return SGL_ERR_WORKSPACE;
+// The block's MLP: x_out = xmid + fc2(gelu(fc1(LN2 xmid))).  In: gbuf = lowp(d x_out), dx = d x_out, gsum = colsum(dx).
+// Out: dx += LN2'(...) = d xmid, gbuf = lowp(dx), gsum = colsum(dx) when the out_proj / v_proj bias gradients are wanted.
+int mlp_backward(const Call& c, const sgl_layer_weights& lw, const sgl_layer_grads& lg, const ShadowLayer& sl,
+                 const char* lb, int acc) {
+  sgl_ctx* ctx = c.ctx;
+  const Layout& lay = c.lay;
+  hipStream_t s = c.s;
+  const int D = ctx->D, I = ctx->I, Ip = ctx->Ip, M = lay.M, dt = ctx->dt;
+  float* dx = c.wsf(lay.w_dx);
+  void* gbuf = c.wsp(lay.w_g);
+  void* du = c.wsp(lay.w_du);
+  void* dhb = c.wsp(lay.w_dh);
+  float* gsum = c.wsf(lay.w_gsum);   // column sums of dx, left by the producer of dx
+  float* csum = c.wsf(lay.w_csum);
+  const bool fuse_cs = mfma16(dt) && lg.fc1_b;  // MFMA epilogue adds colsum(du); strict mode uses colsum()
+  // deterministic: one row of partial sums per 128-row tile, folded in order below
+  if (fuse_cs) CK(hipMemsetAsync(csum, 0, (size_t)((M + 127) / 128) * Ip * 4, s));
+  CK(c.gemm_nt(gbuf, D, c.sh(sl.w2_t), D, M, Ip, D, EPI_GELU_BWD, dt,
+               epi_gelu_bwd(du, lb + lay.r_u, Ip, mfma16(dt), fuse_cs ? csum : nullptr)));
+  if (lg.fc2_w) CK(c.gemm_tn(gbuf, D, lb + lay.r_a, Ip, M, D, I, lg.fc2_w, I, acc, true));
+  if (lg.fc2_b) CK(batch_sum(gsum, 1, (size_t)D, lg.fc2_b, acc, s));
+  CK(c.gemm_nt(du, Ip, c.sh(sl.w1_t), Ip, M, D, Ip, EPI_STORE, dt, epi_store(dhb, D)));
+  if (lg.fc1_w) CK(c.gemm_tn(du, Ip, lb + lay.r_h2, D, M, I, D, lg.fc1_w, D, acc, true));
+  if (fuse_cs)
+    CK(reduce_partials(csum, (M + 127) / 128, Ip, lg.fc1_b, I, acc, s));
+  else
+    RET(c.bias_grad(du, Ip, M, Ip, I, lg.fc1_b, acc));
+  // LN2 backward: dx := dx + LN2'(dh2);  gbuf := lowp(dx);  colsum(dx) is the out_proj bias gradient
+  // (the column sums stay in gsum as well: the v_proj bias gradient below is a function of them)
+  RET(c.ln_backward(dhb, dt, reinterpret_cast<const float*>(lb + lay.r_xmid),
+                    reinterpret_cast<const float*>(lb + lay.r_stats2), M, lw.ln2_w, dx, dx, gbuf, lg.ln2_w, lg.ln2_b, acc,
+                    (lg.o_b || lg.v_b) ? gsum : nullptr));
+  if (lg.o_b) CK(batch_sum(gsum, 1, (size_t)D, lg.o_b, acc, s));
+  return SGL_OK;
+}
+
+// The block's attention: xmid = x_in + out_proj(attn(qkv(LN1 x_in))).  In: gbuf = lowp(d xmid), gsum = colsum(d xmid).
+// Out: dqkv [M][3D] and the gradients of out_proj and the three projections; dx is not touched (the residual).
+int attn_backward(const Call& c, const sgl_layer_weights& lw, const sgl_layer_grads& lg, const ShadowLayer& sl,
+                  const char* lb, int acc) {
+  sgl_ctx* ctx = c.ctx;
+  const Layout& lay = c.lay;
+  hipStream_t s = c.s;
+  const int D = ctx->D, M = lay.M, dt = ctx->dt;
+  void* gbuf = c.wsp(lay.w_g);
+  void* dattn = c.wsp(lay.w_dh);
+  void* dqkv = c.wsp(lay.w_dqkv);
+  float* gsum = c.wsf(lay.w_gsum);
+  const char* q = lb + lay.r_qkv;
+  CK(c.gemm_nt(gbuf, D, c.sh(sl.wo_t), D, M, D, D, EPI_STORE, dt, epi_store(dattn, D)));
+  if (lg.o_w) CK(c.gemm_tn(gbuf, D, lb + lay.r_attn, D, M, D, D, lg.o_w, D, acc, true));
+  CK(attn_bwd(q, q + c.head_bytes(), q + 2 * c.head_bytes(), lb + lay.r_attn, dattn,
+              reinterpret_cast<const float*>(lb + lay.r_lse), ctx->split ? DT_F32_MFMA : dt, dqkv, c.wsf(lay.w_delta),
+              nullptr, lay.B, ctx->H, lay.N, ctx->dh, ctx->DP, 0, s));
+  float* gw[3] = {lg.q_w, lg.k_w, lg.v_w};
+  float* gb[3] = {lg.q_b, lg.k_b, lg.v_b};
+  // when the caller laid the three gradients out back to back (the Python host does), q/k/v are one GEMM
+  const bool w_adj = gw[0] && gw[1] == gw[0] + (size_t)D * D && gw[2] == gw[1] + (size_t)D * D;
+  if (w_adj) CK(c.gemm_tn(dqkv, 3 * D, lb + lay.r_h1, D, M, 3 * D, D, gw[0], D, acc, true));
+  for (int j = 0; j < 3; ++j) {
+    const char* aj = reinterpret_cast<const char*>(dqkv) + (size_t)j * D * ctx->es;
+    if (!w_adj && gw[j]) CK(c.gemm_tn(aj, 3 * D, lb + lay.r_h1, D, M, D, D, gw[j], D, acc, true));
+  }
+  // Bias gradients of the three projections = column sums of dQ, dK, dV over all tokens.  Only dQ's needs a pass:
+  //   sum_n dK[n,:] = sum_q Q[q,:] * scale * (sum_n dS[q,n]) and sum_n dS[q,n] = sum_n P (dP - delta) = delta - delta = 0:
+  //     the k_proj bias has NO gradient (softmax is invariant to a per-query shift of the scores) — exact zeros here,
+  //     rounding noise around zero in the reference;
+  //   sum_n dV[n,:] = sum_q dO[q,:] * (sum_n P[q,n]) = sum_q dO[q,:] = colsum(dY) * W_o, and colsum(dY) is the out_proj bias
+  //     gradient the LayerNorm backward above already produced (gsum): a 1152-vector times W_o instead of a read of dV.
+  // (One column-sum pass over a third of dqkv instead of all of it: 116 -> ~40 us per block at B = 128.)
+  if (gb[0]) RET(c.bias_grad(dqkv, 3 * D, M, D, D, gb[0], acc));
+  if (gb[1] && !acc) CK(hipMemsetAsync(gb[1], 0, (size_t)D * 4, s));
+  if (gb[2]) CK(vecmat_f32(gsum, lw.o_w, D, D, c.wsf(lay.w_cspart), gb[2], acc, s));
+  return SGL_OK;
+}
+
+// LN1 backward: dx := dx + LN1'(dqkv · Wqkv) = d x_in;  gbuf := lowp(dx);  gsum := colsum(dx) for the block below
+int ln1_backward(const Call& c, const sgl_layer_weights& lw, const sgl_layer_grads& lg, const ShadowLayer& sl,
+                 const char* lb, const float* x_in, int acc) {
+  sgl_ctx* ctx = c.ctx;
+  const Layout& lay = c.lay;
+  const int D = ctx->D, M = lay.M, dt = ctx->dt;
+  float* dx = c.wsf(lay.w_dx);
+  void* dh1 = c.wsp(lay.w_dh);  // d LN1 output
+  CK(c.gemm_nt(c.wsp(lay.w_dqkv), 3 * D, c.sh(sl.wqkv_t), 3 * D, M, D, 3 * D, EPI_STORE, dt, epi_store(dh1, D)));
+  RET(c.ln_backward(dh1, dt, x_in, reinterpret_cast<const float*>(lb + lay.r_stats1), M, lw.ln1_w, dx, dx,
+                    c.wsp(lay.w_g), lg.ln1_w, lg.ln1_b, acc, c.wsf(lay.w_gsum)));
   return SGL_OK;
 }
 
@@ -870,139 +1077,29 @@ int sgl_backward_begin_p(sgl_ctx* ctx, const sgl_weights* w, const void* shadow,
                          const float* d_tap_last, const void* saved, size_t saved_bytes, void* ws, size_t ws_bytes,
                          sgl_stream stream) {
   if (!ctx || !w || !shadow || !g || !hs_last) return SGL_ERR_NULL;
-  if (!train_shape_ok(ctx, B, H, W)) return SGL_ERR_BAD_SHAPE;
-  Layout lay(ctx, B, H, W, true);
-  RET(check_bwd_args(ctx, lay, saved, saved_bytes, ws, ws_bytes));
-  if (ctx->split) {
-    ctx->sp_a = at(ws, lay.w_spa);
-    ctx->sp_b = at(ws, lay.w_spb);
-  }
-  hipStream_t s = (hipStream_t)stream;
-  const int D = ctx->D, I = ctx->I, Ip = ctx->Ip, M = lay.M, N = lay.N, dt = ctx->dt, Hh = ctx->H, dh = ctx->dh,
-            DP = ctx->DP;
-  const int acc = g->accumulate;
-  const char* act = reinterpret_cast<const char*>(saved);
-  float* dx = reinterpret_cast<float*>(at(ws, lay.w_dx));
-  void* gbuf = at(ws, lay.w_g);
-  const float* hsL = hs_last;
+  Call c;
+  RET(begin_call(c, BACKWARD, ctx, shadow, B, H, W, saved, saved_bytes, ws, ws_bytes, stream));
+  const Layout& lay = c.lay;
+  hipStream_t s = c.s;
+  const int D = ctx->D, M = lay.M;
+  float* dx = c.wsf(lay.w_dx);
+  void* gbuf = c.wsp(lay.w_g);
+  float* gsum = c.wsf(lay.w_gsum);
   const float* dlast = d_last_hidden;  // gradient w.r.t. post_layernorm output
-  float* gsum = reinterpret_cast<float*>(at(ws, lay.w_gsum));
-
   if (ctx->cfg.use_head && d_pooled) {
-    float* dlast_buf = reinterpret_cast<float*>(at(ws, lay.w_dlast));
-    const float* h0 = reinterpret_cast<const float*>(act + lay.a_h0);
-    const float* hst = reinterpret_cast<const float*>(act + lay.a_hstats);
-    const float* qp = reinterpret_cast<const float*>(act + lay.a_qp);
-    void* hg = at(ws, lay.w_hg);
-    void* hdu = at(ws, lay.w_hdu);
-    void* hdh = at(ws, lay.w_hdh);
-    float* hdao = reinterpret_cast<float*>(at(ws, lay.w_hdao));
-    float* hdh0 = reinterpret_cast<float*>(at(ws, lay.w_hdh0));
-    // pooled = h0 + fc2(gelu(fc1(LN(h0))))
-    CK(cast_f32(d_pooled, hg, dt, (size_t)B * D, s));
-    {
-      EpiParams p;
-      p.out = hdu;
-      p.ldo = Ip;
-      p.aux = act + lay.a_hu;
-      p.ldaux = Ip;
-      CK(gemm_nt(ctx, hg, D, at(shadow, ctx->sh_hw2_t), D, B, Ip, D, EPI_GELU_BWD, dt, p, s));
-    }
-    if (g->head_fc2_w) CK(gemm_tn(ctx, hg, D, act + lay.a_ha, Ip, B, D, I, g->head_fc2_w, I, acc, s));
-    RET(bias_grad(ctx, lay, ws, hg, D, B, D, D, g->head_fc2_b, acc, s));
-    {
-      EpiParams p;
-      p.out = hdh;
-      p.ldo = D;
-      CK(gemm_nt(ctx, hdu, Ip, at(shadow, ctx->sh_hw1_t), Ip, B, D, Ip, EPI_STORE, dt, p, s));
-    }
-    if (g->head_fc1_w) CK(gemm_tn(ctx, hdu, Ip, act + lay.a_hl, D, B, I, D, g->head_fc1_w, D, acc, s));
-    RET(bias_grad(ctx, lay, ws, hdu, Ip, B, Ip, I, g->head_fc1_b, acc, s));
-    // LN backward (+ residual d_pooled): dh0, low-precision copy into hg
-    RET(ln_backward(ctx, lay, ws, hdh, dt, h0, hst, B, w->head_ln_w, d_pooled, hdh0, hg, g->head_ln_w, g->head_ln_b,
-                    acc, s));
-    // h0 = ao · Woᵀ + bo
-    {
-      EpiParams p;
-      p.out = hdao;
-      p.ldo = D;
-      CK(gemm_nt(ctx, hg, D, at(shadow, ctx->sh_hwo_t), D, B, D, D, EPI_F32, DT_F32, p, s));
-    }
-    if (g->out_proj_w) CK(gemm_tn(ctx, hg, D, act + lay.a_ao, D, B, D, D, g->out_proj_w, D, acc, s));
-    RET(bias_grad(ctx, lay, ws, hg, D, B, D, D, g->out_proj_b, acc, s));
-    // attention pool backward
-    const size_t hsz = (size_t)B * Hh * N * DP * ctx->es;
-    void* dkv = at(ws, lay.w_dqkv);  // [M][2D]
-    float* dqpart = reinterpret_cast<float*>(at(ws, lay.w_hdqpart));
-    float* dqp = reinterpret_cast<float*>(at(ws, lay.w_hdqp));
-    CK(pool_attn_bwd(qp, act + lay.a_kvh, act + lay.a_kvh + hsz, dt,
-                     reinterpret_cast<const float*>(act + lay.a_probs), hdao, dkv, dqpart, B, Hh, N, dh, DP, s));
-    if (g->probe || g->in_proj_w || g->in_proj_b) {
-      CK(batch_sum(dqpart, B, (size_t)D, dqp, 0, s));
-      if (g->in_proj_w) {  // d Wq[i,j] = dqp[i] * probe[j]
-        EpiParams p;
-        p.out = g->in_proj_w;
-        p.ldo = D;
-        p.accumulate = acc;
-        CK(gemm_f32_generic(dqp, 1, 1, w->probe, 1, 1, D, D, 1, EPI_F32, DT_F32, p, s));
-      }
-      if (g->in_proj_b) CK(batch_sum(dqp, 1, (size_t)D, g->in_proj_b, acc, s));
-      if (g->probe) {  // dprobe[j] = sum_i dqp[i] Wq[i,j]
-        EpiParams p;
-        p.out = g->probe;
-        p.ldo = D;
-        p.accumulate = acc;
-        CK(gemm_f32_generic(dqp, D, 1, w->in_proj_w, 1, D, 1, D, D, EPI_F32, DT_F32, p, s));
-      }
-    }
-    // k,v projections: dlast (+)= dkv · Wkv ; dWkv = dkvᵀ · last_lp
-    if (d_last_hidden) CK(copy_f32(d_last_hidden, dlast_buf, (size_t)M * D, s));
-    {
-      EpiParams p;
-      p.out = dlast_buf;
-      p.ldo = D;
-      p.accumulate = d_last_hidden ? 1 : 0;
-      CK(gemm_nt(ctx, dkv, 2 * D, at(shadow, ctx->sh_hwkv_t), 2 * D, M, D, 2 * D, EPI_F32, DT_F32, p, s));
-    }
-    if (g->in_proj_w)
-      CK(gemm_tn(ctx, dkv, 2 * D, act + lay.a_lastlp, D, M, 2 * D, D, g->in_proj_w + (size_t)D * D, D, acc, s,
-                 at(ws, lay.w_splitws), kSplitWsBytes));
-    if (g->in_proj_b) RET(bias_grad(ctx, lay, ws, dkv, 2 * D, M, 2 * D, 2 * D, g->in_proj_b + D, acc, s));
+    float* dlast_buf = c.wsf(lay.w_dlast);
+    RET(head_backward(c, w, g, d_pooled, d_last_hidden, dlast_buf));
     dlast = dlast_buf;
   }
-
-  // A destination whose gradient is identically zero (no d_pooled: the pooling head; neither d_pooled nor d_last_hidden:
-  // post_layernorm) is written as zeros when overwriting, like every other destination, and left alone when accumulating.
-  if (!acc) {
-    auto zero = [&](float* p, size_t n) { return p ? hipMemsetAsync(p, 0, n * 4, s) : hipSuccess; };
-    const size_t Dz = (size_t)D, Iz = (size_t)I;
-    if (ctx->cfg.use_head && !d_pooled) {
-      CK(zero(g->probe, Dz));
-      CK(zero(g->in_proj_w, 3 * Dz * Dz));
-      CK(zero(g->in_proj_b, 3 * Dz));
-      CK(zero(g->out_proj_w, Dz * Dz));
-      CK(zero(g->out_proj_b, Dz));
-      CK(zero(g->head_ln_w, Dz));
-      CK(zero(g->head_ln_b, Dz));
-      CK(zero(g->head_fc1_w, Iz * Dz));
-      CK(zero(g->head_fc1_b, Iz));
-      CK(zero(g->head_fc2_w, Dz * Iz));
-      CK(zero(g->head_fc2_b, Dz));
-    }
-    if (!dlast) {
-      CK(zero(g->post_ln_w, Dz));
-      CK(zero(g->post_ln_b, Dz));
-    }
-  }
-
+  RET(zero_dead_grads(c, g, !d_pooled, !dlast));
   // post_layernorm backward -> dx (fp32) and its low-precision copy (A operand of the last block's GEMMs)
   if (dlast) {
-    RET(ln_backward(ctx, lay, ws, dlast, DT_F32, hsL, reinterpret_cast<const float*>(act + lay.a_pstats), M,
-                    w->post_ln_w, d_tap_last, dx, gbuf, g->post_ln_w, g->post_ln_b, acc, s, gsum, 0));
+    RET(c.ln_backward(dlast, DT_F32, hs_last, c.actf(lay.a_pstats), M, w->post_ln_w, d_tap_last, dx, gbuf, g->post_ln_w,
+                      g->post_ln_b, g->accumulate, gsum));
   } else if (d_tap_last) {
     CK(copy_f32(d_tap_last, dx, (size_t)M * D, s));
-    CK(cast_f32(d_tap_last, gbuf, dt, (size_t)M * D, s));
-    CK(colsum(gbuf, dt, D, M, D, D, reinterpret_cast<float*>(at(ws, lay.w_cspart)), gsum, 0, s));
+    CK(cast_f32(d_tap_last, gbuf, ctx->dt, (size_t)M * D, s));
+    CK(colsum(gbuf, ctx->dt, D, M, D, D, c.wsf(lay.w_cspart), gsum, 0, s));
   } else {
     CK(hipMemsetAsync(dx, 0, (size_t)M * D * 4, s));
     CK(hipMemsetAsync(gbuf, 0, (size_t)M * D * ctx->es, s));
@@ -1026,148 +1123,43 @@ int sgl_backward_layer_p(sgl_ctx* ctx, const sgl_weights* w, const void* shadow,
                          size_t saved_bytes, void* ws, size_t ws_bytes, sgl_stream stream) {
   if (!ctx || !w || !shadow || !g || !hs_in || !g->layers || !w->layers) return SGL_ERR_NULL;
   if (layer < 0 || layer >= ctx->L) return SGL_ERR_BAD_SHAPE;
-  if (!train_shape_ok(ctx, B, H, W)) return SGL_ERR_BAD_SHAPE;
-  Layout lay(ctx, B, H, W, true);
-  RET(check_bwd_args(ctx, lay, saved, saved_bytes, ws, ws_bytes));
-  if (ctx->split) {
-    ctx->sp_a = at(ws, lay.w_spa);
-    ctx->sp_b = at(ws, lay.w_spb);
-  }
-  hipStream_t s = (hipStream_t)stream;
-  const int D = ctx->D, I = ctx->I, Ip = ctx->Ip, M = lay.M, N = lay.N, dt = ctx->dt, Hh = ctx->H, dh = ctx->dh,
-            DP = ctx->DP;
+  Call c;
+  RET(begin_call(c, BACKWARD, ctx, shadow, B, H, W, saved, saved_bytes, ws, ws_bytes, stream));
   const int acc = g->accumulate;
   const sgl_layer_weights& lw = w->layers[layer];
   const sgl_layer_grads& lg = g->layers[layer];
   const ShadowLayer& sl = ctx->sh_layers[layer];
   // recompute context: rebuild the block's activations from its input into the shared region first (everything but fc2:
   // hidden_states[layer + 1] is saved); the region is disjoint from the gradient this call carries in ws
-  const char* lb = reinterpret_cast<const char*>(saved) + lay.layer_base(layer);
-  if (lay.rc) {
-    char* rb = at(ws, lay.w_blk);
-    RET(block_to_fc1(ctx, lay, lw, sl, shadow, rb, hs_in, B, true, s));
-    lb = rb;
-  }
-  const float* x_in = hs_in;
-  const float* xmid = reinterpret_cast<const float*>(lb + lay.r_xmid);
-  float* dx = reinterpret_cast<float*>(at(ws, lay.w_dx));
-  void* gbuf = at(ws, lay.w_g);
-  void* du = at(ws, lay.w_du);
-  void* dhb = at(ws, lay.w_dh);
-  void* dqkv = at(ws, lay.w_dqkv);
-  void* sws = at(ws, lay.w_splitws);
-
-  // ---- MLP: x_out = xmid + fc2(gelu(fc1(LN2 xmid)))          gbuf = lowp(d x_out)
-  float* gsum = reinterpret_cast<float*>(at(ws, lay.w_gsum));   // column sums of dx, left by the producer of dx
-  float* csum = reinterpret_cast<float*>(at(ws, lay.w_csum));
-  const bool fuse_cs = mfma16(dt) && lg.fc1_b;  // MFMA epilogue adds colsum(du); strict mode uses colsum()
-  {
-    EpiParams p;
-    p.out = du;
-    p.ldo = Ip;
-    p.aux = lb + lay.r_u;
-    p.ldaux = Ip;
-    p.gelu_grad_form = mfma16(dt);
-    if (fuse_cs) {  // deterministic: one row of partial sums per 128-row tile, folded in order below
-      CK(hipMemsetAsync(csum, 0, (size_t)((M + 127) / 128) * Ip * 4, s));
-      p.colsum = csum;
-      p.colsum_ld = Ip;
-    }
-    CK(gemm_nt(ctx, gbuf, D, at(shadow, sl.w2_t), D, M, Ip, D, EPI_GELU_BWD, dt, p, s));
-  }
-  if (lg.fc2_w) CK(gemm_tn(ctx, gbuf, D, lb + lay.r_a, Ip, M, D, I, lg.fc2_w, I, acc, s, sws, kSplitWsBytes));
-  if (lg.fc2_b) CK(batch_sum(gsum, 1, (size_t)D, lg.fc2_b, acc, s));
-  {
-    EpiParams p;
-    p.out = dhb;
-    p.ldo = D;
-    CK(gemm_nt(ctx, du, Ip, at(shadow, sl.w1_t), Ip, M, D, Ip, EPI_STORE, dt, p, s));
-  }
-  if (lg.fc1_w) CK(gemm_tn(ctx, du, Ip, lb + lay.r_h2, D, M, I, D, lg.fc1_w, D, acc, s, sws, kSplitWsBytes));
-  if (fuse_cs)
-    CK(reduce_partials(csum, (M + 127) / 128, Ip, lg.fc1_b, I, acc, s));
-  else
-    RET(bias_grad(ctx, lay, ws, du, Ip, M, Ip, I, lg.fc1_b, acc, s));
-  // LN2 backward: dx := dx + LN2'(dh2);  gbuf := lowp(dx);  colsum(dx) is the out_proj bias gradient
-  // (the column sums stay in gsum as well: the v_proj bias gradient below is a function of them)
-  RET(ln_backward(ctx, lay, ws, dhb, dt, xmid, reinterpret_cast<const float*>(lb + lay.r_stats2), M, lw.ln2_w, dx, dx,
-                  gbuf, lg.ln2_w, lg.ln2_b, acc, s, (lg.o_b || lg.v_b) ? gsum : nullptr, 0));
-  if (lg.o_b) CK(batch_sum(gsum, 1, (size_t)D, lg.o_b, acc, s));
-
-  // ---- attention: xmid = x_in + out_proj(attn(qkv(LN1 x_in)))
-  {
-    EpiParams p;
-    p.out = dhb;  // d attn
-    p.ldo = D;
-    CK(gemm_nt(ctx, gbuf, D, at(shadow, sl.wo_t), D, M, D, D, EPI_STORE, dt, p, s));
-  }
-  if (lg.o_w) CK(gemm_tn(ctx, gbuf, D, lb + lay.r_attn, D, M, D, D, lg.o_w, D, acc, s, sws, kSplitWsBytes));
-  {
-    const size_t hsz = (size_t)B * Hh * N * DP * ctx->es;
-    const char* q = lb + lay.r_qkv;
-    CK(attn_bwd(q, q + hsz, q + 2 * hsz, lb + lay.r_attn, dhb, reinterpret_cast<const float*>(lb + lay.r_lse),
-                ctx->split ? DT_F32_MFMA : dt, dqkv, reinterpret_cast<float*>(at(ws, lay.w_delta)), nullptr, B, Hh, N, dh,
-                DP, 0, s));
-  }
-  {
-    float* gw[3] = {lg.q_w, lg.k_w, lg.v_w};
-    float* gb[3] = {lg.q_b, lg.k_b, lg.v_b};
-    // when the caller laid the three gradients out back to back (the Python host does), q/k/v are one GEMM
-    const bool w_adj = gw[0] && gw[1] == gw[0] + (size_t)D * D && gw[2] == gw[1] + (size_t)D * D;
-    if (w_adj) CK(gemm_tn(ctx, dqkv, 3 * D, lb + lay.r_h1, D, M, 3 * D, D, gw[0], D, acc, s, sws, kSplitWsBytes));
-    for (int j = 0; j < 3; ++j) {
-      const char* aj = reinterpret_cast<const char*>(dqkv) + (size_t)j * D * ctx->es;
-      if (!w_adj && gw[j]) CK(gemm_tn(ctx, aj, 3 * D, lb + lay.r_h1, D, M, D, D, gw[j], D, acc, s, sws, kSplitWsBytes));
-    }
-    // Bias gradients of the three projections = column sums of dQ, dK, dV over all tokens.  Only dQ's needs a pass:
-    //   sum_n dK[n,:] = sum_q Q[q,:] * scale * (sum_n dS[q,n]) and sum_n dS[q,n] = sum_n P (dP - delta) = delta - delta = 0:
-    //     the k_proj bias has NO gradient (softmax is invariant to a per-query shift of the scores) — exact zeros here,
-    //     rounding noise around zero in the reference;
-    //   sum_n dV[n,:] = sum_q dO[q,:] * (sum_n P[q,n]) = sum_q dO[q,:] = colsum(dY) * W_o, and colsum(dY) is the out_proj bias
-    //     gradient the LayerNorm backward above already produced (gsum): a 1152-vector times W_o instead of a read of dV.
-    // (One column-sum pass over a third of dqkv instead of all of it: 116 -> ~40 us per block at B = 128.)
-    if (gb[0]) RET(bias_grad(ctx, lay, ws, dqkv, 3 * D, M, D, D, gb[0], acc, s));
-    if (gb[1] && !acc) CK(hipMemsetAsync(gb[1], 0, (size_t)D * 4, s));
-    if (gb[2]) CK(vecmat_f32(gsum, lw.o_w, D, D, reinterpret_cast<float*>(at(ws, lay.w_cspart)), gb[2], acc, s));
-  }
-  if (d_tap) CK(add_f32(dx, d_tap, dx, (size_t)M * D, s));
-  const bool ln1_params = lg.ln1_w || lg.ln1_b;
-  if (need_dx || ln1_params) {
-    EpiParams p;
-    p.out = dhb;  // d LN1 output
-    p.ldo = D;
-    CK(gemm_nt(ctx, dqkv, 3 * D, at(shadow, sl.wqkv_t), 3 * D, M, D, 3 * D, EPI_STORE, dt, p, s));
-    RET(ln_backward(ctx, lay, ws, dhb, dt, x_in, reinterpret_cast<const float*>(lb + lay.r_stats1), M, lw.ln1_w, dx, dx,
-                    gbuf, lg.ln1_w, lg.ln1_b, acc, s, gsum, 0));
-  }
+  char* lb = c.block(layer);
+  if (c.lay.rc) RET(block_to_fc1(c, lw, sl, lb, hs_in, true));
+  RET(mlp_backward(c, lw, lg, sl, lb, acc));
+  RET(attn_backward(c, lw, lg, sl, lb, acc));
+  float* dx = c.wsf(c.lay.w_dx);
+  if (d_tap) CK(add_f32(dx, d_tap, dx, (size_t)c.lay.M * ctx->D, c.s));
+  if (need_dx || lg.ln1_w || lg.ln1_b) RET(ln1_backward(c, lw, lg, sl, lb, hs_in, acc));
   return SGL_OK;
 }
 
 int sgl_backward_embed(sgl_ctx* ctx, const sgl_weights* w, const sgl_grads* g, int B, int H, int W, int interpolate_pos,
                        const void* saved, size_t saved_bytes, void* ws, size_t ws_bytes, sgl_stream stream) {
   if (!ctx || !w || !g) return SGL_ERR_NULL;
-  if (!train_shape_ok(ctx, B, H, W)) return SGL_ERR_BAD_SHAPE;
-  Layout lay(ctx, B, H, W, true);
-  RET(check_bwd_args(ctx, lay, saved, saved_bytes, ws, ws_bytes));
-  if (ctx->split) {
-    ctx->sp_a = at(ws, lay.w_spa);
-    ctx->sp_b = at(ws, lay.w_spb);
-  }
-  hipStream_t s = (hipStream_t)stream;
+  Call c;
+  RET(begin_call(c, BACKWARD, ctx, nullptr, B, H, W, saved, saved_bytes, ws, ws_bytes, stream));
+  const Layout& lay = c.lay;
+  hipStream_t s = c.s;
   const int D = ctx->D, M = lay.M, N = lay.N;
   const int acc = g->accumulate;
-  const char* act = reinterpret_cast<const char*>(saved);
-  float* dx = reinterpret_cast<float*>(at(ws, lay.w_dx));
-  void* gbuf = at(ws, lay.w_g);  // low-precision copy of dx (written by the last LN1 backward / begin)
+  float* dx = c.wsf(lay.w_dx);
+  void* gbuf = c.wsp(lay.w_g);  // low-precision copy of dx (written by the last LN1 backward / begin)
   if (g->patch_w)
-    CK(gemm_tn(ctx, gbuf, D, act + lay.a_im2col, ctx->Kp, M, D, ctx->K0, g->patch_w, ctx->K0, acc, s, at(ws, lay.w_splitws),
-               kSplitWsBytes));
-  if (g->patch_b) CK(batch_sum(reinterpret_cast<const float*>(at(ws, lay.w_gsum)), 1, (size_t)D, g->patch_b, acc, s));
+    CK(c.gemm_tn(gbuf, D, c.act + lay.a_im2col, ctx->Kp, M, D, ctx->K0, g->patch_w, ctx->K0, acc, true));
+  if (g->patch_b) CK(batch_sum(c.wsf(lay.w_gsum), 1, (size_t)D, g->patch_b, acc, s));
   if (g->pos) {
     if (lay.gh == ctx->g0 && lay.gw == ctx->g0) {
       CK(batch_sum(dx, B, (size_t)N * D, g->pos, acc, s));
     } else {
-      float* dpos = reinterpret_cast<float*>(at(ws, lay.w_dlast));  // [N][D] scratch
+      float* dpos = c.wsf(lay.w_dlast);  // [N][D] scratch
       CK(batch_sum(dx, B, (size_t)N * D, dpos, 0, s));
       if (!acc) CK(hipMemsetAsync(g->pos, 0, (size_t)ctx->g0 * ctx->g0 * D * 4, s));
       CK(pos_resize_bwd(dpos, lay.gh, lay.gw, g->pos, ctx->g0, D, s));

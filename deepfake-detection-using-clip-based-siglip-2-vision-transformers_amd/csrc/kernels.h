@@ -1,4 +1,4 @@
-// Internal launch API shared by the kernel translation units and the C-ABI host code (encoder.cpp).
+// Internal launch API shared by the kernel translation units and the C-ABI host code (encoder.hip).
 // Every launcher enqueues on the stream it is given, allocates nothing and never synchronises.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -97,9 +97,6 @@ hipError_t im2col(const float* pix, int channels_last, void* out, int out_dtype,
 // dst[r][c] (row stride ldd) = cast(src[r][c]) for r < Rp, c < Cp, zero outside src's R x C
 hipError_t cast_pad(const float* src, int R, int C, int lds_, void* dst, int dst_dtype, int Rp, int Cp, int ldd,
                     hipStream_t s);
-// dst[c][r] (row stride ldd) = cast(src[r][c]) for c < Cp, r < Rp, zero outside
-hipError_t cast_transpose_pad(const float* src, int R, int C, int lds_, void* dst, int dst_dtype, int Cp, int Rp,
-                              int ldd, hipStream_t s);
 // One launch for all weight shadows of a block: up to 6 matrices (row-major copy [Rp][Cp] with ld ldd and, optionally, the
 // transposed copy [Cp][Rp] with ld ldt, both zero padded outside the R x C source) and up to 4 fp32 vectors (copied, zero padded)
 struct CastMat {
@@ -146,7 +143,7 @@ hipError_t pool_attn_bwd(const float* q, const void* K, const void* V, int dtype
 hipError_t gemm_f32_generic(const float* A, long sam, long sak, const float* B, long sbn, long sbk, int M, int N,
                             int K, int epi, int out_dtype, const EpiParams& p, hipStream_t s);
 
-// ---- gemm_bf16.hip: MFMA kernels ----------------------------------------------------------------------
+// ---- gemm_bf16.hip (128x128 tiles), gemm_bf16_v2.hip (256x256 tiles): MFMA kernels ------------------
 // NT: C[M,N] = A[M,K] * B[N,K]^T ; A,B bf16 K-contiguous, lda/ldb multiples of 8, K multiple of 8
 hipError_t gemm_nt_bf16(const void* A, int lda, const void* B, int ldb, int M, int N, int K, int epi,
                         int out_dtype, const EpiParams& p, hipStream_t s);
@@ -174,6 +171,5 @@ hipError_t attn_fwd(const void* q, const void* k, const void* v, int dtype, void
 hipError_t attn_bwd(const void* q, const void* k, const void* v, const void* out, const void* dout,
                     const float* lse, int dtype, void* dqkv, float* delta, float* reserved, int B, int H, int N,
                     int dh, int DP, int ld_qkv, hipStream_t s);
-size_t attn_bwd_scratch_bytes(int dtype, int B, int H, int N, int dh, int DP);
 
 }  // namespace sgl

@@ -177,6 +177,25 @@ OPERAND_DTYPE = {"bf16": torch.bfloat16, "fp32": torch.float32, "bf16x3": torch.
 INFERENCE_ONLY = {"mxfp8"}
 
 
+def _slot_plan(tap_ids, train, L):
+    """Which buffer each of the L + 1 hidden-state slots of sgl_forward_slots uses: (n_rest, plan), plan[l] = (True, i) for
+    the tensor of the i-th entry of tap_ids (distinct), (False, k) for row k of hs_rest [n_rest, B*N, D].  Training keeps
+    every hidden state, so each slot nobody asked for has a row of its own; inference ping-pongs between two rows
+    (neighbours differ in parity)."""
+    tapset = {int(t): i for i, t in enumerate(tap_ids)}
+    n_rest = (L + 1 - len(tapset)) if train else min(2, L + 1 - len(tapset))
+    plan, k = [], 0
+    for l in range(L + 1):
+        if l in tapset:
+            plan.append((True, tapset[l]))
+        elif train:
+            plan.append((False, k))
+            k += 1
+        else:
+            plan.append((False, l & 1))
+    return n_rest, plan
+
+
 @torch.library.custom_op("siglip_hip::encoder_fwd", mutates_args=())
 def encoder_fwd(pixel_values: torch.Tensor, params: Sequence[torch.Tensor], handle: int, train: bool, interp: bool,
                 want_pooled: bool, tap_ids: Sequence[int], first_trainable: int, layout: int, img_h: int,
@@ -214,19 +233,11 @@ def encoder_fwd(pixel_values: torch.Tensor, params: Sequence[torch.Tensor], hand
         shadow, weights = mod._prepared(dev)
         sizes = mod._sizes(B, H, W, train, recompute)
         taps = [torch.empty((B, N, D), dtype=torch.float32, device=dev) for _ in tap_ids]
-        tapset = {int(t): i for i, t in enumerate(tap_ids)}
-        n_rest = (L + 1 - len(tapset)) if train else min(2, L + 1 - len(tapset))
+        n_rest, plan = _slot_plan(tap_ids, train, L)
         hs_rest = torch.empty((n_rest, M, D), dtype=torch.float32, device=dev)
         slots = (_lib._fp * (L + 1))()
-        k = 0
-        for l in range(L + 1):
-            if l in tapset:
-                slots[l] = taps[tapset[l]].data_ptr()
-            elif train:
-                slots[l] = hs_rest[k].data_ptr()
-                k += 1
-            else:
-                slots[l] = hs_rest[l & 1].data_ptr()     # inference: ping-pong (neighbours differ in parity)
+        for l, (is_tap, i) in enumerate(plan):
+            slots[l] = (taps[i] if is_tap else hs_rest[i]).data_ptr()
         last = torch.empty((B, N, D), dtype=torch.float32, device=dev)
         pooled = torch.empty((B, D) if want_pooled else (0,), dtype=torch.float32, device=dev)
         saved = torch.empty(sizes[1] if train else 0, dtype=torch.uint8, device=dev)
@@ -254,7 +265,7 @@ def _(pixel_values, params, handle, train, interp, want_pooled, tap_ids, first_t
     if not all(isinstance(v, int) for v in (B, H, W)):
         raise RuntimeError("siglip_hip::encoder_fwd needs static image shapes under torch.compile (dynamic=False)")
     new = pixel_values.new_empty
-    n_rest = (L + 1 - len(tap_ids)) if train else min(2, L + 1 - len(tap_ids))
+    n_rest, _ = _slot_plan(tap_ids, train, L)
     saved_bytes = mod._sizes(B, H, W, True, bool(recompute))[1] if train else 0
     return [new((B, D) if want_pooled else (0,), dtype=torch.float32), new((B, N, D), dtype=torch.float32),
             *[new((B, N, D), dtype=torch.float32) for _ in tap_ids], new((saved_bytes,), dtype=torch.uint8),
@@ -294,15 +305,10 @@ def encoder_bwd(grads: Sequence[Optional[torch.Tensor]], taps: Sequence[torch.Te
     d_last = prep(grads[1])
     tap_grads = [None] * (L + 1)
     hs_ptr = [None] * (L + 1)
-    k = 0
-    tapset = {int(t): i for i, t in enumerate(tap_ids)}
-    for l in range(L + 1):
-        if l in tapset:
-            hs_ptr[l] = taps[tapset[l]].data_ptr()
-            tap_grads[l] = prep(grads[2 + tapset[l]])
-        else:
-            hs_ptr[l] = hs_rest[k].data_ptr()
-            k += 1
+    for l, (is_tap, i) in enumerate(_slot_plan(tap_ids, True, L)[1]):
+        hs_ptr[l] = (taps[i] if is_tap else hs_rest[i]).data_ptr()
+        if is_tap:
+            tap_grads[l] = prep(grads[2 + i])
 
     with torch.cuda.device(dev):
         chunks, groups = mod._bucket_layout(needs)
@@ -823,13 +829,10 @@ class SiglipVisionModelHIP(nn.Module):
         if self._weights_struct is None or self._weights_key != ptr_key:
             self._weights_struct, self._weights_keep = self._build_weights_struct(params)
             self._weights_key = ptr_key
-        # one (pointers, versions) key per block and one for everything else: only what changed is re-cast, so a
-        # frozen-prefix run (Siglip2sidafrozen.py:757-768) refreshes its 6 trainable blocks, not all 27
+        # only what changed is re-cast, so a frozen-prefix run (Siglip2sidafrozen.py:757-768) refreshes its 6 trainable
+        # blocks, not all 27
         L = self.config.num_hidden_layers
-        keys = [[] for _ in range(L + 1)]
-        for (grp, _), p in zip(self._flat_names, params):
-            keys[int(grp[5:]) if grp.startswith("layer") else L].append((p.data_ptr(), p._version))
-        keys = [tuple(k) for k in keys]
+        keys = self._unit_keys()
         fresh = self._shadow is None or self._shadow.device != dev or self._shadow_key is None
         if fresh or self._shadow_key != keys:
             nbytes = self._sizes(1, self.config.patch_size, self.config.patch_size, False)[0]
@@ -856,6 +859,7 @@ class SiglipVisionModelHIP(nn.Module):
                  "patch_w", "in_proj_w", "out_proj_w", "head_fc1_w", "head_fc1_b", "head_fc2_w"}    # globals
 
     def _unit_keys(self):
+        """One (pointers, versions) key per block and, last entry, one for everything else."""
         L = self.config.num_hidden_layers
         keys = [[] for _ in range(L + 1)]
         for (grp, _), p in zip(self._flat_names, self._flat_params()):

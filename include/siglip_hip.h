@@ -266,10 +266,11 @@ int sgl_op_gemm_tn_ws(int dtype, const void* A, int lda, const void* B, int ldb,
  * dtype: SGL_DTYPE_BF16 (bf16 operands, bf16 MFMA, fp32 softmax), SGL_DTYPE_F32 (fp32 operands, plain FMAs: the reference
  *   kernels), SGL_DTYPE_BF16X3 (fp32 operands on v_mfma_f32_32x32x2_f32: what the strict MFMA mode uses) or
  *   SGL_DTYPE_F16 (the bf16 kernels on fp16 operands, fp16 MFMA, fp32 softmax).
- * ld_qkv > 0 (what the encoder uses since ABI 3): q, k, v point at the three column blocks of the QKV projection's
+ * ld_qkv > 0 (added in ABI 3): q, k, v point at the three column blocks of the QKV projection's
  *   token-major output [B*N][ld_qkv]; head h of token row r is the head_dim elements at r*ld_qkv + h*head_dim (16-byte
  *   aligned: head_dim % 8 == 0, ld_qkv % 8 == 0, pointers 16-byte aligned).  Nothing is padded in memory.
- * ld_qkv == 0: legacy head-major [B][H][N][head_dim_pad] matrices whose pad columns are zero (EPI_QKV's layout).
+ * ld_qkv == 0 (what the encoder uses; DESIGN.md section 8.4 records the measurement behind that): head-major
+ *   [B][H][N][head_dim_pad] matrices whose pad columns are zero (EPI_QKV's layout).
  * out: token-major [B*N][H*head_dim]; lse: [B][H][N]. */
 int sgl_op_attn_fwd(int dtype, const void* q, const void* k, const void* v, void* out, float* lse, int B, int H, int N,
                     int head_dim, int head_dim_pad, int ld_qkv, sgl_stream stream);
