@@ -51,6 +51,77 @@ hipError_t im2col(const float* pix, int channels_last, void* out, int out_dtype,
   return hipGetLastError();
 }
 
+// ---- col2im: the adjoint of im2col.  d_pixels[b][c][y][x] = d_cols[(b, y / P, x / P)][c*P*P + (y % P)*P + x % P] for
+// y < gh*P and x < gw*P, exact zero on the trailing rows / columns the 'valid' convolution never reads.  Patches do not
+// overlap, so every pixel has one source: a gather, no atomics, bitwise reproducible.  Columns >= 3*P*P of d_cols are never
+// read.  One thread writes V consecutive floats of one pixel row of the output (row = W floats in NCHW, 3*W in NHWC):
+// V = 4 (one 16-byte store) when the row length is a multiple of 4, and the four sources are one 16-byte load when they
+// are four consecutive kx of one patch (NCHW, P % 4 == 0); otherwise four 4-byte loads.  HBM-bound: 4 B read + 4 B written
+// per pixel.  Index decode: one 64-bit divide per thread (group -> pixel row); the row number (< 2^31, checked by the
+// launcher) and everything inside the row are 32-bit.
+template <int V>
+__global__ __launch_bounds__(256) void col2im_kernel(const float* __restrict__ dc, float* __restrict__ dpix,
+                                                     int channels_last, int H, int W, int P, int gh, int gw, int Kp,
+                                                     int vec_src, size_t groups, unsigned gpr) {
+  const unsigned rowlen = gpr * V;   // floats per pixel row of the output
+  const unsigned PP = (unsigned)(P * P);
+  for (size_t gi = (size_t)blockIdx.x * 256 + threadIdx.x; gi < groups; gi += (size_t)gridDim.x * 256) {
+    const unsigned row = (unsigned)(gi / gpr);
+    const unsigned e0 = (unsigned)(gi - (size_t)row * gpr) * V;   // first float of the group within its row
+    // NCHW: row = (b*3 + c)*H + y;  NHWC: row = b*H + y
+    const unsigned q = row / (unsigned)H, y = row - q * (unsigned)H;
+    const unsigned b = channels_last ? q : q / 3u, c0 = channels_last ? 0u : q - b * 3u;
+    const unsigned gy = y / (unsigned)P, ky = y - gy * (unsigned)P;
+    const bool row_ok = gy < (unsigned)gh;
+    // the ky-th row of patch (b, gy, 0), channel 0; patch gx is gx*Kp further, channel c is c*P*P further
+    const float* src = dc + ((size_t)b * gh + gy) * gw * Kp + ky * (unsigned)P;
+    float* dst = dpix + (size_t)row * rowlen + e0;
+    float v[V];
+    if (V == 4 && vec_src) {   // NCHW, P % 4 == 0, W % 4 == 0: x % 4 == 0, so the four pixels are kx .. kx + 3 of one patch row
+      const unsigned gx = e0 / (unsigned)P, kx = e0 - gx * (unsigned)P;
+      f32x4 t = {0.f, 0.f, 0.f, 0.f};
+      if (row_ok && gx < (unsigned)gw) t = *reinterpret_cast<const f32x4*>(src + (size_t)gx * Kp + c0 * PP + kx);
+#pragma unroll
+      for (int j = 0; j < V; ++j) v[j] = t[j];
+    } else {
+#pragma unroll
+      for (int j = 0; j < V; ++j) {
+        const unsigned e = e0 + j;
+        const unsigned x = channels_last ? e / 3u : e, c = channels_last ? e - x * 3u : c0;
+        const unsigned gx = x / (unsigned)P, kx = x - gx * (unsigned)P;
+        v[j] = (row_ok && gx < (unsigned)gw) ? src[(size_t)gx * Kp + c * PP + kx] : 0.f;
+      }
+    }
+    if constexpr (V == 4) {
+      *reinterpret_cast<f32x4*>(dst) = f32x4{v[0], v[1], v[2], v[3]};
+    } else {
+      dst[0] = v[0];
+    }
+  }
+}
+
+hipError_t col2im(const float* d_cols, int B, int H, int W, int P, int Kp, float* d_pixels, int channels_last,
+                  hipStream_t s) {
+  if (B <= 0 || H <= 0 || W <= 0 || P <= 0 || Kp < 3 * P * P || (channels_last != 0 && channels_last != 1))
+    return hipErrorInvalidValue;
+  const int gh = H / P, gw = W / P;
+  const size_t rows = (size_t)B * H * (channels_last ? 1 : 3);
+  const size_t rowlen = (size_t)W * (channels_last ? 3 : 1);
+  if (rows >= (1ull << 31) || rowlen >= (1ull << 31)) return hipErrorInvalidValue;   // 32-bit row arithmetic in the kernel
+  const bool v4 = (rowlen % 4) == 0 && (((uintptr_t)d_pixels) & 15) == 0;
+  const int vec_src = v4 && !channels_last && (P % 4) == 0 && (Kp % 4) == 0 && (((uintptr_t)d_cols) & 15) == 0;
+  const unsigned gpr = (unsigned)(v4 ? rowlen / 4 : rowlen);   // groups per row
+  const size_t groups = rows * gpr;
+  const int blocks = (int)((groups + 255) / 256 < 16384 ? (groups + 255) / 256 : 16384);
+  if (v4)
+    hipLaunchKernelGGL(col2im_kernel<4>, dim3(blocks), dim3(256), 0, s, d_cols, d_pixels, channels_last, H, W, P, gh, gw, Kp,
+                       vec_src, groups, gpr);
+  else
+    hipLaunchKernelGGL(col2im_kernel<1>, dim3(blocks), dim3(256), 0, s, d_cols, d_pixels, channels_last, H, W, P, gh, gw, Kp,
+                       0, groups, gpr);
+  return hipGetLastError();
+}
+
 // ---- weight shadows: dst[Rp][Cp] = pad(cast(src[R][C])) and the transposed form dst[Cp][Rp] ------------
 template <typename T>
 __global__ __launch_bounds__(256) void cast_pad_kernel(const float* __restrict__ src, int R, int C, int ld,

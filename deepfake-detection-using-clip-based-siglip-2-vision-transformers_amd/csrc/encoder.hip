@@ -1141,11 +1141,11 @@ int sgl_backward_layer_p(sgl_ctx* ctx, const sgl_weights* w, const void* shadow,
   return SGL_OK;
 }
 
-int sgl_backward_embed(sgl_ctx* ctx, const sgl_weights* w, const sgl_grads* g, int B, int H, int W, int interpolate_pos,
-                       const void* saved, size_t saved_bytes, void* ws, size_t ws_bytes, sgl_stream stream) {
-  if (!ctx || !w || !g) return SGL_ERR_NULL;
-  Call c;
-  RET(begin_call(c, BACKWARD, ctx, nullptr, B, H, W, saved, saved_bytes, ws, ws_bytes, stream));
+namespace {
+
+// Patch-embedding parameter gradients from d hidden_states[0] (dx fp32 and its low-precision copy gbuf in ws)
+int embed_param_backward(const Call& c, const sgl_grads* g) {
+  sgl_ctx* ctx = c.ctx;
   const Layout& lay = c.lay;
   hipStream_t s = c.s;
   const int D = ctx->D, M = lay.M, N = lay.N;
@@ -1157,15 +1157,73 @@ int sgl_backward_embed(sgl_ctx* ctx, const sgl_weights* w, const sgl_grads* g, i
   if (g->patch_b) CK(batch_sum(c.wsf(lay.w_gsum), 1, (size_t)D, g->patch_b, acc, s));
   if (g->pos) {
     if (lay.gh == ctx->g0 && lay.gw == ctx->g0) {
-      CK(batch_sum(dx, B, (size_t)N * D, g->pos, acc, s));
+      CK(batch_sum(dx, lay.B, (size_t)N * D, g->pos, acc, s));
     } else {
       float* dpos = c.wsf(lay.w_dlast);  // [N][D] scratch
-      CK(batch_sum(dx, B, (size_t)N * D, dpos, 0, s));
+      CK(batch_sum(dx, lay.B, (size_t)N * D, dpos, 0, s));
       if (!acc) CK(hipMemsetAsync(g->pos, 0, (size_t)ctx->g0 * ctx->g0 * D * 4, s));
       CK(pos_resize_bwd(dpos, lay.gh, lay.gw, g->pos, ctx->g0, D, s));
     }
   }
+  return SGL_OK;
+}
+
+// The caller's scratch of sgl_backward_embed_px: d_cols [M][Kp] fp32 (the patch GEMM's dX), then W_patch^T [Kp][D] in the
+// compute dtype (rows K0 .. Kp zero).  The bf16x3 split of that one product (A [M][D], B [Kp][D]) is never wider than the
+// operands the call's own split scratch is sized for (Layout: sp_act / sp_wgt), so it needs no room here.
+struct PxLayout {
+  size_t dcols = 0, wpt = 0, total = 0;
+  PxLayout(const sgl_ctx* c, int M) {
+    Bump b;
+    dcols = b.take((size_t)M * c->Kp * 4);
+    wpt = b.take((size_t)c->Kp * c->D * c->es);
+    total = b.off;
+  }
+};
+
+}  // namespace
+
+int sgl_backward_embed(sgl_ctx* ctx, const sgl_weights* w, const sgl_grads* g, int B, int H, int W, int interpolate_pos,
+                       const void* saved, size_t saved_bytes, void* ws, size_t ws_bytes, sgl_stream stream) {
+  if (!ctx || !w || !g) return SGL_ERR_NULL;
+  Call c;
+  RET(begin_call(c, BACKWARD, ctx, nullptr, B, H, W, saved, saved_bytes, ws, ws_bytes, stream));
   (void)interpolate_pos;
+  return embed_param_backward(c, g);
+}
+
+int sgl_query_input_grad_bytes(const sgl_ctx* ctx, int B, int H, int W, size_t* scratch_bytes) {
+  if (!ctx || !scratch_bytes) return SGL_ERR_NULL;
+  if (!train_shape_ok(ctx, B, H, W)) return SGL_ERR_BAD_SHAPE;
+  if (ctx->mx) return SGL_ERR_UNSUPPORTED;   // the MX-fp8 mode has no backward
+  *scratch_bytes = PxLayout(ctx, B * (H / ctx->P) * (W / ctx->P)).total;
+  return SGL_OK;
+}
+
+// sgl_backward_embed, then d_pixels = col2im(lowp(d hidden_states[0]) . W_patch): the patch GEMM's dX as an NT GEMM against
+// the transposed patch weight, which is cast per call into the caller's scratch (no shadow of it exists)
+int sgl_backward_embed_px(sgl_ctx* ctx, const sgl_weights* w, const sgl_grads* g, int B, int H, int W,
+                          int interpolate_pos, float* d_pixels, int channels_last, void* px_scratch,
+                          size_t px_scratch_bytes, const void* saved, size_t saved_bytes, void* ws, size_t ws_bytes,
+                          sgl_stream stream) {
+  if (!ctx || !w || !g || !w->patch_w) return SGL_ERR_NULL;
+  if (!d_pixels || !px_scratch) return SGL_ERR_NULL;
+  if (channels_last != 0 && channels_last != 1) return SGL_ERR_UNSUPPORTED;   // a ready patch operand has no pixels
+  Call c;
+  RET(begin_call(c, BACKWARD, ctx, nullptr, B, H, W, saved, saved_bytes, ws, ws_bytes, stream));
+  const Layout& lay = c.lay;
+  const PxLayout px(ctx, lay.M);
+  if (px_scratch_bytes < px.total) return SGL_ERR_WORKSPACE;
+  (void)interpolate_pos;
+  RET(embed_param_backward(c, g));
+  const int D = ctx->D, Kp = ctx->Kp;
+  float* dcols = reinterpret_cast<float*>(at(px_scratch, px.dcols));
+  void* wpt = at(px_scratch, px.wpt);
+  CastJob job;   // transposed copy only: wpt[k][d] = cast(patch_w[d][k]), zero for k >= K0
+  cast_job_add(job, w->patch_w, D, ctx->K0, ctx->K0, nullptr, D, Kp, Kp, wpt, D);
+  CK(cast_job_run(job, ctx->dt, c.s));
+  CK(c.gemm_nt(c.wsp(lay.w_g), D, wpt, D, lay.M, Kp, D, EPI_F32, DT_F32, epi_f32(dcols, Kp)));
+  CK(col2im(dcols, lay.B, H, W, ctx->P, Kp, d_pixels, channels_last, c.s));
   return SGL_OK;
 }
 
@@ -1309,6 +1367,13 @@ int sgl_op_colsum(int dtype, const void* in, int ld, int M, int N, float* out, i
 int sgl_op_im2col(const float* pixels, int channels_last, void* out, int out_dtype, int B, int H, int W, int P, int Kp,
                   sgl_stream stream) {
   CKV(im2col(pixels, channels_last, out, out_dtype, B, H, W, P, Kp, (hipStream_t)stream));
+  return SGL_OK;
+}
+
+int sgl_op_col2im(const float* d_cols, int B, int H, int W, int P, int Kp, float* d_pixels, int channels_last,
+                  sgl_stream stream) {
+  if (!d_cols || !d_pixels) return SGL_ERR_NULL;
+  CKV(col2im(d_cols, B, H, W, P, Kp, d_pixels, channels_last, (hipStream_t)stream));
   return SGL_OK;
 }
 

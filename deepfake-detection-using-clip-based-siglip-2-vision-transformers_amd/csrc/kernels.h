@@ -94,6 +94,10 @@ hipError_t reduce_partials3(const float* partial, int nblk, int stride, float* o
 // ---- elementwise.hip ---------------------------------------------------------------------------------
 hipError_t im2col(const float* pix, int channels_last, void* out, int out_dtype, int B, int H, int W, int P,
                   int Kp, hipStream_t s);
+// the adjoint of im2col: d_cols fp32 [B*(H/P)*(W/P)][Kp] (columns >= 3*P*P never read) -> d_pixels fp32 (B,3,H,W), NCHW or
+// NHWC storage (channels_last 0 / 1); every pixel is written, the trailing rows / columns no patch covers with zeros
+hipError_t col2im(const float* d_cols, int B, int H, int W, int P, int Kp, float* d_pixels, int channels_last,
+                  hipStream_t s);
 // dst[r][c] (row stride ldd) = cast(src[r][c]) for r < Rp, c < Cp, zero outside src's R x C
 hipError_t cast_pad(const float* src, int R, int C, int lds_, void* dst, int dst_dtype, int Rp, int Cp, int ldd,
                     hipStream_t s);

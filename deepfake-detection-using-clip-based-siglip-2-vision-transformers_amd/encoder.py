@@ -276,12 +276,15 @@ def _(pixel_values, params, handle, train, interp, want_pooled, tap_ids, first_t
 def encoder_bwd(grads: Sequence[Optional[torch.Tensor]], taps: Sequence[torch.Tensor], saved: torch.Tensor,
                 hs_rest: torch.Tensor, params: Sequence[torch.Tensor], handle: int, image_hw: Sequence[int],
                 interp: bool, want_pooled: bool, tap_ids: Sequence[int], needs: Sequence[bool],
-                recompute: bool = False) -> List[torch.Tensor]:
+                recompute: bool = False, want_px: bool = False, px_channels_last: bool = False) -> List[torch.Tensor]:
     """sgl_backward_begin_p -> sgl_backward_layer_p (L-1 ... first trainable block) -> sgl_backward_embed, on the context
     of the policy the forward ran with (recompute: each sgl_backward_layer_p recomputes its block first).
     grads = [d pooled, d last_hidden_state, d tap...] (None = no gradient).  Returns the flat fp32 gradient chunks of
     ``SiglipVisionModelHIP._bucket_layout(needs)`` (the DDP all-reduce units); the autograd formula slices the
-    per-parameter views out of them outside the op, so no output of the op aliases another."""
+    per-parameter views out of them outside the op, so no output of the op aliases another.
+    want_px: the input requires a gradient.  Every block L-1 ... 0 then runs with need_dx = 1 (frozen ones with NULL
+    destinations), sgl_backward_embed_px replaces sgl_backward_embed, and d_pixels (B,3,H,W) fp32, in channels_last memory
+    format when px_channels_last, is one more output after the chunks (no chunk when the whole encoder is frozen)."""
     mod = _module_of(handle)
     lib = _lib.load()
     cfg = mod.config
@@ -345,7 +348,7 @@ def encoder_bwd(grads: Sequence[Optional[torch.Tensor]], taps: Sequence[torch.Te
         train_emb = "emb" in groups
         layer_ids = sorted(int(k_[5:]) for k_ in groups if k_.startswith("layer"))
         first = layer_ids[0] if layer_ids else L
-        stop = 0 if train_emb else first
+        stop = 0 if (train_emb or want_px) else first
         recompute = bool(recompute)
         sizes = mod._sizes(B, H, W, True, recompute)
         ws = mod._workspace(sizes[2], dev)
@@ -358,26 +361,46 @@ def encoder_bwd(grads: Sequence[Optional[torch.Tensor]], taps: Sequence[torch.Te
         _lib.check(st, "sgl_backward_begin_p", cx)
         group_done("head")
         for l in range(L - 1, stop - 1, -1):
-            need_dx = 1 if (l > stop or train_emb) else 0
+            need_dx = 1 if (l > stop or train_emb or want_px) else 0
             st = lib.sgl_backward_layer_p(cx, C.byref(wts), shadow.data_ptr(), C.byref(g), l, B, H, W, hs_ptr[l],
                                           _lib.ptr(tap_grads[l]), need_dx, saved.data_ptr(), sizes[1], ws.data_ptr(),
                                           sizes[2], stream)
             _lib.check(st, f"sgl_backward_layer_p[{l}]", cx)
             group_done(f"layer{l}")
-        if train_emb:
+        d_pixels = None
+        if want_px:
+            d_pixels = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev,
+                                   memory_format=torch.channels_last if px_channels_last else torch.contiguous_format)
+            nbytes = C.c_size_t()
+            _lib.check(lib.sgl_query_input_grad_bytes(cx, B, H, W, C.byref(nbytes)), "sgl_query_input_grad_bytes", cx)
+            px_scratch = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+            st = lib.sgl_backward_embed_px(cx, C.byref(wts), C.byref(g), B, H, W, 1 if interp else 0,
+                                           d_pixels.data_ptr(), 1 if px_channels_last else 0, px_scratch.data_ptr(),
+                                           nbytes.value, saved.data_ptr(), sizes[1], ws.data_ptr(), sizes[2], stream)
+            _lib.check(st, "sgl_backward_embed_px", cx)
+        elif train_emb:
             st = lib.sgl_backward_embed(cx, C.byref(wts), C.byref(g), B, H, W, 1 if interp else 0,
                                         saved.data_ptr(), sizes[1], ws.data_ptr(), sizes[2], stream)
             _lib.check(st, "sgl_backward_embed", cx)
+        if train_emb:
             group_done("emb")
         if overlapped:
             reducer.finish()
-    return flats
+    return flats + ([d_pixels] if want_px else [])
 
 
 @encoder_bwd.register_fake
-def _(grads, taps, saved, hs_rest, params, handle, image_hw, interp, want_pooled, tap_ids, needs, recompute=False):
-    chunks, _ = _module_of(handle)._bucket_layout(needs)
-    return [saved.new_empty((total,), dtype=torch.float32) for total, _, _ in chunks]
+def _(grads, taps, saved, hs_rest, params, handle, image_hw, interp, want_pooled, tap_ids, needs, recompute=False,
+      want_px=False, px_channels_last=False):
+    mod = _module_of(handle)
+    chunks, _ = mod._bucket_layout(needs)
+    outs = [saved.new_empty((total,), dtype=torch.float32) for total, _, _ in chunks]
+    if want_px:
+        H, W, P = int(image_hw[0]), int(image_hw[1]), mod.config.patch_size
+        B = taps[0].shape[0] if len(taps) else hs_rest.shape[1] // ((H // P) * (W // P))
+        outs.append(saved.new_empty((B, 3, H, W), dtype=torch.float32).contiguous(
+            memory_format=torch.channels_last if px_channels_last else torch.contiguous_format))
+    return outs
 
 
 def _encoder_setup_context(ctx, inputs, output):
@@ -388,6 +411,10 @@ def _encoder_setup_context(ctx, inputs, output):
     ctx.handle, ctx.interp, ctx.want_pooled, ctx.tap_ids = handle, interp, want_pooled, list(tap_ids)
     ctx.image_hw = [int(img_h), int(img_w)] if layout == 2 else [int(pixel_values.shape[2]), int(pixel_values.shape[3])]
     ctx.ntaps, ctx.nparams, ctx.train = len(tap_ids), len(params), train
+    # d_pixels comes back in the input's dtype and memory format (the storage the forward read when it is fp32)
+    ctx.px_dtype = pixel_values.dtype
+    ctx.px_channels_last = bool(layout != 2 and pixel_values.dim() == 4 and not pixel_values.is_contiguous()
+                                and pixel_values.is_contiguous(memory_format=torch.channels_last))
     if train:
         # saving the taps (outputs) makes autograd's version counter catch a consumer's in-place edit of a hidden state
         ctx.save_for_backward(*output[2:], *params)
@@ -407,8 +434,18 @@ def _encoder_backward(ctx, grads):
     taps, saved, hs_rest, params = list(saved_t[:nt]), saved_t[nt], saved_t[nt + 1], list(saved_t[nt + 2:])
     needs = [bool(n) for n in ctx.needs_input_grad[1]] if isinstance(ctx.needs_input_grad[1], (list, tuple)) \
         else [p.requires_grad for p in params]
+    want_px = bool(ctx.needs_input_grad[0])
+    if want_px and torch.is_grad_enabled():
+        raise RuntimeError("SiglipVisionModelHIP: double backward (create_graph=True) through d loss / d pixel_values is "
+                           "not supported: the HIP backward is not itself differentiable; take first-order gradients "
+                           "(create_graph=False), or use finite differences of them for a Hessian-vector product")
     flats = torch.ops.siglip_hip.encoder_bwd(list(grads[:2 + nt]), taps, saved, hs_rest, params, ctx.handle, ctx.image_hw,
-                                             ctx.interp, ctx.want_pooled, ctx.tap_ids, needs, ctx.recompute)
+                                             ctx.interp, ctx.want_pooled, ctx.tap_ids, needs, ctx.recompute, want_px,
+                                             ctx.px_channels_last)
+    d_pixels = None
+    if want_px:
+        d_pixels = flats[-1] if ctx.px_dtype == torch.float32 else flats[-1].to(ctx.px_dtype)
+        flats = flats[:-1]
     chunks, _ = _module_of(ctx.handle)._bucket_layout(needs)
     pgrads: List[Optional[torch.Tensor]] = [None] * len(params)
     for flat, (_, _, entries) in zip(flats, chunks):
@@ -416,7 +453,7 @@ def _encoder_backward(ctx, grads):
             pgrads[i] = flat[off:off + n].view(params[i].shape)
     # pytree structure of the inputs: an EMPTY int list is a list node, a non-empty one a leaf (torch/_library/autograd.py)
     # one entry per argument the caller passed (needs_input_grad has that structure): 11, or 12 with recompute
-    return (None, pgrads, None, None, None, None, ([] if len(ctx.tap_ids) == 0 else None), None, None, None, None) + \
+    return (d_pixels, pgrads, None, None, None, None, ([] if len(ctx.tap_ids) == 0 else None), None, None, None, None) + \
         (None,) * (len(ctx.needs_input_grad) - 11)
 
 
@@ -580,9 +617,16 @@ class SiglipVisionModelHIP(nn.Module):
         if pixel_values.device.type != "cuda":
             raise RuntimeError("SiglipVisionModelHIP runs only on an AMD GPU through libsiglip_hip.so "
                                "(no CPU fallback); move the model and pixel_values to 'cuda'")
-        if pixel_values.requires_grad:
-            raise RuntimeError("SiglipVisionModelHIP does not differentiate with respect to pixel_values (the reference "
-                               "never asks for it); detach the input")
+        # the input's own gradient (adversarial examples, saliency): the backward then runs through every block
+        want_px = torch.is_grad_enabled() and pixel_values.requires_grad
+        if want_px and layout == 2:
+            raise RuntimeError("patches= with an operand that requires a gradient: the fused input transform "
+                               "(preprocess.to_patch_operand) is not differentiable; pass the resized, normalised images "
+                               "as pixel_values (B,3,H,W) with requires_grad=True instead, or detach the operand")
+        if want_px and self.compute_dtype in INFERENCE_ONLY:
+            raise RuntimeError(f"compute_dtype={self.compute_dtype!r} is inference-only and cannot differentiate with "
+                               "respect to pixel_values: detach the input, or use compute_dtype='bf16' / 'fp16' / 'bf16x3' / "
+                               "'fp32' for the gradient")
         L = self.config.num_hidden_layers
         if hidden_state_ids is not None:
             tap_ids = tuple(int(i) % (L + 1) for i in hidden_state_ids)
@@ -592,14 +636,15 @@ class SiglipVisionModelHIP(nn.Module):
             tap_ids = ()
         uniq = sorted(set(tap_ids))
         params = self._flat_params()
-        train = torch.is_grad_enabled() and any(p.requires_grad for p in params)
+        train = torch.is_grad_enabled() and (want_px or any(p.requires_grad for p in params))
         if train and self.compute_dtype in INFERENCE_ONLY:
             raise RuntimeError(f"compute_dtype={self.compute_dtype!r} is inference-only and cannot differentiate the "
                                "encoder: freeze it (encoder.requires_grad_(False); heads on top still train), run under "
                                "torch.no_grad(), or use compute_dtype='bf16' to train it")
         # first block that can receive a gradient (frozen prefix, Siglip2sidafrozen.py:757-768); 0 when the embeddings train
+        # (an input that requires a gradient makes every block differentiable: first = 0)
         first = 0
-        if train and not any(p.requires_grad for p in params[:3]):
+        if train and not want_px and not any(p.requires_grad for p in params[:3]):
             first = L
             for (grp, _), p in zip(self._flat_names, params):
                 if p.requires_grad and grp.startswith("layer"):

@@ -117,6 +117,9 @@ def load():
                                         _fp, i, _fp, sz, _fp, sz, _fp])
     _sig(lib, "sgl_backward_embed", i, [C.c_void_p, C.POINTER(SglWeights), C.POINTER(SglGrads), i, i, i, i, _fp, sz,
                                         _fp, sz, _fp])
+    _sig(lib, "sgl_query_input_grad_bytes", i, [C.c_void_p, i, i, i, psz])
+    _sig(lib, "sgl_backward_embed_px", i, [C.c_void_p, C.POINTER(SglWeights), C.POINTER(SglGrads), i, i, i, i, _fp, i, _fp,
+                                           sz, _fp, sz, _fp, sz, _fp])
     _sig(lib, "sgl_backward", i, [C.c_void_p, C.POINTER(SglWeights), _fp, C.POINTER(SglGrads), i, i, i, i, _fp,
                                   C.POINTER(_fp), _fp, _fp, i, i, _fp, sz, _fp, sz, _fp])
     _sig(lib, "sgl_op_layernorm_fwd", i, [_fp, _fp, _fp, _fp, i, _fp, _fp, i, i, f, _fp])
@@ -132,6 +135,7 @@ def load():
     _sig(lib, "sgl_op_attn_bwd", i, [i, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, i, i, i, i, i, i, _fp])
     _sig(lib, "sgl_op_colsum", i, [i, _fp, i, i, i, _fp, i, _fp, sz, _fp])
     _sig(lib, "sgl_op_im2col", i, [_fp, i, _fp, i, i, i, i, i, i, _fp])
+    _sig(lib, "sgl_op_col2im", i, [_fp, i, i, i, i, i, _fp, i, _fp])
     _sig(lib, "sgl_op_pos_resize", i, [_fp, i, _fp, i, i, i, _fp])
     i64 = C.c_int64
     _sig(lib, "sgl_adamw_plan", i64, [C.POINTER(C.c_uint64), i, C.POINTER(C.c_int32), i64])

@@ -174,7 +174,9 @@ int sgl_forward(sgl_ctx* ctx, const sgl_weights* w, const void* shadow, const fl
                 int H, int W, int interpolate_pos, float* hidden_states, int hs_slots, float* last_hidden,
                 float* pooled, void* saved, size_t saved_bytes, void* ws, size_t ws_bytes, sgl_stream stream);
 /* sgl_forward with a frozen prefix declared: blocks < first_trainable_block will not be differentiated
- * (sgl_backward_layer is never called for them), so their GELU pre-activations are not saved. */
+ * (sgl_backward_layer is never called for them), so their GELU pre-activations are not saved.  A caller who wants the
+ * input gradient (sgl_backward_embed_px) passes 0, whatever is frozen: the backward then runs through every block, and
+ * the GELU pre-activations are saved for every block. */
 int sgl_forward_ex(sgl_ctx* ctx, const sgl_weights* w, const void* shadow, const float* pixels, int channels_last, int B,
                    int H, int W, int interpolate_pos, float* hidden_states, int hs_slots, float* last_hidden,
                    float* pooled, void* saved, size_t saved_bytes, void* ws, size_t ws_bytes, int first_trainable_block,
@@ -216,7 +218,28 @@ int sgl_backward_layer_p(sgl_ctx* ctx, const sgl_weights* w, const void* shadow,
 /* Patch-embedding / position-table gradients from the workspace gradient (d hidden_states[0]). */
 int sgl_backward_embed(sgl_ctx* ctx, const sgl_weights* w, const sgl_grads* g, int B, int H, int W, int interpolate_pos,
                        const void* saved, size_t saved_bytes, void* ws, size_t ws_bytes, sgl_stream stream);
-/* d_taps: HOST array of L+1 device pointers (NULL entries allowed) or NULL.  Stops above first_trainable_block. */
+/* ---- gradient with respect to the input pixels (new symbols; sgl_abi_version() stays 3: nothing existing changed) ------
+ * sgl_backward_embed_px does everything sgl_backward_embed does, for whichever of g->patch_w / patch_b / pos are non-NULL
+ * (all three may be NULL: a frozen encoder), and then writes d_pixels = d loss / d pixels: fp32 (B,3,H,W), NCHW, or NHWC
+ * storage when channels_last == 1 (the storage the forward read; 2, the ready patch operand, is SGL_ERR_UNSUPPORTED).
+ * d_pixels is ALWAYS overwritten, every element of it: g->accumulate governs the parameter destinations only; the
+ * trailing rows / columns of an image the patch size does not divide feed nothing and get exact zeros.
+ * Call order: sgl_forward* with first_trainable_block = 0, sgl_backward_begin*, sgl_backward_layer* for EVERY block
+ * L-1 ... 0 with need_dx = 1 (gradient destinations of frozen blocks NULL), then this call instead of sgl_backward_embed.
+ * px_scratch: px_scratch_bytes >= what sgl_query_input_grad_bytes reports for (B, H, W): the patch GEMM's dX
+ * [B*N][round_up(3p^2, 64)] fp32 and the transposed patch weight in the compute dtype, cast per call (the shadow arena has
+ * no such copy and sgl_query_sizes reports what it always reported); the bf16x3 split of that one product fits the split
+ * scratch `ws` already holds.  Needed only during the call.
+ * Errors, all before anything is enqueued: the checks of sgl_backward_embed, plus d_pixels / px_scratch / w->patch_w NULL
+ * -> SGL_ERR_NULL (first), px_scratch_bytes too small -> SGL_ERR_WORKSPACE (after the saved / ws checks); the token limit
+ * of a recompute context applies (SGL_ERR_BAD_SHAPE); an SGL_DTYPE_MXFP8 context -> SGL_ERR_UNSUPPORTED from both. */
+int sgl_query_input_grad_bytes(const sgl_ctx* ctx, int B, int H, int W, size_t* scratch_bytes);
+int sgl_backward_embed_px(sgl_ctx* ctx, const sgl_weights* w, const sgl_grads* g, int B, int H, int W,
+                          int interpolate_pos, float* d_pixels, int channels_last, void* px_scratch,
+                          size_t px_scratch_bytes, const void* saved, size_t saved_bytes, void* ws, size_t ws_bytes,
+                          sgl_stream stream);
+/* d_taps: HOST array of L+1 device pointers (NULL entries allowed) or NULL.  Stops above first_trainable_block.
+ * (No input gradient: a caller who wants d_pixels makes the stepwise calls above.) */
 int sgl_backward(sgl_ctx* ctx, const sgl_weights* w, const void* shadow, const sgl_grads* g, int B, int H, int W,
                  int interpolate_pos, const float* hidden_states, const float* const* d_taps,
                  const float* d_last_hidden, const float* d_pooled, int first_trainable_block, int train_embeddings,
@@ -266,9 +289,10 @@ int sgl_op_gemm_tn_ws(int dtype, const void* A, int lda, const void* B, int ldb,
  * dtype: SGL_DTYPE_BF16 (bf16 operands, bf16 MFMA, fp32 softmax), SGL_DTYPE_F32 (fp32 operands, plain FMAs: the reference
  *   kernels), SGL_DTYPE_BF16X3 (fp32 operands on v_mfma_f32_32x32x2_f32: what the strict MFMA mode uses) or
  *   SGL_DTYPE_F16 (the bf16 kernels on fp16 operands, fp16 MFMA, fp32 softmax).
- * ld_qkv > 0 (added in ABI 3): q, k, v point at the three column blocks of the QKV projection's
- *   token-major output [B*N][ld_qkv]; head h of token row r is the head_dim elements at r*ld_qkv + h*head_dim (16-byte
- *   aligned: head_dim % 8 == 0, ld_qkv % 8 == 0, pointers 16-byte aligned).  Nothing is padded in memory.
+ * ld_qkv > 0 (the argument was added in ABI 3; an optional input layout, NOT the one the encoder uses): q, k, v point at
+ *   the three column blocks of the QKV projection's token-major output [B*N][ld_qkv]; head h of token row r is the
+ *   head_dim elements at r*ld_qkv + h*head_dim (16-byte aligned: head_dim % 8 == 0, ld_qkv % 8 == 0, pointers 16-byte
+ *   aligned).  Nothing is padded in memory.
  * ld_qkv == 0 (what the encoder uses; DESIGN.md section 8.4 records the measurement behind that): head-major
  *   [B][H][N][head_dim_pad] matrices whose pad columns are zero (EPI_QKV's layout).
  * out: token-major [B*N][H*head_dim]; lse: [B][H][N]. */
@@ -282,6 +306,11 @@ int sgl_op_attn_bwd(int dtype, const void* q, const void* k, const void* v, cons
 int sgl_op_colsum(int dtype, const void* in, int ld, int M, int N, float* out, int accumulate, float* scratch,
                   size_t scratch_bytes, sgl_stream stream);
 int sgl_op_im2col(const float* pixels, int channels_last, void* out, int out_dtype, int B, int H, int W, int P, int Kp,
+                  sgl_stream stream);
+/* The adjoint of sgl_op_im2col: d_cols fp32 [B*(H/P)*(W/P)][Kp] (columns k = c*P*P + ky*P + kx; columns >= 3*P*P are never
+ * read and may hold anything) -> d_pixels fp32 (B,3,H,W), NCHW (channels_last == 0) or NHWC storage (1).  Patches do not
+ * overlap: a pure gather, bitwise reproducible.  Every pixel is written; rows >= (H/P)*P and columns >= (W/P)*P get 0. */
+int sgl_op_col2im(const float* d_cols, int B, int H, int W, int P, int Kp, float* d_pixels, int channels_last,
                   sgl_stream stream);
 int sgl_op_pos_resize(const float* table, int native_grid, float* out, int gh, int gw, int D, sgl_stream stream);
 
