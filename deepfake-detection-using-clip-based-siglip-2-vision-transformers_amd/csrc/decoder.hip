@@ -114,6 +114,11 @@ static bool dw_shape_ok(int B, int gh, int gw, int E, int nv) {
   return B > 0 && gh > 0 && gw > 0 && E >= nv && E <= 1024 && (E % nv) == 0 && (256 % (E / nv)) == 0;
 }
 
+// every tensor the kernels touch with 16-byte vector accesses (a null `bias` counts as aligned)
+static bool dw_aligned16(const void* a, const void* b, const void* c, const void* d) {
+  return ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c) | ((uintptr_t)d)) & 15) == 0;
+}
+
 }  // namespace sgl
 
 extern "C" {
@@ -123,7 +128,7 @@ int sgl_op_dwconv3x3(const void* x, int dtype, const float* w, const float* bias
   if (!x || !w || !y) return SGL_ERR_NULL;
   if (dtype != SGL_DTYPE_BF16 && dtype != SGL_DTYPE_F32) return SGL_ERR_UNSUPPORTED;
   const int nv = dtype == SGL_DTYPE_BF16 ? 8 : 4;
-  if (!sgl::dw_shape_ok(B, gh, gw, E, nv)) return SGL_ERR_BAD_SHAPE;
+  if (!sgl::dw_shape_ok(B, gh, gw, E, nv) || !sgl::dw_aligned16(x, w, bias, y)) return SGL_ERR_BAD_SHAPE;
   const size_t total = (size_t)B * gh * gw * (E / nv);
   const int blocks = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
   hipStream_t s = (hipStream_t)stream;
@@ -146,7 +151,7 @@ int sgl_op_dwconv3x3_wgrad(const void* x, const void* dy, int dtype, float* dw10
   if (!x || !dy || !dw10 || !scratch) return SGL_ERR_NULL;
   if (dtype != SGL_DTYPE_BF16 && dtype != SGL_DTYPE_F32) return SGL_ERR_UNSUPPORTED;
   const int nv = dtype == SGL_DTYPE_BF16 ? 8 : 4;
-  if (!sgl::dw_shape_ok(B, gh, gw, E, nv)) return SGL_ERR_BAD_SHAPE;
+  if (!sgl::dw_shape_ok(B, gh, gw, E, nv) || !sgl::dw_aligned16(x, dy, nullptr, nullptr)) return SGL_ERR_BAD_SHAPE;
   const size_t npix = (size_t)B * gh * gw;
   int nblk = (int)(npix < 512 ? npix : 512);
   const int ppb = (int)((npix + nblk - 1) / nblk);

@@ -423,7 +423,9 @@ extern "C" {
 
 int sgl_op_l2norm_tmean_fwd(const float* f, float* out, float* inv_norm, int B, int T, int D, sgl_stream stream) {
   if (!f || !out || !inv_norm) return SGL_ERR_NULL;
-  if (B <= 0 || T <= 0 || D <= 0 || D > 16384) return SGL_ERR_BAD_SHAPE;
+  // D floats of dynamic LDS next to the kernel's 16 static bytes, inside the 64 KiB a launch gets without raising
+  // hipFuncAttributeMaxDynamicSharedMemorySize: D * 4 + 16 <= 65536
+  if (B <= 0 || T <= 0 || D <= 0 || D > 16380) return SGL_ERR_BAD_SHAPE;
   hipLaunchKernelGGL(sgl::l2norm_tmean_fwd_kernel, dim3((unsigned)B), dim3(256), (size_t)D * sizeof(float),
                      (hipStream_t)stream, f, out, inv_norm, T, D);
   return hipGetLastError() == hipSuccess ? SGL_OK : SGL_ERR_HIP;

@@ -171,6 +171,12 @@ def _linear_tokens(x: torch.Tensor, weight: torch.Tensor, bias) -> torch.Tensor:
     return F.linear(x, weight, bias)
 
 
+def _aligned16(t: torch.Tensor) -> torch.Tensor:
+    """`t` itself when its storage pointer is 16-byte aligned, otherwise a fresh copy (`.contiguous()` does not move a
+    contiguous offset view such as `buf[1:]`; the vector kernels need 16-byte aligned operands)."""
+    return t if t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.contiguous_format)
+
+
 class _DepthwiseConv3x3Fn(torch.autograd.Function):
     """Depthwise 3x3 (padding 1) on channels-last (B, gh, gw, E) CUDA tensors through the HIP kernels of
     csrc/decoder.hip: forward, data gradient (same stencil, flipped taps) and the two-stage weight/bias gradient."""
@@ -181,10 +187,10 @@ class _DepthwiseConv3x3Fn(torch.autograd.Function):
         lib = _lib.load()
         if x.dtype not in (torch.float32, torch.bfloat16):
             x = x.float()
-        x = x.contiguous()
+        x = _aligned16(x.contiguous())
         B, gh, gw, E = x.shape
         w = weight.detach().float().reshape(E, 9).t().contiguous()      # tap-major [9][E] (see siglip_hip.h)
-        b = None if bias is None else bias.detach().float().contiguous()
+        b = None if bias is None else _aligned16(bias.detach().float().contiguous())
         y = torch.empty_like(x)
         dt = _lib.SGL_DTYPE_BF16 if x.dtype == torch.bfloat16 else _lib.SGL_DTYPE_F32
         _lib.check(lib.sgl_op_dwconv3x3(x.data_ptr(), dt, w.data_ptr(), _lib.ptr(b), y.data_ptr(), B, gh, gw, E, 0,
@@ -199,7 +205,7 @@ class _DepthwiseConv3x3Fn(torch.autograd.Function):
         from . import lib as _lib
         lib = _lib.load()
         x, w = ctx.saved_tensors
-        dy = dy.to(x.dtype).contiguous()
+        dy = _aligned16(dy.to(x.dtype).contiguous())
         B, gh, gw, E = x.shape
         dt = _lib.SGL_DTYPE_BF16 if x.dtype == torch.bfloat16 else _lib.SGL_DTYPE_F32
         stream = _lib.current_stream_handle()
@@ -244,7 +250,7 @@ class _GateMulFn(torch.autograd.Function):
         from . import lib as _lib
         lib = _lib.load()
         g2, x2 = ctx.saved_tensors
-        dy2 = dy.to(g2.dtype).contiguous()
+        dy2 = _aligned16(dy.to(g2.dtype).contiguous())
         dg = torch.empty_like(g2) if ctx.needs_input_grad[0] else None
         dx = torch.empty_like(x2) if ctx.needs_input_grad[1] else None
         _lib.check(lib.sgl_op_gate_mul_bwd(dy2.data_ptr(), g2.data_ptr(), x2.data_ptr(), _lib.ptr(dg), _lib.ptr(dx),
@@ -256,7 +262,12 @@ class _GateMulFn(torch.autograd.Function):
 def _gate_mul(gate_pre: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
     nv = 8 if gate_pre.dtype == torch.bfloat16 else 4
     if gate_pre.is_cuda and gate_pre.shape == x.shape and gate_pre.numel() % nv == 0 and gate_pre.numel() >= 4096:
-        return _GateMulFn.apply(gate_pre, x)
+        # a contiguous offset view (buf[1:]) keeps its misaligned pointer through .to(dt).contiguous() when it already has
+        # the kernel's dtype (another dtype is cast into a fresh buffer): sgl_op_gate_mul refuses such a pointer
+        dt = gate_pre.dtype if gate_pre.dtype in (torch.float32, torch.bfloat16) else torch.float32
+        misaligned = any(t.dtype == dt and t.is_contiguous() and t.data_ptr() % 16 for t in (gate_pre, x))
+        if not misaligned:
+            return _GateMulFn.apply(gate_pre, x)
     return torch.sigmoid(gate_pre) * x
 
 

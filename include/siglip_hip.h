@@ -319,11 +319,13 @@ int sgl_op_pos_resize(const float* table, int native_grid, float* out, int gh, i
  * (nn.Conv2d(E, E, 3, padding=1, groups=E), Siglip2sidafrozen.py:713-718) on channels-last (B, gh, gw, E) data of
  * dtype f32 or bf16.  w9 holds the nine taps TAP-MAJOR in fp32: w9[k*E + e] = Conv2d.weight[e][0][k/3][k%3].
  * flip = 1 applies the 180-degree rotated taps (the data gradient: dx = sgl_op_dwconv3x3(dy, w9, NULL, flip = 1)).
- * E % 8 == 0 (bf16) / E % 4 == 0 (f32), E <= 1024, 256 % (E / 8 or 4) == 0. */
+ * E % 8 == 0 (bf16) / E % 4 == 0 (f32), E <= 1024, 256 % (E / 8 or 4) == 0.  x, y, w9 and bias (when not NULL) must be
+ * 16-byte aligned (16-byte vector accesses); anything else is SGL_ERR_BAD_SHAPE, before any launch. */
 int sgl_op_dwconv3x3(const void* x, int dtype, const float* w9, const float* bias, void* y, int B, int gh, int gw, int E,
                      int flip, sgl_stream stream);
 /* dw10[k*E + e] (+)= sum over pixels of x(shifted by tap k) * dy for k < 9, and dw10[9*E + e] (+)= sum dy (the bias
- * gradient); two deterministic stages, scratch >= sgl_op_dwconv3x3_wgrad_scratch_bytes(). */
+ * gradient); two deterministic stages, scratch >= sgl_op_dwconv3x3_wgrad_scratch_bytes().  x and dy must be 16-byte
+ * aligned (SGL_ERR_BAD_SHAPE otherwise, before any launch); dw10 and scratch need only their natural 4-byte alignment. */
 size_t sgl_op_dwconv3x3_wgrad_scratch_bytes(int B, int gh, int gw, int E);
 int sgl_op_dwconv3x3_wgrad(const void* x, const void* dy, int dtype, float* dw10, int accumulate, float* scratch,
                            size_t scratch_bytes, int B, int gh, int gw, int E, sgl_stream stream);
@@ -363,7 +365,13 @@ int sgl_op_preprocess_aug(const void* src, int src_is_u8_nhwc, int B, int Hs, in
 
 /* Video tail (hidf_video_classifier.py:304-316): per-frame embeddings f (B*T, D) fp32 -> each frame L2-normalised ->
  * mean over the T frames of a clip -> out (B, D); inv_norm (B*T) keeps 1/|f_t| for the backward
- * d f_t = (g - fhat_t (fhat_t . g)) / (T |f_t|), g = d out[b]. */
+ * d f_t = (g - fhat_t (fhat_t . g)) / (T |f_t|), g = d out[b].
+ * fwd: D <= 16380 (the clip's accumulator is D floats of LDS: D * 4 + 16 bytes within 64 KiB); a larger D is
+ * SGL_ERR_BAD_SHAPE.  Squares are summed in fp32: inv_norm is accurate to (D / 512 + 12) * 2^-24 relative (the D-term
+ * sum, sqrt and the division) as long as the squares are normal fp32 numbers, |f_t|^2 / D >= 2^-126 (|f_t| >= 1.1e-19 sqrt(D));
+ * below that each square rounds by up to 2^-150 absolute and the relative error of inv_norm grows to
+ * D * 2^-151 / |f_t|^2 (|f_t| = 1e-18: 4e-7 at D = 1152, 6e-6 at D = 16380).  A squared norm that overflows fp32
+ * (|f_t| > 1.8e19) gives inv_norm 0, one that underflows to 0 gives inf. */
 int sgl_op_l2norm_tmean_fwd(const float* f, float* out, float* inv_norm, int B, int T, int D, sgl_stream stream);
 int sgl_op_l2norm_tmean_bwd(const float* f, const float* inv_norm, const float* dout, float* df, int B, int T, int D,
                             sgl_stream stream);

@@ -20,6 +20,8 @@ in fp32) against float64, never from a kernel's output; tests/test_kernel_ref_ho
                 pre-activations and takes the largest deviation times 4 (the hardware exp2/rcp may be an ulp or two worse
                 than libm).  Over 2e5 N(0, 1.5) pre-activations it measures 1.9e-6 for gelu (half an ulp of |x| < 8, x 4) and
                 7.7e-6 for its derivative (the formula's own 1 - s cancellation, amplified by x (2z)' <= 35, x 4).
+  ADAMW_C = 2   AdamW (second half of the file, the kernels outside the encoder): the derived rounding counts times 2;
+                measured worst emulation/bound with c = 1 is 0.74 (exp_avg), with c = 2 0.37.
 """
 import math
 
@@ -471,3 +473,663 @@ def pos_resize_bound(table, g0):
     (A = -0.75, t = 0.5) per axis; the source coordinate scale (o + 0.5) - 0.5 carries up to 2 g0 2^-24 absolute error
     over both axes, which the weights (slope <= 1) pass on; 16 products and adds and the weight polynomials are the 24."""
     return ((2 * g0 + 24) * EPS32 * 1.375 ** 2) * table.double().abs().max(0).values
+
+
+# ===============================================================================================================
+# kernels outside the encoder (csrc/preprocess.hip, decoder.hip, decoder_tail.hip, optimizer.hip)
+#
+# Every bound below is derived: output rounding UNIT / TINY, fp32 accumulation from the number of addends the element
+# has (a sum of n fp32 terms in any order is off by at most n 2^-24 sum|terms|; where the kernel's order is fixed by the
+# code, n is the depth of that order: the per-thread strided chain plus the 6 butterfly stages and 2 LDS adds of a
+# 256-thread block), and explicit terms for the hardware approximations:
+#   V_EXP_F32 and V_RCP_F32 (`__builtin_amdgcn_exp2f`, `__builtin_amdgcn_rcpf`, and `__expf` = exp2(x log2 e)): 1 ulp
+#       each (the accuracy the public CDNA3 / CDNA4 ISA guides state for both instructions; no copy of the guide ships
+#       with the toolchain, so the figure is quoted, not read off a local file);  HW_ULPS = 1.
+#   V_RCP_F32 may flush a subnormal RESULT to zero, so a sigmoid below 2^-126 carries the absolute floor 2^-126.
+#   plain `/` and sqrtf: 2.5 ulp and 1 ulp at the worst (hipcc's default is correctly rounded; 2.5 ulp is the OpenCL
+#       figure the device library guarantees without that flag);  log1pf: 2 ulp (OCML's stated accuracy).
+# One constant is fitted, by the convention at the top of this file: ADAMW_C = 2 (see adamw_ref).  tests/
+# test_kernel_ref_host.py runs an fp32 emulation of every operation against its bound and asserts the worst ratio is at
+# most 0.5 for fp32 outputs (a 16-bit store alone reaches its own half-ulp term, so those are held to 1); the measured
+# ratios are listed there next to each assertion.
+# ===============================================================================================================
+ULP32 = 2.0 ** -23
+HW_ULPS = 1.0                    # V_EXP_F32 / V_RCP_F32
+DIV_ULPS, SQRT_ULPS, LOG1P_ULPS = 2.5, 1.0, 2.0
+FLT_MIN = 2.0 ** -126
+BLOCK_TREE = 8                   # wave_sum's 6 butterfly stages + (r0 + r1) + (r2 + r3)
+NV = {F32: 4, BF16: 8}
+
+
+def _f32c(x):
+    """The float32 rounding of a Python scalar, as a Python float (what the kernel receives for a `float` argument)."""
+    return torch.tensor(x, dtype=torch.float32).item()
+
+
+# ---- gate_mul --------------------------------------------------------------------------------------------------
+def sigmoid_fast_ref(z):
+    """float64 sigmoid(z) and the bound of `sigmoidf_fast` = rcp(1 + exp2(fl(-z L))), L = fl(log2 e):
+    the exponent fl(-z L) is off by 2 * 2^-24 |z| log2 e (L's rounding and the product's), i.e. exp2 by the RELATIVE
+    2 * 2^-24 |z|: the bound grows with |z|; V_EXP_F32 adds HW_ULPS ulp.  s = 1 / (1 + e) passes a relative error of e on
+    with the factor (1 - s); the add rounds once (2^-24) and V_RCP_F32 adds HW_ULPS ulp.  Absolute floor 2^-126: the
+    result of V_RCP_F32 may be flushed when subnormal, and exp2 overflows to inf (s = 0) only where s < 2^-126."""
+    z = z.double()
+    s = torch.sigmoid(z)
+    rel_e = 2 * EPS32 * z.abs() + HW_ULPS * ULP32
+    rel_s = (1 - s) * rel_e + EPS32 + HW_ULPS * ULP32
+    return s, s * rel_s * (1 + 1e-3) + FLT_MIN
+
+
+def gate_mul_ref(g, x, out_dt):
+    """y = sigmoid(g) x: bound = |x| err(s) + 2^-24 |y| (the product) + UNIT |y| + TINY (the store)."""
+    s, es = sigmoid_fast_ref(g)
+    x = x.double()
+    y = s * x
+    return y, x.abs() * es + (EPS32 + UNIT[out_dt]) * y.abs() + TINY[out_dt]
+
+
+def gate_mul_bwd_ref(dy, g, x, out_dt):
+    """dx = dy s;  dg = dy x (s (1 - s)).  fl(1 - s) is off by err(s) + 2^-24 (1 - s), so s (1 - s) by
+    (1 - s) err(s) + s (err(s) + 2^-24 (1 - s)) + 2^-24 s (1 - s) <= err(s) + 2 * 2^-24 s (1 - s); two more products."""
+    s, es = sigmoid_fast_ref(g)
+    d, x = dy.double(), x.double()
+    dx = d * s
+    dg = d * x * (s * (1 - s))
+    bdx = d.abs() * es + (EPS32 + UNIT[out_dt]) * dx.abs() + TINY[out_dt]
+    bdg = (d * x).abs() * (es + 2 * EPS32 * s * (1 - s)) + (2 * EPS32 + UNIT[out_dt]) * dg.abs() + TINY[out_dt]
+    return (dg, bdg), (dx, bdx)
+
+
+def gate_mul_emulate(g, x, dy, out_dt):
+    """The kernels in torch fp32 on the CPU (torch.exp2 and a true division standing in for the two builtins)."""
+    L = torch.tensor(LOG2E, dtype=torch.float32)
+    gf, xf, df = g.float(), x.float(), dy.float()
+    s = 1.0 / (1.0 + torch.exp2(-gf * L))
+    return (s * xf).to(out_dt), ((df * xf) * (s * (1.0 - s))).to(out_dt), (df * s).to(out_dt)
+
+
+GATE_SWEEP = [0.0, 1e-3, -1e-3, 20.0, -20.0, 88.0, -88.0, 104.0, -104.0, 200.0, -200.0]
+
+
+# ---- depthwise 3x3 ---------------------------------------------------------------------------------------------
+def _shift(x, dy, dx):
+    """x [B, gh, gw, E] -> the tensor whose (y, x) entry is x(y + dy - 1, x + dx - 1), zeros outside."""
+    B, gh, gw, E = x.shape
+    p = torch.zeros(B, gh + 2, gw + 2, E, dtype=x.dtype, device=x.device)
+    p[:, 1:gh + 1, 1:gw + 1] = x
+    return p[:, dy:dy + gh, dx:dx + gw]
+
+
+def dwconv_ref(x, w9, bias, flip, out_dt):
+    """y[b,y,x,e] = bias[e] + sum_k w9[k or 8 - k][e] x[b, y + k/3 - 1, x + k%3 - 1, e] in float64 on channels-last data;
+    bound = (UNIT |y| + TINY) + (n + 1) 2^-24 (sum |w x| + |bias|), n = the in-range taps of THAT pixel (an fma chain of
+    n links on top of the bias)."""
+    x64, w64 = x.double(), w9.double()
+    ones = torch.ones_like(x64[..., :1])
+    y = torch.zeros_like(x64)
+    mag = torch.zeros_like(x64)
+    n = torch.zeros_like(ones)
+    for k in range(9):
+        wk = w64[8 - k if flip else k]
+        xs = _shift(x64, k // 3, k % 3)
+        y = y + wk * xs
+        mag = mag + (wk * xs).abs()
+        n = n + _shift(ones, k // 3, k % 3)
+    if bias is not None:
+        y = y + bias.double()
+        mag = mag + bias.double().abs()
+    return y, UNIT[out_dt] * y.abs() + TINY[out_dt] + (n + 1) * EPS32 * mag
+
+
+def dwconv_wgrad_ref(x, dy, prior=None):
+    """dw10[k][e] = sum_pixels x(shifted by tap k) dy, row 9 = sum dy (+ prior), fp32 out: 2^-24 |ref| +
+    (npix + 4) 2^-24 (sum |x dy| + |prior|): any order of the npix products (block partials, lanes, the fold)."""
+    x64, d64 = x.double(), dy.double()
+    E = x.shape[-1]
+    npix = x64.numel() // E
+    rows, mags = [], []
+    for k in range(9):
+        t = _shift(x64, k // 3, k % 3) * d64
+        rows.append(t.reshape(-1, E).sum(0))
+        mags.append(t.abs().reshape(-1, E).sum(0))
+    rows.append(d64.reshape(-1, E).sum(0))
+    mags.append(d64.abs().reshape(-1, E).sum(0))
+    ref, mag = torch.stack(rows), torch.stack(mags)
+    if prior is not None:
+        ref, mag = ref + prior.double(), mag + prior.double().abs()
+    return ref, EPS32 * ref.abs() + (npix + 4) * EPS32 * mag
+
+
+# ---- l2norm + temporal mean ------------------------------------------------------------------------------------
+def _block_depth(n):
+    """Depth of a 256-thread block's sum of n terms: each thread's strided chain, then BLOCK_TREE tree adds."""
+    return math.ceil(n / 256) + BLOCK_TREE
+
+
+def l2norm_tmean_fwd_ref(f, B, T):
+    """out[b] = mean_t f_t / |f_t|, inv_norm = 1 / |f_t|.
+    inv_norm: the squared norm is a sum of D positive squares (one rounding each, depth `_block_depth(D)`), relative
+    (depth + 1) 2^-24; a square in the subnormal range rounds by 2^-150 absolute instead, D 2^-150 in all: the bound says
+    what is promised for a row of norm 1e-18 (squares near 2^-126).  A row of norm 1e18 has squares of 1e34 and needs no
+    term.  sqrt and `/` halve / add: rel(inv) = (depth + 1) 2^-25 + D 2^-151 / sumsq + (SQRT_ULPS + DIV_ULPS) ulp.
+    out: T products f inv (rel(inv) + 2^-24 each), T adds, the final * (1 / T) (two roundings)."""
+    D = f.shape[-1]
+    f64 = f.double().view(B, T, D)
+    ss = (f64 * f64).sum(-1)
+    inv = 1.0 / torch.sqrt(ss)
+    rel = (_block_depth(D) + 1) * EPS32 / 2 + D * 2.0 ** -151 / ss + (SQRT_ULPS + DIV_ULPS) * ULP32
+    out = (f64 * inv[..., None]).mean(1)
+    mag = (f64.abs() * (inv * (rel + (T + 3) * EPS32))[..., None]).sum(1) / T
+    return (out, mag + EPS32 * out.abs() + TINY[torch.float32]), (inv.reshape(-1), (inv * rel).reshape(-1))
+
+
+def l2norm_tmean_bwd_ref(f, inv_norm, dout, B, T):
+    """df_t = (g - f_t inv (f_t . g) inv) inv / T from the SAME fp32 inv_norm the kernel is given.
+    dot = (f . g) inv: depth(D) 2^-24 sum|f g| inv + 2 * 2^-24 |dot|;  df: k (4 * 2^-24 (|g| + |f| inv |dot|) +
+    |f| inv err(dot)), k = inv / T (its rounding and the `/` are two of the four)."""
+    D = f.shape[-1]
+    f64, inv = f.double().view(B, T, D), inv_norm.double().view(B, T, 1)
+    g = dout.double().view(B, 1, D)
+    raw = (f64 * g).sum(-1, keepdim=True)
+    dot = raw * inv
+    edot = (_block_depth(D) + 1) * EPS32 * (f64 * g).abs().sum(-1, keepdim=True) * inv + 2 * EPS32 * dot.abs()
+    k = inv / T
+    df = (g - f64 * inv * dot) * k
+    mag = g.abs() + f64.abs() * inv * dot.abs()
+    bound = k * ((4 + DIV_ULPS * 2) * EPS32 * mag + f64.abs() * inv * edot) + EPS32 * df.abs() + TINY[torch.float32]
+    return df.reshape(B * T, D), bound.reshape(B * T, D)
+
+
+def l2norm_emulate(f, dout, B, T):
+    """Both kernels in torch fp32: per-thread strided sums, wave butterfly, four-wave fold."""
+    D = f.shape[-1]
+    ff = f.float().view(B * T, D)
+
+    def block_sum(v):                                     # [rows, D] -> [rows]
+        pad = torch.zeros(v.shape[0], math.ceil(D / 256) * 256)
+        pad[:, :D] = v
+        s = torch.zeros(v.shape[0], 256)
+        for i in range(pad.shape[1] // 256):
+            s = s + pad[:, i * 256:(i + 1) * 256]
+        w = _wave_sum_f32(s.view(-1, 4, 64))
+        return (w[:, 0] + w[:, 1]) + (w[:, 2] + w[:, 3])
+    inv = 1.0 / torch.sqrt(block_sum(ff * ff))
+    acc = torch.zeros(B, D)
+    fv = (ff * inv[:, None]).view(B, T, D)
+    for t in range(T):
+        acc = acc + fv[:, t]
+    out = acc * torch.tensor(1.0 / T, dtype=torch.float32)
+    g = dout.float().repeat_interleave(T, 0)
+    dot = block_sum(ff * g) * inv
+    k = inv / torch.tensor(float(T))
+    df = (g - ff * inv[:, None] * dot[:, None]) * k[:, None]
+    return out, inv, df
+
+
+# ---- seg_loss --------------------------------------------------------------------------------------------------
+def _bilinear_axis(g, S):
+    """align_corners=False source positions of S outputs on g inputs with the kernel's fp32 scale fl(g) / fl(S):
+    W [S, g] interpolation matrix, Dm [S, g] = |d W / d position| (one at each of the two taps, zero where they
+    coincide), all float64."""
+    scale = (torch.tensor(float(g), dtype=torch.float32) / torch.tensor(float(S), dtype=torch.float32)).double()
+    i = torch.arange(S, dtype=torch.float64)
+    s = (scale * (i + 0.5) - 0.5).clamp_min(0.0)
+    i0 = s.floor().clamp_max(g - 1).long()
+    i1 = (i0 + 1).clamp_max(g - 1)
+    w1 = s - i0.double()
+    W = torch.zeros(S, g, dtype=torch.float64)
+    Dm = torch.zeros(S, g, dtype=torch.float64)
+    r = torch.arange(S)
+    W[r, i0] += 1.0 - w1
+    W[r, i1] += w1
+    Dm[r, i0] -= 1.0
+    Dm[r, i1] += 1.0
+    return W, Dm
+
+
+def seg_pixels_ref(lr, tgt):
+    """Per output pixel, float64: z, its bound, p, its bound, bce, its bound.  lr [B, g, g], tgt [B, S, S] (CPU).
+    z = W L W^T.  The fp32 source position fl(fl(scale (i + 0.5)) - 0.5) is off by cs = 3 * 2^-24 g at the most (the two
+    roundings at magnitude <= g, and the clamp / floor keep z continuous), which moves z by cs (|dz/dy| + |dz/dx|), the
+    slopes being differences of neighbouring logits; the three lerps round 6 times on |W| |L| |W|^T.
+    e = __expf(-|z|) = V_EXP_F32(fl(-|z| log2 e)): relative 2 * 2^-24 |z| + HW_ULPS ulp.
+    p = 1 / (1 + e) or e / (1 + e): (1 - p) rel(e) + 2^-24 + DIV_ULPS ulp relative, plus p (1 - p) err(z).
+    bce = max(z, 0) - z t + log1pf(e): |p - t| err(z) + 2 * 2^-24 (|z| + |z t|) + LOG1P_ULPS ulp log1p(e) + e rel(e)
+    + 2 * 2^-24 |bce| (the two adds)."""
+    g, S = lr.shape[-1], tgt.shape[-1]
+    W, Dm = _bilinear_axis(g, S)
+    L, t = lr.double(), tgt.double()
+    z = W @ L @ W.t()
+    cs = 3 * EPS32 * g
+    slope = (Dm @ L @ W.t()).abs() + (W @ L @ Dm.t()).abs()
+    ez = cs * slope + 6 * EPS32 * (W @ L.abs() @ W.t())
+    p = torch.sigmoid(z)
+    e = torch.exp(-z.abs())
+    rel_e = 2 * EPS32 * z.abs() + HW_ULPS * ULP32
+    ep = p * ((1 - p) * rel_e + EPS32 + DIV_ULPS * ULP32) + p * (1 - p) * ez + TINY[torch.float32]
+    bce = z.clamp_min(0) - z * t + torch.log1p(e)
+    ebce = (p - t).abs() * ez + 2 * EPS32 * (z.abs() + (z * t).abs()) + LOG1P_ULPS * ULP32 * torch.log1p(e) + \
+        e * rel_e + 2 * EPS32 * bce.abs()
+    return dict(z=z, ez=ez, p=p, ep=ep, bce=bce, ebce=ebce, t=t, W=W, Dm=Dm, cs=cs)
+
+
+def seg_loss_fwd_ref(lr, tgt):
+    """partial[b][chunk][4] = {sum bce, sum p t, sum p, sum t} over 8 output rows: the per-pixel bounds summed, plus the
+    fixed-order accumulation (8 ceil(S / 256) + BLOCK_TREE) 2^-24 sum|terms| (+ one product rounding for p t)."""
+    r = seg_pixels_ref(lr, tgt)
+    B, S = tgt.shape[0], tgt.shape[-1]
+    chunks = (S + 7) // 8
+    depth = 8 * math.ceil(S / 256) + BLOCK_TREE
+    terms = torch.stack([r["bce"], r["p"] * r["t"], r["p"], r["t"]], -1)              # [B, S, S, 4]
+    errs = torch.stack([r["ebce"], r["t"] * r["ep"] + EPS32 * r["p"] * r["t"], r["ep"], torch.zeros_like(r["t"])], -1)
+    ref = torch.zeros(B, chunks, 4, dtype=torch.float64)
+    bound = torch.zeros(B, chunks, 4, dtype=torch.float64)
+    for c in range(chunks):
+        sl = slice(8 * c, min(8 * c + 8, S))
+        ref[:, c] = terms[:, sl].sum((1, 2))
+        bound[:, c] = errs[:, sl].sum((1, 2)) + depth * EPS32 * terms[:, sl].abs().sum((1, 2))
+    return ref, bound
+
+
+def seg_loss_bwd_ref(lr, tgt, sums, coef, eps):
+    """dlogits_lr = W^T dz W (the transposed interpolation, written out), dz = c_bce (p - t) + c_dice p (1 - p) F,
+    F = (2 t D - 2 I) / D^2, I = sums[1], D = sums[2] + sums[3] + eps from the SAME fp32 sums / coef / eps the kernel reads.
+    F: D rounds twice, 1 / (D D) rounds twice more plus DIV_ULPS ulp, the difference cancels: (8 * 2^-24 + DIV_ULPS ulp)
+    (|2 t D| + |2 I|) / D^2.  err(dz) = |c_bce| (err(p) + 2^-24 |p - t|) + |c_dice| (err(p) |F| + p (1 - p) (err(F) +
+    4 * 2^-24 |F|)) + 2 * 2^-24 |dz|.
+    Gather: W^T err(dz) W, plus the weights' own position error cs on either axis (|Dm|^T |dz| W + W^T |dz| |Dm|), plus
+    the accumulation over the rows and columns that feed one low-res pixel, (rows + cols + 8) 2^-24 W^T |dz| W."""
+    r = seg_pixels_ref(lr, tgt)
+    p, t, W, Dm = r["p"], r["t"], r["W"], r["Dm"].abs()
+    s64, c64 = sums.double(), coef.double()
+    cb, cd = c64[:, 0, None, None], c64[:, 1, None, None]
+    I = s64[:, 1, None, None]
+    D = (s64[:, 2] + s64[:, 3] + _f32c(eps))[:, None, None]
+    F = (2 * t * D - 2 * I) / (D * D)
+    eF = (8 * EPS32 + DIV_ULPS * ULP32) * ((2 * t * D).abs() + (2 * I).abs()) / (D * D)
+    dz = cb * (p - t) + cd * (p * (1 - p)) * F
+    edz = cb.abs() * (r["ep"] + EPS32 * (p - t).abs()) + \
+        cd.abs() * (r["ep"] * F.abs() + p * (1 - p) * (eF + 4 * EPS32 * F.abs())) + 2 * EPS32 * dz.abs()
+    ref = W.t() @ dz @ W
+    cnt = (W > 0).sum(0).double()
+    adz = W.t() @ dz.abs() @ W
+    bound = W.t() @ edz @ W + r["cs"] * (Dm.t() @ dz.abs() @ W + W.t() @ dz.abs() @ Dm) + \
+        (cnt[:, None] + cnt[None, :] + 8) * EPS32 * adz + EPS32 * ref.abs()
+    return ref, bound
+
+
+def seg_loss_emulate(lr, tgt, sums, coef, eps, bwd_tgt=None, swap_wy=False):
+    """Both kernels' per-pixel arithmetic in torch fp32 (gathers and lerps as the kernel orders them); the sums in plain
+    fp32 torch reductions.  Returns partial [B, chunks, 4] and dlogits_lr [B, g, g].
+    Mutants for the host test: bwd_tgt replaces the mask the BACKWARD reads (a transposed or shifted one: a wrong index
+    into the targets), swap_wy exchanges wy and 1 - wy in the backward's row gather."""
+    g, S = lr.shape[-1], tgt.shape[-1]
+    f = torch.float32
+    scale = torch.tensor(float(g), dtype=f) / torch.tensor(float(S), dtype=f)
+    i = torch.arange(S, dtype=f)
+    s = (scale * (i + 0.5) - 0.5).clamp_min(0.0)
+    i0 = s.floor().clamp_max(g - 1).long()
+    i1 = (i0 + 1).clamp_max(g - 1)
+    w = s - i0.to(f)
+    L, t = lr.float(), tgt.float()
+    wx, wy = w[None, None, :], w[None, :, None]
+    top = L[:, i0][:, :, i0] * (1 - wx) + L[:, i0][:, :, i1] * wx
+    bot = L[:, i1][:, :, i0] * (1 - wx) + L[:, i1][:, :, i1] * wx
+    z = top * (1 - wy) + bot * wy
+    e = torch.exp2(-z.abs() * torch.tensor(LOG2E, dtype=f))
+    bce = z.clamp_min(0) - z * t + torch.log1p(e)
+    p = torch.where(z >= 0, 1.0 / (1.0 + e), e / (1.0 + e))
+    chunks = (S + 7) // 8
+    terms = torch.stack([bce, p * t, p, t], -1)
+    part = torch.stack([terms[:, 8 * c:8 * c + 8].sum((1, 2)) for c in range(chunks)], 1)
+    cb, cd = coef.float()[:, 0, None, None], coef.float()[:, 1, None, None]
+    I = sums.float()[:, 1, None, None]
+    D = (sums.float()[:, 2] + sums.float()[:, 3] + torch.tensor(eps, dtype=f))[:, None, None]
+    invD2 = 1.0 / (D * D)
+    tb = t if bwd_tgt is None else bwd_tgt.float()
+    dz = cb * (p - tb) + cd * (p * (1 - p)) * ((2 * tb * D - 2 * I) * invD2)
+    Wm = torch.zeros(S, g, dtype=f)
+    r = torch.arange(S)
+    Wm[r, i0] += 1 - w
+    Wm[r, i1] += w
+    Wy = Wm
+    if swap_wy:
+        Wy = torch.zeros(S, g, dtype=f)
+        Wy[r, i0] += w
+        Wy[r, i1] += 1 - w
+    return part, Wy.t() @ dz @ Wm
+
+
+# ---- AdamW -----------------------------------------------------------------------------------------------------
+ADAMW_C = 2.0
+
+
+def adamw_ref(p, g, m, v, lr, wd, beta1, beta2, eps, step, coef=None):
+    """One torch.optim.AdamW step in float64 from the fp32 p, g, m, v (and the fp32 clip coefficient), and per-element
+    bounds for the fp32 kernel, which rounds every product and sum once (contraction off) and every scalar from double:
+      g' = g coef                            2^-24 |g'|
+      m' = m + (g' - m)(1 - b1)              2^-24 (|m'| + 4 (1 - b1)(|g'| + |m|))
+      v' = v b2 + g'^2 (1 - b2)              2^-24 (|v'| + 2 v b2 + 5 g'^2 (1 - b2))
+      den = sqrt(v') / sqrt(bc2) + eps       the error of v' through the square root, min(sqrt(err), err / (2 sqrt(v')))
+                                             (the second form alone is infinite at v' = 0), + (3 + SQRT_ULPS) 2^-24-ish
+      p' = p (1 - lr wd) - (lr / bc1) m'/den 3 * 2^-24 |p| + |upd| (err(m') / |m'| + err(den) / den + (3 + DIV_ULPS 2) 2^-24)
+                                             + 2^-24 |p'|.
+    The counts above are the roundings of the code, and the fp32 emulation (the kernel's order in torch fp32, the same
+    numbers torch's own fp32 AdamW gives) reaches 0.74 of them for exp_avg, 0.69 for exp_avg_sq, 0.58 for p: three
+    roundings on terms of equal size leave no headroom.  By the file's convention the whole bound carries ADAMW_C = 2, which
+    puts the measured worst at 0.37 (asserted <= 0.5 in tests/test_kernel_ref_host.py).
+    Returns (p', bound), (m', bound), (v', bound)."""
+    p64, g64, m64, v64 = p.double(), g.double(), m.double(), v.double()
+    lr, wd = _f32c(lr), _f32c(wd)
+    gs = g64 * (1.0 if coef is None else float(coef))
+    m2 = m64 + (gs - m64) * (1 - beta1)
+    v2 = v64 * beta2 + gs * gs * (1 - beta2)
+    bc1, bc2 = 1 - beta1 ** step, 1 - beta2 ** step
+    root = torch.sqrt(v2)
+    den = root / math.sqrt(bc2) + eps
+    upd = (lr / bc1) * (m2 / den)
+    p2 = p64 * (1 - lr * wd) - upd
+    em = EPS32 * (m2.abs() + 4 * (1 - beta1) * (gs.abs() + m64.abs()))
+    ev = EPS32 * (v2.abs() + 2 * v64 * beta2 + 5 * gs * gs * (1 - beta2)) + TINY[torch.float32]
+    eroot = torch.minimum(torch.sqrt(ev), ev / (2 * root).clamp_min(1e-300)) + SQRT_ULPS * EPS32 * root
+    eden = (eroot + 2 * EPS32 * root) / math.sqrt(bc2) + EPS32 * den + EPS32 * eps
+    eupd = (lr / bc1) * (em / den + m2.abs() * eden / (den * den)) + (3 + 2 * DIV_ULPS) * EPS32 * upd.abs()
+    ep = 3 * EPS32 * p64.abs() + eupd + EPS32 * p2.abs() + TINY[torch.float32]
+    return (p2, ADAMW_C * ep), (m2, ADAMW_C * (em + TINY[torch.float32])), (v2, ADAMW_C * ev)
+
+
+# ---- antialiased resize, MixUp, normalise, layouts -------------------------------------------------------------
+def aa_axis(out_size, in_size):
+    """The triangle filter of upsample_bilinear2d(antialias=True) along one axis, restated in float64:
+    scale = in / out, support = max(scale, 1), centre = scale (i + 0.5), taps j in [trunc(centre - support + 0.5) clamped
+    at 0, trunc(centre + support + 0.5) clamped at `in`), weight max(0, 1 - |(j - centre + 0.5) / support|) / total.
+    Returns W [out, in] and A [out], the bound on sum_j |w_fp32 - w| of one output: the fp32 centre and tap offsets are
+    off by delta = 2 * 2^-24 (centre + support) / support + 2 * 2^-24, each raw weight by as much (a tap the fp32 range
+    gains or loses sits where the triangle is zero, so this holds for it too), the normalisation doubles it:
+    A = 2 n delta / total + (n + 2) 2^-24 with n taps (the n + 2: their products and the division)."""
+    scale = in_size / out_size
+    support = max(scale, 1.0)
+    i = torch.arange(out_size, dtype=torch.float64)
+    centre = scale * (i + 0.5)
+    lo = torch.trunc(centre - support + 0.5).clamp_min(0)
+    hi = torch.trunc(centre + support + 0.5).clamp_max(in_size)
+    j = torch.arange(in_size, dtype=torch.float64)[None, :]
+    raw = (1.0 - ((j - centre[:, None] + 0.5) / support).abs()).clamp_min(0.0)
+    raw = raw * ((j >= lo[:, None]) & (j < hi[:, None]))
+    total = raw.sum(1)
+    W = raw / total[:, None]
+    n = hi - lo
+    delta = 2 * EPS32 * (centre + support) / support + 2 * EPS32
+    return W, 2 * n * delta / total + (n + 2) * EPS32
+
+
+def resize_ref(src, src_u8, S):
+    """src: uint8 (B, Hs, Ws, 3) or float32 (B, 3, Hs, Ws) in [0, 1] -> float64 (B, 3, S, S) and its bound.
+    Hs == S and Ws == S is the kernel's copy shortcut: exact (the u8 scale fl(1 / 255) apart: two roundings).  Otherwise
+    Wy X Wx^T: pixels lie in [0, 1], so the weights' errors enter as Ay + Ax, and the two fp32 tap sums as
+    (ny + nx + 2) 2^-24 of a value <= 1, which A already counts."""
+    x = src.permute(0, 3, 1, 2).double() / 255.0 if src_u8 else src.double()
+    Hs, Ws = x.shape[-2:]
+    base = 2 * EPS32 if src_u8 else 0.0
+    if Hs == S and Ws == S:
+        return x, torch.full_like(x, base) * x
+    Wy, Ay = aa_axis(S, Hs)
+    Wx, Ax = aa_axis(S, Ws)
+    out = Wy @ x @ Wx.t()
+    bound = (Ay[:, None] + Ax[None, :] + base).expand_as(out).clone()
+    return out, bound
+
+
+def normalise_ref(v, ev, mean, std, out_dt):
+    """(v - mean) fl(1 / std): (err(v) + 2^-24 (|v| + |mean|)) / std + 2 * 2^-24 |out|, then the store."""
+    mean, std = _f32c(mean), _f32c(std)
+    out = (v - mean) / std
+    return out, (ev + EPS32 * (v.abs() + abs(mean))) / abs(std) + (2 * EPS32 + UNIT[out_dt]) * out.abs() + TINY[out_dt]
+
+
+def patch_major(x, bound, P, Kp):
+    """(B, 3, S, S) -> [B g g, Kp], k = c P P + ky P + kx, g = S // P (trailing pixels dropped), pad columns 0 with
+    bound 0: they must be exactly zero."""
+    B, C, S, _ = x.shape
+    g = S // P
+
+    def one(t):
+        t = t[:, :, :g * P, :g * P].reshape(B, C, g, P, g, P).permute(0, 2, 4, 1, 3, 5).reshape(B * g * g, C * P * P)
+        out = torch.zeros(B * g * g, Kp, dtype=t.dtype)
+        out[:, :C * P * P] = t
+        return out
+    return one(x), one(bound)
+
+
+def preprocess_ref(src, src_u8, S, P, Kp, patch, mean, std, mix_index, lam, out_dt):
+    v, ev = resize_ref(src, src_u8, S)
+    if mix_index is not None:
+        lam = _f32c(lam)
+        idx = mix_index.long()
+        a, b = lam * v, (1.0 - lam) * v[idx]
+        ev = abs(lam) * ev + abs(1.0 - lam) * ev[idx] + 3 * EPS32 * (a.abs() + b.abs())
+        v = a + b
+    out, bound = normalise_ref(v, ev, mean, std, out_dt)
+    return patch_major(out, bound, P, Kp) if patch else (out, bound)
+
+
+# ---- augmentation ----------------------------------------------------------------------------------------------
+AUG_FIELDS = ("flip", "cos", "sin", "brightness", "contrast", "saturation", "hue", "order")
+HUE_LIP = 7.0                    # see aug_ref
+HUE_EXCUSED_CAP = 0.01
+
+
+def _grey64(x):
+    return 0.299 * x[0] + 0.587 * x[1] + 0.114 * x[2]
+
+
+def _hue64(x, shift):
+    """The header's hue operator on float64 (3, S, S): RGB -> HSV, h = frac(h + shift), HSV -> RGB.  Also returns the
+    excusable mask: the two largest or the two smallest channels closer than 1e-5, or 6 h within 1e-4 of an integer."""
+    r, g, b = x[0], x[1], x[2]
+    srt = x.sort(0).values
+    mx, mn = srt[2], srt[0]
+    cr = mx - mn
+    eq = cr == 0
+    crd = torch.where(eq, torch.ones_like(cr), cr)
+    sat = cr / torch.where(eq, torch.ones_like(cr), mx)
+    rc, gc, bc = (mx - r) / crd, (mx - g) / crd, (mx - b) / crd
+    isr = mx == r
+    isg = (mx == g) & ~isr
+    isb = ~isr & ~(mx == g)
+    h = (isr * (bc - gc) + isg * (2.0 + rc - bc) + isb * (4.0 + gc - rc)) / 6.0 + 1.0
+    h = h - h.floor()
+    h = h + shift
+    h = h - h.floor()
+    h6 = h * 6.0
+    fi = h6.floor()
+    f = h6 - fi
+    i = fi.long() % 6
+    v = mx
+    p = (v * (1 - sat)).clamp(0, 1)
+    q = (v * (1 - f * sat)).clamp(0, 1)
+    t = (v * (1 - (1 - f) * sat)).clamp(0, 1)
+    R = torch.stack([v, q, p, p, t, v])
+    G = torch.stack([t, v, v, q, p, p])
+    Bl = torch.stack([p, p, t, v, v, q])
+    pick = lambda tab: tab.gather(0, i[None])[0]
+    excused = ((srt[2] - srt[1]) < 1e-5) | ((srt[1] - srt[0]) < 1e-5) | ((h6 - h6.round()).abs() < 1e-4)
+    return torch.stack([pick(R), pick(G), pick(Bl)]), excused
+
+
+def aug_ref(src, src_u8, S, table, mean, std, out_dt):
+    """float64 reference of sgl_op_preprocess_aug, restating the header: resize, flip out(y, x) = in(y, S - 1 - x),
+    rotation about ((S - 1) / 2, (S - 1) / 2) (counter-clockwise positive, out(p) = in(M^-1 p) bilinear, zeros outside),
+    the colour operators in table order with the grey mean taken at the contrast step, normalise.
+    table: one dict per image with AUG_FIELDS (floats already rounded to fp32; order a list of four, order[0] < 0 = no
+    colour).  Returns out (B, 3, S, S), its bound, grey_mean (B), its bound, and the hue-excused mask (B, S, S).
+    Error carried per pixel (one number for the three channels, e):
+      rotation    the fp32 source position is off by 4 * 2^-24 S per axis, a bilinear sample of values in [0, 1] moves by
+                  at most that per axis (continuous across the floor and into the zero border): (8 S + 8) 2^-24, plus the
+                  taps' own e interpolated;
+      brightness  |f| e + 2^-24;   contrast  |f| e + |1 - f| err(mean) + 4 (1 + |f|) 2^-24;
+      saturation  (|f| + |1 - f|) e + (4 + 3 |1 - f|)(1 + |f|) 2^-24   (grey is a convex combination: e + 3 * 2^-24);
+      hue         HUE_LIP e + 48 * 2^-24.  Within a sector the outputs are v, min, v - f cr, min + f cr with
+                  f cr = (a - b) + c cr for two input channels a, b and a constant -1 < c < 2: linear in the inputs with
+                  |coefficients| summing to at most 1 + 2 + 2 * 2 = 7, and continuous from sector to sector; the fp32
+                  evaluation (differences of channels in [0, 1], divisions by cr that cancel again in f cr, h <= 2)
+                  is within 48 roundings of a value <= 1;
+      grey mean   mean(e + 3 * 2^-24) + (ceil(S S / 256) + BLOCK_TREE + 2) 2^-24 mean(grey)."""
+    x, ex = resize_ref(src, src_u8, S)
+    B = x.shape[0]
+    ex = ex.amax(1)                                        # (B, S, S)
+    outs, bounds, gms, gbs, masks = [], [], [], [], []
+    ar = torch.arange(S, dtype=torch.float64)
+    for b in range(B):
+        a = table[b]
+        im, e = x[b], ex[b]
+        if a["flip"] != 0:
+            im, e = im.flip(-1), e.flip(-1)
+        if not (a["cos"] == 1.0 and a["sin"] == 0.0):
+            ctr = 0.5 * (S - 1)
+            dx, dy = ar[None, :] - ctr, ar[:, None] - ctr
+            xs = a["cos"] * dx - a["sin"] * dy + ctr
+            ys = a["sin"] * dx + a["cos"] * dy + ctr
+            x0, y0 = xs.floor(), ys.floor()
+            fx, fy = xs - x0, ys - y0
+            nim, ne = torch.zeros_like(im), torch.zeros_like(e)
+            for jy in (0, 1):
+                for jx in (0, 1):
+                    yy, xx = (y0 + jy).long(), (x0 + jx).long()
+                    w = (fy if jy else 1 - fy) * (fx if jx else 1 - fx)
+                    w = torch.where((yy >= 0) & (yy < S) & (xx >= 0) & (xx < S), w, torch.zeros_like(w))
+                    yc, xc = yy.clamp(0, S - 1), xx.clamp(0, S - 1)
+                    nim = nim + w * im[:, yc, xc]
+                    ne = ne + w * e[yc, xc]
+            im, e = nim, ne + (8 * S + 8) * EPS32
+        gm, gb = torch.zeros((), dtype=torch.float64), torch.zeros((), dtype=torch.float64)
+        mask = torch.zeros(S, S, dtype=torch.bool)
+        order = a["order"]
+        if order[0] >= 0:
+            for op in order:
+                if op == 0:
+                    f = a["brightness"]
+                    im, e = (im * f).clamp(0, 1), abs(f) * e + EPS32
+                elif op == 1:
+                    f = a["contrast"]
+                    grey = _grey64(im)
+                    gm = grey.mean()
+                    gb = (e + 3 * EPS32).mean() + (math.ceil(S * S / 256) + BLOCK_TREE + 2) * EPS32 * gm
+                    im, e = ((im - gm) * f + gm).clamp(0, 1), abs(f) * e + abs(1 - f) * gb + 4 * (1 + abs(f)) * EPS32
+                elif op == 2:
+                    f = a["saturation"]
+                    grey = _grey64(im)
+                    im = ((im - grey) * f + grey).clamp(0, 1)
+                    e = (abs(f) + abs(1 - f)) * e + (4 + 3 * abs(1 - f)) * (1 + abs(f)) * EPS32
+                else:
+                    im, ex_b = _hue64(im, a["hue"])
+                    mask |= ex_b
+                    e = HUE_LIP * e + 48 * EPS32
+        o, bo = normalise_ref(im, e[None].expand_as(im), mean, std, out_dt)
+        outs.append(o), bounds.append(bo), gms.append(gm), gbs.append(gb), masks.append(mask)
+    return torch.stack(outs), torch.stack(bounds), torch.stack(gms), torch.stack(gbs), torch.stack(masks)
+
+
+# ---- seeded inputs shared by tests/test_kernel_ref_host.py and tests/test_kernel_edges_aux_gpu.py ----------------
+def image_source(B, Hs, Ws, u8, seed):
+    """A seeded source batch: uint8 (B, Hs, Ws, 3) or float32 (B, 3, Hs, Ws) in [0, 1].  A smooth colour ramp per image plus
+    noise; the three channels of a uint8 pixel are made distinct (a pixel with two equal channels is one the hue rule may
+    excuse, and one random byte triple in 85 has a pair: over the 1 % cap on an un-resized source)."""
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    yy = torch.linspace(0, 1, Hs)[None, None, :, None]
+    xx = torch.linspace(0, 1, Ws)[None, None, None, :]
+    ph = torch.rand(B, 3, 1, 1, generator=g)
+    img = 0.5 + 0.3 * torch.sin(6.0 * (yy * (1 + ph) + xx * (2 - ph)) + 6.28 * ph) + 0.2 * (torch.rand(B, 3, Hs, Ws, generator=g) - 0.5)
+    img = img.clamp(0, 1)
+    if not u8:
+        return img.contiguous()
+    q = (img * 255).round().to(torch.int64)
+    q[:, 1] = torch.where(q[:, 1] == q[:, 0], (q[:, 1] + 7) % 256, q[:, 1])
+    for _ in range(2):
+        clash = (q[:, 2] == q[:, 0]) | (q[:, 2] == q[:, 1])
+        q[:, 2] = torch.where(clash, (q[:, 2] + 13) % 256, q[:, 2])
+    return q.permute(0, 2, 3, 1).to(torch.uint8).contiguous()
+
+
+def aug_table():
+    """One record per branch of the augmentation kernels (see tests/test_kernel_edges_aux_gpu.py); floats are rounded to
+    fp32 here so the reference and the device table read the same numbers."""
+    c5, s5 = math.cos(math.radians(5.0)), math.sin(math.radians(5.0))
+    N = dict(flip=0.0, cos=1.0, sin=0.0, brightness=1.0, contrast=1.0, saturation=1.0, hue=0.0, order=[-1, 0, 0, 0])
+    rec = lambda **kw: {**N, **kw}
+    allf = dict(brightness=1.1, contrast=0.85, saturation=1.2, hue=0.04)
+    tab = [
+        rec(),                                                                    # no-op
+        rec(flip=1.0),                                                            # flip only
+        rec(cos=c5, sin=s5),                                                      # rotation only, +5 degrees
+        rec(cos=c5, sin=-s5),                                                     # rotation only, -5 degrees
+        rec(flip=1.0, brightness=1.1, order=[0, 1, 2, 3]),                        # (1, 0) shortcut; brightness alone
+        rec(order=[1, 0, 2, 3], **allf),                                          # contrast first
+        # contrast last, after flip + rotation.  No hue step here (saturation twice instead): the zero corners a rotation
+        # leaves are 2 % of the image, every one a pixel the hue rule may excuse (three equal channels), which would
+        # put this image over the per-image cap; hue after other operators is records 5 and 7, hue before contrast 11
+        rec(flip=1.0, cos=c5, sin=s5, order=[0, 2, 2, 1], **allf),
+        rec(order=[0, 2, 3, 0], brightness=0.9, saturation=0.7, hue=-0.03),       # contrast absent: grey_mean = 0
+        rec(contrast=1.3, order=[0, 1, 2, 3]),                                    # contrast alone
+        rec(saturation=0.6, order=[0, 1, 2, 3]),                                  # saturation alone
+        rec(hue=0.05, order=[0, 1, 2, 3]),                                        # hue alone
+        rec(flip=1.0, hue=-0.05, order=[3, 2, 1, 0]),                             # hue alone, negative, first
+    ]
+    for r in tab:
+        for k in AUG_FIELDS[:-1]:
+            r[k] = _f32c(r[k])
+    return tab
+
+
+# name, source is uint8, output dtype code, (Hs, Ws), S, P, Kp, patch-major
+AUG_CASES = [
+    ("u8_f32_nchw_s42", True, F32, (97, 131), 42, 14, 640, False),               # S*S no multiple of 256
+    ("u8_bf16_patch_s14_pad", True, BF16, (30, 30), 14, 7, 192, True),           # S*S < 256; bf16 pad columns
+    ("u8_f16_patch_s45_p14_pad", True, F16, (45, 45), 45, 14, 640, True),        # un-resized; S % P != 0; f16 pad
+    ("f32_f32_patch_s45_p14_pad", False, F32, (50, 50), 45, 14, 640, True),      # S % P != 0; f32 pad columns
+    ("f32_bf16_nchw_s42", False, BF16, (42, 42), 42, 14, 640, False),            # preprocess_aug_kernel<false, bf16>
+    ("f32_f16_nchw_s42", False, F16, (64, 40), 42, 14, 640, False),
+]
+
+
+def aug_case_inputs(name):
+    """(source, table) of one AUG_CASES entry: as many images as the table has records."""
+    i = [c[0] for c in AUG_CASES].index(name)
+    _, u8, _, (Hs, Ws), _, _, _, _ = AUG_CASES[i]
+    tab = aug_table()
+    return image_source(len(tab), Hs, Ws, u8, seed=500 + i), tab
+
+
+def seg_inputs(B, g, S, seed):
+    """Low-res logits [B, g, g] with part of the map scaled to +-30, targets [B, S, S] with image 0 all zero, image 1 all
+    one, image 2 random with zero coefficients (dlogits_lr exactly 0) and image 3 random under a band of ones with non-zero
+    coefficients (SEG_B = 4 images)."""
+    gen_ = torch.Generator(device="cpu").manual_seed(seed)
+    lr = torch.randn(B, g, g, generator=gen_) * 2.5
+    lr[:, : max(1, g // 2), : max(1, g // 3)] *= 12.0
+    lr = lr.clamp(-30, 30)
+    tgt = (torch.rand(B, S, S, generator=gen_) < 0.3).float()
+    tgt[0] = 0.0
+    if B > 1:
+        tgt[1] = 1.0
+    if B > 3:                                            # image 3: a mask that is neither uniform nor symmetric, with
+        tgt[3, : max(1, S // 3), :] = 1.0                # non-zero coefficients: a wrongly indexed mask read shows
+    coef = torch.tensor([[1.7e-5, -0.21], [0.9e-5, -0.4], [0.0, 0.0], [2.0e-5, -0.3]])[:B].clone()
+    return lr, tgt, coef
+
+
+SEG_B = 4
+SEG_CASES = [(1, 8), (4, 56), (3, 42), (27, 320), (16, 257), (14, 14), (27, 14)]
+L2_SHAPES = [(1, 1, 1), (3, 4, 100), (2, 3, 257), (2, 32, 1152), (1, 1, 16380)]
+L2_MAX_D = 16380
+
+
+def l2_inputs(B, T, D, seed):
+    """Frames of norm about 3 sqrt(D), with frame 0 scaled to norm 1e-18 and the last frame to 1e18 when there are at
+    least three frames."""
+    gen_ = torch.Generator(device="cpu").manual_seed(seed)
+    f = torch.randn(B * T, D, generator=gen_) * 3
+    if B * T >= 3:
+        f[0] = f[0] / f[0].norm() * 1e-18
+        f[-1] = f[-1] / f[-1].norm() * 1e18
+    return f, torch.randn(B, D, generator=gen_)
