@@ -7,7 +7,7 @@ exchange pattern here is designed for the MI355X node: images a
 collective is the sum of parameter gradients.
 
 * **Few, large messages.**  The encoder's backward produces one flat fp32 gradient bucket per transformer block
-  (61 MB for so400m); consecutive blocks share one allocation (``SiglipVisionModelHIP._bucket_layout`` cuts the blocks
+  (61 MB for so400m); consecutive blocks share one allocation (``encoder_state.GradPlan.layout`` cuts the blocks
   into at most ``max_buckets`` *chunks*, each one tensor), and the chunk is handed to ``reduce_bucket`` the moment its
   last block is complete: 8 collectives of up to ≈0.37 GB per step for so400m instead of 29 of 61 MB.  xGMI is
   point-to-point (7 links × ≈153 GB/s per GPU), so a ring step is bound by one link: big messages amortise the per-step
@@ -28,7 +28,7 @@ collective is the sum of parameter gradients.
   collective per chunk over the memory ``.grad`` lives in, however many times the encoder ran in that pass.  The rule
   looks at ``.grad`` only, so ``torch.autograd.grad`` on a model whose ``.grad`` is still set also exchanges ``.grad``.
 * ``reduce_grads`` (everything outside the encoder: decoder, heads) is asynchronous and completed by ``finish()`` as well.
-* Chunk sizes taper (``SiglipVisionModelHIP._bucket_layout``): the chunk that completes last holds one block (+ the
+* Chunk sizes taper (``encoder_state.GradPlan.layout``): the chunk that completes last holds one block (+ the
   embeddings), so the exchange that cannot overlap anything is 67 MB, not 244 MB.
 * ``all_gather_eval`` collects per-rank logits / labels for epoch metrics (Siglip2sidafrozen.py:1424-1548).
 * RCCL's channel kernels take CUs from GEMMs that occupy every CU; ``NCCL_MAX_NCHANNELS`` (read by RCCL at

@@ -100,14 +100,14 @@ class FusedAdamW(torch.optim.Optimizer):
         """(table, aux, chunk counts): pointers only — hyper-parameters are launch arguments."""
         key = tuple((p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel(), gi)
                     for p, st, _, gi in ents)
-        encs = [e() for e in self._encoders]
-        encs = [e for e in encs if e is not None and e._shadow is not None and e._shadow.device == dev]
+        encs = [(e, e._shadows.binding()) for e in (ref() for ref in self._encoders) if e is not None]
+        encs = [(e, b) for e, b in encs if b is not None and b[2].device == dev]     # b = (context, weights, arena)
         ema_ptrs = ()
         if self._ema is not None:
             by_param = {id(p): self._ema.shadow[n] for n, p in self._ema.model.named_parameters()
                         if n in self._ema.shadow}
             ema_ptrs = tuple(by_param[id(p)].data_ptr() if id(p) in by_param else 0 for p, _, _, _ in ents)
-        aux_key = (key, tuple((id(e), e._shadow.data_ptr(), id(e._weights_struct)) for e in encs), ema_ptrs)
+        aux_key = (key, tuple((id(e), arena.data_ptr(), id(wts)) for e, (_, wts, arena) in encs), ema_ptrs)
         if key != self._table_key or aux_key != self._aux_key:
             n = len(ents)
             arr = (_lib.SglAdamwTensor * n)()
@@ -122,9 +122,9 @@ class FusedAdamW(torch.optim.Optimizer):
                         raise RuntimeError("EMA shadows must be fp32 with the parameter's layout")
                     aux[i].ema = ema_ptrs[i]
             bound = set()
-            for enc in encs:
+            for _, (ctx, wts, arena) in encs:
                 # only row-major masters can be tiled (channels_last patch weights keep the encoder's own re-cast)
-                lib.sgl_adamw_bind_shadows(enc._ctx, C.byref(enc._weights_struct), enc._shadow.data_ptr(), arr, aux, n)
+                lib.sgl_adamw_bind_shadows(ctx, C.byref(wts), arena.data_ptr(), arr, aux, n)
             chunks = []
             for i, (p, _, _, _) in enumerate(ents):
                 if (aux[i].dst or aux[i].dst_t) and not p.is_contiguous():
@@ -141,7 +141,7 @@ class FusedAdamW(torch.optim.Optimizer):
             self._bufs["chunks"] = tuple(chunks)
             self._bufs["bound"] = bound
             self._table_key, self._aux_key = key, aux_key
-        return self._bufs["table"], self._bufs["aux"], self._bufs["chunks"], encs
+        return self._bufs["table"], self._bufs["aux"], self._bufs["chunks"], [e for e, _ in encs]
 
     def _plan(self, lib, numel, members, dev):
         """Block map over the tensors listed in ``members`` (indices into the table), cached."""
@@ -176,7 +176,7 @@ class FusedAdamW(torch.optim.Optimizer):
         table, aux, chunks, encs = self._device_tables(lib, ents, dev)
         numel = tuple(p.numel() for p, _, _, _ in ents)
         stream = torch.cuda.current_stream(dev).cuda_stream
-        in_sync = [enc._units_in_sync() for enc in encs]
+        in_sync = [enc._shadows.units_in_sync() for enc in encs]
         # one AdamW launch per distinct (betas, eps, step): a single one for every trainer of the reference (one param
         # group, every trainable tensor receives a gradient every step); torch tracks the step per tensor, so do we
         launches = {}
@@ -211,7 +211,7 @@ class FusedAdamW(torch.optim.Optimizer):
         # that caches on `p._version` keys on (the encoder's bf16 weight shadows, saved-tensor checks)
         torch.autograd.graph.increment_version([p for p, _, _, _ in ents])
         for enc, ok in zip(encs, in_sync):
-            enc._adopt_written_shadows(ok, self._bufs["bound"])
+            enc._shadows.adopt(ok, self._bufs["bound"])
         return loss
 
 

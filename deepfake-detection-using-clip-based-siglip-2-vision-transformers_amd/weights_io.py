@@ -35,6 +35,24 @@ _HEAD_MAP = [
     ("attn_pool.proj", "head.attention.out_proj"), ("attn_pool.norm", "head.layernorm"),
     ("attn_pool.mlp.fc1", "head.mlp.fc1"), ("attn_pool.mlp.fc2", "head.mlp.fc2"),
 ]
+# HF -> timm renames of a PARAMETER name (q/k/v stay separate tensors there), applied in order
+_PARAM_NAME_MAP = [
+    ("embeddings.patch_embedding.", "trunk.patch_embed.proj."), ("embeddings.position_embedding.weight", "trunk.pos_embed"),
+    ("post_layernorm.", "trunk.norm."), ("head.probe", "trunk.attn_pool.latent"),
+    ("head.attention.out_proj.", "trunk.attn_pool.proj."), ("head.attention.", "trunk.attn_pool."),
+    ("head.layernorm.", "trunk.attn_pool.norm."), ("head.mlp.", "trunk.attn_pool.mlp."),
+    (".layer_norm1.", ".norm1."), (".layer_norm2.", ".norm2."), (".self_attn.out_proj.", ".attn.proj."),
+    (".self_attn.", ".attn."), ("encoder.layers.", "trunk.blocks."),
+]
+
+
+def hf_param_name_to_timm(name: str) -> str:
+    """``encoder.layers.23.layer_norm1.weight`` -> ``trunk.blocks.23.norm1.weight``: the open_clip/timm spelling of one HF
+    parameter name (no ``vision_model.`` prefix).  Unlike :func:`hf_to_timm`, which fuses tensors, q/k/v keep their own
+    names (``…attn.q_proj.weight``)."""
+    for hf, timm in _PARAM_NAME_MAP:
+        name = name.replace(hf, timm)
+    return name
 
 
 def hf_to_timm(sd: dict, cfg: SiglipVisionConfig, prefix: str = "trunk.") -> "OrderedDict[str, torch.Tensor]":

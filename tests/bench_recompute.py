@@ -36,7 +36,7 @@ def predicted_bytes(model, B, res, recompute):
     last_hidden_state and its gradient, pooled, the input."""
     cfg = model.config
     L, D, N = cfg.num_hidden_layers, cfg.hidden_size, (res // cfg.patch_size) ** 2
-    sh, saved, ws = model._sizes(B, res, res, True, recompute)
+    sh, saved, ws = model._contexts.sizes(B, res, res, True, recompute)
     nparam = sum(p.numel() for p in model.parameters())
     return 8 * nparam + sh + saved + ws + (L + 3) * B * N * D * 4 + B * D * 4 + B * 3 * res * res * 4, saved, ws
 
@@ -114,7 +114,7 @@ def main():
                 evs[i + 1].record(st)
             torch.cuda.synchronize()
             times[rc] += [evs[i].elapsed_time(evs[i + 1]) for i in range(args.steps)]
-    region = models[True]._sizes(B, 384, 384, True, True)[2] - models[False]._sizes(B, 384, 384, True, False)[2]
+    region = models[True]._contexts.sizes(B, 384, 384, True, True)[2] - models[False]._contexts.sizes(B, 384, 384, True, False)[2]
     for rc in policies:
         if not run[rc]:
             continue

@@ -226,16 +226,16 @@ def test_chunk_plan_tapers_and_keeps_qkv_adjacent():
     import __graft_entry__ as g
     pkg = g.load_package()
     order = ["head"] + [f"layer{l}" for l in range(26, -1, -1)] + ["emb"]
-    runs = pkg.encoder._taper(order, 8)
+    runs = pkg.encoder_state._taper(order, 8)
     assert [len(r) for r in runs] == [6, 6, 4, 4, 3, 3, 1, 2] and runs[-1] == ["layer0", "emb"]
     assert sum(runs, []) == order
     for name, sizes in (("tiny", [1, 1, 1, 2]), ("so400m-patch14-384", [6, 6, 4, 4, 3, 3, 1, 2])):
         with torch.device("meta"):                  # the plan needs parameter shapes only
             model = pkg.SiglipVisionModelHIP(pkg.get_config(name), compute_dtype="fp32")
-        params, names = model._flat_params(), model._flat_names
+        params, names = model._table.params(), [(e.label, e.field) for e in model._table.entries]
         needs = [True] * len(params)
-        chunks, groups = model._bucket_layout(needs)
-        assert model._bucket_layout(needs) == (chunks, groups) and model._bucket_layout(needs)[0] is chunks
+        chunks, groups = model._grads.layout(needs)
+        assert model._grads.layout(needs) == (chunks, groups) and model._grads.layout(needs)[0] is chunks
         assert [len(members) for _, members, _ in chunks] == sizes
         assert chunks[0][1][0] == "head" and chunks[-1][1] == ["layer0", "emb"]
         assert sorted(i for _, _, entries in chunks for i, _, _ in entries) == list(range(len(params)))
@@ -254,7 +254,7 @@ def test_chunk_plan_tapers_and_keeps_qkv_adjacent():
                     assert all(names[i][0] == grp for i, _, _ in entries[at:at + 6])
                     fields[at:at + 6] = [None] * 6
         model.set_grad_reducer(pkg.GradBucketReducer(max_buckets=2))
-        assert [len(members) for _, members, _ in model._bucket_layout(needs)[0]] == ([3, 2] if name == "tiny"
+        assert [len(members) for _, members, _ in model._grads.layout(needs)[0]] == ([3, 2] if name == "tiny"
                                                                                      else [19, 10])
 
 

@@ -307,3 +307,33 @@ def test_qkv_bias_gradients_follow_the_identities_the_backward_uses(mode):
         assert gk is not None and torch.count_nonzero(gk).item() == 0          # exact zeros by construction
         rk = ref[pre + "k_proj.bias"].grad.abs().max().item()
         assert rk <= 1e-4 * ref[pre + "q_proj.bias"].grad.abs().max().item()   # and the reference agrees up to rounding noise
+
+
+def test_shallow_copy_runs_on_its_own_state_and_leaves_the_original_intact(pkg, hiplib):
+    """copy.copy shares the parameters but neither the C contexts nor the weight shadows: both modules give the same
+    bits, and deleting the copy takes nothing away from the original."""
+    import copy
+    import gc
+    m = build(pkg, "tiny", 5, "bf16")
+    x = pkg.weights.seeded_pixels(2, 32, 32, seed=9).cuda()
+
+    def run(model):
+        model.zero_grad(set_to_none=True)
+        out = model(pixel_values=x, output_hidden_states=True)
+        (out.pooler_output.square().sum() + out.last_hidden_state.square().mean() + out.hidden_states[1].mean()).backward()
+        return ([out.pooler_output.detach().clone(), out.last_hidden_state.detach().clone()] +
+                [p.grad.clone() for p in model.parameters()])
+
+    first = run(m)
+    c = copy.copy(m)
+    assert c._handle != m._handle and c._contexts is not m._contexts and c._shadows is not m._shadows
+    assert all(a is b for a, b in zip(c.parameters(), m.parameters()))
+    second = run(c)
+    assert c._shadows.arena.data_ptr() != m._shadows.arena.data_ptr()
+    assert len(first) == len(second) == 2 + len(list(m.parameters()))
+    for a, b in zip(first, second):
+        assert torch.equal(a, b)
+    del c
+    gc.collect()
+    for a, b in zip(first, run(m)):
+        assert torch.equal(a, b)

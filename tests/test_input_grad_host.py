@@ -173,9 +173,9 @@ def test_fake_encoder_bwd_returns_d_pixels(pkg, frozen, channels_last):
     m = pkg.SiglipVisionModelHIP(cfg, "bf16")
     if frozen:
         m.requires_grad_(False)
-    params = m._flat_params()
+    params = m._table.params()
     needs = [p.requires_grad for p in params]
-    chunks, _ = m._bucket_layout(needs)
+    chunks, _ = m._grads.layout(needs)
     assert (len(chunks) == 0) == frozen                             # a frozen encoder has no gradient chunk at all
     B, H, W = 2, 37, 45
     with FakeTensorMode(allow_non_fake_inputs=True):
@@ -231,5 +231,5 @@ def test_reducer_accepts_the_empty_chunk_list_of_a_frozen_encoder(pkg):
     assert torch.equal(x.grad, torch.full((3,), 2.0))
     m = pkg.SiglipVisionModelHIP(pkg.get_config("tiny"), "bf16").requires_grad_(False)
     m.set_grad_reducer(red)
-    chunks, groups = m._bucket_layout([False] * len(m._flat_params()))
-    assert chunks == [] and groups == {} and m._alloc_buckets(chunks, torch.device("cpu")) == []
+    chunks, groups = m._grads.layout([False] * len(m._table.params()))
+    assert chunks == [] and groups == {} and m._grads.buffers(chunks, m._table.params(), torch.device("cpu")) == []

@@ -180,14 +180,14 @@ def test_step_writes_encoder_shadows_ema_and_folds_grad_scale():
                 for opt in (opt_f, opt_p):
                     opt.param_groups[0]["lr"] = 5e-4
                 key_before = opt_f._table_key
-            serial = fused._shadow_serial
+            serial = fused._shadows.serial
             opt_f.step()
             opt_p.step()
             if step == 2:
                 assert opt_f._table_key is key_before
-            assert all(fused._units_in_sync()), "every block's shadows were written by the optimizer"
-            assert fused._shadow_serial == serial + 1
-            assert not any(plain._units_in_sync()[:-1]), "without attach_encoder the next forward must re-cast"
+            assert all(fused._shadows.units_in_sync()), "every block's shadows were written by the optimizer"
+            assert fused._shadows.serial == serial + 1
+            assert not any(plain._shadows.units_in_sync()[:-1]), "without attach_encoder the next forward must re-cast"
             for (n, a), (_, b) in zip(fused.named_parameters(), plain.named_parameters()):
                 assert torch.equal(a.detach(), b.detach()), n     # tiled (shadow-writing) and linear paths: same bits
                 ema_ref[n] = ema_ref[n] * 0.9 + a.detach() * 0.1
@@ -195,12 +195,12 @@ def test_step_writes_encoder_shadows_ema_and_folds_grad_scale():
             # the shadows the optimizer wrote give bit for bit the forward of a from-scratch re-cast of the same parameters
             with torch.no_grad():
                 o_f = fused(pixel_values=x).pooler_output.clone()
-                assert fused._shadow_serial == serial + 1, "the forward after the step must not have re-cast anything"
-                fused._shadow_key = None                      # force sgl_prepare_weights on the next forward
+                assert fused._shadows.serial == serial + 1, "the forward after the step must not have re-cast anything"
+                fused._shadows.invalidate()                    # force sgl_prepare_weights on the next forward
                 o_r = fused(pixel_values=x).pooler_output
-                assert fused._shadow_serial == serial + 2
+                assert fused._shadows.serial == serial + 2
             assert torch.equal(o_f, o_r), (o_f - o_r).abs().max()
         # a parameter changed behind the optimizer's back is not adopted: the encoder re-casts that block itself
         with torch.no_grad():
             fused.encoder.layers[0].mlp.fc1.weight.mul_(1.01)
-        assert fused._units_in_sync()[0] is False
+        assert fused._shadows.units_in_sync()[0] is False

@@ -195,11 +195,11 @@ def test_recompute_memory_so400m(pkg, hiplib):
             del out
         # outputs: last_hidden_state and pooled are not part of the held activations
         held[rc] = after - before - B * N * D * 4 - B * D * 4
-        sizes = model._sizes(B, 384, 384, True, rc)
+        sizes = model._contexts.sizes(B, 384, 384, True, rc)
         predicted = sizes[1] + (L + 1) * B * N * D * 4
         assert abs(held[rc] - predicted) <= 0.01 * predicted, (rc, held[rc], predicted)
         if rc:
-            region = sizes[2] - model._sizes(B, 384, 384, True, False)[2]
+            region = sizes[2] - model._contexts.sizes(B, 384, 384, True, False)[2]
         del model
         torch.cuda.empty_cache()
     assert held[True] + region <= 0.2 * held[False], (held, region)
@@ -245,4 +245,4 @@ def test_recompute_large_token_count(pkg, hiplib):
 
 
 def _query(pkg, m, B):
-    return pkg.lib.load().sgl_query_sizes(m._ensure_ctx(True), B, 384, 384, 1, None, None, None)
+    return pkg.lib.load().sgl_query_sizes(m._contexts.get(True), B, 384, 384, 1, None, None, None)

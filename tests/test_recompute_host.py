@@ -185,10 +185,10 @@ def test_fake_encoder_fwd_sizes_saved_by_policy(pkg, hiplib):
     from torch._subclasses.fake_tensor import FakeTensorMode
     cfg = pkg.get_config("tiny")
     m = pkg.SiglipVisionModelHIP(cfg, "bf16")
-    params = m._flat_params()
-    plain, rc = m._sizes(2, 32, 32, True), m._sizes(2, 32, 32, True, True)
+    params = m._table.params()
+    plain, rc = m._contexts.sizes(2, 32, 32, True), m._contexts.sizes(2, 32, 32, True, True)
     assert rc[1] < plain[1] and rc[2] > plain[2] and rc[0] == plain[0]
-    assert m._sizes(2, 32, 32, False, True) == m._sizes(2, 32, 32, False)
+    assert m._contexts.sizes(2, 32, 32, False, True) == m._contexts.sizes(2, 32, 32, False)
     with FakeTensorMode(allow_non_fake_inputs=True):
         x = torch.empty(2, 3, 32, 32)
         old = torch.ops.siglip_hip.encoder_fwd(x, params, m._handle, True, False, True, [1, 3], 0, 0, 0, 0)   # 11 args
