@@ -132,7 +132,7 @@ def encoder_fwd(pixel_values: torch.Tensor, params: Sequence[torch.Tensor], hand
                                    1 if interp else 0, slots, last.data_ptr(),
                                    pooled.data_ptr() if want_pooled else None, saved.data_ptr() if train else None,
                                    sizes[1] if train else 0, _lib.ptr(ws), 0 if ws is None else sizes[2],
-                                   int(first_trainable), _lib.current_stream_handle())
+                                   int(first_trainable), _lib.current_stream_handle(dev))
         _lib.check(st, "sgl_forward_slots", ctx)
     if train:
         mod._shadows.note_forward(saved)
@@ -220,7 +220,7 @@ def encoder_bwd(grads: Sequence[Optional[torch.Tensor]], taps: Sequence[torch.Te
         stop = 0 if (train_emb or want_px) else first
         sizes = contexts.sizes(B, H, W, True, bool(recompute))
         ws = contexts.workspace(sizes[2], dev)
-        stream = _lib.current_stream_handle()
+        stream = _lib.current_stream_handle(dev)
         _, wts, shadow = shadows.binding()
         cx = contexts.get(bool(recompute))
         st = lib.sgl_backward_begin_p(cx, C.byref(wts), shadow.data_ptr(), C.byref(g), B, H, W, hs_ptr[L],

@@ -240,7 +240,7 @@ class WeightShadows:
                 self._weights[2] = pw.detach().contiguous()          # kept alive until the next refresh
                 weights.patch_w = self._weights[2].data_ptr()
             st = lib.sgl_prepare_weights_dirty(ctx, C.byref(weights), self.arena.data_ptr(), self.arena.numel(), dirty,
-                                               glob, _lib.current_stream_handle())
+                                               glob, _lib.current_stream_handle(dev))
             _lib.check(st, "sgl_prepare_weights_dirty", ctx)
             self.keys = keys
             self.serial += 1

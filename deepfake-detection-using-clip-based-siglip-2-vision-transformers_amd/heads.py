@@ -21,6 +21,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .config import isqrt_exact
+from .head_ops import bce_dice_loss_from_lowres, depthwise3x3, gate_mul, l2norm_temporal_mean, linear_tokens
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -34,299 +35,7 @@ class _TapProj(nn.Module):
         self.proj = nn.Linear(in_dim, out_dim)
 
     def forward(self, x):
-        return _linear_tokens(x, self.proj.weight, self.proj.bias)
-
-
-_W_CACHE: dict = {}       # id(parameter) -> (weakref(parameter), version, data_ptr, bf16 W, bf16 Wᵀ or None)
-_SCRATCH: dict = {}       # device -> 64 MiB split-K scratch, reused by every call (stream-ordered)
-
-
-def _cached_bf16(weight: torch.Tensor, want_t: bool):
-    """bf16 copy (and, on demand, transposed copy) of a weight, re-made only when the parameter changed (optimizer steps
-    bump ``_version``): the decoder has ~40 Linear layers and used to re-cast + re-transpose each one on every call.
-    Keyed on the parameter OBJECT (through a weak reference), never on its address alone: the caching allocator hands a
-    freed parameter's address to the next model's weights."""
-    import weakref
-    base = weight._base if weight._base is not None else weight      # conv.weight.view(out, in) is a fresh view per call
-    key = id(base)
-    hit = _W_CACHE.get(key)
-    if (hit is None or hit[0]() is not base or hit[1] != base._version or hit[2] != weight.data_ptr()
-            or hit[3].shape != weight.shape):
-        if len(_W_CACHE) > 256:
-            for k in [k for k, v in _W_CACHE.items() if v[0]() is None]:
-                del _W_CACHE[k]
-            if len(_W_CACHE) > 256:
-                _W_CACHE.clear()
-        hit = (weakref.ref(base), base._version, weight.data_ptr(), weight.detach().to(torch.bfloat16).contiguous(), None)
-        _W_CACHE[key] = hit
-    if want_t and hit[4] is None:
-        hit = hit[:4] + (hit[3].t().contiguous(),)
-        _W_CACHE[key] = hit
-    return hit[3], hit[4]
-
-
-def _split_scratch(dev):
-    buf = _SCRATCH.get(dev)
-    if buf is None:
-        buf = _SCRATCH[dev] = torch.empty(64 << 20, device=dev, dtype=torch.uint8)
-    return buf
-
-
-class _HipLinearFn(torch.autograd.Function):
-    """y = x Wᵀ + b on bf16 token-major activations through the encoder's own MFMA GEMM kernels (sgl_op_gemm_nt /
-    sgl_op_gemm_tn): the decoder's tall-skinny shapes (46656 x 512 x 1152, 46656 x 512 x 512 ...) are where the
-    library GEMM picks 110-240 TFLOP/s kernels.  Used under autocast only (bf16 operands, fp32 accumulate: the
-    arithmetic autocast's F.linear does); fp32 callers keep F.linear."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias):
-        from . import lib as _lib
-        lib = _lib.load()
-        M, K = x.shape
-        N = weight.shape[0]
-        xb = x.to(torch.bfloat16).contiguous()
-        wb, _ = _cached_bf16(weight, False)
-        bf = None if bias is None else bias.detach().float().contiguous()
-        y = torch.empty(M, N, device=x.device, dtype=torch.bfloat16)
-        _lib.check(lib.sgl_op_gemm_nt(_lib.SGL_DTYPE_BF16, xb.data_ptr(), K, wb.data_ptr(), K, M, N, K, _lib.EPI_STORE,
-                                      y.data_ptr(), N, None, 0, _lib.ptr(bf), None, 0, None, 0, None, 1, 1, 1, 8, 8, 1,
-                                      _lib.current_stream_handle()), "sgl_op_gemm_nt")
-        ctx.save_for_backward(xb, wb)
-        ctx.weight = weight
-        ctx.has_bias = bias is not None
-        ctx.wdtype = weight.dtype
-        ctx.xdtype = x.dtype
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        from . import lib as _lib
-        lib = _lib.load()
-        xb, wb = ctx.saved_tensors
-        M, K = xb.shape
-        N = wb.shape[0]
-        dyb = dy.to(torch.bfloat16).contiguous()
-        stream = _lib.current_stream_handle()
-        dx = dw = db = None
-        if ctx.needs_input_grad[0]:   # dX[M,K] = dY[M,N] · W[N,K]: NT form with the K x N transpose of W as "B"
-            cur, cur_t = _cached_bf16(ctx.weight, True)
-            wt = cur_t if cur is wb else wb.t().contiguous()      # the cached pair only if it is still this forward's weight
-            dx = torch.empty(M, K, device=xb.device, dtype=torch.bfloat16)
-            _lib.check(lib.sgl_op_gemm_nt(_lib.SGL_DTYPE_BF16, dyb.data_ptr(), N, wt.data_ptr(), N, M, K, N,
-                                          _lib.EPI_STORE, dx.data_ptr(), K, None, 0, None, None, 0, None, 0, None, 1, 1,
-                                          1, 8, 8, 1, stream), "sgl_op_gemm_nt(dX)")
-            dx = dx.to(ctx.xdtype)
-        if ctx.needs_input_grad[1]:   # dW[N,K] = dYᵀ · X
-            dw = torch.empty(N, K, device=xb.device, dtype=torch.float32)
-            scratch = _split_scratch(xb.device)   # split-K slabs: deterministic sum
-            _lib.check(lib.sgl_op_gemm_tn_ws(_lib.SGL_DTYPE_BF16, dyb.data_ptr(), N, xb.data_ptr(), K, M, N, K, 0,
-                                             dw.data_ptr(), K, 0, scratch.data_ptr(), scratch.numel(), stream),
-                       "sgl_op_gemm_tn_ws(dW)")
-            dw = dw.to(ctx.wdtype)
-        if ctx.has_bias and ctx.needs_input_grad[2]:
-            db = dyb.float().sum(0) if M < 64 else _hip_colsum(lib, _lib, dyb, M, N, stream)
-        return dx, dw, db
-
-
-@torch.compiler.disable
-def _hip_linear(x2d, weight, bias):
-    return _HipLinearFn.apply(x2d, weight, bias)
-
-
-@torch.compiler.disable
-def _hip_dwconv(x, weight, bias):
-    return _DepthwiseConv3x3Fn.apply(x, weight, bias)
-
-
-def _hip_colsum(lib, _lib, t, M, N, stream):
-    out = torch.empty(N, device=t.device, dtype=torch.float32)
-    nbytes = ((M + 511) // 512 if (M + 511) // 512 < 256 else 256) * N * 4
-    scratch = torch.empty(max(nbytes, 4), device=t.device, dtype=torch.uint8)
-    _lib.check(lib.sgl_op_colsum(_lib.SGL_DTYPE_BF16, t.data_ptr(), N, M, N, out.data_ptr(), 0, scratch.data_ptr(),
-                                 scratch.numel(), stream), "sgl_op_colsum")
-    return out
-
-
-# developer A/B switch: "hip" (default) every token-major Linear / 1x1 convolution of the decoder under bf16 autocast runs on
-# this repo's MFMA GEMMs (256x256-tile kernels for large shapes, the 128x128-tile kernels for narrow ones: E = 256
-# projections, the gate's bottleneck, the 1-channel head); "wide": only shapes with >= 512 columns (round 2's rule, the
-# rest on the vendor GEMM behind F.linear); "torch": F.linear everywhere
-_HIP_LINEAR = __import__("os").environ.get("SGL_HEADS_LINEAR", "hip")
-
-
-def _linear_tokens(x: torch.Tensor, weight: torch.Tensor, bias) -> torch.Tensor:
-    """F.linear on (..., K) token-major data; under CUDA bf16 autocast it runs on the HIP GEMMs (bf16 operands, fp32
-    accumulate: the arithmetic autocast's F.linear does).  fp32 callers (strict parity runs, CPU) keep F.linear."""
-    K, N = x.shape[-1], weight.shape[0]
-    if (_HIP_LINEAR != "torch" and x.is_cuda and torch.is_autocast_enabled()
-            and torch.get_autocast_dtype("cuda") == torch.bfloat16 and K % 8 == 0 and x.numel() // K >= 64):
-        wide = N % 8 == 0 and N >= 512 and K >= 512 and x.numel() // K >= 2048
-        if wide or _HIP_LINEAR == "hip":
-            if N % 8:   # the 1-channel mask head: pad the output columns to the GEMM's 8-column granularity
-                pad = 8 - N % 8
-                weight = F.pad(weight, (0, 0, 0, pad))
-                bias = None if bias is None else F.pad(bias, (0, pad))
-            y = _hip_linear(x.reshape(-1, K), weight, bias)
-            return y.reshape(*x.shape[:-1], y.shape[-1])[..., :N]
-    return F.linear(x, weight, bias)
-
-
-def _aligned16(t: torch.Tensor) -> torch.Tensor:
-    """`t` itself when its storage pointer is 16-byte aligned, otherwise a fresh copy (`.contiguous()` does not move a
-    contiguous offset view such as `buf[1:]`; the vector kernels need 16-byte aligned operands)."""
-    return t if t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.contiguous_format)
-
-
-class _DepthwiseConv3x3Fn(torch.autograd.Function):
-    """Depthwise 3x3 (padding 1) on channels-last (B, gh, gw, E) CUDA tensors through the HIP kernels of
-    csrc/decoder.hip: forward, data gradient (same stencil, flipped taps) and the two-stage weight/bias gradient."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias):
-        from . import lib as _lib
-        lib = _lib.load()
-        if x.dtype not in (torch.float32, torch.bfloat16):
-            x = x.float()
-        x = _aligned16(x.contiguous())
-        B, gh, gw, E = x.shape
-        w = weight.detach().float().reshape(E, 9).t().contiguous()      # tap-major [9][E] (see siglip_hip.h)
-        b = None if bias is None else _aligned16(bias.detach().float().contiguous())
-        y = torch.empty_like(x)
-        dt = _lib.SGL_DTYPE_BF16 if x.dtype == torch.bfloat16 else _lib.SGL_DTYPE_F32
-        _lib.check(lib.sgl_op_dwconv3x3(x.data_ptr(), dt, w.data_ptr(), _lib.ptr(b), y.data_ptr(), B, gh, gw, E, 0,
-                                        _lib.current_stream_handle()), "sgl_op_dwconv3x3")
-        ctx.save_for_backward(x, w)
-        ctx.has_bias = bias is not None
-        ctx.wdtype = weight.dtype
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        from . import lib as _lib
-        lib = _lib.load()
-        x, w = ctx.saved_tensors
-        dy = _aligned16(dy.to(x.dtype).contiguous())
-        B, gh, gw, E = x.shape
-        dt = _lib.SGL_DTYPE_BF16 if x.dtype == torch.bfloat16 else _lib.SGL_DTYPE_F32
-        stream = _lib.current_stream_handle()
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dx = torch.empty_like(x)
-            _lib.check(lib.sgl_op_dwconv3x3(dy.data_ptr(), dt, w.data_ptr(), None, dx.data_ptr(), B, gh, gw, E, 1, stream),
-                       "sgl_op_dwconv3x3(flip)")
-        dw = db = None
-        if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
-            dw10 = torch.empty(10, E, device=x.device, dtype=torch.float32)   # nine tap rows + the bias row
-            nbytes = lib.sgl_op_dwconv3x3_wgrad_scratch_bytes(B, gh, gw, E)
-            scratch = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
-            _lib.check(lib.sgl_op_dwconv3x3_wgrad(x.data_ptr(), dy.data_ptr(), dt, dw10.data_ptr(), 0,
-                                                  scratch.data_ptr(), nbytes, B, gh, gw, E, stream),
-                       "sgl_op_dwconv3x3_wgrad")
-            dw = dw10[:9].t().reshape(E, 1, 3, 3).to(ctx.wdtype)
-            db = dw10[9] if ctx.has_bias else None
-        return dx, dw, db
-
-
-class _GateMulFn(torch.autograd.Function):
-    """y = sigmoid(g) * x in one HBM pass (csrc/decoder_tail.hip), backward (dg w.r.t. the PRE-sigmoid gate, dx) in one
-    more: the SE-style gate of the SID decoder (`gate * x`, Siglip2sidafrozen.py:741-742) on (B*N, E*K) activations."""
-
-    @staticmethod
-    def forward(ctx, g, x):
-        from . import lib as _lib
-        lib = _lib.load()
-        dt = g.dtype if g.dtype in (torch.float32, torch.bfloat16) else torch.float32
-        g2, x2 = g.to(dt).contiguous(), x.to(dt).contiguous()
-        y = torch.empty_like(x2)
-        code = _lib.SGL_DTYPE_BF16 if dt == torch.bfloat16 else _lib.SGL_DTYPE_F32
-        _lib.check(lib.sgl_op_gate_mul(g2.data_ptr(), x2.data_ptr(), y.data_ptr(), g2.numel(), code,
-                                       _lib.current_stream_handle()), "sgl_op_gate_mul")
-        ctx.save_for_backward(g2, x2)
-        ctx.code, ctx.gdt, ctx.xdt = code, g.dtype, x.dtype
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        from . import lib as _lib
-        lib = _lib.load()
-        g2, x2 = ctx.saved_tensors
-        dy2 = _aligned16(dy.to(g2.dtype).contiguous())
-        dg = torch.empty_like(g2) if ctx.needs_input_grad[0] else None
-        dx = torch.empty_like(x2) if ctx.needs_input_grad[1] else None
-        _lib.check(lib.sgl_op_gate_mul_bwd(dy2.data_ptr(), g2.data_ptr(), x2.data_ptr(), _lib.ptr(dg), _lib.ptr(dx),
-                                           g2.numel(), ctx.code, _lib.current_stream_handle()), "sgl_op_gate_mul_bwd")
-        return (None if dg is None else dg.to(ctx.gdt)), (None if dx is None else dx.to(ctx.xdt))
-
-
-@torch.compiler.disable
-def _gate_mul(gate_pre: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
-    nv = 8 if gate_pre.dtype == torch.bfloat16 else 4
-    if gate_pre.is_cuda and gate_pre.shape == x.shape and gate_pre.numel() % nv == 0 and gate_pre.numel() >= 4096:
-        # a contiguous offset view (buf[1:]) keeps its misaligned pointer through .to(dt).contiguous() when it already has
-        # the kernel's dtype (another dtype is cast into a fresh buffer): sgl_op_gate_mul refuses such a pointer
-        dt = gate_pre.dtype if gate_pre.dtype in (torch.float32, torch.bfloat16) else torch.float32
-        misaligned = any(t.dtype == dt and t.is_contiguous() and t.data_ptr() % 16 for t in (gate_pre, x))
-        if not misaligned:
-            return _GateMulFn.apply(gate_pre, x)
-    return torch.sigmoid(gate_pre) * x
-
-
-class _SegLossFromLowresFn(torch.autograd.Function):
-    """`bce_dice_loss(F.interpolate(logit_lr, (S,S), 'bilinear'), masks)` over the images flagged in `sel`, without
-    ever forming the (B,1,S,S) logits: csrc/decoder_tail.hip evaluates every output pixel from its four low-res logits in
-    registers (forward: per-image partial sums; backward: transposed interpolation gathered per low-res pixel, fixed order).
-    No host synchronisation: an empty selection gives 0 (the reference skips the term, Siglip2sidafrozen.py:1380-1389)."""
-
-    @staticmethod
-    def forward(ctx, logit_lr, masks, sel, bce_w, dice_w, eps):
-        from . import lib as _lib
-        lib = _lib.load()
-        B, g = logit_lr.shape[0], logit_lr.shape[-1]
-        S = masks.shape[-1]
-        lr = logit_lr.detach().reshape(B, g, g).float().contiguous()
-        t = masks.reshape(B, S, S).float().contiguous()
-        chunks = lib.sgl_op_seg_loss_chunks(S)
-        partial = torch.empty(B, chunks, 4, device=lr.device, dtype=torch.float32)
-        _lib.check(lib.sgl_op_seg_loss_fwd(lr.data_ptr(), t.data_ptr(), partial.data_ptr(), B, g, S,
-                                           _lib.current_stream_handle()), "sgl_op_seg_loss_fwd")
-        sums = partial.sum(1)                                   # (B, 4), fixed order
-        w = sel.to(torch.float32)
-        n = w.sum()
-        nz = (n > 0).to(torch.float32)
-        n1 = n.clamp(min=1.0)
-        bce = (sums[:, 0] * w).sum() / (n1 * float(S * S))
-        dice_b = 2.0 * sums[:, 1] / (sums[:, 2] + sums[:, 3] + eps)
-        dice = 1.0 - (dice_b * w).sum() / n1
-        loss = (bce_w * bce + dice_w * dice) * nz
-        ctx.save_for_backward(lr, t, sums, w, n1, nz)
-        ctx.cfg = (B, g, S, bce_w, dice_w, eps, logit_lr.shape, logit_lr.dtype)
-        return loss
-
-    @staticmethod
-    def backward(ctx, dloss):
-        from . import lib as _lib
-        lib = _lib.load()
-        lr, t, sums, w, n1, nz = ctx.saved_tensors
-        B, g, S, bce_w, dice_w, eps, shape, dtype = ctx.cfg
-        up = dloss.float() * nz
-        coef = torch.stack([up * bce_w * w / (n1 * float(S * S)), -up * dice_w * w / n1], dim=1).contiguous()
-        dlr = torch.empty_like(lr)
-        _lib.check(lib.sgl_op_seg_loss_bwd(lr.data_ptr(), t.data_ptr(), sums.contiguous().data_ptr(), coef.data_ptr(),
-                                           dlr.data_ptr(), B, g, S, float(eps), _lib.current_stream_handle()),
-                   "sgl_op_seg_loss_bwd")
-        return dlr.reshape(shape).to(dtype), None, None, None, None, None
-
-
-@torch.compiler.disable
-def bce_dice_loss_from_lowres(logit_lr: torch.Tensor, masks: torch.Tensor, has_mask: torch.Tensor = None,
-                              bce_w: float = 1.0, dice_w: float = 0.5, eps: float = 1e-6) -> torch.Tensor:
-    """`bce_dice_loss(upsample(logit_lr)[has_mask], masks[has_mask])` (Siglip2sidafrozen.py:174-181,743) from the (B,1,g,g)
-    logits of `SegFormerMaskDecoder(..., return_lowres=True)`; CUDA only (HIP kernels), fp32 statistics."""
-    if not logit_lr.is_cuda:
-        raise RuntimeError("bce_dice_loss_from_lowres runs on the GPU (HIP kernels); use bce_dice_loss on CPU tensors")
-    if has_mask is None:
-        has_mask = torch.ones(logit_lr.shape[0], dtype=torch.bool, device=logit_lr.device)
-    return _SegLossFromLowresFn.apply(logit_lr, masks, has_mask, float(bce_w), float(dice_w), float(eps))
+        return linear_tokens(x, self.proj.weight, self.proj.bias)
 
 
 class SegFormerMaskDecoder(nn.Module):
@@ -359,26 +68,9 @@ class SegFormerMaskDecoder(nn.Module):
 
     @staticmethod
     def _pointwise(conv: nn.Conv2d, x: torch.Tensor) -> torch.Tensor:
-        """A 1x1 convolution on token-major data (..., C_in) -> (..., C_out): a plain GEMM (hipBLASLt) instead of a
-        MIOpen convolution; the parameters keep their Conv2d shapes, so checkpoints are unchanged."""
-        return _linear_tokens(x, conv.weight.view(conv.out_channels, conv.in_channels), conv.bias)
-
-    @staticmethod
-    def _depthwise3x3(conv: nn.Conv2d, x: torch.Tensor) -> torch.Tensor:
-        """Depthwise 3x3, zero padding 1, on channels-last data (B, gh, gw, E): nine shifted multiply-adds (the same
-        arithmetic as nn.Conv2d(E, E, 3, padding=1, groups=E); MIOpen has only a naive fp32 NHWC solver for it)."""
-        e = x.shape[-1]
-        if x.is_cuda and e % 8 == 0 and e <= 1024 and 256 % (e // 8) == 0 and 256 % (e // 4) == 0:
-            return _hip_dwconv(x, conv.weight, conv.bias)   # one HBM pass (csrc/decoder.hip)
-        w = conv.weight                      # (E, 1, 3, 3)
-        xp = F.pad(x, (0, 0, 1, 1, 1, 1))    # pad gw and gh by one
-        gh, gw = x.shape[1], x.shape[2]
-        out = None
-        for dy in range(3):
-            for dx in range(3):
-                term = xp[:, dy:dy + gh, dx:dx + gw, :] * w[:, 0, dy, dx]
-                out = term if out is None else out + term
-        return out + conv.bias if conv.bias is not None else out
+        """A 1x1 convolution on token-major data (..., C_in) -> (..., C_out): a plain GEMM instead of a MIOpen
+        convolution; the parameters keep their Conv2d shapes, so checkpoints are unchanged."""
+        return linear_tokens(x, conv.weight, conv.bias)
 
     def forward(self, hidden_list: Sequence[torch.Tensor], grid_hw: Tuple[int, int], target_size: int = 448,
                 return_lowres: bool = False):
@@ -391,14 +83,14 @@ class SegFormerMaskDecoder(nn.Module):
         for proj, smooth, h in zip(self.projs, self.smooth, hidden_list):
             x = proj(h)                                              # (B, N, E)
             b, _, e = x.shape
-            x = self._depthwise3x3(smooth[0], x.reshape(b, gh, gw, e))
+            x = depthwise3x3(x.reshape(b, gh, gw, e), smooth[0].weight, smooth[0].bias)
             x = F.gelu(self._pointwise(smooth[1], x))
             for extra in list(smooth)[3:]:                           # Dropout2d when configured: acts on channels
                 x = extra(x.permute(0, 3, 1, 2)).permute(0, 2, 3, 1)
             feats.append(x)
         x = torch.cat(feats, dim=-1)                                 # (B, gh, gw, E*K)
         gate_pre = self._pointwise(self.fuse_attn[2], F.gelu(self._pointwise(self.fuse_attn[0], x)))
-        x = self._pointwise(self.fuse[0], _gate_mul(gate_pre, x))       # sigmoid(gate) * x in one pass on the GPU
+        x = self._pointwise(self.fuse[0], gate_mul(gate_pre, x))        # sigmoid(gate) * x in one pass on the GPU
         for extra in list(self.fuse)[1:]:
             x = extra(x.permute(0, 3, 1, 2)).permute(0, 2, 3, 1)
         if self.head_before_upsample or return_lowres:
@@ -516,47 +208,6 @@ class CifakeBinaryHead(nn.Module):
             f = self.attention(f) if isinstance(self.attention, SingleTokenAttention) else self.attention(f, f, f)[0]
             f = f.squeeze(1)
         return f if return_features else self.classifier(f).squeeze(-1)
-
-
-class _L2NormTemporalMeanFn(torch.autograd.Function):
-    """(B*T, D) frame embeddings -> per-frame L2-norm -> mean over the T frames of a clip -> (B, D), one HIP launch forward
-    and one backward (csrc/preprocess.hip) instead of norm / div / view / mean and their four backward kernels
-    (hidf_video_classifier.py:308-316)."""
-
-    @staticmethod
-    def forward(ctx, f, batch_size):
-        from . import lib as _lib
-        lib = _lib.load()
-        f32 = f.float().contiguous()
-        BT, D = f32.shape
-        T = BT // batch_size
-        out = torch.empty(batch_size, D, device=f.device, dtype=torch.float32)
-        inv = torch.empty(BT, device=f.device, dtype=torch.float32)
-        _lib.check(lib.sgl_op_l2norm_tmean_fwd(f32.data_ptr(), out.data_ptr(), inv.data_ptr(), batch_size, T, D,
-                                               _lib.current_stream_handle()), "sgl_op_l2norm_tmean_fwd")
-        ctx.save_for_backward(f32, inv)
-        ctx.dims, ctx.dtype = (batch_size, T, D), f.dtype
-        return out.to(f.dtype)
-
-    @staticmethod
-    def backward(ctx, dout):
-        from . import lib as _lib
-        lib = _lib.load()
-        f32, inv = ctx.saved_tensors
-        B, T, D = ctx.dims
-        g = dout.float().contiguous()
-        df = torch.empty_like(f32)
-        _lib.check(lib.sgl_op_l2norm_tmean_bwd(f32.data_ptr(), inv.data_ptr(), g.data_ptr(), df.data_ptr(), B, T, D,
-                                               _lib.current_stream_handle()), "sgl_op_l2norm_tmean_bwd")
-        return df.to(ctx.dtype), None
-
-
-@torch.compiler.disable
-def l2norm_temporal_mean(frame_features: torch.Tensor, batch_size: int) -> torch.Tensor:
-    """`l2_normalize(f).view(B, T, D).mean(1)`; fused HIP kernels on CUDA tensors, PyTorch ops elsewhere."""
-    if frame_features.is_cuda and frame_features.dim() == 2 and frame_features.shape[0] % batch_size == 0:
-        return _L2NormTemporalMeanFn.apply(frame_features, batch_size)
-    return l2_normalize(frame_features).view(batch_size, -1, frame_features.shape[-1]).mean(dim=1)
 
 
 class VideoBinaryHead(nn.Module):

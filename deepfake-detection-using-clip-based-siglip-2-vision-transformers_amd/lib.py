@@ -181,6 +181,27 @@ def ptr(t) -> int | None:
     return None if t is None else t.data_ptr()
 
 
-def current_stream_handle() -> int:
+def current_stream_handle(device) -> int:
+    """The current stream of ``device``: the stream work on that device's tensors is ordered on."""
     import torch
-    return torch.cuda.current_stream().cuda_stream
+    return torch.cuda.current_stream(device).cuda_stream
+
+
+def call(symbol: str, device, *args) -> None:
+    """Make the stream-taking ``sgl_op_*`` call ``symbol`` for operands that live on ``device``: under that device's guard
+    and on its current stream, which every such entry point takes as its last argument (``args`` are the ones before
+    it).  Raises ``SglError`` naming the symbol on a non-zero status."""
+    import torch
+    fn = getattr(load(), symbol)
+    with torch.cuda.device(device):
+        status = fn(*args, current_stream_handle(device))
+    check(status, symbol)
+
+
+def dtype_code(dtype) -> int:
+    """``SGL_DTYPE_*`` of a torch dtype the element-wise kernels store."""
+    import torch
+    codes = {torch.float32: SGL_DTYPE_F32, torch.bfloat16: SGL_DTYPE_BF16, torch.float16: SGL_DTYPE_F16}
+    if dtype not in codes:
+        raise ValueError(f"output dtype must be float32, bfloat16 or float16, not {dtype}")
+    return codes[dtype]

@@ -236,9 +236,7 @@ def global_grad_norm(parameters) -> torch.Tensor:
     bmap = torch.frombuffer(bytearray(bytes(bm)), dtype=torch.int32).to(dev)
     partials = torch.empty(max(nb, 1), device=dev, dtype=torch.float32)
     out = torch.zeros(2, device=dev, dtype=torch.float32)
-    with torch.cuda.device(dev):
-        _lib.check(lib.sgl_op_grad_norm(table.data_ptr(), bmap.data_ptr(), nb, 0.0, partials.data_ptr(), out.data_ptr(),
-                                        torch.cuda.current_stream(dev).cuda_stream), "sgl_op_grad_norm")
+    _lib.call("sgl_op_grad_norm", dev, table.data_ptr(), bmap.data_ptr(), nb, 0.0, partials.data_ptr(), out.data_ptr())
     return out[0]
 
 
@@ -294,11 +292,8 @@ class ExponentialMovingAverage:
         """average <- average*decay + weight*(1-decay) for every tracked tensor, one launch."""
         if not self.shadow:
             return
-        lib = _lib.load()
-        table, bmap, nb, dev = self._plan(lib)
-        with torch.cuda.device(dev):
-            _lib.check(lib.sgl_op_ema(table.data_ptr(), bmap.data_ptr(), nb, float(self.decay),
-                                      torch.cuda.current_stream(dev).cuda_stream), "sgl_op_ema")
+        table, bmap, nb, dev = self._plan(_lib.load())
+        _lib.call("sgl_op_ema", dev, table.data_ptr(), bmap.data_ptr(), nb, float(self.decay))
 
     def apply_shadow(self):
         """Evaluate with the averaged weights: every tracked parameter points at its average until ``restore()``."""

@@ -57,18 +57,40 @@ def _mix(mix_index, B, dev):
     return idx
 
 
-_DTYPE_CODES = {torch.float32: _lib.SGL_DTYPE_F32, torch.bfloat16: _lib.SGL_DTYPE_BF16, torch.float16: _lib.SGL_DTYPE_F16}
-
-
-def _dtype_code(dtype: torch.dtype) -> int:
-    if dtype not in _DTYPE_CODES:
-        raise ValueError(f"output dtype must be float32, bfloat16 or float16, not {dtype}")
-    return _DTYPE_CODES[dtype]
-
-
 def _operand_dtype(compute_dtype: str) -> torch.dtype:
     """dtype of the patch-GEMM operand of an encoder in ``compute_dtype`` (strict modes read fp32)."""
     return {"bf16": torch.bfloat16, "fp16": torch.float16, "mxfp8": torch.bfloat16}.get(compute_dtype, torch.float32)
+
+
+def _patch_geometry(config, size):
+    """(S, (P, Kp)): the image side and the patch GEMM's patch size and padded K for ``config``."""
+    cfg = get_config(config)
+    P = cfg.patch_size
+    return int(size or cfg.image_size), (P, (3 * P * P + 63) // 64 * 64)
+
+
+def _transform(images, size, patch, dtype, mean, std, mix_index=None, lam=1.0, params=None) -> torch.Tensor:
+    """The one launch behind the four public transforms.  ``patch`` None: the (B,3,size,size) image tensor; ``(P, Kp)``:
+    the patch GEMM's operand rows.  ``params`` None: sgl_op_preprocess (MixUp); a list of per-sample draws:
+    sgl_op_preprocess_aug."""
+    src, is_u8, B, Hs, Ws = _source(images)
+    dev = src.device
+    if params is not None and len(params) != B:
+        raise ValueError("one augmentation record per image")
+    if patch is None:
+        out, layout = torch.empty((B, 3, size, size), device=dev, dtype=dtype), (size, 1, 3, 0)
+    else:
+        P, Kp = patch
+        out, layout = torch.empty((B * (size // P) ** 2, Kp), device=dev, dtype=dtype), (size, P, Kp, 1)
+    common = (src.data_ptr(), is_u8, B, Hs, Ws, out.data_ptr(), _lib.dtype_code(dtype), *layout, float(mean), float(std))
+    if params is None:
+        idx = _mix(mix_index, B, dev)
+        _lib.call("sgl_op_preprocess", dev, *common, _lib.ptr(idx), float(lam))
+    else:
+        tab = augment_table(params, dev)
+        gm = torch.empty(B, device=dev, dtype=torch.float32)      # per-image means for the contrast operator
+        _lib.call("sgl_op_preprocess_aug", dev, *common, tab.data_ptr(), gm.data_ptr())
+    return out
 
 
 def resize_normalize(images: torch.Tensor, size: int, mean: float = 0.5, std: float = 0.5,
@@ -76,16 +98,7 @@ def resize_normalize(images: torch.Tensor, size: int, mean: float = 0.5, std: fl
                      dtype: torch.dtype = torch.float32) -> torch.Tensor:
     """(B,3,size,size) = Normalize(mean,std)(MixUp(Resize(size, antialias=True)(images))): the tensor the reference's GPU
     transform returns, in one pass."""
-    lib = _lib.load()
-    src, is_u8, B, Hs, Ws = _source(images)
-    out = torch.empty((B, 3, size, size), device=src.device, dtype=dtype)
-    code = _dtype_code(dtype)
-    idx = _mix(mix_index, B, src.device)
-    with torch.cuda.device(src.device):
-        _lib.check(lib.sgl_op_preprocess(src.data_ptr(), is_u8, B, Hs, Ws, out.data_ptr(), code, size, 1, 3, 0, float(mean),
-                                         float(std), _lib.ptr(idx), float(lam), _lib.current_stream_handle()),
-                   "sgl_op_preprocess")
-    return out
+    return _transform(images, size, None, dtype, mean, std, mix_index, lam)
 
 
 def to_patch_operand(images: torch.Tensor, config, size: Optional[int] = None, compute_dtype: str = "bf16",
@@ -93,22 +106,9 @@ def to_patch_operand(images: torch.Tensor, config, size: Optional[int] = None, c
                      lam: float = 1.0) -> PatchOperand:
     """Resize (antialias) + MixUp + Normalize straight into the patch-embedding GEMM's operand for ``config`` (its patch
     size and K padding); feed the result to ``SiglipVisionModelHIP(patches=...)`` / ``encode_image(patches=...)``."""
-    lib = _lib.load()
-    cfg = get_config(config)
-    S = int(size or cfg.image_size)
-    P = cfg.patch_size
-    g = S // P
-    Kp = (3 * P * P + 63) // 64 * 64
-    src, is_u8, B, Hs, Ws = _source(images)
-    dt = _operand_dtype(compute_dtype)
-    out = torch.empty((B * g * g, Kp), device=src.device, dtype=dt)
-    code = _dtype_code(dt)
-    idx = _mix(mix_index, B, src.device)
-    with torch.cuda.device(src.device):
-        _lib.check(lib.sgl_op_preprocess(src.data_ptr(), is_u8, B, Hs, Ws, out.data_ptr(), code, S, P, Kp, 1, float(mean),
-                                         float(std), _lib.ptr(idx), float(lam), _lib.current_stream_handle()),
-                   "sgl_op_preprocess")
-    return PatchOperand(out, B, S, S)
+    S, patch = _patch_geometry(config, size)
+    out = _transform(images, S, patch, _operand_dtype(compute_dtype), mean, std, mix_index, lam)
+    return PatchOperand(out, images.shape[0], S, S)
 
 
 # ---- augmentation branch (hidf_video_classifier.py:2868-2874) ----------------------------------------------------------
@@ -153,43 +153,15 @@ def augment_resize_normalize(images: torch.Tensor, size: int, params: list, mean
     """(B,3,size,size) = Normalize(ColorJitter(Rotation(Flip(Resize(images))))) with the given per-sample draws: the tensor
     the video trainer's augmenting GPU transform returns, in one pass over the pixels (plus a per-image mean pre-pass for
     the contrast operator)."""
-    lib = _lib.load()
-    src, is_u8, B, Hs, Ws = _source(images)
-    if len(params) != B:
-        raise ValueError("one augmentation record per image")
-    out = torch.empty((B, 3, size, size), device=src.device, dtype=dtype)
-    code = _dtype_code(dtype)
-    tab = augment_table(params, src.device)
-    gm = torch.empty(B, device=src.device, dtype=torch.float32)
-    with torch.cuda.device(src.device):
-        _lib.check(lib.sgl_op_preprocess_aug(src.data_ptr(), is_u8, B, Hs, Ws, out.data_ptr(), code, size, 1, 3, 0,
-                                             float(mean), float(std), tab.data_ptr(), gm.data_ptr(),
-                                             _lib.current_stream_handle()), "sgl_op_preprocess_aug")
-    return out
+    return _transform(images, size, None, dtype, mean, std, params=params)
 
 
 def augment_to_patch_operand(images: torch.Tensor, config, params: list, size: Optional[int] = None,
                              compute_dtype: str = "bf16", mean: float = 0.5, std: float = 0.5) -> PatchOperand:
     """The augmenting transform written straight into the patch GEMM's operand (see ``to_patch_operand``)."""
-    lib = _lib.load()
-    cfg = get_config(config)
-    S = int(size or cfg.image_size)
-    P = cfg.patch_size
-    g = S // P
-    Kp = (3 * P * P + 63) // 64 * 64
-    src, is_u8, B, Hs, Ws = _source(images)
-    if len(params) != B:
-        raise ValueError("one augmentation record per image")
-    dt = _operand_dtype(compute_dtype)
-    out = torch.empty((B * g * g, Kp), device=src.device, dtype=dt)
-    code = _dtype_code(dt)
-    tab = augment_table(params, src.device)
-    gm = torch.empty(B, device=src.device, dtype=torch.float32)
-    with torch.cuda.device(src.device):
-        _lib.check(lib.sgl_op_preprocess_aug(src.data_ptr(), is_u8, B, Hs, Ws, out.data_ptr(), code, S, P, Kp, 1,
-                                             float(mean), float(std), tab.data_ptr(), gm.data_ptr(),
-                                             _lib.current_stream_handle()), "sgl_op_preprocess_aug")
-    return PatchOperand(out, B, S, S)
+    S, patch = _patch_geometry(config, size)
+    out = _transform(images, S, patch, _operand_dtype(compute_dtype), mean, std, params=params)
+    return PatchOperand(out, images.shape[0], S, S)
 
 
 class GpuTransform(nn.Module):

@@ -103,7 +103,7 @@ def main():
     gh = S // P
     M, K0 = B * gh * gh, 3 * P * P
     Kp = (K0 + 63) // 64 * 64
-    s = pkg.lib.current_stream_handle()
+    s = pkg.lib.current_stream_handle(x.device)
     g = torch.randn(M, D, device="cuda").bfloat16()
     wpt = torch.randn(Kp, D, device="cuda").bfloat16()
     dcols = torch.empty(M, Kp, device="cuda")

@@ -1,6 +1,6 @@
 """Developer tool: the SID multi-task training step (frozen-prefix encoder + SegFormer decoder + CE/BCE/Dice loss,
 Siglip2sidafrozen.py:750-803,1375-1398) against the encoder alone, to see what the PyTorch heads cost around the HIP path.
-   python tests/bench_mtl.py [B] [freeze_below]"""
+   python tests/bench_mtl.py [B] [freeze_below] [ultra|base] [timed steps]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -12,6 +12,7 @@ K = int(sys.argv[2]) if len(sys.argv) > 2 else 21
 ULTRA = len(sys.argv) > 3 and sys.argv[3] == "ultra"   # the script's default decoder (Siglip2sidafrozen.py:1139-1140)
 SEG_LAYERS = (1, 2, 3, 4, 5, 6, 7, 8, 9, 10, -1) if ULTRA else (2, 6, 10, -1)
 EMBED = 512 if ULTRA else 256
+STEPS = int(sys.argv[4]) if len(sys.argv) > 4 else 5
 cfg = pkg.get_config("so400m-patch14-384")
 enc = pkg.SiglipVisionModelHIP(cfg, "bf16")
 enc.load_state_dict(pkg.weights.seeded_state_dict(cfg, 0))
@@ -36,6 +37,6 @@ def step_enc():
 for name, fn in (("encoder only (+AdamW)", step_enc), ("SID multi-task step (+AdamW)", step_full)):
     for _ in range(2): fn()
     torch.cuda.synchronize(); t0 = time.perf_counter()
-    for _ in range(5): fn()
-    torch.cuda.synchronize(); dt = (time.perf_counter() - t0) / 5
+    for _ in range(STEPS): fn()
+    torch.cuda.synchronize(); dt = (time.perf_counter() - t0) / STEPS
     print(f"{name}: {dt*1e3:8.1f} ms/step  {B/dt:8.1f} img/s  (B={B}, blocks<{K} frozen, decoder taps={len(SEG_LAYERS)} E={EMBED})")

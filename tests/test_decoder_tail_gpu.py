@@ -16,7 +16,7 @@ def test_gate_mul_forward_backward(pkg, hiplib, dtype, tol, shape):
     g = (torch.randn(shape, device="cuda") * 2).to(dtype).requires_grad_(True)
     x = torch.randn(shape, device="cuda").to(dtype).requires_grad_(True)
     dy = torch.randn(shape, device="cuda").to(dtype)
-    y = H._gate_mul(g, x)
+    y = pkg.head_ops.gate_mul(g, x)
     y.backward(dy)
     gr, xr = g.detach().float().requires_grad_(True), x.detach().float().requires_grad_(True)
     ref = torch.sigmoid(gr) * xr

@@ -58,12 +58,14 @@ def test_fp16_operand_dtype_map(pkg):
     assert encoder.OPERAND_DTYPE["fp16"] == torch.float16
     assert encoder.COMPUTE_DTYPES["fp16"] == pkg.lib.SGL_DTYPE_F16
     assert preprocess._operand_dtype("fp16") == torch.float16
-    assert preprocess._dtype_code(torch.float16) == pkg.lib.SGL_DTYPE_F16
+    assert pkg.lib.dtype_code(torch.float16) == pkg.lib.SGL_DTYPE_F16 == 3
+    assert pkg.lib.dtype_code(torch.float32) == pkg.lib.SGL_DTYPE_F32 == 0
+    assert pkg.lib.dtype_code(torch.bfloat16) == pkg.lib.SGL_DTYPE_BF16 == 1
     # the existing modes keep their operand dtypes
     assert preprocess._operand_dtype("bf16") == torch.bfloat16
     assert preprocess._operand_dtype("bf16x3") == torch.float32 and preprocess._operand_dtype("fp32") == torch.float32
     with pytest.raises(ValueError):
-        preprocess._dtype_code(torch.float64)
+        pkg.lib.dtype_code(torch.float64)
 
 
 @pytest.mark.parametrize("case", gu.CASES)

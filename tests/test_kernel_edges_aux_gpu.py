@@ -286,9 +286,9 @@ def test_dwconv3x3_refusals_write_nothing(lib):
 
 
 def test_dwconv_wrapper_copies_a_misaligned_operand(pkg, lib):
-    """heads._DepthwiseConv3x3Fn on an input, a bias and an upstream gradient that are contiguous views 4 bytes into their
+    """head_ops._DepthwiseConv3x3Fn on an input, a bias and an upstream gradient that are contiguous views 4 bytes into their
     buffers (`.contiguous()` leaves such a view where it is): correct values, forward and backward."""
-    H = pkg.heads
+    H = pkg.head_ops
     B, gh, gw, E = 2, 5, 7, 64
     n = B * gh * gw * E
     g = gen(5)
@@ -464,10 +464,10 @@ def test_gate_mul_refusals_write_nothing(lib, dtype):
 
 @pytest.mark.parametrize("which", ["gate", "x", "both"])
 def test_gate_mul_wrapper_falls_back_on_an_offset_view(pkg, lib, which):
-    """heads._gate_mul on 4096-element views that start 4 bytes into an fp32 buffer: sgl_op_gate_mul refuses such a pointer
+    """head_ops.gate_mul on 4096-element views that start 4 bytes into an fp32 buffer: sgl_op_gate_mul refuses such a pointer
     and `.contiguous()` does not move a contiguous view, so the wrapper computes sigmoid(g) * x itself, forward and
     backward (bit-identical to torch's composition: it IS that composition)."""
-    H = pkg.heads
+    H = pkg.head_ops
     n = 4096
     g = gen(21)
     gb, xb = randn(g, n + 8).requires_grad_(True), randn(g, n + 8).requires_grad_(True)
@@ -475,7 +475,7 @@ def test_gate_mul_wrapper_falls_back_on_an_offset_view(pkg, lib, which):
     gate, x = gb[og:og + n], xb[ox:ox + n]
     assert (gate.data_ptr() % 16 != 0) == bool(og) and (x.data_ptr() % 16 != 0) == bool(ox)
     dy = randn(g, n)
-    y = H._gate_mul(gate, x)
+    y = H.gate_mul(gate, x)
     dgb, dxb = torch.autograd.grad(y, (gb, xb), dy)
     gr, xr = gb.detach().clone().requires_grad_(True), xb.detach().clone().requires_grad_(True)
     yr = torch.sigmoid(gr[og:og + n]) * xr[ox:ox + n]
@@ -485,13 +485,13 @@ def test_gate_mul_wrapper_falls_back_on_an_offset_view(pkg, lib, which):
 
 def test_gate_mul_wrapper_accepts_an_offset_upstream_gradient(pkg, lib):
     """Aligned operands take the kernel; an upstream gradient that is an offset view is copied, not refused."""
-    H = pkg.heads
+    H = pkg.head_ops
     n = 4096
     g = gen(22)
     gate, x = (randn(g, n) * 3).requires_grad_(True), randn(g, n).requires_grad_(True)
     dy = randn(g, n + 4)[1:n + 1]
     assert dy.data_ptr() % 16 and dy.is_contiguous()
-    y = H._gate_mul(gate, x)
+    y = H.gate_mul(gate, x)
     dgate, dx = torch.autograd.grad(y, (gate, x), dy)
     ref, bound = kr.gate_mul_ref(gate.detach(), x.detach(), torch.float32)
     within(y.detach(), ref, bound, "wrapper y")

@@ -329,7 +329,7 @@ def test_config4_sid_default_decoder_bf16_autocast(pkg, oracle, hiplib):
     model = H.SigLIP2MTL(enc, seg_layers=seg_layers, embed_dim=512, freeze_below=9)
     heads_cpu = copy.deepcopy({"cls": model.cls_head, "dec": model.decoder})
     model = model.cuda()
-    B = 8    # M = 8 * 256 = 2048 tokens: the decoder's Linear layers take the HIP MFMA path (heads._linear_tokens)
+    B = 8    # M = 8 * 256 = 2048 tokens: the decoder's Linear layers take the HIP MFMA path (head_ops.linear_tokens)
     x = pkg.weights.seeded_pixels(B, 224, 224, seed=62)
     y = torch.tensor([0, 1, 2, 1, 0, 2, 2, 1])
     masks = (pkg.weights.seeded_tensor("masks", (B, 1, 224, 224), 1.0) > 0.2).float()
