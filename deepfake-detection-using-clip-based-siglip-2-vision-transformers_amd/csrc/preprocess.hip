@@ -292,6 +292,113 @@ __global__ __launch_bounds__(256) void patch_pad_zero_kernel(TOut* __restrict__ 
     Elem<TOut>::st(out + (idx / padw) * Kp + K0 + idx % padw, 0.f);
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Adjoint of preprocess_kernel<false, float>(patch_major = 0) with respect to a float source: the forward is linear,
+//     out[b] = (lam Wy src[b] Wx^T + (1 - lam) Wy src[mix[b]] Wx^T - mean) / std,
+// so d_src[b] = Wy^T (lam G[b] + (1 - lam) sum_{j : mix[j] == b} G[j]) Wx / std with the SAME fp32 weights (aa_axis / aa_w).
+// Gather form: one thread = one source element, which sums the outputs whose taps include it; nothing is scattered, no
+// atomics, every element of d_src is stored exactly once, and the order of the sums is fixed (j, then oy, then ox).
+// A pre-pass writes two small tables per axis into caller scratch, so that the per-element loop neither normalises a
+// filter (up to 33 taps per output at ratio 16) nor searches:
+//   AaAxis  [S]   the forward's filter of every output index
+//   SrcSpan [in]  the outputs [first, first + count) whose taps [lo, hi) include source index j.  lo and hi are
+//                 non-decreasing in the output index, so the set is one range; it is found by testing lo <= j < hi with
+//                 the forward's own fp32 expressions (aa_axis) over a window that is wider than any rounding of the
+//                 inverted formula could move it: inverting in floating point alone would drop or invent a boundary tap.
+// ---------------------------------------------------------------------------------------------------------------
+struct SrcSpan {
+  int first, count;
+};
+
+__device__ __forceinline__ bool aa_covers(int o, int j, int in, float scale) {
+  const AaAxis a = aa_axis(o, in, scale);                // only lo and n are used: the normalisation loop is dead code
+  return a.lo <= j && j < a.lo + a.n;
+}
+
+__device__ __forceinline__ SrcSpan src_span(int j, int in, int out, float scale) {
+  const float support = scale >= 1.0f ? scale : 1.0f;
+  // covering outputs satisfy (j + 0.5 - support) / scale - 0.5 <= o < (j + 0.5 + support) / scale - 0.5 in exact arithmetic
+  int o0 = (int)floorf(((float)j - support - 1.0f) / scale - 0.5f) - 1;
+  int o1 = (int)ceilf(((float)j + support + 1.0f) / scale - 0.5f) + 1;
+  if (o0 < 0) o0 = 0;
+  if (o1 > out - 1) o1 = out - 1;
+  int first = o0;
+  while (first <= o1 && !aa_covers(first, j, in, scale)) ++first;
+  int end = first;
+  while (end <= o1 && aa_covers(end, j, in, scale)) ++end;
+  SrcSpan s;
+  s.first = first;
+  s.count = end - first;
+  return s;
+}
+
+__host__ __device__ __forceinline__ size_t bwd_span_offset(int S) {   // the SrcSpan tables follow the two AaAxis tables
+  return (size_t)2 * S * sizeof(AaAxis);
+}
+
+__global__ __launch_bounds__(256) void preprocess_bwd_tables_kernel(AaAxis* __restrict__ ty, AaAxis* __restrict__ tx,
+                                                                    SrcSpan* __restrict__ ry, SrcSpan* __restrict__ rx,
+                                                                    int Hs, int Ws, int S) {
+  const float sy = (float)Hs / (float)S, sx = (float)Ws / (float)S;
+  const int total = 2 * S + Hs + Ws;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
+    if (i < S) ty[i] = aa_axis(i, Hs, sy);
+    else if (i < 2 * S) tx[i - S] = aa_axis(i - S, Ws, sx);
+    else if (i < 2 * S + Hs) ry[i - 2 * S] = src_span(i - 2 * S, Hs, S, sy);
+    else rx[i - 2 * S - Hs] = src_span(i - 2 * S - Hs, Ws, S, sx);
+  }
+}
+
+// sum over the outputs of image j that read source element (y, x) of channel c: (Wy^T G[j, c] Wx)[y, x]
+__device__ __forceinline__ float bwd_filter_sum(const float* __restrict__ g, const AaAxis* __restrict__ ty,
+                                                const AaAxis* __restrict__ tx, SrcSpan py, SrcSpan px, int y, int x,
+                                                int S) {
+  float acc = 0.f;
+  for (int oy = py.first; oy < py.first + py.count; ++oy) {
+    const AaAxis ay = ty[oy];
+    const float* grow = g + (size_t)oy * S;
+    float row = 0.f;
+    for (int ox = px.first; ox < px.first + px.count; ++ox) {
+      const AaAxis ax = tx[ox];
+      row += aa_w(ax, x - ax.lo) * grow[ox];
+    }
+    acc += aa_w(ay, y - ay.lo) * row;
+  }
+  return acc;
+}
+
+__global__ __launch_bounds__(256) void preprocess_bwd_kernel(const float* __restrict__ d_out, float* __restrict__ d_src,
+                                                             int B, int Hs, int Ws, int S, float inv_std,
+                                                             const int* __restrict__ mix_index, float lam,
+                                                             const AaAxis* __restrict__ ty, const AaAxis* __restrict__ tx,
+                                                             const SrcSpan* __restrict__ ry,
+                                                             const SrcSpan* __restrict__ rx) {
+  const size_t total = (size_t)B * 3 * Hs * Ws;
+  const bool copy = ty == nullptr;                       // Hs == S && Ws == S: the forward's copy shortcut
+  const size_t plane = (size_t)S * S;
+  for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
+    const int x = (int)(idx % Ws), y = (int)((idx / Ws) % Hs);
+    const int c = (int)((idx / ((size_t)Hs * Ws)) % 3), b = (int)(idx / ((size_t)3 * Hs * Ws));
+    SrcSpan py = {0, 0}, px = {0, 0};
+    if (!copy) {
+      py = ry[y];
+      px = rx[x];
+    }
+    auto image = [&](int j) {
+      const float* g = d_out + ((size_t)j * 3 + c) * plane;
+      return copy ? g[(size_t)y * S + x] : bwd_filter_sum(g, ty, tx, py, px, y, x, S);
+    };
+    float v = image(b);
+    if (mix_index) {
+      v = lam * v;
+      const float oml = 1.0f - lam;
+      for (int j = 0; j < B; ++j)                        // mix_index need not be a permutation: 0, 1 or many j per b
+        if (mix_index[j] == b) v += oml * image(j);
+    }
+    d_src[idx] = v * inv_std;
+  }
+}
+
 }  // namespace sgl
 
 extern "C" {
@@ -322,6 +429,40 @@ int sgl_op_preprocess(const void* src, int src_is_u8_nhwc, int B, int Hs, int Ws
     else SGL_PP(false, float);
   }
 #undef SGL_PP
+  return hipGetLastError() == hipSuccess ? SGL_OK : SGL_ERR_HIP;
+}
+
+size_t sgl_op_preprocess_bwd_scratch_bytes(int B, int Hs, int Ws, int S) {
+  if (B <= 0 || Hs <= 0 || Ws <= 0 || S <= 0) return 0;
+  if (Hs == S && Ws == S) return 0;                      // the copy shortcut reads no table
+  return sgl::bwd_span_offset(S) + ((size_t)Hs + (size_t)Ws) * sizeof(sgl::SrcSpan);
+}
+
+int sgl_op_preprocess_bwd(const float* d_out, int B, int Hs, int Ws, int S, float std, const int* mix_index, float lam,
+                          float* d_src, void* scratch, size_t scratch_bytes, sgl_stream stream) {
+  if (!d_out || !d_src) return SGL_ERR_NULL;
+  if (B <= 0 || Hs <= 0 || Ws <= 0 || S <= 0 || std == 0.f) return SGL_ERR_BAD_SHAPE;
+  if ((long long)2 * S + Hs + Ws > 0x7fffffffLL) return SGL_ERR_BAD_SHAPE;
+  if ((float)Hs / (float)S > 16.f || (float)Ws / (float)S > 16.f) return SGL_ERR_UNSUPPORTED;  // the forward's limit
+  const size_t need = sgl_op_preprocess_bwd_scratch_bytes(B, Hs, Ws, S);
+  if (need && !scratch) return SGL_ERR_NULL;
+  if (scratch_bytes < need) return SGL_ERR_WORKSPACE;
+  hipStream_t s = (hipStream_t)stream;
+  sgl::AaAxis *ty = nullptr, *tx = nullptr;
+  sgl::SrcSpan *ry = nullptr, *rx = nullptr;
+  if (need) {
+    ty = reinterpret_cast<sgl::AaAxis*>(scratch);
+    tx = ty + S;
+    ry = reinterpret_cast<sgl::SrcSpan*>(reinterpret_cast<char*>(scratch) + sgl::bwd_span_offset(S));
+    rx = ry + Hs;
+    const int entries = 2 * S + Hs + Ws;
+    hipLaunchKernelGGL(sgl::preprocess_bwd_tables_kernel, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, s, ty, tx,
+                       ry, rx, Hs, Ws, S);
+  }
+  const size_t total = (size_t)B * 3 * Hs * Ws;
+  const int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);   // 256 CUs x 8 blocks, grid-stride
+  hipLaunchKernelGGL(sgl::preprocess_bwd_kernel, dim3(blocks), dim3(256), 0, s, d_out, d_src, B, Hs, Ws, S, 1.0f / std,
+                     mix_index, lam, ty, tx, ry, rx);
   return hipGetLastError() == hipSuccess ? SGL_OK : SGL_ERR_HIP;
 }
 

@@ -93,11 +93,71 @@ def _transform(images, size, patch, dtype, mean, std, mix_index=None, lam=1.0, p
     return out
 
 
+def _wants_grad(images) -> bool:
+    """A floating source that autograd would differentiate: the only case that leaves today's no-graph path."""
+    return torch.is_grad_enabled() and images.is_floating_point() and images.requires_grad
+
+
+def _refuse_grad(images, what: str) -> None:
+    """Everything but ``resize_normalize`` has no backward: refuse rather than return a silently missing gradient."""
+    if images.is_cuda and _wants_grad(images):
+        raise RuntimeError(
+            f"{what} is not differentiable with respect to its source images (the colour operators and the patch-operand "
+            "layout have no backward); use preprocess.resize_normalize(images, size), which is, and pass its result to "
+            "the encoder as pixel_values=, or detach the images / run under torch.no_grad()")
+
+
+def resize_normalize_backward(grad_out: torch.Tensor, source_hw, mix_index: Optional[torch.Tensor] = None,
+                              lam: float = 1.0, std: float = 0.5) -> torch.Tensor:
+    """The vector-Jacobian product of ``resize_normalize`` as a function: ``grad_out`` (B,3,S,S) -> fp32 (B,3,Hs,Ws), the
+    gradient with respect to a float source of size ``source_hw = (Hs, Ws)`` (for a uint8 source: with respect to
+    ``bytes / 255``).  The transform is linear, so no source values are needed; one ``sgl_op_preprocess_bwd``, a gather with
+    a fixed summation order: bitwise reproducible.  ``mix_index`` / ``lam`` / ``std`` as given to the forward."""
+    if not grad_out.is_cuda:
+        raise RuntimeError("the GPU input pipeline runs on CUDA tensors only (no CPU path)")
+    if grad_out.dim() != 4 or grad_out.shape[1] != 3 or grad_out.shape[2] != grad_out.shape[3]:
+        raise ValueError(f"grad_out must be (B,3,S,S), got {tuple(grad_out.shape)}")
+    g = grad_out.detach().float().contiguous()
+    B, S = g.shape[0], g.shape[2]
+    Hs, Ws = int(source_hw[0]), int(source_hw[1])
+    dev = g.device
+    idx = _mix(mix_index, B, dev)
+    d_src = torch.empty((B, 3, Hs, Ws), device=dev, dtype=torch.float32)
+    nbytes = _lib.load().sgl_op_preprocess_bwd_scratch_bytes(B, Hs, Ws, S)
+    scratch = torch.empty(nbytes, device=dev, dtype=torch.uint8) if nbytes else None
+    _lib.call("sgl_op_preprocess_bwd", dev, g.data_ptr(), B, Hs, Ws, S, float(std), _lib.ptr(idx), float(lam),
+              d_src.data_ptr(), _lib.ptr(scratch), nbytes)
+    return d_src
+
+
+class _ResizeNormalize(torch.autograd.Function):
+    """``resize_normalize`` for a source that requires grad: the same single forward launch, one
+    ``sgl_op_preprocess_bwd`` backward.  Nothing is saved: the transform is linear in the source."""
+
+    @staticmethod
+    def forward(ctx, images, size, mean, std, mix_index, lam, dtype):
+        ctx.src = (images.shape, images.dtype)
+        ctx.args = (std, mix_index, lam)
+        return _transform(images.detach(), size, None, dtype, mean, std, mix_index, lam)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        shape, src_dtype = ctx.src
+        std, mix_index, lam = ctx.args
+        d_src = resize_normalize_backward(grad_out, shape[2:], mix_index, lam, std)
+        return d_src.to(src_dtype), None, None, None, None, None, None
+
+
 def resize_normalize(images: torch.Tensor, size: int, mean: float = 0.5, std: float = 0.5,
                      mix_index: Optional[torch.Tensor] = None, lam: float = 1.0,
                      dtype: torch.dtype = torch.float32) -> torch.Tensor:
     """(B,3,size,size) = Normalize(mean,std)(MixUp(Resize(size, antialias=True)(images))): the tensor the reference's GPU
-    transform returns, in one pass."""
+    transform returns, in one pass.  Differentiable with respect to a floating ``images`` that requires grad (any float
+    dtype, any strides): ``images.grad`` arrives in the source's dtype and shape; ``mix_index`` / ``lam`` get no gradient.
+    uint8 sources have no gradient of their own: see ``resize_normalize_backward``."""
+    if images.is_cuda and _wants_grad(images):
+        return _ResizeNormalize.apply(images, size, mean, std, mix_index, lam, dtype)
     return _transform(images, size, None, dtype, mean, std, mix_index, lam)
 
 
@@ -106,6 +166,7 @@ def to_patch_operand(images: torch.Tensor, config, size: Optional[int] = None, c
                      lam: float = 1.0) -> PatchOperand:
     """Resize (antialias) + MixUp + Normalize straight into the patch-embedding GEMM's operand for ``config`` (its patch
     size and K padding); feed the result to ``SiglipVisionModelHIP(patches=...)`` / ``encode_image(patches=...)``."""
+    _refuse_grad(images, "to_patch_operand")
     S, patch = _patch_geometry(config, size)
     out = _transform(images, S, patch, _operand_dtype(compute_dtype), mean, std, mix_index, lam)
     return PatchOperand(out, images.shape[0], S, S)
@@ -153,12 +214,14 @@ def augment_resize_normalize(images: torch.Tensor, size: int, params: list, mean
     """(B,3,size,size) = Normalize(ColorJitter(Rotation(Flip(Resize(images))))) with the given per-sample draws: the tensor
     the video trainer's augmenting GPU transform returns, in one pass over the pixels (plus a per-image mean pre-pass for
     the contrast operator)."""
+    _refuse_grad(images, "augment_resize_normalize")
     return _transform(images, size, None, dtype, mean, std, params=params)
 
 
 def augment_to_patch_operand(images: torch.Tensor, config, params: list, size: Optional[int] = None,
                              compute_dtype: str = "bf16", mean: float = 0.5, std: float = 0.5) -> PatchOperand:
     """The augmenting transform written straight into the patch GEMM's operand (see ``to_patch_operand``)."""
+    _refuse_grad(images, "augment_to_patch_operand")
     S, patch = _patch_geometry(config, size)
     out = _transform(images, S, patch, _operand_dtype(compute_dtype), mean, std, params=params)
     return PatchOperand(out, images.shape[0], S, S)
@@ -174,11 +237,13 @@ class GpuTransform(nn.Module):
         self.resolution, self.mean, self.std = int(resolution), float(mean), float(std)
         self.data_augmentation, self.generator = bool(data_augmentation), generator
 
-    @torch.no_grad()
     def forward(self, images, mix_index=None, lam: float = 1.0):
         """``data_augmentation=True`` (hidf_video_classifier.py ``--data_augmentation``, :2866-2874) inserts flip / rotation /
-        colour jitter between resize and normalize while the module is in training mode; draws come from ``generator``."""
+        colour jitter between resize and normalize while the module is in training mode; draws come from ``generator``.
+        The plain branch is differentiable with respect to floating ``images`` that require grad (``resize_normalize``);
+        the augmentation branch refuses such a source."""
         if self.data_augmentation and self.training:
+            _refuse_grad(images, "GpuTransform(data_augmentation=True) in training mode")
             if mix_index is not None:
                 raise ValueError("MixUp and the augmentation branch belong to different trainers; use one of them")
             params = sample_augmentation(images.shape[0], self.generator)

@@ -344,6 +344,22 @@ int sgl_op_dwconv3x3_wgrad(const void* x, const void* dy, int dtype, float* dw10
 int sgl_op_preprocess(const void* src, int src_is_u8_nhwc, int B, int Hs, int Ws, void* out, int out_dtype, int S, int P,
                       int Kp, int patch_major, float mean, float std, const int* mix_index, float lam,
                       sgl_stream stream);
+/* The adjoint of sgl_op_preprocess(patch_major = 0) for a float source: d_out fp32 (B,3,S,S) NCHW, the gradient with
+ * respect to the transform's output -> d_src fp32 (B,3,Hs,Ws) NCHW, the gradient with respect to the source,
+ *   d_src[b] = Wy^T (lam * d_out[b] + (1 - lam) * sum over {j : mix_index[j] == b} of d_out[j]) Wx / std
+ * (mix_index == NULL: Wy^T d_out[b] Wx / std) with the fp32 filter weights the forward applies; mean does not enter.
+ * mix_index (device int32[B]) need not be a permutation: an image may be referenced by several others, by itself or by
+ * none.  The transform is linear, so no source values are needed; for a uint8 source the result is the gradient with
+ * respect to the byte scaled to [0,1] (byte / 255).  A gather: d_src is always overwritten, every element, by one plain
+ * store, with a fixed summation order and no atomics: bitwise reproducible.
+ * scratch: sgl_op_preprocess_bwd_scratch_bytes() bytes of device memory, 4-byte aligned, for the per-axis filter tables a
+ * pre-pass writes (0 bytes, and scratch may be NULL, when Hs == S and Ws == S: the forward's copy shortcut).
+ * Refused before anything is enqueued, d_src untouched: d_out or d_src NULL (or scratch NULL when bytes are needed)
+ * SGL_ERR_NULL; std == 0 or a dimension < 1 SGL_ERR_BAD_SHAPE; Hs > 16 * S or Ws > 16 * S SGL_ERR_UNSUPPORTED (the
+ * forward's limit); scratch_bytes too small SGL_ERR_WORKSPACE. */
+size_t sgl_op_preprocess_bwd_scratch_bytes(int B, int Hs, int Ws, int S);
+int sgl_op_preprocess_bwd(const float* d_out, int B, int Hs, int Ws, int S, float std, const int* mix_index, float lam,
+                          float* d_src, void* scratch, size_t scratch_bytes, sgl_stream stream);
 
 /* Augmentation branch of the video trainer's GPU transform (hidf_video_classifier.py:2868-2874): K.Resize(S, antialias) ->
  * RandomHorizontalFlip -> RandomRotation(+-5 deg, bilinear, zeros outside) -> ColorJitter -> K.Normalize, one pass, same
