@@ -704,10 +704,8 @@ hipError_t pool_attn_fwd(const float* q, const void* K, const void* V, int dtype
                          int H, int N, int dh, int DP, hipStream_t s) {
   if (B * H == 0) return hipSuccess;
   if (DP % 8 || DP < 8 || DP > 2048) return hipErrorInvalidValue;
-  const int CPR = DP / 8;
-  const size_t need = (size_t)N * CPR > (size_t)256 * 8 ? (size_t)N * CPR : (size_t)256 * 8;
-  const size_t smem = (need + N + 8) * sizeof(float);
-  if (smem > 64 * 1024) return hipErrorInvalidValue;   // N * DP / 8 chunk partials must fit the default LDS window
+  if (N < 0 || N > pool_attn_max_tokens(DP, 0)) return hipErrorInvalidValue;   // the default LDS window (kernels.h)
+  const size_t smem = pool_attn_lds_floats(N, DP, 0) * sizeof(float);
   if (dtype == DT_BF16)
     hipLaunchKernelGGL(pool_attn_fwd_kernel<bf16>, dim3(B * H), dim3(256), smem, s, q, (const bf16*)K, (const bf16*)V,
                        (bf16*)out, probs, H, N, dh, DP);
@@ -812,10 +810,8 @@ hipError_t pool_attn_bwd(const float* q, const void* K, const void* V, int dtype
                          hipStream_t s) {
   if (B * H == 0) return hipSuccess;
   if (DP % 8 || dh % 8 || DP < 8 || DP > 2048) return hipErrorInvalidValue;
-  const int CPR = DP / 8;
-  const size_t need = (size_t)N * CPR > (size_t)256 * 8 ? (size_t)N * CPR : (size_t)256 * 8;
-  const size_t smem = (need + 2 * (size_t)N + 8) * sizeof(float);
-  if (smem > 64 * 1024) return hipErrorInvalidValue;
+  if (N < 0 || N > pool_attn_max_tokens(DP, 1)) return hipErrorInvalidValue;   // the default LDS window (kernels.h)
+  const size_t smem = pool_attn_lds_floats(N, DP, 1) * sizeof(float);
   if (dtype == DT_BF16)
     hipLaunchKernelGGL(pool_attn_bwd_kernel<bf16>, dim3(B * H), dim3(256), smem, s, q, (const bf16*)K, (const bf16*)V,
                        probs, dout, (bf16*)dkv, dq_partial, H, N, dh, DP);

@@ -520,13 +520,16 @@ bool shape_ok(const sgl_ctx* c, int B, int H, int W) {
   if (H < c->P || W < c->P) return false;  // 'valid' conv: trailing pixels beyond gh*P are ignored
   const long N = (long)(H / c->P) * (W / c->P);
   if ((long)B * N > (1l << 24)) return false;
+  if (c->cfg.use_head && N > pool_attn_max_tokens(c->DP, 0)) return false;   // the pooling head's LDS window (kernels.h)
   return true;
 }
 
-// shape_ok plus, on a recompute context, the training token limit
+// shape_ok plus the pooling head's (smaller) backward token limit and, on a recompute context, the training token limit
 bool train_shape_ok(const sgl_ctx* c, int B, int H, int W) {
   if (!shape_ok(c, B, H, W)) return false;
-  return !c->recompute || (long)B * (H / c->P) * (W / c->P) <= rc_max_tokens(c);
+  const long N = (long)(H / c->P) * (W / c->P);
+  if (c->cfg.use_head && N > pool_attn_max_tokens(c->DP, 1)) return false;
+  return !c->recompute || (long)B * N <= rc_max_tokens(c);
 }
 
 // The prologue of every encoder call, after the entry point's own pointer checks (ctx among them) and before anything is
@@ -1379,6 +1382,143 @@ int sgl_op_col2im(const float* d_cols, int B, int H, int W, int P, int Kp, float
 
 int sgl_op_pos_resize(const float* table, int native_grid, float* out, int gh, int gw, int D, sgl_stream stream) {
   CKV(pos_resize(table, native_grid, out, gh, gw, D, (hipStream_t)stream));
+  return SGL_OK;
+}
+
+// -------------------------------------------------------------------------------------------------------
+// the kernels only the encoder calls, one thin entry point each (tests and bindings)
+// -------------------------------------------------------------------------------------------------------
+static bool lo_dtype_ok(int dt) { return dt == DT_F32 || dt == DT_BF16 || dt == DT_F16; }
+static bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+
+int sgl_op_pool_attn_fwd(int dtype, const float* q, const void* K, const void* V, void* out, float* probs, int B, int H,
+                         int N, int head_dim, int head_dim_pad, sgl_stream stream) {
+  if (!q || !K || !V || !out || !probs) return SGL_ERR_NULL;
+  if (B <= 0 || H <= 0 || N <= 0 || head_dim <= 0 || head_dim % 8 || head_dim_pad % 8 || head_dim > head_dim_pad)
+    return SGL_ERR_BAD_SHAPE;
+  if (!lo_dtype_ok(dtype) || !aligned16(K) || !aligned16(V)) return SGL_ERR_UNSUPPORTED;
+  CKV(pool_attn_fwd(q, K, V, dtype, out, probs, B, H, N, head_dim, head_dim_pad, (hipStream_t)stream));
+  return SGL_OK;
+}
+
+int sgl_op_pool_attn_bwd(int dtype, const float* q, const void* K, const void* V, const float* probs, const float* dout,
+                         void* dkv, float* dq_partial, int B, int H, int N, int head_dim, int head_dim_pad,
+                         sgl_stream stream) {
+  if (!q || !K || !V || !probs || !dout || !dkv || !dq_partial) return SGL_ERR_NULL;
+  if (B <= 0 || H <= 0 || N <= 0 || head_dim <= 0 || head_dim % 8 || head_dim_pad % 8 || head_dim > head_dim_pad)
+    return SGL_ERR_BAD_SHAPE;
+  if (!lo_dtype_ok(dtype) || !aligned16(K) || !aligned16(V) || !aligned16(dkv)) return SGL_ERR_UNSUPPORTED;
+  CKV(pool_attn_bwd(q, K, V, dtype, probs, dout, dkv, dq_partial, B, H, N, head_dim, head_dim_pad, (hipStream_t)stream));
+  return SGL_OK;
+}
+
+int sgl_op_pos_resize_bwd(const float* dout, int gh, int gw, float* dtable, int native_grid, int D, sgl_stream stream) {
+  if (!dout || !dtable) return SGL_ERR_NULL;
+  if (gh <= 0 || gw <= 0 || native_grid <= 0 || D <= 0) return SGL_ERR_BAD_SHAPE;
+  CKV(pos_resize_bwd(dout, gh, gw, dtable, native_grid, D, (hipStream_t)stream));
+  return SGL_OK;
+}
+
+int sgl_op_cast_pad(const float* src, int R, int C, int lds, void* dst, int dst_dtype, int Rp, int Cp, int ldd,
+                    sgl_stream stream) {
+  if (!src || !dst) return SGL_ERR_NULL;
+  if (R < 0 || C < 0 || Rp < R || Cp < C || lds < C || ldd < Cp) return SGL_ERR_BAD_SHAPE;
+  if (!lo_dtype_ok(dst_dtype)) return SGL_ERR_UNSUPPORTED;
+  CKV(cast_pad(src, R, C, lds, dst, dst_dtype, Rp, Cp, ldd, (hipStream_t)stream));
+  return SGL_OK;
+}
+
+int sgl_op_cast_job(const sgl_cast_mat* mats, int nmat, const sgl_cast_vec* vecs, int nvec, int dst_dtype,
+                    sgl_stream stream) {
+  if ((nmat > 0 && !mats) || (nvec > 0 && !vecs)) return SGL_ERR_NULL;
+  if (nmat < 0 || nmat > 6 || nvec < 0 || nvec > 4) return SGL_ERR_BAD_SHAPE;
+  for (int k = 0; k < nmat; ++k)
+    if (!mats[k].src || (!mats[k].dst && !mats[k].dst_t)) return SGL_ERR_NULL;
+  for (int k = 0; k < nvec; ++k)
+    if (!vecs[k].src || !vecs[k].dst) return SGL_ERR_NULL;
+  for (int k = 0; k < nmat; ++k) {
+    const sgl_cast_mat& m = mats[k];
+    if (m.R <= 0 || m.C <= 0 || m.Rp < m.R || m.Cp < m.C || m.lds < m.C || (m.dst && m.ldd < m.Cp) ||
+        (m.dst_t && m.ldt < m.Rp))
+      return SGL_ERR_BAD_SHAPE;
+  }
+  for (int k = 0; k < nvec; ++k)
+    if (vecs[k].n < 0 || vecs[k].np < vecs[k].n) return SGL_ERR_BAD_SHAPE;
+  if (!lo_dtype_ok(dst_dtype)) return SGL_ERR_UNSUPPORTED;
+  CastJob job;
+  for (int k = 0; k < nmat; ++k) {
+    const sgl_cast_mat& m = mats[k];
+    cast_job_add(job, m.src, m.R, m.C, m.lds, m.dst, m.Rp, m.Cp, m.ldd, m.dst_t, m.ldt);
+  }
+  for (int k = 0; k < nvec; ++k) cast_job_add_vec(job, vecs[k].src, vecs[k].n, vecs[k].dst, vecs[k].np);
+  CKV(cast_job_run(job, dst_dtype, (hipStream_t)stream));
+  return SGL_OK;
+}
+
+int sgl_op_split3(const float* src, int R, int C, int ld, void* dst, int Cs, int b_side, int stacked, sgl_stream stream) {
+  if (!src || !dst) return SGL_ERR_NULL;
+  if (R <= 0 || C <= 0 || ld < C || Cs != round_up(C, 8)) return SGL_ERR_BAD_SHAPE;
+  if (!aligned16(dst)) return SGL_ERR_UNSUPPORTED;   // 16-byte stores of eight bf16
+  if (stacked)
+    CKV(split3_stack(src, R, C, ld, dst, Cs, b_side ? 1 : 0, (hipStream_t)stream));
+  else
+    CKV(split3_rows(src, R, C, ld, dst, Cs, b_side ? 1 : 0, (hipStream_t)stream));
+  return SGL_OK;
+}
+
+int sgl_op_batch_sum(const float* in, int B, size_t n, float* out, int accumulate, sgl_stream stream) {
+  if (!in || !out) return SGL_ERR_NULL;
+  if (B <= 0 || n >= ((size_t)1 << 31) * 256) return SGL_ERR_BAD_SHAPE;   // one thread per element, grid.x < 2^31
+  CKV(batch_sum(in, B, n, out, accumulate, (hipStream_t)stream));
+  return SGL_OK;
+}
+
+int sgl_op_vecmat(const float* v, const float* W, int rows, int cols, float* scratch, size_t scratch_bytes, float* out,
+                  int accumulate, sgl_stream stream) {
+  if (!v || !W || !scratch || !out) return SGL_ERR_NULL;
+  if (rows <= 0 || cols <= 0) return SGL_ERR_BAD_SHAPE;
+  if (scratch_bytes < (size_t)16 * cols * 4) return SGL_ERR_WORKSPACE;
+  CKV(vecmat_f32(v, W, rows, cols, scratch, out, accumulate, (hipStream_t)stream));
+  return SGL_OK;
+}
+
+int sgl_op_reduce_partials(const float* partial, int nblk, int stride, float* out, int n, int accumulate,
+                           sgl_stream stream) {
+  if (!partial || !out) return SGL_ERR_NULL;
+  if (nblk <= 0 || n <= 0 || stride < n) return SGL_ERR_BAD_SHAPE;
+  CKV(reduce_partials(partial, nblk, stride, out, n, accumulate, (hipStream_t)stream));
+  return SGL_OK;
+}
+
+int sgl_op_reduce_partials3(const float* partial, int nblk, int stride, float* out0, float* out1, float* out2, int n,
+                            int accumulate0, int accumulate1, int accumulate2, sgl_stream stream) {
+  if (!partial) return SGL_ERR_NULL;
+  if (nblk <= 0 || n <= 0 || stride < 3 * (long)n) return SGL_ERR_BAD_SHAPE;
+  CKV(reduce_partials3(partial, nblk, stride, out0, out1, out2, n, accumulate0, accumulate1, accumulate2,
+                       (hipStream_t)stream));
+  return SGL_OK;
+}
+
+int sgl_op_reduce_splits(const float* ws, int splits, size_t stride, int N1, int N2, float* out, int ldo, int accumulate,
+                         sgl_stream stream) {
+  if (!ws || !out) return SGL_ERR_NULL;
+  if (splits <= 0 || N1 <= 0 || N2 <= 0 || ldo < N2 || (splits > 1 && stride < (size_t)N1 * N2)) return SGL_ERR_BAD_SHAPE;
+  CKV(reduce_splits(ws, splits, stride, N1, N2, out, ldo, accumulate, (hipStream_t)stream));
+  return SGL_OK;
+}
+
+int sgl_op_add_f32(const float* a, const float* b, float* out, size_t n, sgl_stream stream) {
+  if (!a || !out) return SGL_ERR_NULL;
+  // copy_f32_kernel moves float4s without looking at the pointers
+  if (!aligned16(a) || !aligned16(out) || (b && !aligned16(b))) return SGL_ERR_UNSUPPORTED;
+  CKV(add_f32(a, b, out, n, (hipStream_t)stream));
+  return SGL_OK;
+}
+
+int sgl_op_cast_f32(const float* src, void* dst, int dst_dtype, size_t n, sgl_stream stream) {
+  if (!src || !dst) return SGL_ERR_NULL;
+  if (!lo_dtype_ok(dst_dtype)) return SGL_ERR_UNSUPPORTED;
+  CKV(cast_f32(src, dst, dst_dtype, n, (hipStream_t)stream));
   return SGL_OK;
 }
 

@@ -137,6 +137,22 @@ hipError_t copy_f32(const float* src, float* dst, size_t n, hipStream_t s);
 hipError_t cast_f32(const float* src, void* dst, int dst_dtype, size_t n, hipStream_t s);
 hipError_t add_f32(const float* a, const float* b, float* out, size_t n, hipStream_t s);  // b may be null
 // attention-pool (1 query per image): q [H*dh] fp32, K/V head-major [B][H][N][DP]
+// One workgroup per (image, head) keeps, in the default 64 KiB LDS window, one fp32 partial per 8-column chunk of every
+// token (the region is reused for the output fold, hence its floor of 256 * 8 floats), the N probabilities (backward: the
+// N score gradients as well) and 8 floats of reduction scratch.  pool_attn_lds_floats is that size;
+// pool_attn_max_tokens the largest N for which it fits: floor(16376 / (DP / 8 + 1)) forward, floor(16376 / (DP / 8 + 2))
+// backward (DP 80: 1488 / 1364; DP 64: 1819 / 1637).  The launchers refuse more with hipErrorInvalidValue, and
+// encoder.hip's shape checks refuse it first (SGL_ERR_BAD_SHAPE).
+static inline size_t pool_attn_lds_floats(int N, int DP, int backward) {
+  const size_t part = (size_t)N * (DP / 8) > (size_t)256 * 8 ? (size_t)N * (DP / 8) : (size_t)256 * 8;
+  return part + (backward ? 2 : 1) * (size_t)N + 8;
+}
+static inline int pool_attn_max_tokens(int DP, int backward) {
+  // 16384 floats less the 8 of scratch, over the floats one token takes.  The 2048-float floor never decides: at this n
+  // the partials alone are n * c >= 16376 * c / (c + 2) - c floats, which is 5457 at c = DP / 8 = 1 and stays above 2048
+  // up to c = 14000 (a head dimension of 112000).
+  return (int)((64 * 1024 / sizeof(float) - 8) / (size_t)(DP / 8 + (backward ? 2 : 1)));
+}
 hipError_t pool_attn_fwd(const float* q, const void* K, const void* V, int dtype, void* out /*[B][H*dh]*/,
                          float* probs /*[B][H][N]*/, int B, int H, int N, int dh, int DP, hipStream_t s);
 hipError_t pool_attn_bwd(const float* q, const void* K, const void* V, int dtype, const float* probs,

@@ -59,6 +59,15 @@ class SglAdamwAux(C.Structure):
                 ("reserved", C.c_int)]
 
 
+class SglCastMat(C.Structure):
+    _fields_ = [("src", _fp), ("dst", _fp), ("dst_t", _fp)] + [(n, C.c_int) for n in ("R", "C", "lds", "Rp", "Cp", "ldd",
+                                                                                    "ldt")]
+
+
+class SglCastVec(C.Structure):
+    _fields_ = [("src", _fp), ("dst", _fp), ("n", C.c_int), ("np", C.c_int)]
+
+
 _lib = None
 
 
@@ -137,6 +146,19 @@ def load():
     _sig(lib, "sgl_op_im2col", i, [_fp, i, _fp, i, i, i, i, i, i, _fp])
     _sig(lib, "sgl_op_col2im", i, [_fp, i, i, i, i, i, _fp, i, _fp])
     _sig(lib, "sgl_op_pos_resize", i, [_fp, i, _fp, i, i, i, _fp])
+    _sig(lib, "sgl_op_pool_attn_fwd", i, [i, _fp, _fp, _fp, _fp, _fp, i, i, i, i, i, _fp])
+    _sig(lib, "sgl_op_pool_attn_bwd", i, [i, _fp, _fp, _fp, _fp, _fp, _fp, _fp, i, i, i, i, i, _fp])
+    _sig(lib, "sgl_op_pos_resize_bwd", i, [_fp, i, i, _fp, i, i, _fp])
+    _sig(lib, "sgl_op_cast_pad", i, [_fp, i, i, i, _fp, i, i, i, i, _fp])
+    _sig(lib, "sgl_op_cast_job", i, [C.POINTER(SglCastMat), i, C.POINTER(SglCastVec), i, i, _fp])
+    _sig(lib, "sgl_op_split3", i, [_fp, i, i, i, _fp, i, i, i, _fp])
+    _sig(lib, "sgl_op_batch_sum", i, [_fp, i, sz, _fp, i, _fp])
+    _sig(lib, "sgl_op_vecmat", i, [_fp, _fp, i, i, _fp, sz, _fp, i, _fp])
+    _sig(lib, "sgl_op_reduce_partials", i, [_fp, i, i, _fp, i, i, _fp])
+    _sig(lib, "sgl_op_reduce_partials3", i, [_fp, i, i, _fp, _fp, _fp, i, i, i, i, _fp])
+    _sig(lib, "sgl_op_reduce_splits", i, [_fp, i, sz, i, i, _fp, i, i, _fp])
+    _sig(lib, "sgl_op_add_f32", i, [_fp, _fp, _fp, sz, _fp])
+    _sig(lib, "sgl_op_cast_f32", i, [_fp, _fp, i, sz, _fp])
     i64 = C.c_int64
     _sig(lib, "sgl_adamw_plan", i64, [C.POINTER(C.c_uint64), i, C.POINTER(C.c_int32), i64])
     _sig(lib, "sgl_op_grad_norm", i, [_fp, _fp, i64, f, _fp, _fp, _fp])

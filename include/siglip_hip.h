@@ -38,7 +38,14 @@ typedef enum {
   SGL_OK = 0,
   SGL_ERR_BAD_SHAPE = -1,   /* B <= 0, image smaller than one patch, too many tokens, a non-native grid without
                                interpolate_pos, hs_slots / layer out of range.  Rectangular grids (H / p, W / p) and
-                               trailing pixels beyond the last whole patch are supported */
+                               trailing pixels beyond the last whole patch are supported.
+                               With use_head = 1 the pooling head limits the tokens of ONE image, N = (H / p) * (W / p),
+                               with c = round_up(head_dim, 16) / 8: N <= floor(16376 / (c + 1)) for inference and
+                               N <= floor(16376 / (c + 2)) for training (sgl_query_sizes(train = 1), a forward given
+                               `saved`, every sgl_backward_*).  so400m (head_dim 72): 1488 / 1364 tokens, so the
+                               largest square images are 532 px (inference) and 504 px (training), 546 / 518 px are
+                               refused; base (head_dim 64): 1819 / 1637 tokens, 672 / 640 px pass, 688 / 656 px are
+                               refused.  A context with use_head = 0 has no such limit */
   SGL_ERR_UNSUPPORTED = -2, /* dtype / config outside what the kernels implement */
   SGL_ERR_WORKSPACE = -3,   /* saved / workspace / shadow buffer smaller than sgl_query_sizes reports */
   SGL_ERR_HIP = -4,         /* a HIP call failed: see sgl_last_hip_error */
@@ -313,6 +320,71 @@ int sgl_op_im2col(const float* pixels, int channels_last, void* out, int out_dty
 int sgl_op_col2im(const float* d_cols, int B, int H, int W, int P, int Kp, float* d_pixels, int channels_last,
                   sgl_stream stream);
 int sgl_op_pos_resize(const float* table, int native_grid, float* out, int gh, int gw, int D, sgl_stream stream);
+
+/* ---- the kernels only the encoder calls (new symbols; sgl_abi_version() stays 3: nothing existing changed) -----------
+ * These exist for tests and bindings: each is one launcher of csrc/kernels.h behind the argument checks below.  A NULL
+ * required pointer is SGL_ERR_NULL (checked first), a non-positive or inconsistent dimension SGL_ERR_BAD_SHAPE, an
+ * unknown dtype code, a pointer a vector access needs aligned and is not, or a launcher's own refusal
+ * SGL_ERR_UNSUPPORTED; nothing is enqueued on a refusal.  dtype codes: SGL_DTYPE_F32 / BF16 / F16.
+ *
+ * Pooling-head attention, one query per head: q fp32 [H * head_dim] (shared by all images); K, V head-major
+ * [B][H][N][head_dim_pad] of `dtype` with ZERO pad columns, 16-byte aligned; out [B][H * head_dim] of `dtype`; probs
+ * fp32 [B][H][N].  head_dim % 8 == 0, head_dim_pad % 8 == 0.  One workgroup per (image, head) holds its partials in the
+ * default 64 KiB LDS window: N <= floor(16376 / (head_dim_pad / 8 + 1)) forward and floor(16376 / (head_dim_pad / 8 + 2))
+ * backward (head_dim_pad 80: 1488 / 1364; 64: 1819 / 1637), SGL_ERR_UNSUPPORTED above. */
+int sgl_op_pool_attn_fwd(int dtype, const float* q, const void* K, const void* V, void* out, float* probs, int B, int H,
+                         int N, int head_dim, int head_dim_pad, sgl_stream stream);
+/* probs as written by the forward, dout fp32 [B][H * head_dim] -> dkv token-major [B * N][2 * H * head_dim] of `dtype`
+ * (dK block, then dV block; 16-byte aligned; every element written) and dq_partial fp32 [B][H * head_dim] (the per-image
+ * gradient of q, summed over images by the caller). */
+int sgl_op_pool_attn_bwd(int dtype, const float* q, const void* K, const void* V, const float* probs, const float* dout,
+                         void* dkv, float* dq_partial, int B, int H, int N, int head_dim, int head_dim_pad,
+                         sgl_stream stream);
+/* The transpose of sgl_op_pos_resize: dtable [native_grid^2][D] += R^T dout, dout [gh * gw][D].  ADDS into dtable; a
+ * gather in a fixed order, bitwise reproducible. */
+int sgl_op_pos_resize_bwd(const float* dout, int gh, int gw, float* dtable, int native_grid, int D, sgl_stream stream);
+/* dst [Rp][Cp] (row stride ldd) = src [R][C] (fp32, row stride lds) rounded to nearest, zero outside R x C. */
+int sgl_op_cast_pad(const float* src, int R, int C, int lds, void* dst, int dst_dtype, int Rp, int Cp, int ldd,
+                    sgl_stream stream);
+/* All weight shadows of one transformer block in one launch: up to 6 matrices (the row-major padded copy dst [Rp][Cp],
+ * row stride ldd, and / or the transposed copy dst_t [Cp][Rp], row stride ldt; either may be NULL) and up to 4 fp32
+ * vectors (dst[i] = i < n ? src[i] : 0 for i < np).  More than 6 / 4 is SGL_ERR_BAD_SHAPE. */
+typedef struct {
+  const float* src;
+  void* dst;
+  void* dst_t;
+  int R, C, lds, Rp, Cp, ldd, ldt;
+} sgl_cast_mat;
+typedef struct {
+  const float* src;
+  float* dst;
+  int n, np;
+} sgl_cast_vec;
+int sgl_op_cast_job(const sgl_cast_mat* mats, int nmat, const sgl_cast_vec* vecs, int nvec, int dst_dtype,
+                    sgl_stream stream);
+/* The operand split of SGL_DTYPE_BF16X3: hi = bf16(x), lo = bf16(x - hi), Cs = round_up(C, 8), zeros in columns C..Cs.
+ * stacked == 0: dst [R][3 * Cs] bf16, row = [hi | hi | lo] (b_side 0) or [hi | lo | hi] (b_side 1);
+ * stacked == 1: dst [3 * R][Cs] bf16, planes  hi, hi, lo  (b_side 0) or  hi, lo, hi  (b_side 1).  dst 16-byte aligned. */
+int sgl_op_split3(const float* src, int R, int C, int ld, void* dst, int Cs, int b_side, int stacked, sgl_stream stream);
+/* out[j] (+)= sum_b in[b * n + j], j < n. */
+int sgl_op_batch_sum(const float* in, int B, size_t n, float* out, int accumulate, sgl_stream stream);
+/* out[j] (+)= sum_i v[i] * W[i * cols + j]; scratch: 16 * cols floats (SGL_ERR_WORKSPACE below that). */
+int sgl_op_vecmat(const float* v, const float* W, int rows, int cols, float* scratch, size_t scratch_bytes, float* out,
+                  int accumulate, sgl_stream stream);
+/* out[j] (+)= sum_b partial[b * stride + j], j < n, in a fixed order. */
+int sgl_op_reduce_partials(const float* partial, int nblk, int stride, float* out, int n, int accumulate,
+                           sgl_stream stream);
+/* out_k[j] (+)= sum_b partial[b * stride + k * n + j] for k = 0, 1, 2 in one launch; a NULL output is skipped. */
+int sgl_op_reduce_partials3(const float* partial, int nblk, int stride, float* out0, float* out1, float* out2, int n,
+                            int accumulate0, int accumulate1, int accumulate2, sgl_stream stream);
+/* out[r * ldo + c] (+)= sum_s ws[s * stride + r * N2 + c] in a fixed order.  N2, ldo and stride multiples of 4, out and ws
+ * 16-byte aligned: SGL_ERR_UNSUPPORTED otherwise. */
+int sgl_op_reduce_splits(const float* ws, int splits, size_t stride, int N1, int N2, float* out, int ldo, int accumulate,
+                         sgl_stream stream);
+/* out[i] = a[i] + b[i] (b NULL: a copy), i < n; a, b and out 16-byte aligned (SGL_ERR_UNSUPPORTED otherwise). */
+int sgl_op_add_f32(const float* a, const float* b, float* out, size_t n, sgl_stream stream);
+/* dst[i] = src[i] rounded to nearest in dst_dtype. */
+int sgl_op_cast_f32(const float* src, void* dst, int dst_dtype, size_t n, sgl_stream stream);
 
 /* ---- SID mask-decoder tail ---------------------------------------------------------------
  * Depthwise 3x3 convolution, zero padding 1, of SegFormerStrongDecoder's per-tap smoothing block

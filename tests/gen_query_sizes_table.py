@@ -1,9 +1,12 @@
 """Dump sgl_query_sizes over a sweep of (config, mode, policy, train, shape) as JSON: the table
 tests/test_input_grad_host.py holds the library to (tests/golden/pixgrad/query_sizes_parent.json).
 
-The committed table was written by the library built from the commit BEFORE the input-gradient entry points were added
-(they take a scratch argument of their own so that nothing here moves).  To regenerate it, build that commit's library
-and point SGL_LIB_PATH at it:
+The table was first written by the library built from the commit BEFORE the input-gradient entry points were added
+(they take a scratch argument of their own so that nothing here moves).  It was written again when sgl_query_sizes
+learnt the pooling head's token limit (csrc/kernels.h, pool_attn_max_tokens): 317 of the 2166 entries, every shape with
+more tokens per image than the head takes (so400m at 384 x 1152 and 771 x 398, large at 384 x 1152 for training), went
+from sizes for a call that would have failed to [-1, 0, 0, 0]; no other entry moved.  To regenerate it from an earlier
+commit, build that commit's library and point SGL_LIB_PATH at it:
 
     SGL_LIB_PATH=<parent checkout>/…/libsiglip_hip.so python tests/gen_query_sizes_table.py
 

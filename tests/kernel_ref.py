@@ -22,6 +22,8 @@ in fp32) against float64, never from a kernel's output; tests/test_kernel_ref_ho
                 7.7e-6 for its derivative (the formula's own 1 - s cancellation, amplified by x (2z)' <= 35, x 4).
   ADAMW_C = 2   AdamW (second half of the file, the kernels outside the encoder): the derived rounding counts times 2;
                 measured worst emulation/bound with c = 1 is 0.74 (exp_avg), with c = 2 0.37.
+  POS_BWD_C = 32  pos_resize_bwd (last part of the file, the kernels only the encoder calls): per-weight absolute error of
+                the fp32 cubic polynomials in units of 2^-24; measured 11.6, times 2.76.
 """
 import math
 
@@ -1133,3 +1135,278 @@ def l2_inputs(B, T, D, seed):
         f[0] = f[0] / f[0].norm() * 1e-18
         f[-1] = f[-1] / f[-1].norm() * 1e18
     return f, torch.randn(B, D, generator=gen_)
+
+
+# ===============================================================================================================
+# kernels only the encoder calls (csrc/elementwise.hip, layernorm.hip; tests/test_kernel_edges_internal_gpu.py)
+#
+# Casts and splits are exact (bit-equal to torch's round-to-nearest).  Sums carry the fp32-accumulation bound of `sum_ref`,
+# no constant.  The pooling-head attention bounds are derived term by term below; their one measured ingredient is the
+# `__expf` term, evaluated on the test's own scores (`expf_eval_term`, the convention of `gelu_eval_term`).  One constant
+# is fitted, by the convention at the top of this file:
+#   POS_BWD_C = 32  pos_resize_bwd: the absolute error, in units of 2^-24, of one fp32 cubic weight beyond the share of the
+#                 source coordinate's rounding (which is derived: resize_matrix_slack).  Measured on the axes of
+#                 POS_BWD_GRIDS as max(|R32 - R64| - coordinate slack) / 2^-24 = 11.6 (axis 2 -> 5; 17.2 over all pairs
+#                 of {2, 3, 14, 16, 24, 27, 37} x 1..39); 11.6 x 2.76 = 32.  With it the emulation's worst err/bound over
+#                 POS_BWD_GRIDS (D = 5 and 144, three seeds, zero and normal priors) is 0.16; with c = 0 it is 1.85.
+# ===============================================================================================================
+POS_BWD_C = 32.0
+
+
+def sum_ref(terms, prior=None, n=None):
+    """ref = terms.sum(0) (+ prior) in float64; bound n u / (1 - n u) sum|terms| with n the number of addends (the prior
+    of an accumulating kernel is one more): any order of n - 1 fp32 additions, and one more rounding for a product that
+    was rounded before it was added (callers pass n accordingly)."""
+    t = terms.double()
+    ref, mag = t.sum(0), t.abs().sum(0)
+    cnt = t.shape[0] if n is None else n
+    if prior is not None:
+        ref, mag, cnt = ref + prior.double(), mag + prior.double().abs(), cnt + 1
+    g = cnt * EPS32 / (1 - cnt * EPS32)
+    return ref, g * mag
+
+
+def vecmat_ref(v, W, prior=None):
+    """out[j] = sum_i v[i] W[i, j]: `rows` products (fused or not: n = rows + 1) in any order."""
+    return sum_ref(v.double()[:, None] * W.double(), prior, n=W.shape[0] + 1)
+
+
+def split3_ref(x):
+    """hi = bf16(x), lo = bf16(x - hi): the subtraction is exact in fp32 (the rounding error of a narrower format is
+    representable), so both are torch round-to-nearest conversions."""
+    hi = x.float().to(torch.bfloat16)
+    lo = (x.float() - hi.float()).to(torch.bfloat16)
+    return hi, lo
+
+
+def split3_layout(x, Cs, b_side, stacked):
+    """The documented operand: rows [hi | hi | lo] / [hi | lo | hi] of Cs-wide segments, or the same three as planes."""
+    R, C = x.shape
+    hi, lo = (torch.zeros(R, Cs, dtype=torch.bfloat16, device=x.device) for _ in range(2))
+    hi[:, :C], lo[:, :C] = split3_ref(x)
+    seg = [hi, lo, hi] if b_side else [hi, hi, lo]
+    return torch.cat(seg, 0) if stacked else torch.cat(seg, 1)
+
+
+def split3_special_values():
+    """+-0, fp32 subnormals, bf16 rounding ties (round to even both ways), values next to ties, the largest fp32 that does
+    not round to a bf16 infinity, and its neighbours."""
+    bits = [0x00000000, 0x80000000, 0x00000001, 0x807FFFFF, 0x00400000, 0x3F808000, 0x3F818000, 0x3F808001, 0x3F807FFF,
+            0xBF818000, 0x7F7F7FFF, 0xFF7F7FFF, 0x7F7F0000, 0x7F7E8000, 0x00800000, 0x00808000, 0x3EAAAAAB, 0x4B7FFFFF]
+    return torch.tensor(bits, dtype=torch.int64).to(torch.int32).view(torch.float32)
+
+
+# ---- position-table resize, backward ---------------------------------------------------------------------------
+def _cubic_w(t):
+    A = -0.75
+    x0, x1, x2, x3 = t + 1.0, t, 1.0 - t, 2.0 - t
+    return torch.stack([((A * x0 - 5 * A) * x0 + 8 * A) * x0 - 4 * A, ((A + 2) * x1 - (A + 3)) * x1 * x1 + 1,
+                        ((A + 2) * x2 - (A + 3)) * x2 * x2 + 1, ((A * x3 - 5 * A) * x3 + 8 * A) * x3 - 4 * A], -1)
+
+
+def resize_matrix(n_in, n_out, dtype=torch.float64, shift=None, mask=False):
+    """Dense [n_out, n_in] matrix of the one-axis bicubic resize (A = -0.75, align_corners=False, clamped taps) in
+    `dtype`; in float32 every step is the kernel's (cubic_taps of csrc/elementwise.hip), clamped taps that meet on one
+    border entry being added in tap order.  `shift` [n_out] moves the source coordinates (see resize_matrix_slack);
+    mask=True returns which entries are taps instead."""
+    o = torch.arange(n_out, dtype=dtype)
+    scale = (torch.tensor(float(n_in), dtype=dtype) / torch.tensor(float(n_out), dtype=dtype))
+    src = scale * (o + 0.5) - 0.5
+    if shift is not None:
+        src = src + shift
+    fl = torch.floor(src)
+    w = _cubic_w(src - fl)
+    M = torch.zeros(n_out, n_in, dtype=dtype)
+    for k in range(4):
+        idx = (fl.long() - 1 + k).clamp(0, n_in - 1)
+        M[torch.arange(n_out), idx] += 1.0 if mask else w[:, k]
+    return M != 0 if mask else M
+
+
+def resize_matrix_slack(n_in, n_out, c):
+    """How far an entry of the fp32 resize matrix can be from the float64 one, entry by entry.
+    Coordinate: scale = n_in / n_out, scale * (o + 0.5) and the - 0.5 are one rounding each of a number no larger than
+    |src| + 0.5, so the coordinate is off by at most delta = 4 2^-24 (|src| + 1).  The matrix is a continuous function of
+    the coordinate (the cubic convolution kernel is C1 and the clamp merges taps continuously), so over +-delta an entry
+    moves by at most the larger of its two end-point changes (delta is 1e-5 at the most: an entry is monotone over it
+    except within delta^2 of an extremum).  At g0 = 27 this reaches 120 2^-24 (a weight of 0.2 at coordinate 23.8 is off
+    by 22 2^-24), and an integer coordinate (scale 5.4 at o = 2 gives 13.0) gets taps the float64 matrix does not have.
+    Polynomials: Horner steps on coefficients up to 8 |A| = 6 leave an ABSOLUTE error of a few 2^-24 whatever the weight
+    (5.2 2^-24 on the weight -0.024 of 27 -> 5): c 2^-24 on every tap, c = POS_BWD_C from the emulation."""
+    o = torch.arange(n_out, dtype=torch.float64)
+    src = (n_in / n_out) * (o + 0.5) - 0.5
+    delta = 4 * EPS32 * (src.abs() + 1)
+    R = resize_matrix(n_in, n_out)
+    Rp, Rm = resize_matrix(n_in, n_out, shift=delta), resize_matrix(n_in, n_out, shift=-delta)
+    taps = (resize_matrix(n_in, n_out, mask=True) | resize_matrix(n_in, n_out, shift=delta, mask=True)
+            | resize_matrix(n_in, n_out, shift=-delta, mask=True))
+    return torch.maximum((Rp - R).abs(), (Rm - R).abs()) + c * EPS32 * taps.double()
+
+
+def pos_resize_bwd_ref(dout, g0, gh, gw, prior, c=POS_BWD_C):
+    """dtable = prior + R^T dout with R = Ry (x) Rx dense in float64.  Bound per table element:
+      terms 2^-24 (|Ry|^T |dout| |Rx| + |prior|)  +  ((|Ry| + Ey)^T |dout| (|Rx| + Ex) - |Ry|^T |dout| |Rx|)
+    terms = one product and one addition for each output that touches the element (2 n_y n_x), the n_y row products and
+    additions, the add into the table.  E = resize_matrix_slack(c): the fp32 evaluation of the weights, whose error is
+    absolute in the weight (coordinate error times slope, polynomial cancellation), not relative to it.  The plain form
+    (terms + c) 2^-24 sum|w||dout| does not describe that: the emulation would need c = 212 at grid (27, 1, 5), where
+    weights of 0.02 to 0.2 carry 5 to 22 2^-24 each, and c would grow with g0 (tests/test_kernel_ref_host.py asserts it).
+    Where the weights are of order 1 the two forms agree."""
+    D = dout.shape[-1]
+    Ry, Rx = resize_matrix(g0, gh), resize_matrix(g0, gw)
+    G = dout.double().view(gh, gw, D)
+    ref = torch.einsum("ya,yxd,xb->abd", Ry, G, Rx) + prior.double().view(g0, g0, D)
+    mag = torch.einsum("ya,yxd,xb->abd", Ry.abs(), G.abs(), Rx.abs())
+    Ey, Ex = resize_matrix_slack(g0, gh, c), resize_matrix_slack(g0, gw, c)
+    weights = (torch.einsum("ya,yxd,xb->abd", Ry.abs() + Ey, G.abs(), Rx.abs() + Ex) - mag).clamp_min(0)
+    ny, nx = (Ey != 0).sum(0).double(), (Ex != 0).sum(0).double()
+    terms = (2 * ny[:, None] * nx[None, :] + 2 * ny[:, None] + 1)[:, :, None]
+    bound = terms * EPS32 * (mag + prior.double().abs().view(g0, g0, D)) + weights
+    return ref.reshape(g0 * g0, D), bound.reshape(g0 * g0, D)
+
+
+def pos_resize_weight_excess(n_in, n_out):
+    """max over entries of (|R32 - R64| - coordinate slack) / 2^-24: what POS_BWD_C has to cover (one axis)."""
+    d = (resize_matrix(n_in, n_out, torch.float32).double() - resize_matrix(n_in, n_out)).abs()
+    return ((d - resize_matrix_slack(n_in, n_out, 0.0)) / EPS32).max().item()
+
+
+def pos_resize_bwd_emulate(dout, g0, gh, gw, prior):
+    """pos_resize_bwd_kernel in torch fp32: fp32 weights, per table element the (oy, ox) order of the kernel, products and
+    additions rounded separately (the kernel may fuse them: one rounding fewer)."""
+    D = dout.shape[-1]
+    Ry, Rx = resize_matrix(g0, gh, torch.float32), resize_matrix(g0, gw, torch.float32)
+    G = dout.float().view(gh, gw, D)
+    acc = torch.zeros(g0, g0, D)
+    for oy in range(gh):
+        row = torch.zeros(g0, D)
+        for ox in range(gw):
+            row = row + Rx[ox][:, None] * G[oy, ox][None, :]
+        acc = acc + Ry[oy][:, None, None] * row[None]
+    return (prior.float().view(g0, g0, D) + acc).view(g0 * g0, D)
+
+
+POS_BWD_GRIDS = [(2, 3, 7), (3, 7, 3), (14, 16, 27), (27, 1, 5), (27, 16, 27), (14, 27, 16),   # test_posresize_rect's
+                 (3, 3, 3), (2, 37, 5), (27, 1, 1)]                                           # identity, steep up, steep down
+
+
+# ---- pooling-head attention (one query per head) ----------------------------------------------------------------
+def pool_inputs(kind, B, H, N, dh, DP, tdt, seed=0):
+    """q [H * dh] fp32 (a different query per head), K, V [B, H, N, DP] of `tdt` with zero pad columns, dout [B, H * dh].
+    gauss: unit normals.  big: scores of magnitude about 60 and one dominant key per (image, head) at about +90 (the max
+    subtraction).  equal: every key of a head the same vector (all-equal scores)."""
+    g = torch.Generator().manual_seed(seed * 7919 + N * 31 + dh)
+    rn = lambda *s: torch.randn(*s, generator=g)
+    q = rn(H, dh)
+    K, V = torch.zeros(B, H, N, DP), torch.zeros(B, H, N, DP)
+    K[..., :dh], V[..., :dh] = rn(B, H, N, dh), rn(B, H, N, dh)
+    if kind == "big":
+        K[..., :dh] *= 20.0
+        qn = q / (q * q).sum(-1, keepdim=True)
+        for b in range(B):
+            for h in range(H):
+                K[b, h, (7 * b + 3 * h + N // 2) % N, :dh] = qn[h] * (90.0 * math.sqrt(dh))
+    elif kind == "equal":
+        K[..., :dh] = K[:, :, :1, :dh]
+    else:
+        assert kind == "gauss"
+    return q.reshape(-1).contiguous(), K.to(tdt), V.to(tdt), rn(B, H * dh)
+
+
+def expf_eval_term(x64):
+    """4 x the largest relative deviation of the kernel's `__expf(x)` = exp2(x log2 e), evaluated in fp32 at the fp32
+    rounding of the float64 arguments `x64` (so the rounding of the max subtraction is counted), from float64 exp, over
+    the arguments above -80 (below, the result is under 2^-115 and the absolute floor of pool_attn_fwd_ref takes over).
+    The hardware exp2 may be an ulp or two worse than libm: hence the 4."""
+    x = x64.flatten()
+    x = x[x > -80.0]
+    if x.numel() == 0:
+        return 4 * EPS32
+    e32 = torch.exp2(x.float() * torch.tensor(LOG2E, dtype=torch.float32)).double()
+    e64 = torch.exp(x)
+    return max(4.0 * ((e32 - e64).abs() / e64).max().item(), 4 * EPS32)
+
+
+POOL_FLOOR = 2.0 ** -120         # absolute floor of a probability (fp32 results below 2^-126 may be flushed)
+
+
+def pool_attn_fwd_ref(q, K, V, H, dh, out_dt):
+    """float64 softmax attention, one query per head: (probs [B, H, N], bound), (out [B, H * dh], bound).
+    scores: a dh-term fp32 dot and the scale: eS_n = (dh + 2) 2^-24 scale sum|q||k_n|.  A score error moves every
+    probability of the row by at most e^(2 max eS) - 1 relative.  Then `__expf` (expf_eval_term on these scores), the
+    N-term sum of positive terms (N 2^-24 relative in any order), 1 / sum and the product (4 roundings):
+      bound(p) = p (2 max_n eS_n + E_exp + (N + 4) 2^-24) + 2^-120.
+    out_d = sum_n p_n V_nd with the kernel's own p: sum_n bound(p_n) |V_nd| + (N + 2) 2^-24 sum p |V| + u_out |out| + tiny."""
+    B, _, N, DP = K.shape
+    q64, K64, V64 = q.double().view(H, dh), K.double()[..., :dh], V.double()[..., :dh]
+    scale = dh ** -0.5
+    S = torch.einsum("hd,bhnd->bhn", q64, K64) * scale
+    eS = (dh + 2) * EPS32 * scale * torch.einsum("hd,bhnd->bhn", q64.abs(), K64.abs())
+    x = S - S.max(-1, keepdim=True).values
+    Pr = torch.softmax(S, -1)
+    rel = 2 * eS.max(-1, keepdim=True).values + expf_eval_term(x) + (N + 4) * EPS32
+    bP = Pr * rel + POOL_FLOOR
+    out = torch.einsum("bhn,bhnd->bhd", Pr, V64)
+    bout = (torch.einsum("bhn,bhnd->bhd", bP, V64.abs()) + (N + 2) * EPS32 * torch.einsum("bhn,bhnd->bhd", Pr, V64.abs())
+            + UNIT[out_dt] * out.abs() + TINY[out_dt])
+    return (Pr, bP), (out.reshape(B, H * dh), bout.reshape(B, H * dh))
+
+
+def pool_attn_bwd_ref(q, K, V, probs, dout, H, dh, out_dt):
+    """float64 backward from the fp32 probabilities the kernel is given: (dkv [B * N, 2 H dh], bound), (dq [B, H dh], bound).
+      dp_n = do . V_n                 e_dp_n = (dh + 1) 2^-24 sum|do||V_n|
+      dot  = sum_n p_n dp_n           e_dot  = sum p_n e_dp_n + (N + 2) 2^-24 sum p_n |dp_n|
+      ds_n = p_n (dp_n - dot) scale   e_ds_n = scale p_n (e_dp_n + e_dot + 3 2^-24 (|dp_n| + |dot|))
+      dK_nd = ds_n q_d                e_ds_n |q_d| + (2^-24 + u_out) |dK| + tiny
+      dV_nd = p_n do_d                (2^-24 + u_out) |dV| + tiny
+      dq_d  = sum_n ds_n K_nd         sum_n e_ds_n |K_nd| + (N + 3) 2^-24 sum_n |ds_n K_nd|
+    Each also carries the absolute floor 2^-120 times (1 + the magnitude of its other factor): a probability in fp32's
+    subnormal range (the `big` family has them) has no relative precision, and the hardware may flush it."""
+    B, _, N, DP = K.shape
+    q64, K64, V64 = q.double().view(H, dh), K.double()[..., :dh], V.double()[..., :dh]
+    P64, dO = probs.double().view(B, H, N), dout.double().view(B, H, dh)
+    scale = dh ** -0.5
+    dp = torch.einsum("bhd,bhnd->bhn", dO, V64)
+    e_dp = (dh + 1) * EPS32 * torch.einsum("bhd,bhnd->bhn", dO.abs(), V64.abs())
+    dot = (P64 * dp).sum(-1, keepdim=True)
+    e_dot = (P64 * e_dp).sum(-1, keepdim=True) + (N + 2) * EPS32 * (P64 * dp.abs()).sum(-1, keepdim=True)
+    ds = P64 * (dp - dot) * scale
+    e_ds = scale * P64 * (e_dp + e_dot + 3 * EPS32 * (dp.abs() + dot.abs()))
+    u, tiny = UNIT[out_dt], TINY[out_dt]
+    dK = ds[..., None] * q64[None, :, None, :]
+    bK = e_ds[..., None] * q64.abs()[None, :, None, :] + (EPS32 + u) * dK.abs() + tiny + POOL_FLOOR * (1 + q64.abs()[None, :, None, :])
+    dV = P64[..., None] * dO[:, :, None, :]
+    bV = (EPS32 + u) * dV.abs() + tiny + POOL_FLOOR * (1 + dO.abs()[:, :, None, :])
+    tok = lambda t: t.permute(0, 2, 1, 3).reshape(B * N, H * dh)          # [B, H, N, dh] -> token-major [B N, H dh]
+    dkv, bkv = torch.cat([tok(dK), tok(dV)], 1), torch.cat([tok(bK), tok(bV)], 1)
+    dq = torch.einsum("bhn,bhnd->bhd", ds, K64)
+    bq = (torch.einsum("bhn,bhnd->bhd", e_ds, K64.abs())
+          + (N + 3) * EPS32 * torch.einsum("bhn,bhnd->bhd", ds.abs(), K64.abs())
+          + POOL_FLOOR * (1 + K64.abs().sum(2)))
+    return (dkv, bkv), (dq.reshape(B, H * dh), bq.reshape(B, H * dh))
+
+
+def pool_attn_emulate(q, K, V, dout, H, dh, out_dt, probs=None):
+    """pool_attn_fwd_kernel / pool_attn_bwd_kernel in torch fp32 (chunk partials of 8 columns, exp as exp2(x log2 e),
+    plain fp32 sums in torch's order).  Returns probs, out and, when dout is given, dkv and dq from `probs` (the
+    backward's input; default: its own)."""
+    B, _, N, DP = K.shape
+    f = torch.float32
+    qf, Kf, Vf = q.float().view(H, dh), K.float()[..., :dh], V.float()[..., :dh]
+    scale = torch.tensor(dh ** -0.5, dtype=f)
+    part = (qf[None, :, None, :] * Kf).view(B, H, N, dh // 8, 8).sum(-1)
+    S = part.sum(-1) * scale
+    e = torch.exp2((S - S.max(-1, keepdim=True).values) * torch.tensor(LOG2E, dtype=f))
+    Pr = e * (1.0 / e.sum(-1, keepdim=True))
+    out = (Pr[..., None] * Vf).sum(2).reshape(B, H * dh).to(out_dt)
+    if dout is None:
+        return Pr, out
+    Pb = Pr if probs is None else probs.float().view(B, H, N)
+    dO = dout.float().view(B, H, dh)
+    dp = (dO[:, :, None, :] * Vf).view(B, H, N, dh // 8, 8).sum(-1).sum(-1)
+    dot = (Pb * dp).sum(-1, keepdim=True)
+    ds = Pb * (dp - dot) * scale
+    tok = lambda t: t.permute(0, 2, 1, 3).reshape(B * N, H * dh)
+    dkv = torch.cat([tok(ds[..., None] * qf[None, :, None, :]), tok(Pb[..., None] * dO[:, :, None, :])], 1).to(out_dt)
+    dq = (ds[..., None] * Kf).sum(2).reshape(B, H * dh)
+    return Pr, out, dkv, dq

@@ -621,6 +621,94 @@ def test_rectangular_images_package_vs_oracle(pkg, oracle, hiplib, cfg_name, B, 
                     f"rect package {cfg_name} {H}x{W} {mode} rc{int(recompute)}")
 
 
+# The pooling head's token limit (csrc/kernels.h pool_attn_max_tokens; hostile has so400m's head dimension 72 and patch 14):
+# 36 x 36 = 1296 tokens is the largest square grid that trains (limit 1364), 38 x 38 = 1444 the largest that infers (1488).
+@pytest.mark.parametrize("mode", ["fp32", "bf16x3"])
+def test_largest_trainable_square_504px_raw_abi_vs_oracle(pkg, oracle, hiplib, mode):
+    B, H, W = 1, 504, 504
+    with Session(pkg, hiplib, "hostile", mode, 0, seed=19) as ses:
+        ref = Reference.get(pkg, oracle, "hostile", 19, B, H, W, 1, taps_of(ses.Lyr))
+        r = train_once(ses, B, H, W, fill=0xFF, what=f"hostile {H}x{W}")
+        assert len(r["grads"]) == len(ref.grads)
+        check_vs_oracle(ref, r["out"], r["grads"], mode, f"pool limit abi hostile {H}x{W} {mode}")
+
+
+@pytest.mark.parametrize("mode", ["fp32", "bf16x3"])
+def test_largest_inference_square_532px_raw_abi_vs_oracle(pkg, oracle, hiplib, mode):
+    B, H, W = 1, 532, 532
+    with Session(pkg, hiplib, "hostile", mode, 0, seed=19) as ses:
+        x = pkg.weights.seeded_pixels(B, H, W, seed=1)
+        with torch.no_grad():
+            want = oracle.vision_forward(x, pkg.weights.seeded_state_dict(ses.cfg, seed=19), ses.cfg, True, True)
+        run = infer_once(ses, B, H, W, fill=0xFF, what=f"hostile {H}x{W} inference")
+        out = run.outputs(pooled=True)
+        x3 = 6.0 if mode == "bf16x3" else 1.0
+        N, D = 38 * 38, ses.D
+        for k, w in (("pooled", want["pooler_output"]), ("last", want["last_hidden_state"].reshape(B * N, D))):
+            err = float((out[k].cpu() - w).abs().max())
+            print(f"[pool limit abi hostile {H}x{W} {mode}] {k} err {err:.2e} (bound {2e-5 * x3:.1e})")
+            assert err <= 2e-5 * x3, f"{k} err {err:.3e} > {2e-5 * x3:.1e}"
+
+
+def test_largest_token_counts_run_in_plain_bf16(pkg, hiplib):
+    """The oracle bars above exist for fp32 and bf16x3 only (Reference.bar), so the pool_attn<bf16> instantiations are run
+    at the same two sizes without them: 504 px training and 532 px inference in plain bf16 write no guard, give finite
+    outputs and gradients, and give the same bits when run a second time (every reduction has a fixed order)."""
+    with Session(pkg, hiplib, "hostile", "bf16", 0, seed=19) as ses:
+        a = train_once(ses, 1, 504, 504, fill=0xFF, what="hostile 504x504 bf16")
+        b = train_once(ses, 1, 504, 504, fill=0xFF, what="hostile 504x504 bf16, again")
+        assert_finite(a["out"], "504 px bf16 outputs")
+        assert_finite(a["grads"], "504 px bf16 gradients")
+        assert_same(a["out"], b["out"], "504 px bf16 outputs, two runs")
+        assert_same(a["grads"], b["grads"], "504 px bf16 gradients, two runs")
+        o1 = infer_once(ses, 1, 532, 532, fill=0xFF, what="hostile 532x532 bf16 inference").outputs(pooled=True)
+        o2 = infer_once(ses, 1, 532, 532, fill=0xFF, what="hostile 532x532 bf16 inference, again").outputs(pooled=True)
+        assert_finite(o1, "532 px bf16 outputs")
+        assert_same(o1, o2, "532 px bf16 outputs, two runs")
+
+
+@pytest.mark.parametrize("mode", ["fp32", "bf16"])
+def test_raw_abi_refuses_546px_and_touches_nothing(pkg, hiplib, mode):
+    """39 x 39 = 1521 tokens through sgl_forward, every arena filled with 0xFF first (sized for two 532 px images, which
+    is more than one 546 px image needs): SGL_ERR_BAD_SHAPE, and after a synchronize every byte of the workspace, the
+    hidden states and both outputs is still 0xFF.  The same call on a context without the head runs."""
+    with Session(pkg, hiplib, "hostile", mode, 0, seed=19) as ses:
+        shadow = ses.new_shadow(0xFF)
+        assert ses.prepare(shadow, full=True) == ah.OK
+        run = Run(ses, 2, 532, 532, False, 0xFF)
+        run.B, run.H, run.W = 1, 546, 546
+        px = ses.pixels(1, 546, 546, 1)
+        torch.cuda.synchronize()
+        assert ses.forward(run, shadow, px) == ah.ERR_BAD_SHAPE
+        torch.cuda.synchronize()
+        for name, a in run.arenas():
+            assert a.untouched() and a.guards_intact(), f"`{name}` was written by a refused sgl_forward"
+    with Session(pkg, hiplib, "hostile", mode, 0, use_head=0, seed=19) as ses:
+        run = infer_once(ses, 1, 546, 546, fill=0xFF, pooled=False, what="hostile 546x546 without the head")
+        assert_finite(run.outputs(pooled=False), "546 px without the head")
+
+
+@pytest.mark.parametrize("mode", ["fp32", "bf16"])
+def test_package_refuses_546px_before_any_launch(pkg, hiplib, mode):
+    """39 x 39 = 1521 tokens is above the pooling head's 1488: the package raises its status error, and raises it from
+    sgl_query_sizes (host arithmetic, the first ABI call of a forward), so no forward entry point was entered and nothing
+    was launched; 532 px right below it still runs.  Training refuses 518 px the same way."""
+    cfg = pkg.get_config("hostile")
+    model = pkg.SiglipVisionModelHIP(cfg, compute_dtype=mode)
+    model.load_state_dict(pkg.weights.seeded_state_dict(cfg, seed=19))
+    model = model.to(DEV).eval()
+    px = pkg.weights.seeded_pixels(1, 546, 546, seed=1).to(DEV)
+    torch.cuda.synchronize()
+    with torch.no_grad():
+        with pytest.raises(pkg.lib.SglError, match="sgl_query_sizes: bad shape"):
+            model(pixel_values=px, interpolate_pos_encoding=True)
+        torch.cuda.synchronize()
+        o = model(pixel_values=px[:, :, :532, :532].contiguous(), interpolate_pos_encoding=True)
+    assert o.pooler_output.shape == (1, cfg.hidden_size) and bool(torch.isfinite(o.pooler_output).all())
+    with pytest.raises(pkg.lib.SglError, match="sgl_query_sizes: bad shape"):   # training: 518 px is already too many
+        model.train()(pixel_values=px[:, :, :518, :518].contiguous(), interpolate_pos_encoding=True)
+
+
 # =====================================================================================================================
 # f. bf16x3 at >= 2048 tokens: the two gemm_nt6_kernel<0|4, float, bfloat16> instantiations
 # =====================================================================================================================

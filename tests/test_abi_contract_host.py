@@ -20,11 +20,11 @@ CFGS = {"tiny": (32, 32), "hostile": (42, 42)}
 class Host:
     """One context with dummy device pointers and the real sizes of a (B, H, W) geometry."""
 
-    def __init__(self, pkg, lib, cfg_name="hostile", mode="bf16", recompute=0, B=2, HW=None, train=True):
+    def __init__(self, pkg, lib, cfg_name="hostile", mode="bf16", recompute=0, B=2, HW=None, train=True, use_head=1):
         self.pkg, self.lib = pkg, lib
-        self.cfg = ah.make_config(pkg, cfg_name)
+        self.cfg = ah.make_config(pkg, cfg_name, use_head)
         self.L = self.cfg.num_hidden_layers
-        self.ctx = lib.sgl_create_ex(C.byref(ah.sgl_config(pkg, self.cfg, mode)), recompute)
+        self.ctx = lib.sgl_create_ex(C.byref(ah.sgl_config(pkg, self.cfg, mode, use_head)), recompute)
         assert self.ctx
         self.w, self._wl = ah.weights_struct(pkg, self.cfg, lambda n: DUMMY)
         Lb = pkg.lib
@@ -214,6 +214,54 @@ def test_bad_shapes_are_err_bad_shape(host, cfg_name):
         for e in FORWARDS:
             assert hn.call(e, interp=0) == ah.ERR_BAD_SHAPE, (e, gh, gw)
             assert ht.call(e, interp=0) == ah.ERR_BAD_SHAPE, (e, gh, gw)
+
+
+# The pooling head keeps one fp32 partial per 8-column chunk of every token of an image in the 64 KiB LDS window
+# (csrc/kernels.h pool_attn_max_tokens): N <= floor(16376 / (DP / 8 + 1)) forward, floor(16376 / (DP / 8 + 2)) backward.
+# hostile: head dimension 72, DP 80 (so400m's), patch 14 -> 1488 / 1364 tokens; tiny: head dimension 16, DP 16, patch 16
+# -> 5458 / 4094.  (grid, train, accepted): squares either side of each limit, then rectangles just over it (and one exactly at it).
+POOL_LIMIT_CASES = {
+    "hostile": [((36, 36), 1, True), ((37, 37), 1, False), ((37, 37), 0, True), ((38, 38), 0, True), ((39, 39), 0, False),
+                ((36, 38), 1, False), ((35, 39), 1, False), ((31, 44), 1, True), ((36, 38), 0, True),
+                ((38, 40), 0, False), ((10, 149), 0, False), ((31, 48), 0, True), ((1, 1489), 0, False)],
+    "tiny": [((63, 63), 1, True), ((64, 64), 1, False), ((64, 64), 0, True), ((73, 73), 0, True), ((74, 74), 0, False),
+             ((63, 65), 1, False), ((46, 89), 1, True), ((53, 103), 0, False), ((2, 2729), 0, True)],
+}
+
+
+@pytest.mark.parametrize("mode,recompute", [("bf16", 0), ("fp32", 1)])
+@pytest.mark.parametrize("cfg_name", ["hostile", "tiny"])
+def test_pool_head_token_limit_is_err_bad_shape_before_any_launch(host, cfg_name, mode, recompute):
+    """504 / 518 / 532 / 546 px for hostile (= so400m's head): sgl_query_sizes and every forward / backward entry point refuse
+    an image whose token count the pooling head cannot hold, with SGL_ERR_BAD_SHAPE and without a device.  An accepted
+    shape passes the shape check (shown by the NEXT check failing: one byte of workspace short).  use_head = 0: no limit."""
+    P = {"hostile": 14, "tiny": 16}[cfg_name]
+    lim = {"hostile": (1488, 1364), "tiny": (5458, 4094)}[cfg_name]
+    if cfg_name == "hostile":
+        assert [(g[0] * P, t, a) for g, t, a in POOL_LIMIT_CASES[cfg_name][:5]] == \
+            [(504, 1, True), (518, 1, False), (518, 0, True), (532, 0, True), (546, 0, False)]
+    for (gh, gw), train, accepted in POOL_LIMIT_CASES[cfg_name]:
+        assert accepted == (gh * gw <= lim[train]), (gh, gw, train)            # the table agrees with the formula
+        for use_head in (1, 0):
+            h = host(cfg_name, mode, recompute, B=1, HW=(gh * P + 3, gw * P), train=bool(train), use_head=use_head)
+            want_ok = accepted or not use_head
+            what = (cfg_name, gh, gw, train, use_head)
+            assert h.size_status == (ah.OK if want_ok else ah.ERR_BAD_SHAPE), what
+            entries = FORWARDS + (BACKWARDS if train else [])
+            for e in entries:
+                if want_ok:
+                    short = dict(saved_bytes=h.saved_bytes - 1) if train else dict(ws_bytes=h.ws_bytes - 1)
+                    assert h.call(e, **short) == ah.ERR_WORKSPACE, (e,) + what
+                else:
+                    assert h.call(e) == ah.ERR_BAD_SHAPE, (e,) + what
+                    assert h.call(e, ws_bytes=1 << 40, saved_bytes=(1 << 40) if train else 0) == ah.ERR_BAD_SHAPE, \
+                        (e,) + what
+            if not train and use_head:     # a backward at a shape only the forward accepts is refused as well
+                hb = host(cfg_name, mode, recompute, B=1, HW=(gh * P, gw * P), train=True, use_head=1)
+                if gh * gw > lim[1]:
+                    assert hb.size_status == ah.ERR_BAD_SHAPE, what
+                    for e in BACKWARDS:
+                        assert hb.call(e, ws_bytes=1 << 40, saved_bytes=1 << 40) == ah.ERR_BAD_SHAPE, (e,) + what
 
 
 def test_mxfp8_refuses_training(host, pkg, hiplib):

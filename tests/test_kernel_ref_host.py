@@ -492,3 +492,160 @@ def test_aug_reference_matches_fp32_oracle_and_hue_cap_holds(case):
     # flip mutant S - 1 - x -> S - x: the flipped records move by one pixel
     shifted = torch.roll(out, 1, dims=-1)
     assert kr.worst_ratio(shifted[1][keep[1]], out[1][keep[1]], bound[1][keep[1]]) > 10
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the kernels only the encoder calls (tests/test_kernel_edges_internal_gpu.py)
+# ---------------------------------------------------------------------------------------------------------------
+def _pos_case(g0, gh, gw, D, seed, prior_scale=1.0):
+    g = torch.Generator().manual_seed(seed)
+    return torch.randn(gh * gw, D, generator=g), torch.randn(g0 * g0, D, generator=g) * prior_scale
+
+
+def test_pos_resize_bwd_reference_is_the_autograd_of_bicubic_interpolate():
+    """The dense float64 resize matrix, transposed, against float64 autograd of F.interpolate(bicubic) on every grid."""
+    for g0, gh, gw in kr.POS_BWD_GRIDS:
+        dout, prior = _pos_case(g0, gh, gw, 5, 0)
+        t = torch.randn(g0 * g0, 5, dtype=torch.float64, requires_grad=True)
+        kr.pos_resize_ref(t, g0, gh, gw).backward(dout.double())
+        ref, _ = kr.pos_resize_bwd_ref(dout, g0, gh, gw, prior)
+        assert (t.grad + prior.double() - ref).abs().max().item() < 1e-13, (g0, gh, gw)
+        fwd = kr.resize_matrix(g0, gh)                     # and the matrix itself against the forward reference
+        assert fwd.sum(1).sub(1).abs().max().item() < 1e-14
+
+
+def test_pos_resize_bwd_constant_is_measured_from_the_emulation():
+    """POS_BWD_C: the per-weight excess of the fp32 polynomials over the derived coordinate slack, measured on the axes the
+    GPU test uses (11.6), times 2 to 4.  The emulation then sits at 0.16 of the bound at the worst (asserted <= 0.5) for
+    zero and normal priors, D = 5 and 144; without the constant it leaves the bound (1.85)."""
+    excess = max(kr.pos_resize_weight_excess(g0, n) for g0, gh, gw in kr.POS_BWD_GRIDS for n in (gh, gw))
+    assert 2.0 * excess <= kr.POS_BWD_C <= 4.0 * excess, excess
+    worst, worst0 = 0.0, 0.0
+    for g0, gh, gw in kr.POS_BWD_GRIDS:
+        for seed in range(3):
+            for D in (5, 144):
+                for ps in (0.0, 1.0):
+                    dout, prior = _pos_case(g0, gh, gw, D, seed, ps)
+                    emu = kr.pos_resize_bwd_emulate(dout, g0, gh, gw, prior)
+                    ref, bound = kr.pos_resize_bwd_ref(dout, g0, gh, gw, prior)
+                    worst = max(worst, kr.assert_within(emu, ref, bound, f"emulation {g0}->{gh}x{gw}"))
+                    worst0 = max(worst0, kr.worst_ratio(emu, ref, kr.pos_resize_bwd_ref(dout, g0, gh, gw, prior, c=0.0)[1]))
+    assert 0.05 < worst <= 0.5, worst
+    assert worst0 > 1.0, worst0
+
+
+def test_pos_resize_bwd_relative_form_cannot_hold_small_weights():
+    """Why the bound is not (terms + c) 2^-24 sum|w||dout|: at 27 -> 1 x 5 the fp32 weights of 0.02 to 0.2 are off by 5 to
+    22 2^-24 each, so that form needs c above 100 for the emulation (and more the larger g0)."""
+    g0, gh, gw = 27, 1, 5
+    need = 0.0
+    for seed in range(3):
+        dout, prior = _pos_case(g0, gh, gw, 5, seed, 0.0)
+        emu = kr.pos_resize_bwd_emulate(dout, g0, gh, gw, prior).double()
+        Ry, Rx = kr.resize_matrix(g0, gh), kr.resize_matrix(g0, gw)
+        G = dout.double().view(gh, gw, 5)
+        ref = torch.einsum("ya,yxd,xb->abd", Ry, G, Rx).reshape(g0 * g0, 5)
+        mag = torch.einsum("ya,yxd,xb->abd", Ry.abs(), G.abs(), Rx.abs()).reshape(g0 * g0, 5)
+        live = mag > 0
+        need = max(need, ((emu - ref).abs()[live] / (kr.EPS32 * mag[live])).max().item())
+    assert need > 100.0, need
+
+
+def test_pos_resize_bwd_bound_catches_a_narrow_scan():
+    """tap_range scanning +-1 source rows instead of +-3 (borders widened as the kernel does) drops whole contributions
+    on the steep upscale: outputs 30..36 of 37 reach table row 0 through their first tap.  Far outside the bound."""
+    g0, gh, gw = 2, 37, 5
+    dout, prior = _pos_case(g0, gh, gw, 5, 0)
+    ref, bound = kr.pos_resize_bwd_ref(dout, g0, gh, gw, prior)
+    narrow, Rx = kr.resize_matrix(g0, gh), kr.resize_matrix(g0, gw)
+    oy = torch.arange(gh)
+    for ty in range(g0):
+        lo = 0 if ty == 0 else math.floor((ty - 1 + 0.5) * gh / g0 - 0.5) - 1
+        hi = gh - 1 if ty == g0 - 1 else math.ceil((ty + 1 + 0.5) * gh / g0 - 0.5) + 1
+        narrow[(oy < lo) | (oy > hi), ty] = 0.0
+    assert not torch.equal(narrow, kr.resize_matrix(g0, gh))
+    got = torch.einsum("ya,yxd,xb->abd", narrow, dout.double().view(gh, gw, 5), Rx).reshape(g0 * g0, 5) + prior.double()
+    assert kr.worst_ratio(got, ref, bound) > 20
+
+
+@pytest.mark.parametrize("tdt", [torch.float32, torch.bfloat16, torch.float16], ids=["f32", "bf16", "f16"])
+@pytest.mark.parametrize("kind", ["gauss", "big", "equal"])
+def test_pool_attn_bounds_hold_for_the_emulation_and_catch_mutants(kind, tdt):
+    """pool_attn_emulate (the kernels' recipe in torch fp32) inside every bound: at most 0.5 for the fp32 quantities
+    (probs <= 0.12, dq <= 0.03, fp32 out <= 0.02; fp32 dkv 0.5 = the one rounding of dV), at most 1 for 16-bit stores
+    (their own half ulp).  Outside: the backward without `- dot`, the scale rsqrt(DP) for rsqrt(dh), a truncating store."""
+    worst = [0.0] * 4
+    for dh, DP in ((8, 16), (72, 80)):
+        for N in (1, 25, 257, 1364):
+            B, H = 2, 3
+            q, K, V, do = kr.pool_inputs(kind, B, H, N, dh, DP, tdt, 1)
+            (Pr, bP), (o, bo) = kr.pool_attn_fwd_ref(q, K, V, H, dh, tdt)
+            P32 = Pr.float()
+            (dkv, bkv), (dq, bq) = kr.pool_attn_bwd_ref(q, K, V, P32, do, H, dh, tdt)
+            eP, eo, ekv, edq = kr.pool_attn_emulate(q, K, V, do, H, dh, tdt, P32)
+            what = f"{kind} dh={dh} N={N}"
+            rs = [kr.assert_within(eP, Pr, bP, what + " probs"), kr.assert_within(eo, o, bo, what + " out"),
+                  kr.assert_within(ekv, dkv, bkv, what + " dkv"), kr.assert_within(edq, dq, bq, what + " dq")]
+            worst = [max(a, b) for a, b in zip(worst, rs)]
+            assert (Pr.sum(-1) - 1).abs().max().item() < 1e-12
+            if N < 25 or kind != "gauss":
+                continue
+            # mutants, in float64 so that only the mutation differs
+            scale, bad = dh ** -0.5, DP ** -0.5
+            S = torch.einsum("hd,bhnd->bhn", q.double().view(H, dh), K.double()[..., :dh])
+            assert kr.worst_ratio(torch.softmax(S * bad, -1), Pr, bP) > 100, what
+            dp = torch.einsum("bhd,bhnd->bhn", do.double().view(B, H, dh), V.double()[..., :dh])
+            ds_mut = P32.double() * dp * scale                                    # `- dot` dropped
+            dq_mut = torch.einsum("bhn,bhnd->bhd", ds_mut, K.double()[..., :dh]).reshape(B, H * dh)
+            assert kr.worst_ratio(dq_mut, dq, bq) > 100, what
+            if tdt != torch.float32:
+                assert kr.worst_ratio(kr.truncate_to(dkv, tdt), dkv, bkv) > 1.5, what
+    lim = 0.5 if tdt == torch.float32 else 1.0
+    assert worst[0] <= 0.5 and worst[3] <= 0.5 and worst[1] <= lim and worst[2] <= lim, worst
+
+
+def test_pool_attn_reference_is_the_autograd_of_softmax_attention():
+    B, H, N, dh, DP = 2, 3, 33, 24, 32
+    q, K, V, do = kr.pool_inputs("gauss", B, H, N, dh, DP, torch.float32, 4)
+    q64 = q.double().view(H, dh).requires_grad_(True)
+    K64, V64 = K.double()[..., :dh].requires_grad_(True), V.double()[..., :dh].requires_grad_(True)
+    Pr = torch.softmax(torch.einsum("hd,bhnd->bhn", q64, K64) * dh ** -0.5, -1)
+    out = torch.einsum("bhn,bhnd->bhd", Pr, V64).reshape(B, H * dh)
+    out.backward(do.double())
+    (rP, _), (ro, _) = kr.pool_attn_fwd_ref(q, K, V, H, dh, torch.float32)
+    assert (rP - Pr).abs().max().item() < 1e-14 and (ro - out).abs().max().item() < 1e-13
+    # the backward reference takes the probabilities in fp32: compare at that precision
+    (dkv, _), (dq, _) = kr.pool_attn_bwd_ref(q, K, V, Pr.detach().float(), do, H, dh, torch.float32)
+    tok = lambda t: t.permute(0, 2, 1, 3).reshape(B * N, H * dh)
+    assert (dkv - torch.cat([tok(K64.grad), tok(V64.grad)], 1)).abs().max().item() < 1e-6
+    assert (dq.view(B, H, dh).sum(0) - q64.grad).abs().max().item() < 1e-5
+
+
+def test_sum_bound_holds_for_any_fp32_order_and_split3_reconstructs():
+    """sum_ref: a sequential fp32 chain and a pairwise tree of 1152 terms inside n 2^-24 sum|terms| (measured 0.01 to
+    0.03), a sum that loses one term outside.  split3: hi + lo within 2^-17 |x| for normal x, exact layout segments."""
+    g = torch.Generator().manual_seed(0)
+    t = torch.randn(1152, 65, generator=g)
+    prior = torch.randn(65, generator=g)
+    ref, bound = kr.sum_ref(t, prior)
+    seq = prior.clone()
+    for i in range(t.shape[0]):
+        seq = seq + t[i]
+    tree = t.clone()
+    while tree.shape[0] > 1:
+        if tree.shape[0] % 2:
+            tree = torch.cat([tree, torch.zeros(1, tree.shape[1])])
+        tree = tree[0::2] + tree[1::2]
+    assert kr.assert_within(seq, ref, bound, "sequential") <= 0.5
+    assert kr.assert_within(tree[0] + prior, ref, bound, "tree") <= 0.5
+    assert kr.worst_ratio(seq - t[-1], ref, bound) > 10
+    rv, bv = kr.vecmat_ref(t[:, 0], t, None)
+    assert kr.assert_within((t[:, :1] * t).sum(0), rv, bv, "vecmat") <= 0.5
+    x = torch.cat([torch.randn(4096, generator=g) * torch.logspace(-20, 20, 4096), kr.split3_special_values()])
+    hi, lo = kr.split3_ref(x)
+    normal = (x.abs() >= 2.0 ** -100) & torch.isfinite(hi.float())
+    rec = hi.double() + lo.double()
+    assert bool(((rec - x.double()).abs()[normal] <= 2.0 ** -17 * x.double().abs()[normal]).all())
+    lay = kr.split3_layout(x[:18].view(2, 9), 16, 1, False)
+    assert lay.shape == (2, 48) and torch.equal(lay[:, 16:25], lo[:18].view(2, 9)) and bool((lay[:, 9:16] == 0).all())
+    assert torch.equal(kr.split3_layout(x[:18].view(2, 9), 16, 0, True)[4:6, :9], lo[:18].view(2, 9))
