@@ -60,18 +60,24 @@ __device__ __forceinline__ float src_px(const void* src, int b, int c, int y, in
     return reinterpret_cast<const float*>(src)[(((size_t)b * 3 + c) * Hs + y) * Ws + x];
 }
 
-template <bool SRC_U8>
-__device__ __forceinline__ float resample(const void* src, int b, int c, int oy, int ox, int Hs, int Ws, float sy,
-                                          float sx) {
-  if (sy == 1.0f && sx == 1.0f) return src_px<SRC_U8>(src, b, c, oy, ox, Hs, Ws);
-  const AaAxis ay = aa_axis(oy, Hs, sy), ax = aa_axis(ox, Ws, sx);
+// output pixel (oy, ox) of the h x w image px(y, x) resized by (sy, sx): the one filter loop of every forward kernel here
+template <typename Px>
+__device__ __forceinline__ float resample_px(Px px, int oy, int ox, int h, int w, float sy, float sx) {
+  if (sy == 1.0f && sx == 1.0f) return px(oy, ox);
+  const AaAxis ay = aa_axis(oy, h, sy), ax = aa_axis(ox, w, sx);
   float acc = 0.f;
   for (int jy = 0; jy < ay.n; ++jy) {
     float row = 0.f;
-    for (int jx = 0; jx < ax.n; ++jx) row += aa_w(ax, jx) * src_px<SRC_U8>(src, b, c, ay.lo + jy, ax.lo + jx, Hs, Ws);
+    for (int jx = 0; jx < ax.n; ++jx) row += aa_w(ax, jx) * px(ay.lo + jy, ax.lo + jx);
     acc += aa_w(ay, jy) * row;
   }
   return acc;
+}
+
+template <bool SRC_U8>
+__device__ __forceinline__ float resample(const void* src, int b, int c, int oy, int ox, int Hs, int Ws, float sy,
+                                          float sx) {
+  return resample_px([&](int y, int x) { return src_px<SRC_U8>(src, b, c, y, x, Hs, Ws); }, oy, ox, Hs, Ws, sy, sx);
 }
 
 // patch_major: out[(b*gh + gy)*gw + gx][k], k = c*P*P + ky*P + kx (k >= 3*P*P zero)   | else out[b][c][y][x] (NCHW)
@@ -293,6 +299,106 @@ __global__ __launch_bounds__(256) void patch_pad_zero_kernel(TOut* __restrict__ 
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// Test-time views of the app (appv3.py:3214-3250 detect_core, :3315 make_multicrops, :3381 compute_patch_grid): V windows
+// onto B same-size sources in one pass.  A view = integer crop box -> quarter turns (exact, or on PIL's fixed canvas:
+// Image.rotate(90 k) with expand=False, nearest, fill 0) -> mirror -> the resize + normalise of preprocess_kernel with
+// `in` = the oriented extents.  The oriented image is never built: a tap (y, x) of it is mapped to a crop coordinate by
+// an integer affine map and read from the source (or is zero outside the canvas); include/siglip_hip.h has the rules.
+// The records travel by value in the kernel arguments (64 x 32 bytes of the 4 KB a launch may carry): no device table,
+// no copy, nothing to keep alive, graph-capturable.  Same thread mapping and store pattern as preprocess_kernel.
+// ---------------------------------------------------------------------------------------------------------------
+struct View {   // == sgl_view
+  int src, x0, y0, x1, y1, turns, keep_canvas, flip;
+};
+constexpr int kViewChunk = 64;
+struct ViewChunk {
+  View v[kViewChunk];
+};
+
+// oriented extents of a record: an exact odd turn swaps them, a turn on the kept canvas does not
+__host__ __device__ __forceinline__ void view_extent(const View& r, int* oh, int* ow) {
+  const int w = r.x1 - r.x0, h = r.y1 - r.y0;
+  const bool swap = (r.turns & 1) && !r.keep_canvas;
+  *oh = swap ? w : h;
+  *ow = swap ? h : w;
+}
+
+// crop coordinate of oriented pixel (y, x): cx = ax + axx x + axy y, cy = ay + ayx x + ayy y; outside [0,w) x [0,h): zero
+struct ViewMap {
+  int src, x0, y0, w, h, oh, ow;
+  int ax, axx, axy, ay, ayx, ayy;
+};
+
+__device__ __forceinline__ ViewMap view_map(const View& r) {
+  ViewMap m;
+  m.src = r.src, m.x0 = r.x0, m.y0 = r.y0;
+  const int w = m.w = r.x1 - r.x0, h = m.h = r.y1 - r.y0;
+  view_extent(r, &m.oh, &m.ow);
+  m.ax = 0, m.axx = 1, m.axy = 0, m.ay = 0, m.ayx = 0, m.ayy = 1;
+  if (r.turns == 2) {                                    // exact on either canvas (PIL: transpose(ROTATE_180))
+    m.ax = w - 1, m.axx = -1, m.ay = h - 1, m.ayy = -1;
+  } else if (r.turns != 0) {
+    // exact: rot90(C, 1)[y][x] = C[x][w-1-y], rot90(C, 3)[y][x] = C[h-1-x][y].  Kept canvas: PIL's nearest affine
+    // transform samples floor((w+h)/2 - (y + 0.5)), floor((h-w)/2 + (x + 0.5)) at one turn (mirrored roles at three);
+    // >> 1 is the floor for the negative half-integers too.  w == h makes the two rules coincide.
+    const int hi = r.keep_canvas ? (w + h - 1) >> 1 : (r.turns == 1 ? w - 1 : h - 1);
+    const int lo = r.keep_canvas ? ((r.turns == 1 ? h - w : w - h) + 1) >> 1 : 0;
+    m.axx = 0, m.ayy = 0;
+    if (r.turns == 1) m.ax = hi, m.axy = -1, m.ay = lo, m.ayx = 1;
+    else m.ax = lo, m.axy = 1, m.ay = hi, m.ayx = -1;
+  }
+  if (r.flip) {                                          // x -> ow - 1 - x
+    m.ax += m.axx * (m.ow - 1), m.axx = -m.axx;
+    m.ay += m.ayx * (m.ow - 1), m.ayx = -m.ayx;
+  }
+  return m;
+}
+
+template <bool SRC_U8>
+__device__ __forceinline__ float view_px(const void* src, const ViewMap& m, int c, int y, int x, int Hs, int Ws) {
+  const int cx = m.ax + m.axx * x + m.axy * y, cy = m.ay + m.ayx * x + m.ayy * y;
+  if (cx < 0 || cx >= m.w || cy < 0 || cy >= m.h) return 0.f;
+  return src_px<SRC_U8>(src, m.src, c, m.y0 + cy, m.x0 + cx, Hs, Ws);
+}
+
+// out: the rows of this chunk's first view onward; layouts as preprocess_kernel with b = the view's index in the chunk
+template <bool SRC_U8, typename TOut>
+__global__ __launch_bounds__(256) void preprocess_views_kernel(const void* __restrict__ src, TOut* __restrict__ out,
+                                                               const ViewChunk chunk, int nv, int Hs, int Ws, int S, int P,
+                                                               int Kp, int patch_major, float mean, float inv_std) {
+  const int g = patch_major ? S / P : 0, K0 = 3 * P * P;
+  const size_t total = patch_major ? (size_t)nv * g * g * Kp : (size_t)nv * 3 * S * S;
+  for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
+    int v, c, oy, ox;
+    bool live = true;
+    if (patch_major) {
+      const int k = (int)(idx % Kp);
+      const size_t m = idx / Kp;
+      const int gx = (int)(m % g), gy = (int)((m / g) % g);
+      v = (int)(m / ((size_t)g * g));
+      live = k < K0;
+      c = k / (P * P);
+      const int r = k - c * P * P;
+      oy = gy * P + r / P;
+      ox = gx * P + r % P;
+    } else {
+      ox = (int)(idx % S);
+      oy = (int)((idx / S) % S);
+      c = (int)((idx / ((size_t)S * S)) % 3);
+      v = (int)(idx / ((size_t)3 * S * S));
+    }
+    float val = 0.f;
+    if (live) {
+      const ViewMap m = view_map(chunk.v[v]);
+      const float sy = (float)m.oh / (float)S, sx = (float)m.ow / (float)S;
+      val = resample_px([&](int y, int x) { return view_px<SRC_U8>(src, m, c, y, x, Hs, Ws); }, oy, ox, m.oh, m.ow, sy, sx);
+      val = (val - mean) * inv_std;
+    }
+    Elem<TOut>::st(out + idx, val);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // Adjoint of preprocess_kernel<false, float>(patch_major = 0) with respect to a float source: the forward is linear,
 //     out[b] = (lam Wy src[b] Wx^T + (1 - lam) Wy src[mix[b]] Wx^T - mean) / std,
 // so d_src[b] = Wy^T (lam G[b] + (1 - lam) sum_{j : mix[j] == b} G[j]) Wx / std with the SAME fp32 weights (aa_axis / aa_w).
@@ -429,6 +535,64 @@ int sgl_op_preprocess(const void* src, int src_is_u8_nhwc, int B, int Hs, int Ws
     else SGL_PP(false, float);
   }
 #undef SGL_PP
+  return hipGetLastError() == hipSuccess ? SGL_OK : SGL_ERR_HIP;
+}
+
+size_t sgl_op_preprocess_views_scratch_bytes(int V, int S) {
+  (void)V, (void)S;
+  return 0;                                              // the records travel in the kernel arguments
+}
+
+int sgl_op_preprocess_views(const void* src, int src_is_u8_nhwc, int B, int Hs, int Ws, const sgl_view* views, int V,
+                            void* out, int out_dtype, int S, int P, int Kp, int patch_major, float mean, float std,
+                            void* scratch, size_t scratch_bytes, sgl_stream stream) {
+  static_assert(sizeof(sgl_view) == sizeof(sgl::View) && sizeof(sgl_view) == 32, "record layout");
+  static_assert(sizeof(sgl::ViewChunk) <= 2048, "a chunk of records must fit the kernel arguments");
+  if (!src || !views || !out) return SGL_ERR_NULL;
+  if (B <= 0 || Hs <= 0 || Ws <= 0 || S <= 0 || V <= 0 || std == 0.f) return SGL_ERR_BAD_SHAPE;
+  if (patch_major && (P <= 0 || S < P || Kp < 3 * P * P)) return SGL_ERR_BAD_SHAPE;
+  const sgl::View* rec = reinterpret_cast<const sgl::View*>(views);
+  for (int v = 0; v < V; ++v) {
+    const sgl::View& r = rec[v];
+    if (r.src < 0 || r.src >= B || r.x0 < 0 || r.x0 >= r.x1 || r.x1 > Ws || r.y0 < 0 || r.y0 >= r.y1 || r.y1 > Hs ||
+        r.turns < 0 || r.turns > 3 || (r.keep_canvas | 1) != 1 || (r.flip | 1) != 1)
+      return SGL_ERR_BAD_SHAPE;
+  }
+  if (out_dtype != SGL_DTYPE_BF16 && out_dtype != SGL_DTYPE_F16 && out_dtype != SGL_DTYPE_F32) return SGL_ERR_UNSUPPORTED;
+  for (int v = 0; v < V; ++v) {
+    int oh, ow;
+    sgl::view_extent(rec[v], &oh, &ow);
+    if ((float)oh / (float)S > 16.f || (float)ow / (float)S > 16.f) return SGL_ERR_UNSUPPORTED;   // tap loops stay short
+  }
+  if (scratch_bytes < sgl_op_preprocess_views_scratch_bytes(V, S)) return SGL_ERR_WORKSPACE;   // 0 bytes: never taken
+  (void)scratch;
+  const int g = patch_major ? S / P : 0;
+  const size_t per_view = patch_major ? (size_t)g * g * Kp : (size_t)3 * S * S;
+  const size_t esize = out_dtype == SGL_DTYPE_F32 ? 4 : 2;
+  hipStream_t s = (hipStream_t)stream;
+  const float inv_std = 1.0f / std;
+  for (int v0 = 0; v0 < V; v0 += sgl::kViewChunk) {      // one launch per 64 views
+    const int nv = V - v0 < sgl::kViewChunk ? V - v0 : sgl::kViewChunk;
+    sgl::ViewChunk chunk = {};
+    for (int v = 0; v < nv; ++v) chunk.v[v] = rec[v0 + v];
+    void* dst = reinterpret_cast<char*>(out) + (size_t)v0 * per_view * esize;
+    const size_t total = (size_t)nv * per_view;
+    const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);   // 256 CUs x 16, grid-stride
+    if (blocks == 0) continue;                           // patch-major with S / P == 0 cannot happen (S >= P)
+#define SGL_PV(U8, T)                                                                                                \
+  hipLaunchKernelGGL((sgl::preprocess_views_kernel<U8, T>), dim3(blocks), dim3(256), 0, s, src, (T*)dst, chunk, nv, Hs, \
+                     Ws, S, P, Kp, patch_major, mean, inv_std)
+    if (src_is_u8_nhwc) {
+      if (out_dtype == SGL_DTYPE_BF16) SGL_PV(true, sgl::bf16);
+      else if (out_dtype == SGL_DTYPE_F16) SGL_PV(true, sgl::f16);
+      else SGL_PV(true, float);
+    } else {
+      if (out_dtype == SGL_DTYPE_BF16) SGL_PV(false, sgl::bf16);
+      else if (out_dtype == SGL_DTYPE_F16) SGL_PV(false, sgl::f16);
+      else SGL_PV(false, float);
+    }
+#undef SGL_PV
+  }
   return hipGetLastError() == hipSuccess ? SGL_OK : SGL_ERR_HIP;
 }
 

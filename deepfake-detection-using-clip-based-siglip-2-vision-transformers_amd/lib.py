@@ -68,6 +68,10 @@ class SglCastVec(C.Structure):
     _fields_ = [("src", _fp), ("dst", _fp), ("n", C.c_int), ("np", C.c_int)]
 
 
+class SglView(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("src", "x0", "y0", "x1", "y1", "turns", "keep_canvas", "flip")]
+
+
 _lib = None
 
 
@@ -176,6 +180,9 @@ def load():
     _sig(lib, "sgl_op_preprocess_bwd_scratch_bytes", sz, [i, i, i, i])
     _sig(lib, "sgl_op_preprocess_bwd", i, [_fp, i, i, i, i, f, _fp, f, _fp, _fp, sz, _fp])
     _sig(lib, "sgl_op_preprocess_aug", i, [_fp, i, i, i, i, _fp, i, i, i, i, i, f, f, _fp, _fp, _fp])
+    _sig(lib, "sgl_op_preprocess_views_scratch_bytes", sz, [i, i])
+    _sig(lib, "sgl_op_preprocess_views", i, [_fp, i, i, i, i, C.POINTER(SglView), i, _fp, i, i, i, i, i, f, f, _fp, sz,
+                                             _fp])
     _sig(lib, "sgl_op_l2norm_tmean_fwd", i, [_fp, _fp, _fp, i, i, i, _fp])
     _sig(lib, "sgl_op_l2norm_tmean_bwd", i, [_fp, _fp, _fp, _fp, i, i, i, _fp])
     _sig(lib, "sgl_op_gate_mul", i, [_fp, _fp, _fp, sz, i, _fp])

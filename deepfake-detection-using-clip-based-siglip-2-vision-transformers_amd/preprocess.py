@@ -14,6 +14,9 @@ reference's CPU transform ``Resize + ToTensor`` produces).  Resampling is torch'
 (``F.interpolate(mode="bilinear", antialias=True)``, the arithmetic torchvision ``Resize(antialias=True)`` runs in the
 reference's CPU transform, cifake…:1795-1797); kornia itself is not installed here, so equality with ``K.Resize`` is
 "parity unpinned".  CUDA only: there is no CPU path.
+
+Inference side (appv3.py ``detect_core``): ``View`` / ``detect_views`` + ``views_to_patch_operand`` build the app's 9 crops, its
+90-degree rotated view and its 4 x 4 grid cells, 42 encoder rows per image, in one pass of ``sgl_op_preprocess_views``.
 """
 from __future__ import annotations
 
@@ -225,6 +228,170 @@ def augment_to_patch_operand(images: torch.Tensor, config, params: list, size: O
     S, patch = _patch_geometry(config, size)
     out = _transform(images, S, patch, _operand_dtype(compute_dtype), mean, std, params=params)
     return PatchOperand(out, images.shape[0], S, S)
+
+
+# ---- test-time views of the app (appv3.py:3214-3250 detect_core, :3315 make_multicrops, :3381 compute_patch_grid) ------
+@dataclass(frozen=True)
+class View:
+    """One window onto source image ``src``: the half-open crop ``box = (x0, y0, x1, y1)`` (PIL's ``crop``), ``turns``
+    counter-clockwise quarter turns (exact, extents swapping, or with ``keep_canvas`` what PIL's
+    ``rotate(90 * turns)`` leaves on the crop's own canvas), then an optional left-right ``flip``.  The rules are in
+    ``include/siglip_hip.h`` (``sgl_view``)."""
+    src: int
+    box: tuple
+    turns: int = 0
+    keep_canvas: bool = False
+    flip: bool = False
+
+    def oriented_hw(self):
+        x0, y0, x1, y1 = self.box
+        swap = self.turns % 2 == 1 and not self.keep_canvas
+        return (x1 - x0, y1 - y0) if swap else (y1 - y0, x1 - x0)
+
+
+def view_table(views, B: int, Hs: int, Ws: int):
+    """Pack ``views`` into the host table of ``sgl_view`` records ``sgl_op_preprocess_views`` reads (a ctypes array), and
+    raise ``ValueError`` for every record the C side would refuse as a bad shape."""
+    views = list(views)
+    if not views:
+        raise ValueError("at least one view is needed")
+    tab = (_lib.SglView * len(views))()
+    for n, v in enumerate(views):
+        if not isinstance(v, View):
+            raise ValueError(f"view {n}: not a View: {v!r}")
+        fields = (v.src, *v.box, v.turns, v.keep_canvas, v.flip)
+        if len(v.box) != 4 or any(isinstance(f, float) or int(f) != f for f in fields):
+            raise ValueError(f"view {n}: src, the four box coordinates and turns must be integers: {v!r}")
+        x0, y0, x1, y1 = (int(t) for t in v.box)
+        if not 0 <= v.src < B:
+            raise ValueError(f"view {n}: src {v.src} outside the batch of {B}")
+        if not (0 <= x0 < x1 <= Ws and 0 <= y0 < y1 <= Hs):
+            raise ValueError(f"view {n}: box {tuple(v.box)} is empty or outside the {Ws} x {Hs} (w x h) source")
+        if v.turns not in (0, 1, 2, 3):
+            raise ValueError(f"view {n}: turns must be 0..3 (counter-clockwise quarter turns), got {v.turns}")
+        if v.keep_canvas not in (0, 1) or v.flip not in (0, 1):
+            raise ValueError(f"view {n}: keep_canvas and flip are flags")
+        tab[n] = _lib.SglView(int(v.src), x0, y0, x1, y1, int(v.turns), int(v.keep_canvas), int(v.flip))
+    return tab
+
+
+def _views_transform(images, views, size, patch, dtype, mean, std) -> torch.Tensor:
+    """The launches behind the two view transforms (one per 64 views): ``patch`` as in ``_transform``."""
+    src, is_u8, B, Hs, Ws = _source(images)
+    dev = src.device
+    tab = view_table(views, B, Hs, Ws)
+    V = len(tab)
+    if patch is None:
+        out, layout = torch.empty((V, 3, size, size), device=dev, dtype=dtype), (size, 1, 3, 0)
+    else:
+        P, Kp = patch
+        out, layout = torch.empty((V * (size // P) ** 2, Kp), device=dev, dtype=dtype), (size, P, Kp, 1)
+    nbytes = _lib.load().sgl_op_preprocess_views_scratch_bytes(V, size)
+    scratch = torch.empty(nbytes, device=dev, dtype=torch.uint8) if nbytes else None
+    _lib.call("sgl_op_preprocess_views", dev, src.data_ptr(), is_u8, B, Hs, Ws, tab, V, out.data_ptr(),
+              _lib.dtype_code(dtype), *layout, float(mean), float(std), _lib.ptr(scratch), nbytes)
+    return out
+
+
+def views_resize_normalize(images: torch.Tensor, views, size: int, mean: float = 0.5, std: float = 0.5,
+                           dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """(V,3,size,size): every ``View`` of the same-size sources ``images`` cropped, turned, mirrored, resized (antialias)
+    and normalised in one pass: what the app builds per window with PIL ``crop`` / ``rotate`` and
+    ``Resize -> ToTensor -> Normalize``.  Inference only: a source that requires grad is refused."""
+    _refuse_grad(images, "views_resize_normalize")
+    return _views_transform(images, views, size, None, dtype, mean, std)
+
+
+def views_to_patch_operand(images: torch.Tensor, views, config, size: Optional[int] = None, compute_dtype: str = "bf16",
+                           mean: float = 0.5, std: float = 0.5) -> PatchOperand:
+    """The views written straight into the patch GEMM's operand (see ``to_patch_operand``): ``PatchOperand(batch=V)`` for
+    ``SiglipVisionModelHIP(patches=...)`` / ``encode_image(patches=...)``, one encoder batch of V rows."""
+    _refuse_grad(images, "views_to_patch_operand")
+    S, patch = _patch_geometry(config, size)
+    views = list(views)
+    out = _views_transform(images, views, S, patch, _operand_dtype(compute_dtype), mean, std)
+    return PatchOperand(out, len(views), S, S)
+
+
+CROP_WEIGHTS = (0.20, 0.10, 0.10, 0.10, 0.10, 0.10, 0.10, 0.10, 0.10)
+
+
+def multicrop_views(h: int, w: int, src: int = 0):
+    """The app's 9-crop ensemble (``make_multicrops``, appv3.py:3315-3350) of an ``h x w`` image: centre (half size), left,
+    right, top, bottom and the four quadrants, with the ``(9,)`` weights ``[0.20, 0.10 x 8]``.  For ``w < 4`` or ``h < 4``
+    one full view with weight 1 (the app resizes that one bicubically: a stated deviation, this path has one filter)."""
+    if w < 4 or h < 4:
+        return [View(src, (0, 0, w, h))], torch.tensor([1.0])
+    mw, mh = w // 2, h // 2
+    cx0, cy0 = (w - mw) // 2, (h - mh) // 2
+    boxes = [(cx0, cy0, cx0 + mw, cy0 + mh), (0, 0, mw, h), (w - mw, 0, w, h), (0, 0, w, mh), (0, h - mh, w, h),
+             (0, 0, mw, mh), (w - mw, 0, w, mh), (0, h - mh, mw, h), (w - mw, h - mh, w, h)]
+    return [View(src, b) for b in boxes], torch.tensor(CROP_WEIGHTS, dtype=torch.float32)
+
+
+def rotated_view(box, src: int = 0) -> View:
+    """The app's dual-view stabiliser input, ``pil.rotate(90, expand=False)`` of the window ``box`` (appv3.py:3241)."""
+    return View(src, tuple(box), turns=1, keep_canvas=True)
+
+
+def patch_grid_views(h: int, w: int, rows: int = 4, cols: int = 4, src: int = 0, min_side: int = 64) -> list:
+    """The cell boxes of the app's heat-map grid (``compute_patch_grid``, appv3.py:3381-3405), row-major: cells of
+    ``pw = max(8, w // cols)`` by ``ph = max(8, h // rows)``, the last row and column extended to the edge, an empty cell
+    ``None``.  Below ``min_side`` (the app's MIN_SIDE) on either side the app computes no grid: ``[]``."""
+    if w < min_side or h < min_side:
+        return []
+    pw, ph = max(8, w // cols), max(8, h // rows)
+    out = []
+    for r in range(rows):
+        for c in range(cols):
+            x0, y0 = c * pw, r * ph
+            x1 = w if c == cols - 1 else min(w, x0 + pw)
+            y1 = h if r == rows - 1 else min(h, y0 + ph)
+            out.append(None if x1 <= x0 or y1 <= y0 else View(src, (x0, y0, x1, y1)))
+    return out
+
+
+@dataclass
+class DetectViews:
+    """The app's whole view set for one image, and where each family sits in it.  ``views[crops]`` are the multi-crop
+    windows (``weights`` their ``(C,)`` weights), ``views[rot]`` the rotated full frame; grid cell ``n`` (row-major, empty
+    cells skipped: ``cells`` lists the kept (row, col)) is ``views[grid_start + 2 n]`` followed by its rotated view."""
+    views: list
+    weights: torch.Tensor
+    crops: slice
+    rot: int
+    grid_start: int
+    cells: list
+
+    @property
+    def grid(self) -> slice:
+        """The unrotated cell views."""
+        return slice(self.grid_start, len(self.views), 2)
+
+    @property
+    def grid_rot(self) -> slice:
+        """The cells' rotated views."""
+        return slice(self.grid_start + 1, len(self.views), 2)
+
+
+def detect_views(h: int, w: int, grid=(4, 4), src: int = 0) -> DetectViews:
+    """Everything ``detect_core`` + ``compute_patch_grid`` look at for one ``h x w`` image, as one list for one
+    ``views_to_patch_operand`` call: the 9 crops, the rotated full frame, then every non-empty grid cell followed by its
+    rotated view (9 + 1 + 2 * 16 = 42 encoder rows for the 4 x 4 grid).  With logits ``z`` (V,) of that batch:
+    ``core_signals_batched(z[d.crops][None], d.weights, z_freqs, z[d.rot][None], ...)`` is the image's verdict and
+    ``core_signals_batched(z[d.grid][:, None], ones(1), z_freqs_cells, z[d.grid_rot], ...)`` the cells' (multicrop=False)."""
+    crops, weights = multicrop_views(h, w, src)
+    views = list(crops)
+    rot = len(views)
+    views.append(rotated_view((0, 0, w, h), src))
+    start = len(views)
+    cells = []
+    rows, cols = grid
+    for n, cell in enumerate(patch_grid_views(h, w, rows, cols, src)):
+        if cell is not None:
+            cells.append((n // cols, n % cols))
+            views += [cell, rotated_view(cell.box, src)]
+    return DetectViews(views, weights, slice(0, rot), rot, start, cells)
 
 
 class GpuTransform(nn.Module):

@@ -433,6 +433,53 @@ size_t sgl_op_preprocess_bwd_scratch_bytes(int B, int Hs, int Ws, int S);
 int sgl_op_preprocess_bwd(const float* d_out, int B, int Hs, int Ws, int S, float std, const int* mix_index, float lam,
                           float* d_src, void* scratch, size_t scratch_bytes, sgl_stream stream);
 
+/* ---- test-time views (new symbols; sgl_abi_version() stays 3: nothing existing changed) -------------------------------
+ * The app's inference-side windows (appv3.py:3214-3250 detect_core, :3315 make_multicrops, :3381 compute_patch_grid):
+ * V views of B same-size sources (layouts as sgl_op_preprocess) in one pass, inference only (no backward).  A view is
+ * an integer crop box, an optional quarter turn and an optional mirror; the result is resized to S x S, normalised and
+ * stored as out[v][c][y][x] (patch_major == 0) or as the patch GEMM's operand rows out[(v*g + gy)*g + gx][k]
+ * (patch_major != 0, g = S / P, columns >= 3*P*P exactly zero): sgl_op_preprocess's two layouts with b = v.
+ *
+ * Record constraints: 0 <= src < B; 0 <= x0 < x1 <= Ws and 0 <= y0 < y1 <= Hs (half-open, as PIL's crop);
+ * turns in 0..3, counter-clockwise quarter turns (PIL's sign); keep_canvas and flip in {0, 1}.
+ * With C the crop (h x w), the oriented image O is
+ *   1. turns == 0: O = C;
+ *   2. turns > 0, keep_canvas == 0: O = C rotated exactly (numpy.rot90(C, turns); PIL transpose(ROTATE_90) applied
+ *      `turns` times; rotate(expand=True)): the extents swap for odd turns;
+ *   3. turns > 0, keep_canvas == 1: O = what PIL's C.rotate(90 * turns) returns with its defaults (expand=False, nearest,
+ *      fill 0), the reference's rotated view.  The canvas stays h x w.  For turns == 2, or when w == h, this is the exact
+ *      rotation; otherwise the centre part of the rotated crop is kept and the rest is zero:
+ *        turns == 1:  O[y][x] = C[x + ((h - w + 1) >> 1)][((w + h - 1) >> 1) - y]
+ *        turns == 3:  O[y][x] = C[((w + h - 1) >> 1) - x][y + ((w - h + 1) >> 1)]
+ *      where the indices fall inside C, zero elsewhere (>> is the arithmetic shift: floor).  When w - h is odd the centre
+ *      falls on half pixels and this truncation decides which columns are kept: a w = 8, h = 5 crop at one turn gives
+ *      O[y][x] = C[x - 1][6 - y] for x in 1..5 and zero for x in {0, 6, 7}.  Zero is pixel value 0 in [0, 1], so
+ *      -mean / std after normalisation;
+ *   4. flip == 1: O mirrored left-right (after the turn).
+ * O is then resized to S x S with the arithmetic of sgl_op_preprocess (torch's antialiased triangle filter, `in` = O's
+ * extents) and normalised as (v - mean) / std.  The kernel runs the same filter code, so the full-frame view
+ * (0, 0, Ws, Hs) without turn or flip equals sgl_op_preprocess on the same source bit for bit, and a plain crop equals
+ * sgl_op_preprocess on the contiguous cropped copy bit for bit, in both layouts and every output dtype.
+ *
+ * views is a HOST pointer (read during the call, not afterwards; the records reach the device by value in the kernel
+ * arguments, 64 per launch: no allocation, no synchronisation, no copy, the caller's stream only, graph-capturable).
+ * scratch: sgl_op_preprocess_views_scratch_bytes() bytes of device memory; this design needs none (0; scratch may be NULL).
+ * Refused before anything is enqueued, out untouched: src, views or out NULL -> SGL_ERR_NULL; V <= 0, a record outside
+ * the constraints above, or sgl_op_preprocess's shape rules (dimensions >= 1, std != 0, patch_major: P >= 1, S >= P,
+ * Kp >= 3*P*P) -> SGL_ERR_BAD_SHAPE; an out_dtype other than F32 / BF16 / F16 -> SGL_ERR_UNSUPPORTED; an oriented extent
+ * above 16 * S on either axis (the tap-length cap of sgl_op_preprocess) -> SGL_ERR_UNSUPPORTED; scratch_bytes below the
+ * reported size -> SGL_ERR_WORKSPACE.
+ * Deviations from the app, stated: PIL rounds to 8 bits after each resize pass and this path does not (within
+ * 1.05 / 255 of PIL's BILINEAR resize on uint8 sources); the frequency features (extract_freq_vector) and the MAX_SIDE
+ * pre-shrink stay on the host; the sources of one call share one size (ragged batches: one call per size). */
+typedef struct sgl_view {
+  int32_t src, x0, y0, x1, y1, turns, keep_canvas, flip;
+} sgl_view;
+size_t sgl_op_preprocess_views_scratch_bytes(int V, int S);
+int sgl_op_preprocess_views(const void* src, int src_is_u8_nhwc, int B, int Hs, int Ws, const sgl_view* views, int V,
+                            void* out, int out_dtype, int S, int P, int Kp, int patch_major, float mean, float std,
+                            void* scratch, size_t scratch_bytes, sgl_stream stream);
+
 /* Augmentation branch of the video trainer's GPU transform (hidf_video_classifier.py:2868-2874): K.Resize(S, antialias) ->
  * RandomHorizontalFlip -> RandomRotation(+-5 deg, bilinear, zeros outside) -> ColorJitter -> K.Normalize, one pass, same
  * sources / outputs as sgl_op_preprocess.  Random draws stay with the caller: aug is a DEVICE table of B samples.
