@@ -419,6 +419,20 @@ class CoralCalibrator:
 
 
 @torch.no_grad()
+def app_freq_logits(images_u8: torch.Tensor, d, freq_mlp: nn.Module, jitter: bool = False):
+    """``(z_freqs (1, C), z_freqs_cells (G, 1))``: the frequency-MLP logits `detect_core` computes per crop and
+    `compute_patch_grid` per cell (appv3.py:3226-3237), in the shapes `core_signals_batched` takes for the image and for its
+    cells.  ``d`` is `preprocess.detect_views(h, w)` of the one uint8 NHWC image ``images_u8``; one
+    `preprocess.views_freq_features` pass over ``d.freq`` (the app's `extract_freq_vector` of every window) and one
+    ``freq_mlp`` (`FreqMLPApp`) forward.  The app's eval-mode jitter is off unless ``jitter=True``."""
+    from . import preprocess as _pp
+    feats = _pp.views_freq_features(images_u8, [d.views[n] for n in d.freq])
+    z = freq_mlp(feats, jitter=jitter)
+    C = len(range(len(d.views))[d.crops])
+    return z[:C][None], z[C:][:, None]
+
+
+@torch.no_grad()
 def core_signals_batched(z_sigs: torch.Tensor, crop_weights: torch.Tensor, z_freqs: torch.Tensor, z_rot: torch.Tensor,
                          fusion_head: nn.Module, coral: "CoralCalibrator", freq_temp: float = 1.25,
                          coral_temp: float = 1.0) -> dict:

@@ -17,9 +17,12 @@ reference's CPU transform, cifake…:1795-1797); kornia itself is not installed 
 
 Inference side (appv3.py ``detect_core``): ``View`` / ``detect_views`` + ``views_to_patch_operand`` build the app's 9 crops, its
 90-degree rotated view and its 4 x 4 grid cells, 42 encoder rows per image, in one pass of ``sgl_op_preprocess_views``.
+``views_freq_features`` is the app's 24-D frequency / SRM vector (``extract_freq_vector``) of the crops and cells, one pass
+of ``sgl_op_freq_features``; ``heads.app_freq_logits`` turns it into the ``z_freqs`` of ``core_signals_batched``.
 """
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass
 from typing import Optional
 
@@ -373,13 +376,20 @@ class DetectViews:
         """The cells' rotated views."""
         return slice(self.grid_start + 1, len(self.views), 2)
 
+    @property
+    def freq(self) -> list:
+        """Indices of the views the app takes frequency features from (``extract_freq_vector``): ``crops``, then ``grid``."""
+        return list(range(len(self.views))[self.crops]) + list(range(len(self.views))[self.grid])
+
 
 def detect_views(h: int, w: int, grid=(4, 4), src: int = 0) -> DetectViews:
     """Everything ``detect_core`` + ``compute_patch_grid`` look at for one ``h x w`` image, as one list for one
     ``views_to_patch_operand`` call: the 9 crops, the rotated full frame, then every non-empty grid cell followed by its
     rotated view (9 + 1 + 2 * 16 = 42 encoder rows for the 4 x 4 grid).  With logits ``z`` (V,) of that batch:
     ``core_signals_batched(z[d.crops][None], d.weights, z_freqs, z[d.rot][None], ...)`` is the image's verdict and
-    ``core_signals_batched(z[d.grid][:, None], ones(1), z_freqs_cells, z[d.grid_rot], ...)`` the cells' (multicrop=False)."""
+    ``core_signals_batched(z[d.grid][:, None], ones(1), z_freqs_cells, z[d.grid_rot], ...)`` the cells' (multicrop=False),
+    with ``z_freqs, z_freqs_cells = heads.app_freq_logits(images_u8, d, freq_mlp)`` (one ``views_freq_features`` pass over
+    ``d.freq`` and one ``FreqMLPApp`` forward): all of ``detect_core`` stays on the device."""
     crops, weights = multicrop_views(h, w, src)
     views = list(crops)
     rot = len(views)
@@ -392,6 +402,103 @@ def detect_views(h: int, w: int, grid=(4, 4), src: int = 0) -> DetectViews:
             cells.append((n // cols, n % cols))
             views += [cell, rotated_view(cell.box, src)]
     return DetectViews(views, weights, slice(0, rot), rot, start, cells)
+
+
+# ---- the app's 24-D frequency / SRM feature vectors (appv3.py:1618-1728 extract_freq_vector) -----------------------------
+FREQ_MAX_SIDE = 4096      # window side cap of sgl_op_freq_features (65 resize taps)
+
+
+def _freq_tables():
+    """The three (256, 256) uint8 index tables over the fftshift-ed plane, by the app's own torch calls and dtypes
+    (``fft_features``, appv3.py:1640-1684): band 0..2, log-radius bucket 0..38, sector 0..7; 255 = member of none."""
+    h = w = 256
+    cy, cx = h // 2, w // 2
+    yy, xx = torch.meshgrid(torch.arange(h), torch.arange(w), indexing="ij")
+    r = torch.sqrt((yy - cy) ** 2 + (xx - cx) ** 2)
+    rmax = float(r.max())
+    r1, r2 = 0.15 * rmax, 0.45 * rmax
+    band = torch.full((h, w), 2, dtype=torch.uint8)
+    band[(r > r1) & (r <= r2)] = 1
+    band[r <= r1] = 0
+    rb = torch.logspace(math.log10(1.0), math.log10(rmax + 1.0), 40)
+    ridx = (torch.bucketize(r.flatten() + 1.0, rb) - 1).view(h, w)
+    bucket = torch.where((ridx >= 0) & (ridx < 39), ridx, torch.full_like(ridx, 255)).to(torch.uint8)
+    ang = torch.atan2(yy - cy, xx - cx)
+    sector = torch.full((h, w), 255, dtype=torch.uint8)
+    for n in range(8):
+        a0 = -math.pi + n * (2 * math.pi / 8)            # numpy.linspace(-pi, pi, 8, endpoint=False)[n]: start + n * step
+        sector[(ang >= a0) & (ang < a0 + math.pi / 4)] = n
+    return band, bucket, sector
+
+
+class FreqGeometry:
+    """Owner of the index tables ``sgl_op_freq_features`` reduces against: built once on the host, uploaded once per
+    device as one (3, 256, 256) uint8 tensor and kept for the process (192 KiB per device)."""
+
+    def __init__(self):
+        self._host = None
+        self._device = {}
+
+    def host(self):
+        if self._host is None:
+            self._host = _freq_tables()
+        return self._host
+
+    def on(self, device) -> torch.Tensor:
+        key = torch.device(device)
+        if key not in self._device:
+            self._device[key] = torch.stack(self.host()).contiguous().to(key)
+        return self._device[key]
+
+
+_freq_geometry = FreqGeometry()
+
+
+def freq_geometry():
+    """``(band, bucket, sector)``: the (256, 256) uint8 masks of the spectral features over the fftshift-ed plane (centre
+    (128, 128)): the radial band 0..2 (``r <= 0.15 rmax``, ``<= 0.45 rmax``, above), the log-radius bucket 0..38 of the
+    slope fit and the 45-degree sector 0..7 of the anisotropy; 255 where a pixel belongs to none."""
+    return _freq_geometry.host()
+
+
+def freq_geometry_on(device) -> torch.Tensor:
+    """The (3, 256, 256) uint8 device copy of ``freq_geometry()`` that ``sgl_op_freq_features`` takes as its ``geometry``
+    argument: uploaded once per device and kept."""
+    return _freq_geometry.on(device)
+
+
+def views_freq_features(images_u8: torch.Tensor, views, standardize: bool = True, return_gray: bool = False):
+    """(V, 24) float32: the app's frequency / SRM vector (``extract_freq_vector``: 7 spectral, 8 wavelet, 9 SRM values,
+    standardised unless ``standardize=False``) of every plain ``View`` (a crop box; no turn, no flip) of the same-size uint8
+    NHWC sources, in one ``sgl_op_freq_features`` pass.  ``return_gray=True`` also returns the (V, 256, 256) uint8 planes,
+    bit for bit PIL's ``crop(box).convert("L").resize((256, 256), BICUBIC)``.  Inference only."""
+    if _wants_grad(images_u8):
+        raise ValueError("views_freq_features is not differentiable (integer gray plane, histogram); detach the source or "
+                         "run under torch.no_grad(), and pass uint8 NHWC images")
+    if images_u8.dtype != torch.uint8:
+        raise ValueError(f"views_freq_features reads uint8 NHWC sources only (the app's PIL images), got {images_u8.dtype}; "
+                         "convert with (images * 255).round().to(torch.uint8).permute(0, 2, 3, 1)")
+    if images_u8.dim() != 4 or images_u8.shape[-1] != 3:
+        raise ValueError(f"uint8 images must be NHWC (B,H,W,3), got {tuple(images_u8.shape)}")
+    B, Hs, Ws = images_u8.shape[0], images_u8.shape[1], images_u8.shape[2]
+    tab = view_table(views, B, Hs, Ws)
+    for n, v in enumerate(tab):
+        if v.turns or v.keep_canvas or v.flip:
+            raise ValueError(f"view {n}: the frequency features are taken from unrotated, unmirrored windows only (as the "
+                             "app does); pass View(src, box), and use views_resize_normalize for turned or flipped views")
+        if v.x1 - v.x0 > FREQ_MAX_SIDE or v.y1 - v.y0 > FREQ_MAX_SIDE:
+            raise ValueError(f"view {n}: window side above {FREQ_MAX_SIDE}; shrink the source first (the app's MAX_SIDE "
+                             "pre-shrink) or split the window")
+    src, _, B, Hs, Ws = _source(images_u8)
+    dev = src.device
+    V = len(tab)
+    out = torch.empty((V, 24), device=dev, dtype=torch.float32)
+    gray = torch.empty((V, 256, 256), device=dev, dtype=torch.uint8) if return_gray else None
+    nbytes = _lib.load().sgl_op_freq_features_scratch_bytes(V, Hs, Ws)
+    scratch = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    _lib.call("sgl_op_freq_features", dev, src.data_ptr(), B, Hs, Ws, tab, V, freq_geometry_on(dev).data_ptr(),
+              out.data_ptr(), int(bool(standardize)), _lib.ptr(gray), scratch.data_ptr(), nbytes)
+    return (out, gray) if return_gray else out
 
 
 class GpuTransform(nn.Module):

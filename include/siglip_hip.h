@@ -470,8 +470,9 @@ int sgl_op_preprocess_bwd(const float* d_out, int B, int Hs, int Ws, int S, floa
  * above 16 * S on either axis (the tap-length cap of sgl_op_preprocess) -> SGL_ERR_UNSUPPORTED; scratch_bytes below the
  * reported size -> SGL_ERR_WORKSPACE.
  * Deviations from the app, stated: PIL rounds to 8 bits after each resize pass and this path does not (within
- * 1.05 / 255 of PIL's BILINEAR resize on uint8 sources); the frequency features (extract_freq_vector) and the MAX_SIDE
- * pre-shrink stay on the host; the sources of one call share one size (ragged batches: one call per size). */
+ * 1.05 / 255 of PIL's BILINEAR resize on uint8 sources); the MAX_SIDE pre-shrink stays on the host (the frequency
+ * features, extract_freq_vector, are sgl_op_freq_features below); the sources of one call share one size (ragged
+ * batches: one call per size). */
 typedef struct sgl_view {
   int32_t src, x0, y0, x1, y1, turns, keep_canvas, flip;
 } sgl_view;
@@ -479,6 +480,53 @@ size_t sgl_op_preprocess_views_scratch_bytes(int V, int S);
 int sgl_op_preprocess_views(const void* src, int src_is_u8_nhwc, int B, int Hs, int Ws, const sgl_view* views, int V,
                             void* out, int out_dtype, int S, int P, int Kp, int patch_major, float mean, float std,
                             void* scratch, size_t scratch_bytes, sgl_stream stream);
+
+/* ---- frequency / SRM feature vectors (new symbols; sgl_abi_version() stays 3: nothing existing changed) ----------------
+ * The app's 24 numbers per window (appv3.py:1618-1728 extract_freq_vector, DETECT_USE_CLAHE off), which detect_core feeds
+ * FreqMLP for each of its 9 crops and each grid cell: V windows onto B same-size uint8 NHWC sources in one pass,
+ * inference only.  A window is an sgl_view with turns == keep_canvas == flip == 0 (the app takes these features from
+ * unrotated windows only).  out is V x 24 floats; per view, in this order:
+ *   a. the gray plane, bit for bit PIL's crop(box).convert("L").resize((256, 256), BICUBIC):
+ *      L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16, then PIL's two uint8 passes, horizontal then vertical: bicubic
+ *      a = -0.5, support = 2 * max(in / 256, 1), taps clamped to the box (nothing outside it is read), weights
+ *      normalised by their sequential sum in double, converted to 22-bit fixed point rounding half away from zero, each
+ *      pass clip8((sum k p + 2^21) >> 22).  The coefficients are computed on the device, one output index per thread, in
+ *      fp64 with contraction off (add, mul, div only: IEEE-exact, so they are PIL's integers);
+ *   b. exact-integer statistics of that plane: the three SRM kernels (zero padding k / 2, normalised by abs-sum + 1e-6)
+ *      give integers times 1 / (255 abs-sum), the two db1 levels (2 x 2 blocks, factor 1/2; cH along height, cV along
+ *      width, cD both) integers times 1 / 510 and 1 / 1020; sum n .. n^4 and the eight sum c^2 are taken in 64-bit
+ *      integers, the central moments in 128-bit integers, then mean, population variance, kurtosis m4 / (v + 1e-6)^2 and
+ *      mean |c|^2 in double;
+ *   c. the 256 x 256 FFT of plane / 255, transformed in fp64 (twiddles from a table made in double) and rounded to fp32
+ *      bin by bin, so that a bin's error is its own rounding and not a fraction of the DC term's; from the fp32 |F| and
+ *      angle(F) over the fftshift-ed plane: the band sums El, Em, Eh (ratios to their total + 1e-6, and
+ *      (Eh + 1e-6) / (El + 1e-6)), the
+ *      least-squares slope over bucket index 0..38 of the bucket means of log(|F| + 1e-6) (empty buckets count as 0), the
+ *      entropy of the 50-bin histogram of the phase over [-pi, pi] (the maximum joins the last bin; the app's fp32
+ *      formula with its 1e-6 terms), and the population variance of the 8 sector means of |F|;
+ *   d. the 24 values 7 spectral, 8 wavelet, 9 SRM; with standardize != 0, (v - mean) / (std + 1e-6) of the fp32 vector
+ *      with the unbiased std, all zeros when std < 1e-6.
+ * geometry: DEVICE pointer to 3 x 256 x 256 bytes, the band (0..2), bucket (0..38) and sector (0..7) index of every pixel
+ * of the fftshift-ed plane, 255 = member of none (the DC pixel's bucket, the atan2 == pi half-row's sector).  The caller
+ * builds them once with the app's own torch calls and keeps them (preprocess.freq_geometry); the kernels only reduce.
+ * This argument is the one addition to the signature first proposed for this entry: a call that allocates nothing and
+ * copies nothing cannot own 192 KiB of device tables.
+ * All floating sums have a fixed order (no float atomics; integer atomics for the histogram and the integer sums): two
+ * calls give the same bits.  gray_out, when not NULL, receives the V gray planes (V x 256 x 256 bytes).
+ * views is a HOST pointer read during the call; records reach the device in the kernel arguments, 64 per launch group
+ * (seven launches per 64 views).  scratch: sgl_op_freq_features_scratch_bytes() bytes of device memory, owned by the caller,
+ * 16-byte aligned (SGL_ERR_UNSUPPORTED otherwise), contents undefined before and after.  No allocation, no
+ * synchronisation, the caller's stream only.
+ * Refused before anything is enqueued, out and gray_out untouched: src, views, geometry, out (or a needed scratch) NULL
+ * -> SGL_ERR_NULL; B, Hs, Ws or V <= 0, src outside the batch, an empty box or one outside the source ->
+ * SGL_ERR_BAD_SHAPE; a view with turns, keep_canvas or flip set, or a window side above 4096 (the resize stays within
+ * 65 taps) -> SGL_ERR_UNSUPPORTED; scratch_bytes below the reported size -> SGL_ERR_WORKSPACE.
+ * Not covered: CLAHE, float sources, a backward pass, the app's optional forensic detectors. */
+size_t sgl_op_freq_features_scratch_bytes(int V, int Hs, int Ws);
+int sgl_op_freq_features(const void* src_u8_nhwc, int B, int Hs, int Ws, const sgl_view* views, int V,
+                         const unsigned char* geometry, float* out /* V x 24 */, int standardize,
+                         unsigned char* gray_out /* V x 256 x 256 or NULL */, void* scratch, size_t scratch_bytes,
+                         sgl_stream stream);
 
 /* Augmentation branch of the video trainer's GPU transform (hidf_video_classifier.py:2868-2874): K.Resize(S, antialias) ->
  * RandomHorizontalFlip -> RandomRotation(+-5 deg, bilinear, zeros outside) -> ColorJitter -> K.Normalize, one pass, same
