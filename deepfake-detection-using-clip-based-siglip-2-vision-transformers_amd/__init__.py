@@ -7,4 +7,6 @@ from .config import SiglipVisionConfig, get_config, NAMED_CONFIGS  # noqa: F401
 from .encoder import (SiglipVisionModelHIP, OpenClipStyleEncoder, create_model_and_transforms,  # noqa: F401
                       VisionModelOutput)
 from .ddp import GradBucketReducer  # noqa: F401
+from .head_ops import seg_eval_from_lowres  # noqa: F401
+from .heads import MaskMetrics  # noqa: F401
 from .optim import FusedAdamW, global_grad_norm, ExponentialMovingAverage  # noqa: F401

@@ -14,6 +14,12 @@
 //   bce  = mean over all pixels of the selected images of  max(z,0) - z t + log(1 + exp(-|z|))
 //   dice = 1 - mean_b( 2 sum(p t) / (sum p + sum t + eps) ),  p = sigmoid(z)
 //   loss = bce_w * bce + dice_w * dice
+//
+//   seg_eval       the validation half (Siglip2sidafrozen.py:183-240,1078-1106,1424-1569): per masked image, how many
+//                  foreground / background pixels have their up-sampled logit between consecutive cut values, plus one
+//                  4096-bin logit histogram per class for the pixel AUC.  Dice / IoU at any of the cuts, the threshold sweep
+//                  and the AUC are all functions of those integer counts (heads.MaskMetrics); one read of the mask and of
+//                  the g x g logits, integer atomics only (order-independent sums: bitwise reproducible), no host sync.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -179,6 +185,111 @@ __global__ __launch_bounds__(256) void seg_loss_bwd_kernel(const float* __restri
   }
 }
 
+// ---- seg_eval ----------------------------------------------------------------------------------------------------------
+// One block per (image, band of SEG_EVAL_ROWS output rows).  A band is one contiguous run of mask elements, so it is walked
+// as a flat array: scalar elements up to the first 16-byte boundary, 16-byte vectors (4 floats / 16 bytes of mask), a scalar
+// tail; any element alignment of the mask works.  Counters live in LDS (32-bit: a band has < 2^31 pixels) and are flushed
+// once per block, non-zero bins only, consecutive lanes to consecutive bins: up-sampled logits are smooth, so the bins a
+// band touches are a few contiguous runs.  The per-cut histogram has only K+1 bins per class (a wave's 64 lanes would pile
+// onto two or three addresses), so it is kept in SEG_EVAL_COPIES copies indexed by lane.
+constexpr int SEG_EVAL_ROWS = 64;
+constexpr int SEG_EVAL_COPIES = 8;
+constexpr int SEG_EVAL_KMAX = 64;
+constexpr int SEG_EVAL_NB = SGL_SEG_EVAL_AUC_BINS;
+
+template <bool AUC>
+__device__ __forceinline__ void seg_eval_count(float z, int c, const float* cs, int* hl, unsigned* al) {
+  // k = number of cuts strictly below z (cs is padded to 64 entries with +inf; NaN compares false: k = 0)
+  int k = 0;
+#pragma unroll
+  for (int step = SEG_EVAL_KMAX; step > 0; step >>= 1)
+    if (k + step <= SEG_EVAL_KMAX && cs[k + step - 1] < z) k += step;
+  atomicAdd(&hl[c * (SEG_EVAL_KMAX + 1) + k], 1);
+  if (AUC) {
+    const float f = (z + 16.0f) * ((float)SEG_EVAL_NB / 32.0f);
+    int bin = 0;                                                 // NaN and everything below -16
+    if (f >= 0.0f) bin = f < (float)SEG_EVAL_NB ? (int)f : SEG_EVAL_NB - 1;
+    atomicAdd(&al[c * SEG_EVAL_NB + bin], 1u);
+  }
+}
+
+__device__ __forceinline__ int seg_eval_class(float t) { return t > 0.5f ? 1 : 0; }
+__device__ __forceinline__ int seg_eval_class(uint8_t t) { return t ? 1 : 0; }      // an integer above 0.5 is one that is not 0
+
+template <typename TT, bool AUC>
+__global__ __launch_bounds__(256) void seg_eval_kernel(const float* __restrict__ lr /*[B][g][g]*/,
+                                                       const TT* __restrict__ tgt /*[B][S][S]*/,
+                                                       const uint8_t* __restrict__ sel, const float* __restrict__ cuts,
+                                                       int K, int32_t* __restrict__ hist,
+                                                       unsigned long long* __restrict__ auc, int g, int S, float scale,
+                                                       int bands) {
+  constexpr int VEC = 16 / (int)sizeof(TT);
+  constexpr int HL = 2 * (SEG_EVAL_KMAX + 1);
+  __shared__ float cs[SEG_EVAL_KMAX];
+  __shared__ int hl[SEG_EVAL_COPIES][HL];
+  __shared__ unsigned al[AUC ? 2 * SEG_EVAL_NB : 1];
+  const int b = blockIdx.x / bands, band = blockIdx.x - b * bands;
+  if (sel && !sel[b]) return;                                    // its hist row was zeroed by the entry point
+  const int tid = threadIdx.x;
+  if (tid < SEG_EVAL_KMAX) cs[tid] = tid < K ? cuts[tid] : __builtin_inff();
+  for (int i = tid; i < SEG_EVAL_COPIES * HL; i += 256) (&hl[0][0])[i] = 0;
+  if (AUC)
+    for (int i = tid; i < 2 * SEG_EVAL_NB; i += 256) al[i] = 0u;
+  __syncthreads();
+
+  const float* L = lr + (size_t)b * g * g;
+  const int r0 = band * SEG_EVAL_ROWS, r1 = r0 + SEG_EVAL_ROWS < S ? r0 + SEG_EVAL_ROWS : S;
+  const TT* P = tgt + (size_t)b * S * S + (size_t)r0 * S;        // the band: n contiguous elements
+  const int n = (r1 - r0) * S;
+  int head = (int)(((16u - (unsigned)((uintptr_t)P & 15u)) & 15u) / (unsigned)sizeof(TT));
+  if (head > n) head = n;
+  const int nvec = (n - head) / VEC;
+  int* myh = hl[tid & (SEG_EVAL_COPIES - 1)];
+
+  auto pixel = [&](int i, int j, int c) {                        // i: output row (absolute), j: output column
+    int y0, y1, x0, x1;
+    float wy, wx;
+    bil_src(i, scale, g, y0, y1, wy);
+    bil_src(j, scale, g, x0, x1, wx);
+    const float top = L[y0 * g + x0] * (1.f - wx) + L[y0 * g + x1] * wx;
+    const float bot = L[y1 * g + x0] * (1.f - wx) + L[y1 * g + x1] * wx;
+    const float z = top * (1.f - wy) + bot * wy;
+    seg_eval_count<AUC>(z, c, cs, myh, al);
+  };
+
+  for (int v = tid; v < nvec; v += 256) {
+    const int idx = head + v * VEC;
+    alignas(16) TT t[VEC];
+    *reinterpret_cast<uint4*>(t) = *reinterpret_cast<const uint4*>(P + idx);
+    int i = idx / S, j = idx - i * S;
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) {
+      pixel(r0 + i, j, seg_eval_class(t[e]));
+      if (++j == S) { j = 0; ++i; }
+    }
+  }
+  const int rest = n - nvec * VEC;                               // head + tail scalars, fewer than 2 * VEC
+  for (int t = tid; t < rest; t += 256) {
+    const int idx = t < head ? t : nvec * VEC + t;
+    const int i = idx / S, j = idx - i * S;
+    pixel(r0 + i, j, seg_eval_class(P[idx]));
+  }
+  __syncthreads();
+
+  for (int i = tid; i < 2 * (K + 1); i += 256) {
+    const int c = i / (K + 1), k = i - c * (K + 1);
+    int v = 0;
+#pragma unroll
+    for (int q = 0; q < SEG_EVAL_COPIES; ++q) v += hl[q][c * (SEG_EVAL_KMAX + 1) + k];
+    if (v) atomicAdd(&hist[((size_t)b * 2 + c) * (K + 1) + k], v);
+  }
+  if (AUC)
+    for (int i = tid; i < 2 * SEG_EVAL_NB; i += 256) {
+      const unsigned v = al[i];
+      if (v) atomicAdd(&auc[i], (unsigned long long)v);
+    }
+}
+
 }  // namespace sgl
 
 extern "C" {
@@ -239,6 +350,38 @@ int sgl_op_seg_loss_bwd(const float* logits_lr, const float* targets, const floa
   if (B <= 0 || g <= 0 || S <= 0 || g > 4096 || S > 8192) return SGL_ERR_BAD_SHAPE;
   hipLaunchKernelGGL(sgl::seg_loss_bwd_kernel, dim3((unsigned)(B * g)), dim3(256), (size_t)S * 2 * sizeof(float),
                      (hipStream_t)stream, logits_lr, targets, sums, coef, dlogits_lr, g, S, (float)g / (float)S, eps);
+  return hipGetLastError() == hipSuccess ? SGL_OK : SGL_ERR_HIP;
+}
+
+int sgl_op_seg_eval_auc_bins(void) { return SGL_SEG_EVAL_AUC_BINS; }
+
+int sgl_op_seg_eval(const float* logits_lr, const void* targets, int target_dtype, const uint8_t* sel, const float* cuts,
+                    int K, int32_t* hist, unsigned long long* auc_hist, int B, int g, int S, sgl_stream stream) {
+  if (!logits_lr || !targets || !cuts || !hist) return SGL_ERR_NULL;
+  if (B <= 0 || g <= 0 || S <= 0 || K < 1 || K > sgl::SEG_EVAL_KMAX || S > 32768 || g > 32768) return SGL_ERR_BAD_SHAPE;
+  if (target_dtype != SGL_DTYPE_F32 && target_dtype != SGL_DTYPE_U8) return SGL_ERR_UNSUPPORTED;
+  if (target_dtype == SGL_DTYPE_F32 && ((uintptr_t)targets & 3)) return SGL_ERR_BAD_SHAPE;
+  const int bands = (S + sgl::SEG_EVAL_ROWS - 1) / sgl::SEG_EVAL_ROWS;
+  if ((long long)B * bands > 0x7fffffffLL) return SGL_ERR_BAD_SHAPE;
+  hipStream_t s = (hipStream_t)stream;
+  if (hipMemsetAsync(hist, 0, (size_t)B * 2 * (K + 1) * sizeof(int32_t), s) != hipSuccess) return SGL_ERR_HIP;
+  const dim3 grid((unsigned)(B * bands)), block(256);
+  const float scale = (float)g / (float)S;
+  if (target_dtype == SGL_DTYPE_F32) {
+    if (auc_hist)
+      hipLaunchKernelGGL((sgl::seg_eval_kernel<float, true>), grid, block, 0, s, logits_lr, (const float*)targets, sel, cuts,
+                         K, hist, auc_hist, g, S, scale, bands);
+    else
+      hipLaunchKernelGGL((sgl::seg_eval_kernel<float, false>), grid, block, 0, s, logits_lr, (const float*)targets, sel, cuts,
+                         K, hist, auc_hist, g, S, scale, bands);
+  } else {
+    if (auc_hist)
+      hipLaunchKernelGGL((sgl::seg_eval_kernel<uint8_t, true>), grid, block, 0, s, logits_lr, (const uint8_t*)targets, sel,
+                         cuts, K, hist, auc_hist, g, S, scale, bands);
+    else
+      hipLaunchKernelGGL((sgl::seg_eval_kernel<uint8_t, false>), grid, block, 0, s, logits_lr, (const uint8_t*)targets, sel,
+                         cuts, K, hist, auc_hist, g, S, scale, bands);
+  }
   return hipGetLastError() == hipSuccess ? SGL_OK : SGL_ERR_HIP;
 }
 

@@ -1,6 +1,6 @@
 """The HIP-backed operations of the heads: autograd Functions over the ``sgl_op_*`` kernels and, for each, ONE dispatcher that
 holds the rule for when the kernel is eligible and the torch composition used when it is not: ``linear_tokens``,
-``depthwise3x3``, ``gate_mul``, ``bce_dice_loss_from_lowres``, ``l2norm_temporal_mean``.  Every launch goes through
+``depthwise3x3``, ``gate_mul``, ``bce_dice_loss_from_lowres``, ``seg_eval_from_lowres``, ``l2norm_temporal_mean``.  Every launch goes through
 ``lib.call`` (guard and stream of the device the operands live on).  ``heads.py`` holds the modules and losses built on these.
 """
 from __future__ import annotations
@@ -307,6 +307,72 @@ def bce_dice_loss_from_lowres(logit_lr: torch.Tensor, masks: torch.Tensor, has_m
     if has_mask is None:
         has_mask = torch.ones(logit_lr.shape[0], dtype=torch.bool, device=logit_lr.device)
     return _SegLossFromLowresFn.apply(logit_lr, masks, has_mask, float(bce_w), float(dice_w), float(eps))
+
+
+def check_cuts(cuts) -> None:
+    """The contract `sgl_op_seg_eval` leaves to its caller: 1..64 finite-or-infinite (never NaN), strictly increasing cuts."""
+    c = [float(v) for v in cuts]
+    if not 1 <= len(c) <= 64:
+        raise ValueError(f"seg_eval takes 1 to 64 cuts, not {len(c)}")
+    if any(v != v for v in c) or any(b <= a for a, b in zip(c, c[1:])):
+        raise ValueError("seg_eval cuts must be strictly increasing")
+
+
+@torch.no_grad()
+@torch.compiler.disable
+def seg_eval_from_lowres(logit_lr: torch.Tensor, masks: torch.Tensor, has_mask: torch.Tensor = None, cuts=None,
+                         auc_hist: torch.Tensor = None) -> torch.Tensor:
+    """Per-image pixel counts between consecutive logit cuts, straight from the (B,1,g,g) logits of
+    `SegFormerMaskDecoder(..., return_lowres=True)`: `hist[b, c, k]` (int32, (B, 2, K+1)) is the number of pixels of class
+    c (1 where `masks` > 0.5) of image b whose bilinearly up-sampled logit z has exactly k of the K cuts strictly below it,
+    so `z > cuts[j]` holds for the pixels with k > j.  One HIP launch (csrc/decoder_tail.hip: seg_eval), no host
+    synchronisation, the (B,1,S,S) logits are never formed.  CUDA only.
+
+    logit_lr   fp32 / bf16 / fp16, upcast to fp32 as `bce_dice_loss_from_lowres` does (the same fp32 z).
+    masks      (B,1,S,S) or (B,S,S); float (any float dtype, read as fp32), uint8 or bool (read as bytes).
+    has_mask   (B,) selection; images outside it get an all-zero row (None: every image).
+    cuts       strictly increasing logit values, K <= 64: a sequence or CPU tensor is checked and uploaded; a CUDA fp32
+               tensor is used as it is (checking it would need a synchronisation: the order is then the caller's contract).
+    auc_hist   optional (2, 4096) int64 CUDA tensor that the launch ADDS to: per class, pixels per logit bin of width 1/128
+               on [-16, 16) (`lib.SEG_EVAL_AUC_BINS` bins; outside values in the end bins, NaN in bin 0)."""
+    if not logit_lr.is_cuda or not masks.is_cuda:
+        raise RuntimeError("seg_eval_from_lowres runs on the GPU (HIP kernels); MaskMetrics.update_from_hist takes counts "
+                           "made elsewhere")
+    if cuts is None:
+        raise ValueError("seg_eval_from_lowres needs the logit cuts")
+    dev = logit_lr.device
+    B, g = logit_lr.shape[0], logit_lr.shape[-1]
+    S = masks.shape[-1]
+    if logit_lr.numel() != B * g * g or masks.numel() != B * S * S:
+        raise ValueError(f"expected (B,1,g,g) logits and (B,1,S,S) masks, got {tuple(logit_lr.shape)} and {tuple(masks.shape)}")
+    lr = logit_lr.detach().reshape(B, g, g).float().contiguous()
+    if masks.dtype == torch.bool:
+        t, tcode = masks.contiguous().view(torch.uint8), _lib.SGL_DTYPE_U8
+    elif masks.dtype == torch.uint8:
+        t, tcode = masks.contiguous(), _lib.SGL_DTYPE_U8
+    elif masks.dtype.is_floating_point:
+        t, tcode = masks.float().contiguous(), _lib.SGL_DTYPE_F32
+    else:
+        raise ValueError(f"masks must be float, uint8 or bool, not {masks.dtype}")
+    if isinstance(cuts, torch.Tensor) and cuts.is_cuda:
+        if cuts.dtype != torch.float32 or cuts.dim() != 1 or not 1 <= cuts.numel() <= 64 or cuts.device != dev:
+            raise ValueError("device cuts must be a 1-D fp32 tensor of 1 to 64 values on the logits' device")
+        c = cuts.contiguous()
+    else:
+        vals = cuts.tolist() if isinstance(cuts, torch.Tensor) else list(cuts)
+        check_cuts(vals)
+        c = torch.tensor(vals, dtype=torch.float32).to(dev)
+    K = c.numel()
+    sel = None if has_mask is None else has_mask.to(device=dev, dtype=torch.uint8).contiguous()
+    if sel is not None and sel.numel() != B:
+        raise ValueError(f"has_mask must have {B} entries")
+    if auc_hist is not None and (auc_hist.dtype != torch.int64 or tuple(auc_hist.shape) != (2, _lib.SEG_EVAL_AUC_BINS)
+                                 or not auc_hist.is_contiguous() or auc_hist.device != dev):
+        raise ValueError(f"auc_hist must be a contiguous (2, {_lib.SEG_EVAL_AUC_BINS}) int64 tensor on the logits' device")
+    hist = torch.empty(B, 2, K + 1, device=dev, dtype=torch.int32)
+    _lib.call("sgl_op_seg_eval", dev, lr.data_ptr(), t.data_ptr(), tcode, _lib.ptr(sel), c.data_ptr(), K, hist.data_ptr(),
+              _lib.ptr(auc_hist), B, g, S)
+    return hist
 
 
 # ---------------------------------------------------------------------------------------------------------

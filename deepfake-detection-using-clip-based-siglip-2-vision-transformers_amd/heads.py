@@ -21,7 +21,9 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .config import isqrt_exact
-from .head_ops import bce_dice_loss_from_lowres, depthwise3x3, gate_mul, l2norm_temporal_mean, linear_tokens
+from . import lib as _lib
+from .head_ops import (bce_dice_loss_from_lowres, depthwise3x3, gate_mul, l2norm_temporal_mean, linear_tokens,
+                       seg_eval_from_lowres)
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -539,6 +541,192 @@ def dice_iou_from_logits(logits, targets, thr: float = 0.5, eps: float = 1e-6):
     union = (p_bin + targets - p_bin * targets).sum(dim=(1, 2, 3)) + eps
     dice = 2 * inter / (p_bin.sum(dim=(1, 2, 3)) + targets.sum(dim=(1, 2, 3)) + eps)
     return dice.detach().cpu().tolist(), (inter / union).detach().cpu().tolist(), p_bin
+
+
+class MaskMetrics:
+    """The localisation numbers of the SID validation loop (Siglip2sidafrozen.py:1424-1569) accumulated on the device from
+    the LOW-RESOLUTION logits of `SigLIP2MTL.forward(..., return_lowres=True)`: Dice / IoU at `mask_thr`
+    (`dice_iou_from_logits`, :183-189), the threshold sweep (`sweep_mask_thresholds`, :204-240) and the pixel AUC
+    (`PixelAUCBuffer`, :1078-1106).  All three are functions of integer pixel counts that one HIP launch per batch produces
+    (`head_ops.seg_eval_from_lowres`); `update` never synchronises with the host, `compute` does once.
+
+    Cuts.  The reference predicts `sigmoid(z) > thr` on fp32 tensors; here a pixel is predicted when `z > logit(float32(thr))`
+    (the logit formed in float64 and rounded to fp32).  The thresholds are `np.linspace(thr_min, thr_max, thr_steps)` plus
+    `mask_thr`; they may come in any order and may repeat: the cuts are their sorted, de-duplicated logits and every
+    threshold keeps the index of its cut, so the sweep still scans in the order given (ascending for the defaults).
+
+    State (all additive, so `merge`, or `all_reduce(SUM)` on each tensor of `state()`, combines data-parallel ranks):
+    `tp`, `fp`, `fn` int64 (K,) over all masked images; `dice_sum`, `iou_sum` float64 (K,), the sums over images of the
+    per-image Dice / IoU; `count` int64 (3,) = masked images, foreground pixels, background pixels; `auc_hist` int64
+    (2, 4096).
+
+    Differences from the reference, all deliberate: the AUC is over ALL pixels (binned to 1/128 in logit, ties inside a bin
+    counted one half; `pix_auc_halfwidth` bounds what the binning can hide) instead of a 400 000-pixel reservoir sample;
+    soft masks are thresholded at 0.5 (SID masks are {0,1}); per-image ratios are formed in float64, not fp32.
+    Out of scope: `--use_morphological_postprocess` (a Kornia opening on the full-resolution probabilities),
+    `--early_exit_thresh` (a caller can zero the low-res rows of the skipped images: the bilinear map of zeros is zeros),
+    overlays and plots."""
+
+    STATE_KEYS = ("tp", "fp", "fn", "dice_sum", "iou_sum", "count", "auc_hist")
+
+    def __init__(self, thr_min: float = 0.1, thr_max: float = 0.9, thr_steps: int = 17, mask_thr: float = 0.5,
+                 eps: float = 1e-6):
+        self.sweep_thresholds = np.linspace(thr_min, thr_max, thr_steps)
+        self.mask_thr, self.eps = float(mask_thr), float(eps)
+        thr = np.concatenate([self.sweep_thresholds, [self.mask_thr]])
+        if not np.all((thr > 0) & (thr < 1)):
+            raise ValueError("mask thresholds must lie strictly between 0 and 1")
+        t32 = thr.astype(np.float32).astype(np.float64)
+        logits = np.log(t32 / (1.0 - t32)).astype(np.float32)
+        cuts, index = np.unique(logits, return_inverse=True)             # sorted, duplicates removed, thr -> cut
+        if len(cuts) > 64:
+            raise ValueError(f"{len(cuts)} distinct thresholds: sgl_op_seg_eval takes at most 64 cuts")
+        self.cuts = cuts
+        self.sweep_index, self.mask_index = index[:-1].astype(np.int64), int(index[-1])
+        self._cuts_dev = {}          # device -> (pinned host copy, device copy)
+        self._state = None
+
+    # ---- state ---------------------------------------------------------------------------------------------------
+    def _zeros(self, device):
+        K, i64, f64 = len(self.cuts), torch.int64, torch.float64
+        return {"tp": torch.zeros(K, dtype=i64, device=device), "fp": torch.zeros(K, dtype=i64, device=device),
+                "fn": torch.zeros(K, dtype=i64, device=device), "dice_sum": torch.zeros(K, dtype=f64, device=device),
+                "iou_sum": torch.zeros(K, dtype=f64, device=device), "count": torch.zeros(3, dtype=i64, device=device),
+                "auc_hist": torch.zeros(2, _lib.SEG_EVAL_AUC_BINS, dtype=i64, device=device)}
+
+    def _ensure(self, device):
+        if self._state is None:
+            self._state = self._zeros(device)
+        elif self._state["tp"].device != torch.device(device):
+            raise RuntimeError(f"MaskMetrics state lives on {self._state['tp'].device}, the update is on {device}")
+        return self._state
+
+    def reset(self):
+        self._state = None
+
+    def state(self) -> dict:
+        """The accumulated tensors (on the device of the updates; zeros on the CPU before the first one)."""
+        return dict(self._state if self._state is not None else self._zeros("cpu"))
+
+    def load_state(self, state: dict):
+        ref = self._zeros("cpu")
+        for k in self.STATE_KEYS:
+            if tuple(state[k].shape) != tuple(ref[k].shape) or state[k].dtype != ref[k].dtype:
+                raise ValueError(f"state['{k}'] must be {ref[k].dtype} {tuple(ref[k].shape)}")
+        self._state = {k: state[k].clone() for k in self.STATE_KEYS}
+        return self
+
+    def merge(self, other: "MaskMetrics"):
+        """Add another accumulator's state (same thresholds) to this one."""
+        if not np.array_equal(self.cuts, other.cuts) or not np.array_equal(self.sweep_index, other.sweep_index) \
+                or self.mask_index != other.mask_index:
+            raise ValueError("merge needs accumulators built with the same thresholds")
+        if other._state is not None:
+            mine = self._ensure(other._state["tp"].device if self._state is None else self._state["tp"].device)
+            for k in self.STATE_KEYS:
+                mine[k] += other._state[k].to(mine[k].device)
+        return self
+
+    # ---- accumulation ----------------------------------------------------------------------------------------------
+    def device_cuts(self, device) -> torch.Tensor:
+        """The fp32 cuts on `device`, uploaded once from pinned memory without blocking the host."""
+        device = torch.device(device)
+        if device not in self._cuts_dev:
+            host = torch.from_numpy(self.cuts.copy())
+            if device.type == "cuda":
+                host = host.pin_memory()
+            self._cuts_dev[device] = (host, host.to(device, non_blocking=True))
+        return self._cuts_dev[device][1]
+
+    @torch.no_grad()
+    def update(self, logit_lr: torch.Tensor, masks: torch.Tensor, has_mask: torch.Tensor = None):
+        """One validation batch: (B,1,g,g) low-res logits, (B,1,S,S) masks, (B,) has_mask.  One kernel launch and a few
+        ops on (B, K+1) integers; nothing is copied to the host."""
+        st = self._ensure(logit_lr.device)
+        hist = seg_eval_from_lowres(logit_lr, masks, has_mask, cuts=self.device_cuts(logit_lr.device),
+                                    auc_hist=st["auc_hist"])
+        return self.update_from_hist(hist, has_mask)
+
+    @torch.no_grad()
+    def update_from_hist(self, hist: torch.Tensor, has_mask: torch.Tensor = None, auc_hist: torch.Tensor = None):
+        """Accumulate from counts made elsewhere: `hist` (B, 2, K+1) as `seg_eval_from_lowres` returns it (any integer or
+        float dtype, any device; rows of images outside `has_mask` are ignored), optionally a (2, 4096) `auc_hist` to add."""
+        K = len(self.cuts)
+        if hist.dim() != 3 or hist.shape[1] != 2 or hist.shape[2] != K + 1:
+            raise ValueError(f"hist must be (B, 2, {K + 1}), got {tuple(hist.shape)}")
+        st = self._ensure(hist.device)
+        h = hist.to(torch.int64)
+        if has_mask is not None:
+            w = has_mask.to(device=h.device, dtype=torch.int64)
+            h = h * w[:, None, None]
+            n_img = w.sum()
+        else:
+            n_img = torch.full((), h.shape[0], dtype=torch.int64, device=h.device)
+        above = h.flip(-1).cumsum(-1).flip(-1)          # above[b, c, k] = pixels of class c with at least k cuts below z
+        tp, fp = above[:, 1, 1:], above[:, 0, 1:]       # predicted at cut j  <=>  k >= j + 1
+        fg, bg = above[:, 1, 0], above[:, 0, 0]
+        fn = fg[:, None] - tp
+        tpf, pred, fgf = tp.double(), (tp + fp).double(), fg.double()[:, None]
+        dice = 2.0 * tpf / (pred + fgf + self.eps)      # dice_iou_from_logits' eps placement, per image
+        iou = tpf / ((pred + fgf - tpf) + self.eps)
+        st["tp"] += tp.sum(0)
+        st["fp"] += fp.sum(0)
+        st["fn"] += fn.sum(0)
+        st["dice_sum"] += dice.sum(0)                   # images outside has_mask contribute 0 / eps = 0
+        st["iou_sum"] += iou.sum(0)
+        st["count"] += torch.stack([n_img, fg.sum(), bg.sum()])
+        if auc_hist is not None:
+            st["auc_hist"] += auc_hist.to(device=h.device, dtype=torch.int64)
+        return self
+
+    # ---- results -----------------------------------------------------------------------------------------------------
+    def compute(self) -> dict:
+        """One device-to-host copy, then the reference's arithmetic on counts.  Keys: `dice`, `iou` (mean over masked images
+        at `mask_thr`, 0.0 without any, as :1546-1547), `best` (the dict of `sweep_mask_thresholds`), `thresholds`,
+        `f1_curve`, `dice_curve`, `iou_curve` (per sweep threshold), `pix_auc`, `pix_auc_halfwidth` (nan when a class has
+        no pixel, as `PixelAUCBuffer.auc`), `num_images`."""
+        st = self.state()
+        K = len(self.cuts)
+        packed = torch.cat([st["tp"], st["fp"], st["fn"], st["dice_sum"].view(torch.int64), st["iou_sum"].view(torch.int64),
+                            st["count"], st["auc_hist"].reshape(-1)]).cpu()
+        tp, fp, fn = (packed[i * K:(i + 1) * K].numpy() for i in range(3))
+        dice_sum = packed[3 * K:4 * K].view(torch.float64).numpy()
+        iou_sum = packed[4 * K:5 * K].view(torch.float64).numpy()
+        n_img, n_fg, n_bg = (int(v) for v in packed[5 * K:5 * K + 3])
+        auc_hist = packed[5 * K + 3:].reshape(2, -1).numpy()
+
+        mean = (lambda s: s / n_img) if n_img else (lambda s: np.zeros_like(s))
+        dice_c, iou_c = mean(dice_sum), mean(iou_sum)
+        denom = 2.0 * tp + fp + fn
+        f1_c = np.where(denom > 0, 2.0 * tp / np.maximum(denom, 1), 0.0)       # f1_score(..., zero_division=0)
+        if n_fg == 0 or n_bg == 0:                                             # `len(np.unique(mask_flat)) > 1` fails
+            f1_c = np.zeros_like(f1_c)
+        best = {"f1": 0, "dice": 0, "iou": 0, "thr_f1": 0.5, "thr_dice": 0.5, "thr_iou": 0.5}
+        curves = {"f1": [], "dice": [], "iou": []}
+        for thr, j in zip(self.sweep_thresholds, self.sweep_index):
+            vals = {"f1": float(f1_c[j]), "dice": float(dice_c[j]), "iou": float(iou_c[j])}
+            for name, v in vals.items():
+                curves[name].append(v)
+                if n_img and v > best[name]:                                   # strict >, in scan order (:230-238)
+                    best[name], best["thr_" + name] = v, float(thr)
+        out = {"dice": float(dice_c[self.mask_index]), "iou": float(iou_c[self.mask_index]), "best": best,
+               "thresholds": [float(t) for t in self.sweep_thresholds], "f1_curve": curves["f1"],
+               "dice_curve": curves["dice"], "iou_curve": curves["iou"], "num_images": n_img}
+        out["pix_auc"], out["pix_auc_halfwidth"] = self.auc_from_hist(auc_hist)
+        return out
+
+    @staticmethod
+    def auc_from_hist(auc_hist) -> Tuple[float, float]:
+        """(AUC, half-width) of a (2, NB) [background, foreground] histogram over increasing score bins: the probability that
+        a foreground pixel's bin is above a background pixel's, pairs in the same bin counted one half; the half-width
+        0.5 * sum_b pos_b neg_b / (P N) is the most the order inside the bins could add or take away."""
+        neg, pos = np.asarray(auc_hist[0], dtype=np.float64), np.asarray(auc_hist[1], dtype=np.float64)
+        P, N = pos.sum(), neg.sum()
+        if P == 0 or N == 0:
+            return float("nan"), float("nan")
+        below = np.cumsum(neg) - neg
+        same = float((pos * neg).sum())
+        return float(((pos * below).sum() + 0.5 * same) / (P * N)), float(0.5 * same / (P * N))
 
 
 class FocalLoss(nn.Module):

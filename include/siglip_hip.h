@@ -33,6 +33,7 @@ typedef void* sgl_stream; /* hipStream_t */
 
 enum { SGL_DTYPE_F32 = 0, SGL_DTYPE_BF16 = 1, SGL_DTYPE_BF16X3 = 2, SGL_DTYPE_F16 = 3, SGL_DTYPE_MXFP8 = 5 };
 /* code 4 is not assigned: sgl_create rejects it like every other unknown code */
+enum { SGL_DTYPE_U8 = 6 };   /* a STORAGE type only (the mask bytes sgl_op_seg_eval reads): never a compute dtype */
 
 typedef enum {
   SGL_OK = 0,
@@ -578,6 +579,30 @@ int sgl_op_seg_loss_fwd(const float* logits_lr, const float* targets, float* par
                         sgl_stream stream);
 int sgl_op_seg_loss_bwd(const float* logits_lr, const float* targets, const float* sums, const float* coef,
                         float* dlogits_lr, int B, int g, int S, float eps, sgl_stream stream);
+
+/* The localisation metrics of the validation loop (:183-240 dice_iou_from_logits / sweep_mask_thresholds, :1078-1106
+ * PixelAUCBuffer) as integer counts, again straight from the low-resolution logit map, in one pass and without a host
+ * synchronisation.  Per output pixel of every selected image:
+ *   z = the bilinear (align_corners=False) value of its four low-res logits, formed exactly as in sgl_op_seg_loss_fwd (the
+ *       loss and the metrics see the same fp32 logit);
+ *   c = 1 when its target is > 0.5, else 0 (SID masks are {0,1}, :908,913; a SOFT mask is thresholded at 0.5);
+ *   k = the number of cuts strictly below z, so  z > cuts[j]  <=>  j < k  (a NaN logit is below every cut: k = 0);
+ *   hist[b][c][k] += 1;
+ *   auc_hist[c][min(max(floor((z + 16) * NB / 32), 0), NB - 1)] += 1  with NB = SGL_SEG_EVAL_AUC_BINS: uniform bins of
+ *       width 1/128 on logits in [-16, 16), everything outside in the end bins, NaN in bin 0.
+ * logits_lr [B][g][g] fp32; targets [B][S][S] contiguous, target_dtype SGL_DTYPE_F32 or SGL_DTYPE_U8 (any element-aligned
+ * address: 16-byte loads start at the first 16-byte boundary of each 64-row band); sel [B] bytes, NULL = every image;
+ * cuts [K] fp32 in DEVICE memory, strictly increasing (the caller's contract: not checked here), 1 <= K <= 64.
+ * hist [B][2][K+1] int32 is OVERWRITTEN (an image with sel[b] == 0 gets an all-zero row); auc_hist [2][NB] unsigned 64-bit
+ * is ACCUMULATED into (zero it once per evaluation; images with sel[b] == 0 add nothing) and may be NULL, which skips it.
+ * All counters are integers added with atomics: the result does not depend on the order and is bitwise reproducible.
+ * Refused before anything is enqueued: logits_lr, targets, cuts or hist NULL -> SGL_ERR_NULL; B, g or S <= 0, K < 1,
+ * K > 64, S > 32768, g > 32768, fp32 targets not 4-byte aligned -> SGL_ERR_BAD_SHAPE; another target_dtype ->
+ * SGL_ERR_UNSUPPORTED. */
+#define SGL_SEG_EVAL_AUC_BINS 4096
+int sgl_op_seg_eval_auc_bins(void);   /* SGL_SEG_EVAL_AUC_BINS, for callers that bind the library without the header */
+int sgl_op_seg_eval(const float* logits_lr, const void* targets, int target_dtype, const uint8_t* sel, const float* cuts,
+                    int K, int32_t* hist, unsigned long long* auc_hist, int B, int g, int S, sgl_stream stream);
 
 /* ---- optimizer step tail -----------------------------------------------------------------
  * Replaces, for a list of fp32 tensors, the reference's per-step pair
