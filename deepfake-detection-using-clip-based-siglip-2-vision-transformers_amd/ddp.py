@@ -269,22 +269,31 @@ def all_gather_eval(*tensors: torch.Tensor, group=None):
     return outs[0] if len(outs) == 1 else tuple(outs)
 
 
+@torch.no_grad()
+def write_flat(tensors, flat: torch.Tensor) -> None:
+    """Scatter ``flat`` (the concatenation of ``tensors``, flattened) back into ``tensors`` (parameters or buffers of a
+    module).  The copy goes into the tensor ITSELF, never into its ``.data``: ``p.data`` is a new tensor with a version
+    counter of its own, so a copy into it leaves ``p._version`` where it was, and everything keyed on
+    ``(data_ptr, _version)`` (the encoder's weight shadows, the decoder's weight cache) would keep serving the casts of
+    the old values."""
+    off = 0
+    for t in tensors:
+        n = t.numel()
+        t.copy_(flat[off:off + n].view_as(t))
+        off += n
+
+
 def broadcast_parameters(module: torch.nn.Module, src: int = 0, group=None) -> None:
     """Rank ``src``'s parameters and buffers to every rank (one flat message per dtype)."""
     if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
         return
-    tensors = [p.data for p in module.parameters()] + [b.data for b in module.buffers()]
     by_dtype: dict[torch.dtype, list[torch.Tensor]] = {}
-    for t in tensors:
+    for t in [*module.parameters(), *module.buffers()]:
         by_dtype.setdefault(t.dtype, []).append(t)
     for ts in by_dtype.values():
-        flat = torch.cat([t.reshape(-1) for t in ts])
+        flat = torch.cat([t.detach().reshape(-1) for t in ts])
         dist.broadcast(flat, src=src, group=group)
-        off = 0
-        for t in ts:
-            n = t.numel()
-            t.copy_(flat[off:off + n].view_as(t))
-            off += n
+        write_flat(ts, flat)
 
 
 def shard_batch(global_batch: int, rank: int, world: int) -> tuple[int, int]:

@@ -41,8 +41,21 @@ class WeightCache:
             entry[2] = entry[1].t().contiguous()
         return entry[1], entry[2]
 
+    def drop(self, weight: torch.Tensor) -> bool:
+        """Forget ``weight``'s entry (the next ``get`` re-casts it); says whether there was one."""
+        return self._entries.pop(weight, None) is not None
+
 
 _weights = WeightCache()
+
+
+def invalidate_weights(module: torch.nn.Module) -> int:
+    """Drop the cached bf16 operands of every parameter of ``module`` (and its sub-modules): the decoder's counterpart of
+    ``WeightShadows.invalidate``.  Needed only after a write the key cannot see, which is an in-place write through
+    ``p.data`` (``p.data.copy_(...)``: ``p.data`` has a version counter of its own, so ``p._version`` and ``data_ptr``
+    both stay).  Returns the number of entries dropped.  A forward whose backward has not run yet keeps the operands it
+    used."""
+    return sum(_weights.drop(p) for p in module.parameters())
 _scratch: dict = {}       # device -> 64 MiB split-K scratch, reused by every call (stream-ordered)
 
 

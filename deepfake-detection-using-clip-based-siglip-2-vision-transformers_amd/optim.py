@@ -93,6 +93,11 @@ class FusedAdamW(torch.optim.Optimizer):
                     st["step"] = torch.tensor(0.0)
                     st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                     st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                for k in ("exp_avg", "exp_avg_sq"):
+                    # load_state_dict keeps the strides the state was saved with (a checkpoint written from a
+                    # channels_last model, loaded before or without model.to(memory_format=...)): same layout, as for .grad
+                    if st[k].stride() != p.stride():
+                        st[k] = torch.empty_like(p).copy_(st[k])
                 ents.append((p, st, group, gi))
         return ents
 
@@ -296,14 +301,23 @@ class ExponentialMovingAverage:
         _lib.call("sgl_op_ema", dev, table.data_ptr(), bmap.data_ptr(), nb, float(self.decay))
 
     def apply_shadow(self):
-        """Evaluate with the averaged weights: every tracked parameter points at its average until ``restore()``."""
+        """Evaluate with the averaged weights: every tracked parameter points at its average until ``restore()``.
+
+        The averages sit at fixed addresses and a ``.data`` swap leaves ``p._version`` alone, so two swaps with an
+        ``update()`` (or a checkpoint load into ``shadow``) between them would show the same ``(data_ptr, _version)`` to
+        everything that caches casts of the weights (the encoder's shadows, the decoder's weight cache), which would then
+        serve the casts of the OLD averages: every swap bumps the version of the parameters it re-points."""
         if self._live is not None:
             raise RuntimeError("apply_shadow() called twice without restore()")
         self._live = {}
+        swapped = []
         for n, p in self.model.named_parameters():
             if n in self.shadow:
                 self._live[n] = p.data
                 p.data = self.shadow[n]
+                swapped.append(p)
+        if swapped:
+            torch.autograd.graph.increment_version(swapped)
 
     def restore(self):
         if self._live is None:

@@ -55,6 +55,36 @@ def _worker(rank, world, port, q):
         ws = [torch.zeros_like(m.weight) for _ in range(world)]
         dist.all_gather(ws, m.weight.data)
         ok_bcast = torch.equal(ws[0], ws[1])
+        # a broadcast AFTER something read the weights (a warm-up forward, a sanity eval, a resume that loads and then
+        # re-broadcasts): every tensor's version must move on the receiving rank, or whatever caches casts keyed on
+        # (version, address) keeps the old values; the decoder's weight cache stands in for a forward here
+        m2 = torch.nn.Sequential(torch.nn.Linear(24, 9), torch.nn.BatchNorm1d(9))
+        with torch.no_grad():
+            m2[1].running_mean.fill_(float(rank + 1))
+            m2[1].num_batches_tracked.fill_(7 * (rank + 1))
+        cache = pkg.head_ops._weights
+        w_before, wt_before = (t.clone() for t in cache.get(m2[0].weight, want_t=True))
+        tensors = [*m2.parameters(), *m2.buffers()]
+        versions = [t._version for t in tensors]
+        mine = [t.detach().clone() for t in tensors]
+        pkg.ddp.broadcast_parameters(m2, src=0)
+        stale = [] if torch.equal(w_before[:9], mine[0].bfloat16()) else ["the read before the broadcast was wrong"]
+        for i, (t, own) in enumerate(zip(tensors, mine)):
+            got = [torch.zeros_like(own) for _ in range(world)]
+            dist.all_gather(got, own)
+            if not torch.equal(t.detach(), got[0]):
+                stale.append(f"tensor {i} is not rank 0's")
+            if rank != 0 and torch.equal(got[0], got[1]) and i < 2:
+                stale.append(f"tensor {i} did not differ between ranks: nothing tested")
+            if rank != 0 and t._version == versions[i]:
+                stale.append(f"tensor {i}: _version did not move")
+        w_after, wt_after = cache.get(m2[0].weight, want_t=True)
+        want = m2[0].weight.detach().bfloat16()
+        if not (torch.equal(w_after[:9], want) and not w_after[9:].any() and torch.equal(wt_after, w_after.t())):
+            stale.append("weight cache serves the values from before the broadcast")
+        if rank != 0 and torch.equal(w_after, w_before):
+            stale.append("weight cache entry unchanged on the receiving rank")
+        stale = "; ".join(stale)
         # bf16 wire with fp32 accumulation (all-to-all of shards + all-gather), deferred averaging, no_sync, async heads
         red2 = pkg.GradBucketReducer(wire="bf16", average="defer")
         b2 = [torch.randn(1001), torch.randn(64)]
@@ -104,7 +134,7 @@ def _worker(rank, world, port, q):
         ok_gather = all_lg.shape == (7, 2) and all_lb.tolist() == [0, 1, 2, 10, 11, 12, 13] and \
             torch.equal(all_lg[3:], torch.arange(8, dtype=torch.float32).view(4, 2) + 100)
         q.put((rank, ok_buckets, ok_head and ok_nosync and ok_wire and ok_acc and ok_gather, ok_bcast,
-               pkg.ddp.shard_batch(11, rank, world)))
+               pkg.ddp.shard_batch(11, rank, world), stale))
     finally:
         dist.destroy_process_group()
 
@@ -123,6 +153,7 @@ def test_bucket_reducer_world2_gloo():
         assert p.exitcode == 0
     assert res[0][1:4] == (True, True, True) and res[1][1:4] == (True, True, True)
     assert res[0][4] == (0, 6) and res[1][4] == (6, 11)      # whole images, contiguous, covering the batch
+    assert res[0][5] == "" and res[1][5] == "", (res[0][5], res[1][5])   # broadcast after a read: nothing stale
 
 
 def test_shard_batch_covers_everything():

@@ -2,6 +2,8 @@
 torch.nn.utils.clip_grad_norm_ followed by torch.optim.AdamW.step() (Siglip2sidafrozen.py:1396-1398), run on the CPU in
 fp32 on the same seeded tensors.  Floating point: the kernel follows torch's operation order; the only differences are
 fused multiply-adds and 1/x pre-computation of the two bias-correction factors -> tolerance 2e-6 relative."""
+import copy
+
 import pytest
 import torch
 
@@ -101,6 +103,38 @@ def test_state_dict_round_trips_with_torch_adamw():
     opt2.step()
     t.step()
     torch.testing.assert_close(p.detach(), q.detach(), rtol=2e-6, atol=1e-7)
+
+
+@pytest.mark.parametrize("param_cl,state_cl", [(False, True), (True, False)])
+def test_loaded_state_in_another_memory_format_than_its_parameter(param_cl, state_cl):
+    """``load_state_dict`` keeps the strides the moments were saved with.  A checkpoint written from a channels_last
+    model and loaded into a contiguous one (or the other way round) pairs moments and weights of different layouts: the
+    update is elementwise over storage, so the moments are first brought to the parameter's layout.  Against
+    torch.optim.AdamW (strided arithmetic) on the same values; (5, 3, 4, 2): the two layouts differ."""
+    pkg = entry.load_package()
+    fmt = lambda cl: torch.channels_last if cl else torch.contiguous_format
+    g = torch.Generator().manual_seed(5)
+    w0, g0, g1 = (torch.randn(5, 3, 4, 2, generator=g).cuda() for _ in range(3))
+    src_p = torch.nn.Parameter(w0.clone(memory_format=fmt(state_cl)))
+    src = pkg.FusedAdamW([src_p], lr=1e-2, weight_decay=0.1)
+    src_p.grad = g0.clone()
+    src.step()
+    assert src.state[src_p]["exp_avg"].stride() == src_p.stride()
+    p = torch.nn.Parameter(src_p.detach().clone(memory_format=fmt(param_cl)))
+    r = torch.nn.Parameter(src_p.detach().clone(memory_format=fmt(param_cl)))
+    assert p.stride() != src_p.stride()
+    opt = pkg.FusedAdamW([p], lr=1e-2, weight_decay=0.1)
+    ref = torch.optim.AdamW([r], lr=1e-2, weight_decay=0.1)
+    opt.load_state_dict(copy.deepcopy(src.state_dict()))           # (load_state_dict adopts the tensors it is given)
+    ref.load_state_dict(copy.deepcopy(src.state_dict()))
+    assert opt.state[p]["exp_avg"].stride() != p.stride()          # the case under test
+    p.grad, r.grad = g1.clone(), g1.clone()
+    opt.step()
+    ref.step()
+    assert opt.state[p]["exp_avg"].stride() == p.stride()
+    torch.testing.assert_close(p.detach(), r.detach(), rtol=2e-6, atol=1e-7)
+    torch.testing.assert_close(opt.state[p]["exp_avg"], ref.state[r]["exp_avg"], rtol=2e-6, atol=1e-9)
+    torch.testing.assert_close(opt.state[p]["exp_avg_sq"], ref.state[r]["exp_avg_sq"], rtol=2e-6, atol=1e-12)
 
 
 def test_global_grad_norm_and_errors():
