@@ -473,6 +473,30 @@ __device__ __forceinline__ float bwd_filter_sum(const float* __restrict__ g, con
   return acc;
 }
 
+// bwd_filter_sum for the three channels of one pixel (planes `plane` apart): each weight is evaluated once, the three
+// sums run side by side with bwd_filter_sum's operations in bwd_filter_sum's order, so three loads are in flight per tap
+__device__ __forceinline__ void bwd_filter_sum3(const float* __restrict__ g, size_t plane, const AaAxis* __restrict__ ty,
+                                                const AaAxis* __restrict__ tx, SrcSpan py, SrcSpan px, int y, int x, int S,
+                                                float* out) {
+  float acc[3] = {0.f, 0.f, 0.f};
+  for (int oy = py.first; oy < py.first + py.count; ++oy) {
+    const AaAxis ay = ty[oy];
+    const float* grow = g + (size_t)oy * S;
+    float row[3] = {0.f, 0.f, 0.f};
+    for (int ox = px.first; ox < px.first + px.count; ++ox) {
+      const AaAxis ax = tx[ox];
+      const float w = aa_w(ax, x - ax.lo);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) row[c] += w * grow[c * plane + ox];
+    }
+    const float wy = aa_w(ay, y - ay.lo);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) acc[c] += wy * row[c];
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) out[c] = acc[c];
+}
+
 __global__ __launch_bounds__(256) void preprocess_bwd_kernel(const float* __restrict__ d_out, float* __restrict__ d_src,
                                                              int B, int Hs, int Ws, int S, float inv_std,
                                                              const int* __restrict__ mix_index, float lam,
@@ -503,6 +527,124 @@ __global__ __launch_bounds__(256) void preprocess_bwd_kernel(const float* __rest
     }
     d_src[idx] = v * inv_std;
   }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Adjoint of preprocess_views_kernel<false, float>(patch_major = 0) with respect to a float source.  Every view is linear
+// in the source, out[v] = (Wy_v O_v Wx_v^T - mean) / std with O_v the oriented crop, so
+//     d_src[b] = (sum over {v : view v names image b} of orient_v^T (Wy_v^T G[v] Wx_v)) / std.
+// The same gather as preprocess_bwd_kernel: every source element (b, c, y, x) has one owner that sums its terms and stores
+// it once.  A thread owns the three channels of one source pixel (b, y, x): the map, the spans and the filter weights are
+// the same for the three, so they are evaluated once and three independent loads are in flight per tap (the loop is
+// bound by load latency, not bandwidth).  A block owns a 16 x 16 pixel tile, a wave four rows of 16: a wave's stores are
+// four 64-byte runs, and its reads of G are a few runs whether the view is turned or not (with a whole source row per
+// wave a view with an odd turn reads G with stride S, 64 lines per load).  The record loop is wave-uniform and the
+// records are kernel arguments.  For every record of its image whose box holds (x, y) the thread
+// inverts view_map (a signed permutation plus offset) to the oriented pixel (Y, X), drops the term when that falls off
+// the kept canvas, and adds bwd_filter_sum (as bwd_filter_sum3) over the two SrcSpans of (Y, X); a view with
+// oh == ow == S reads G[v][c][Y][X] (the forward's copy shortcut).  Order per element: view ascending, then oy, then ox;
+// one multiply by 1 / std at the end.
+// V > 64: one launch per 64 records on the caller's stream; the first stores the partial sum, each later one loads it,
+// goes on adding in the same order and stores it back, the last one scales: the bits of one long loop over all V.
+// Tables: per view that is not a copy, AaAxis[S] (y), AaAxis[S] (x), SrcSpan[oh], SrcSpan[ow] in caller scratch at the
+// byte offset that travels next to the record; one pre-pass launch per 64 records writes them (aa_axis / src_span).
+// ---------------------------------------------------------------------------------------------------------------
+struct ViewTableChunk {
+  size_t off[kViewChunk];
+};
+
+__host__ __device__ __forceinline__ size_t view_table_bytes(int oh, int ow, int S) {
+  if (oh == S && ow == S) return 0;                      // the copy shortcut reads no table
+  return bwd_span_offset(S) + ((size_t)oh + (size_t)ow) * sizeof(SrcSpan);
+}
+
+// grid: (blocks over the 2 S + oh + ow entries, views of the chunk)
+__global__ __launch_bounds__(256) void views_bwd_tables_kernel(char* __restrict__ scratch, const ViewChunk chunk,
+                                                               const ViewTableChunk tabs, int S) {
+  const int v = blockIdx.y;
+  int oh, ow;
+  view_extent(chunk.v[v], &oh, &ow);
+  if (oh == S && ow == S) return;
+  char* base = scratch + tabs.off[v];
+  AaAxis* ty = reinterpret_cast<AaAxis*>(base);
+  AaAxis* tx = ty + S;
+  SrcSpan* ry = reinterpret_cast<SrcSpan*>(base + bwd_span_offset(S));
+  SrcSpan* rx = ry + oh;
+  const float sy = (float)oh / (float)S, sx = (float)ow / (float)S;   // the forward's scales
+  const int total = 2 * S + oh + ow;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
+    if (i < S) ty[i] = aa_axis(i, oh, sy);
+    else if (i < 2 * S) tx[i - S] = aa_axis(i - S, ow, sx);
+    else if (i < 2 * S + oh) ry[i - 2 * S] = src_span(i - 2 * S, oh, S, sy);
+    else rx[i - 2 * S - oh] = src_span(i - 2 * S - oh, ow, S, sx);
+  }
+}
+
+constexpr int kBwdTile = 16;   // 16 x 16 pixels per block: kBwdTile * kBwdTile == the block's 256 threads
+
+// d_out: the rows of this chunk's first view onward.  first: store (no load); last: scale by inv_std
+__global__ __launch_bounds__(256) void preprocess_views_bwd_kernel(const float* __restrict__ d_out,
+                                                                   float* __restrict__ d_src,
+                                                                   const char* __restrict__ scratch,
+                                                                   const ViewChunk chunk, const ViewTableChunk tabs,
+                                                                   int nv, int B, int Hs, int Ws, int S, int first,
+                                                                   int last, float inv_std) {
+  const size_t src_plane = (size_t)Hs * Ws, plane = (size_t)S * S;
+  const int tiles_x = (Ws + kBwdTile - 1) / kBwdTile, tiles_y = (Hs + kBwdTile - 1) / kBwdTile;
+  const size_t tiles = (size_t)B * tiles_y * tiles_x;
+  for (size_t t = blockIdx.x; t < tiles; t += gridDim.x) {     // a block = one 16 x 16 tile of one source image
+    const int x = (int)(t % tiles_x) * kBwdTile + (int)(threadIdx.x % kBwdTile);
+    const int y = (int)((t / tiles_x) % tiles_y) * kBwdTile + (int)(threadIdx.x / kBwdTile);
+    const int b = (int)(t / ((size_t)tiles_x * tiles_y));
+    if (x >= Ws || y >= Hs) continue;
+    float* dst = d_src + (size_t)b * 3 * src_plane + (size_t)y * Ws + x;     // channel c at dst[c * src_plane]
+    float acc[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) acc[c] = first ? 0.f : dst[c * src_plane];
+    for (int v = 0; v < nv; ++v) {
+      const View& r = chunk.v[v];
+      if (r.src != b || x < r.x0 || x >= r.x1 || y < r.y0 || y >= r.y1) continue;
+      const ViewMap m = view_map(r);
+      // cx = ax + axx X + axy Y, cy = ay + ayx X + ayy Y with (axx, ayy) or (axy, ayx) the +-1 pair: its own inverse
+      const int dx = x - m.x0 - m.ax, dy = y - m.y0 - m.ay;
+      const int X = m.axx != 0 ? dx * m.axx : dy * m.ayx;
+      const int Y = m.axx != 0 ? dy * m.ayy : dx * m.axy;
+      if (X < 0 || X >= m.ow || Y < 0 || Y >= m.oh) continue;   // kept canvas, w != h: this crop pixel was cut off
+      const float* g = d_out + (size_t)v * 3 * plane;
+      if (m.oh == S && m.ow == S) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) acc[c] += g[c * plane + (size_t)Y * S + X];
+      } else {
+        const char* base = scratch + tabs.off[v];
+        const AaAxis* ty = reinterpret_cast<const AaAxis*>(base);
+        const AaAxis* tx = ty + S;
+        const SrcSpan* ry = reinterpret_cast<const SrcSpan*>(base + bwd_span_offset(S));
+        const SrcSpan* rx = ry + m.oh;
+        float f[3];
+        bwd_filter_sum3(g, plane, ty, tx, ry[Y], rx[X], Y, X, S, f);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) acc[c] += f[c];
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) dst[c * src_plane] = last ? acc[c] * inv_std : acc[c];
+  }
+}
+
+// the record checks sgl_op_preprocess_views and its adjoint share: SGL_OK, SGL_ERR_BAD_SHAPE or SGL_ERR_UNSUPPORTED
+static int views_check(const View* rec, int V, int B, int Hs, int Ws, int S) {
+  for (int v = 0; v < V; ++v) {
+    const View& r = rec[v];
+    if (r.src < 0 || r.src >= B || r.x0 < 0 || r.x0 >= r.x1 || r.x1 > Ws || r.y0 < 0 || r.y0 >= r.y1 || r.y1 > Hs ||
+        r.turns < 0 || r.turns > 3 || (r.keep_canvas | 1) != 1 || (r.flip | 1) != 1)
+      return SGL_ERR_BAD_SHAPE;
+  }
+  for (int v = 0; v < V; ++v) {
+    int oh, ow;
+    view_extent(rec[v], &oh, &ow);
+    if ((float)oh / (float)S > 16.f || (float)ow / (float)S > 16.f) return SGL_ERR_UNSUPPORTED;   // tap loops stay short
+  }
+  return SGL_OK;
 }
 
 }  // namespace sgl
@@ -552,18 +694,10 @@ int sgl_op_preprocess_views(const void* src, int src_is_u8_nhwc, int B, int Hs, 
   if (B <= 0 || Hs <= 0 || Ws <= 0 || S <= 0 || V <= 0 || std == 0.f) return SGL_ERR_BAD_SHAPE;
   if (patch_major && (P <= 0 || S < P || Kp < 3 * P * P)) return SGL_ERR_BAD_SHAPE;
   const sgl::View* rec = reinterpret_cast<const sgl::View*>(views);
-  for (int v = 0; v < V; ++v) {
-    const sgl::View& r = rec[v];
-    if (r.src < 0 || r.src >= B || r.x0 < 0 || r.x0 >= r.x1 || r.x1 > Ws || r.y0 < 0 || r.y0 >= r.y1 || r.y1 > Hs ||
-        r.turns < 0 || r.turns > 3 || (r.keep_canvas | 1) != 1 || (r.flip | 1) != 1)
-      return SGL_ERR_BAD_SHAPE;
-  }
+  const int rec_status = sgl::views_check(rec, V, B, Hs, Ws, S);
+  if (rec_status == SGL_ERR_BAD_SHAPE) return rec_status;
   if (out_dtype != SGL_DTYPE_BF16 && out_dtype != SGL_DTYPE_F16 && out_dtype != SGL_DTYPE_F32) return SGL_ERR_UNSUPPORTED;
-  for (int v = 0; v < V; ++v) {
-    int oh, ow;
-    sgl::view_extent(rec[v], &oh, &ow);
-    if ((float)oh / (float)S > 16.f || (float)ow / (float)S > 16.f) return SGL_ERR_UNSUPPORTED;   // tap loops stay short
-  }
+  if (rec_status != SGL_OK) return rec_status;
   if (scratch_bytes < sgl_op_preprocess_views_scratch_bytes(V, S)) return SGL_ERR_WORKSPACE;   // 0 bytes: never taken
   (void)scratch;
   const int g = patch_major ? S / P : 0;
@@ -592,6 +726,60 @@ int sgl_op_preprocess_views(const void* src, int src_is_u8_nhwc, int B, int Hs, 
       else SGL_PV(false, float);
     }
 #undef SGL_PV
+  }
+  return hipGetLastError() == hipSuccess ? SGL_OK : SGL_ERR_HIP;
+}
+
+size_t sgl_op_preprocess_views_bwd_scratch_bytes(const sgl_view* views, int V, int S) {
+  if (!views || V <= 0 || S <= 0) return 0;
+  const sgl::View* rec = reinterpret_cast<const sgl::View*>(views);
+  size_t bytes = 0;
+  for (int v = 0; v < V; ++v) {
+    int oh, ow;
+    sgl::view_extent(rec[v], &oh, &ow);
+    if (oh > 0 && ow > 0) bytes += sgl::view_table_bytes(oh, ow, S);   // an empty box is refused by the call itself
+  }
+  return bytes;
+}
+
+int sgl_op_preprocess_views_bwd(const float* d_out, int B, int Hs, int Ws, const sgl_view* views, int V, int S, float std,
+                                float* d_src, void* scratch, size_t scratch_bytes, sgl_stream stream) {
+  static_assert(sizeof(sgl::ViewChunk) + sizeof(sgl::ViewTableChunk) <= 3072, "records and offsets travel as arguments");
+  static_assert(sizeof(sgl::AaAxis) % 4 == 0 && sizeof(sgl::SrcSpan) % 4 == 0, "tables stay 4-byte aligned");
+  if (!d_out || !views || !d_src) return SGL_ERR_NULL;
+  if (B <= 0 || Hs <= 0 || Ws <= 0 || S <= 0 || V <= 0 || std == 0.f) return SGL_ERR_BAD_SHAPE;
+  if ((long long)34 * S > 0x7fffffffLL) return SGL_ERR_BAD_SHAPE;   // 2 S + oh + ow entries of a view's tables in an int
+  const sgl::View* rec = reinterpret_cast<const sgl::View*>(views);
+  const int rec_status = sgl::views_check(rec, V, B, Hs, Ws, S);
+  if (rec_status != SGL_OK) return rec_status;
+  const size_t need = sgl_op_preprocess_views_bwd_scratch_bytes(views, V, S);
+  if (need && !scratch) return SGL_ERR_NULL;
+  if (scratch_bytes < need) return SGL_ERR_WORKSPACE;
+  hipStream_t s = (hipStream_t)stream;
+  const size_t tiles = (size_t)B * ((Hs + sgl::kBwdTile - 1) / sgl::kBwdTile) * ((Ws + sgl::kBwdTile - 1) / sgl::kBwdTile);
+  const int blocks = (int)(tiles < 8192 ? tiles : 8192);                               // 256 CUs x 32, grid-stride
+  const float inv_std = 1.0f / std;
+  size_t off = 0;
+  for (int v0 = 0; v0 < V; v0 += sgl::kViewChunk) {      // one launch per 64 views, as the forward
+    const int nv = V - v0 < sgl::kViewChunk ? V - v0 : sgl::kViewChunk;
+    sgl::ViewChunk chunk = {};
+    sgl::ViewTableChunk tabs = {};
+    int entries = 0;                                     // the longest table of the chunk; 0: copies only
+    for (int v = 0; v < nv; ++v) {
+      chunk.v[v] = rec[v0 + v];
+      int oh, ow;
+      sgl::view_extent(chunk.v[v], &oh, &ow);
+      tabs.off[v] = off;
+      const size_t bytes = sgl::view_table_bytes(oh, ow, S);
+      off += bytes;
+      if (bytes && 2 * S + oh + ow > entries) entries = 2 * S + oh + ow;
+    }
+    if (entries)
+      hipLaunchKernelGGL(sgl::views_bwd_tables_kernel, dim3((unsigned)((entries + 255) / 256), (unsigned)nv), dim3(256), 0,
+                         s, reinterpret_cast<char*>(scratch), chunk, tabs, S);
+    hipLaunchKernelGGL(sgl::preprocess_views_bwd_kernel, dim3(blocks), dim3(256), 0, s,
+                       d_out + (size_t)v0 * 3 * S * S, d_src, reinterpret_cast<const char*>(scratch), chunk, tabs, nv, B,
+                       Hs, Ws, S, (int)(v0 == 0), (int)(v0 + nv == V), inv_std);
   }
   return hipGetLastError() == hipSuccess ? SGL_OK : SGL_ERR_HIP;
 }

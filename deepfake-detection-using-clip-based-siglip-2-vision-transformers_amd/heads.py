@@ -434,6 +434,19 @@ def app_freq_logits(images_u8: torch.Tensor, d, freq_mlp: nn.Module, jitter: boo
     return z[:C][None], z[C:][:, None]
 
 
+def app_visual_prob(z_views: torch.Tensor, d) -> torch.Tensor:
+    """``(1,)``: the ``visual_prob`` of `core_signals_batched` (appv3.py:3231-3246) for the ``(V,)`` classifier logits of one
+    image's view batch ``d = preprocess.detect_views(h, w)``: ``0.6 sigmoid(sum_c w_c z[d.crops]) + 0.4 sigmoid(z[d.rot])``,
+    in plain differentiable torch (no ``no_grad``; fp32, or float64 for float64 logits).  With
+    ``preprocess.views_resize_normalize(x, d.views, S, differentiable=True)`` as the encoder's ``pixel_values=`` it makes
+    the app's visual probability a differentiable function of the source image ``x``.  The frequency branch reads integer
+    SRM moments of a uint8 plane and has no gradient."""
+    z = z_views if z_views.dtype == torch.float64 else z_views.float()
+    w = d.weights.to(z.device, z.dtype)
+    z_sig0 = (z[d.crops][None] * w).sum(-1)
+    return 0.6 * torch.sigmoid(z_sig0) + 0.4 * torch.sigmoid(z[d.rot][None])
+
+
 @torch.no_grad()
 def core_signals_batched(z_sigs: torch.Tensor, crop_weights: torch.Tensor, z_freqs: torch.Tensor, z_rot: torch.Tensor,
                          fusion_head: nn.Module, coral: "CoralCalibrator", freq_temp: float = 1.25,

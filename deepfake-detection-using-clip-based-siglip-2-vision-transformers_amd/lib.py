@@ -185,6 +185,8 @@ def load():
     _sig(lib, "sgl_op_preprocess_views_scratch_bytes", sz, [i, i])
     _sig(lib, "sgl_op_preprocess_views", i, [_fp, i, i, i, i, C.POINTER(SglView), i, _fp, i, i, i, i, i, f, f, _fp, sz,
                                              _fp])
+    _sig(lib, "sgl_op_preprocess_views_bwd_scratch_bytes", sz, [C.POINTER(SglView), i, i])
+    _sig(lib, "sgl_op_preprocess_views_bwd", i, [_fp, i, i, i, C.POINTER(SglView), i, i, f, _fp, _fp, sz, _fp])
     _sig(lib, "sgl_op_freq_features_scratch_bytes", sz, [i, i, i])
     _sig(lib, "sgl_op_freq_features", i, [_fp, i, i, i, C.POINTER(SglView), i, _fp, _fp, i, _fp, _fp, sz, _fp])
     _sig(lib, "sgl_op_l2norm_tmean_fwd", i, [_fp, _fp, _fp, i, i, i, _fp])

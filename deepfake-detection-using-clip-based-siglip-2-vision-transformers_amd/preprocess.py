@@ -17,6 +17,9 @@ reference's CPU transform, cifake…:1795-1797); kornia itself is not installed 
 
 Inference side (appv3.py ``detect_core``): ``View`` / ``detect_views`` + ``views_to_patch_operand`` build the app's 9 crops, its
 90-degree rotated view and its 4 x 4 grid cells, 42 encoder rows per image, in one pass of ``sgl_op_preprocess_views``.
+``views_resize_normalize(differentiable=True)`` is differentiable with respect to a float source (one
+``sgl_op_preprocess_views_bwd``, the adjoint of all views at once; ``views_resize_normalize_backward`` is the VJP as a
+function), which with ``heads.app_visual_prob`` gives the gradient of the app's visual probability in the source image.
 ``views_freq_features`` is the app's 24-D frequency / SRM vector (``extract_freq_vector``) of the crops and cells, one pass
 of ``sgl_op_freq_features``; ``heads.app_freq_logits`` turns it into the ``z_freqs`` of ``core_signals_batched``.
 """
@@ -104,9 +107,16 @@ def _wants_grad(images) -> bool:
     return torch.is_grad_enabled() and images.is_floating_point() and images.requires_grad
 
 
-def _refuse_grad(images, what: str) -> None:
-    """Everything but ``resize_normalize`` has no backward: refuse rather than return a silently missing gradient."""
+def _refuse_grad(images, what: str, views: bool = False) -> None:
+    """Everything but ``resize_normalize`` and ``views_resize_normalize(differentiable=True)`` has no backward: refuse
+    rather than return a silently missing gradient.  ``views``: name the differentiable route of the view transforms."""
     if images.is_cuda and _wants_grad(images):
+        if views:
+            raise RuntimeError(
+                f"{what} is not differentiable with respect to its source images as called (the patch-operand layout has "
+                "no backward, and the NCHW views are differentiable only on request); use "
+                "preprocess.views_resize_normalize(images, views, size, differentiable=True) and pass its result to the "
+                "encoder as pixel_values=, or detach the images / run under torch.no_grad()")
         raise RuntimeError(
             f"{what} is not differentiable with respect to its source images (the colour operators and the patch-operand "
             "layout have no backward); use preprocess.resize_normalize(images, size), which is, and pass its result to "
@@ -296,12 +306,64 @@ def _views_transform(images, views, size, patch, dtype, mean, std) -> torch.Tens
     return out
 
 
+def views_resize_normalize_backward(grad_out: torch.Tensor, views, source_shape, std: float = 0.5) -> torch.Tensor:
+    """The vector-Jacobian product of ``views_resize_normalize`` as a function: ``grad_out`` (V,3,S,S) -> fp32 (B,3,Hs,Ws),
+    the gradient with respect to float sources of ``source_shape = (B, Hs, Ws)`` (for uint8 sources: with respect to
+    ``bytes / 255``), summed over the views of each source.  The transform is linear, so no source values are needed; one
+    ``sgl_op_preprocess_views_bwd``, a gather with a fixed summation order: bitwise reproducible.  A source that no view
+    names, and every pixel outside all boxes, gets exactly zero.  ``views`` / ``std`` as given to the forward."""
+    if not grad_out.is_cuda:
+        raise RuntimeError("the GPU input pipeline runs on CUDA tensors only (no CPU path)")
+    if grad_out.dim() != 4 or grad_out.shape[1] != 3 or grad_out.shape[2] != grad_out.shape[3]:
+        raise ValueError(f"grad_out must be (V,3,S,S), got {tuple(grad_out.shape)}")
+    B, Hs, Ws = (int(t) for t in source_shape)
+    tab = view_table(views, B, Hs, Ws)
+    V, S = len(tab), grad_out.shape[2]
+    if grad_out.shape[0] != V:
+        raise ValueError(f"grad_out has {grad_out.shape[0]} rows for {V} views")
+    g = grad_out.detach().float().contiguous()
+    dev = g.device
+    d_src = torch.empty((B, 3, Hs, Ws), device=dev, dtype=torch.float32)
+    nbytes = _lib.load().sgl_op_preprocess_views_bwd_scratch_bytes(tab, V, S)
+    scratch = torch.empty(nbytes, device=dev, dtype=torch.uint8) if nbytes else None
+    _lib.call("sgl_op_preprocess_views_bwd", dev, g.data_ptr(), B, Hs, Ws, tab, V, S, float(std), d_src.data_ptr(),
+              _lib.ptr(scratch), nbytes)
+    return d_src
+
+
+class _ViewsResizeNormalize(torch.autograd.Function):
+    """``views_resize_normalize(differentiable=True)`` for a source that requires grad: the same forward launches, one
+    ``sgl_op_preprocess_views_bwd`` backward.  Nothing is saved: the transform is linear in the source."""
+
+    @staticmethod
+    def forward(ctx, images, views, size, mean, std, dtype):
+        ctx.src = (images.shape, images.dtype)
+        ctx.args = (views, std)
+        return _views_transform(images.detach(), views, size, None, dtype, mean, std)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        shape, src_dtype = ctx.src
+        views, std = ctx.args
+        d_src = views_resize_normalize_backward(grad_out, views, (shape[0], shape[2], shape[3]), std)
+        return d_src.to(src_dtype), None, None, None, None, None
+
+
 def views_resize_normalize(images: torch.Tensor, views, size: int, mean: float = 0.5, std: float = 0.5,
-                           dtype: torch.dtype = torch.float32) -> torch.Tensor:
+                           dtype: torch.dtype = torch.float32, differentiable: bool = False) -> torch.Tensor:
     """(V,3,size,size): every ``View`` of the same-size sources ``images`` cropped, turned, mirrored, resized (antialias)
     and normalised in one pass: what the app builds per window with PIL ``crop`` / ``rotate`` and
-    ``Resize -> ToTensor -> Normalize``.  Inference only: a source that requires grad is refused."""
-    _refuse_grad(images, "views_resize_normalize")
+    ``Resize -> ToTensor -> Normalize``.  ``differentiable=True`` makes it differentiable with respect to a floating
+    ``images`` that requires grad (any float dtype, any strides; the same launches, so the same bits): ``images.grad``
+    arrives in the source's dtype and shape, summed over all views.  Without it such a source is refused, as before.
+    uint8 sources have no gradient of their own: see ``views_resize_normalize_backward``."""
+    if differentiable:
+        views = list(views)
+        if images.is_cuda and _wants_grad(images):
+            return _ViewsResizeNormalize.apply(images, views, size, mean, std, dtype)
+    else:
+        _refuse_grad(images, "views_resize_normalize", views=True)
     return _views_transform(images, views, size, None, dtype, mean, std)
 
 
@@ -309,7 +371,7 @@ def views_to_patch_operand(images: torch.Tensor, views, config, size: Optional[i
                            mean: float = 0.5, std: float = 0.5) -> PatchOperand:
     """The views written straight into the patch GEMM's operand (see ``to_patch_operand``): ``PatchOperand(batch=V)`` for
     ``SiglipVisionModelHIP(patches=...)`` / ``encode_image(patches=...)``, one encoder batch of V rows."""
-    _refuse_grad(images, "views_to_patch_operand")
+    _refuse_grad(images, "views_to_patch_operand", views=True)
     S, patch = _patch_geometry(config, size)
     views = list(views)
     out = _views_transform(images, views, S, patch, _operand_dtype(compute_dtype), mean, std)

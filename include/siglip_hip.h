@@ -436,7 +436,8 @@ int sgl_op_preprocess_bwd(const float* d_out, int B, int Hs, int Ws, int S, floa
 
 /* ---- test-time views (new symbols; sgl_abi_version() stays 3: nothing existing changed) -------------------------------
  * The app's inference-side windows (appv3.py:3214-3250 detect_core, :3315 make_multicrops, :3381 compute_patch_grid):
- * V views of B same-size sources (layouts as sgl_op_preprocess) in one pass, inference only (no backward).  A view is
+ * V views of B same-size sources (layouts as sgl_op_preprocess) in one pass (the adjoint of the NCHW layout with respect
+ * to a float source is sgl_op_preprocess_views_bwd below; the patch-operand layout is inference only).  A view is
  * an integer crop box, an optional quarter turn and an optional mirror; the result is resized to S x S, normalised and
  * stored as out[v][c][y][x] (patch_major == 0) or as the patch GEMM's operand rows out[(v*g + gy)*g + gx][k]
  * (patch_major != 0, g = S / P, columns >= 3*P*P exactly zero): sgl_op_preprocess's two layouts with b = v.
@@ -481,6 +482,29 @@ size_t sgl_op_preprocess_views_scratch_bytes(int V, int S);
 int sgl_op_preprocess_views(const void* src, int src_is_u8_nhwc, int B, int Hs, int Ws, const sgl_view* views, int V,
                             void* out, int out_dtype, int S, int P, int Kp, int patch_major, float mean, float std,
                             void* scratch, size_t scratch_bytes, sgl_stream stream);
+/* The adjoint of sgl_op_preprocess_views(patch_major = 0) for a float source (new symbols; sgl_abi_version() stays 3):
+ * d_out fp32 (V,3,S,S), the gradient with respect to the views -> d_src fp32 (B,3,Hs,Ws) NCHW, the gradient with respect
+ * to the sources (for a uint8 source: with respect to byte / 255).  With A_v the linear part of view v (crop, orient,
+ * resize with the fp32 filter weights the forward applies),
+ *   d_src[b] = (sum over {v : views[v].src == b} of A_v^T d_out[v]) / std;
+ * mean does not enter, and the zero fill of a kept canvas receives no gradient.  The patch-operand layout has no adjoint.
+ * A gather: every source element has one owning thread (which owns the three channels of its pixel) that sums, view
+ * index ascending (then oy, then ox), the terms of every view whose box holds it, then multiplies by 1 / std once.  No atomics; every element of d_src is written by a plain
+ * store, exactly 0 where no view covers it and for a source no view names; two calls on the same inputs give the same
+ * bits.  views is a HOST pointer read during the call only; the records reach the device by value in the kernel
+ * arguments, 64 per launch.  For V > 64 the first launch stores its partial sum and every later one loads it, goes on
+ * adding and stores it again, in stream order: the bits do not depend on where the chunks end.  The caller's stream only,
+ * no allocation, no copy, no host synchronisation: graph-capturable.
+ * scratch: sgl_op_preprocess_views_bwd_scratch_bytes(views, V, S) bytes of device memory, 4-byte aligned: per view that
+ * is not an S x S copy, the filter of every output index and the output range of every oriented row and column
+ * (2 * S * 20 + (oh + ow) * 8 bytes; the size follows the oriented extents, hence the records), written by a pre-pass
+ * launch in front of each gather launch.  The size function returns 0 for NULL views or V, S < 1.
+ * Refused before anything is enqueued, d_src untouched: d_out, views or d_src NULL (or scratch NULL when bytes are
+ * needed) SGL_ERR_NULL; V <= 0, a dimension < 1, std == 0 or a record outside the constraints of sgl_view
+ * SGL_ERR_BAD_SHAPE; an oriented extent above 16 * S SGL_ERR_UNSUPPORTED; scratch_bytes too small SGL_ERR_WORKSPACE. */
+size_t sgl_op_preprocess_views_bwd_scratch_bytes(const sgl_view* views, int V, int S);
+int sgl_op_preprocess_views_bwd(const float* d_out, int B, int Hs, int Ws, const sgl_view* views, int V, int S, float std,
+                                float* d_src, void* scratch, size_t scratch_bytes, sgl_stream stream);
 
 /* ---- frequency / SRM feature vectors (new symbols; sgl_abi_version() stays 3: nothing existing changed) ----------------
  * The app's 24 numbers per window (appv3.py:1618-1728 extract_freq_vector, DETECT_USE_CLAHE off), which detect_core feeds
