@@ -31,6 +31,7 @@
 #include <stdint.h>
 
 #include "common.hip.h"
+#include "kernels.h"
 #include "siglip_hip.h"
 
 namespace sgl {
@@ -426,11 +427,8 @@ int sgl_op_freq_features(const void* src_u8_nhwc, int B, int Hs, int Ws, const s
   using namespace sgl::freq;
   if (!src_u8_nhwc || !views || !geometry || !out) return SGL_ERR_NULL;
   if (B <= 0 || Hs <= 0 || Ws <= 0 || V <= 0) return SGL_ERR_BAD_SHAPE;
-  for (int v = 0; v < V; ++v) {
-    const sgl_view& r = views[v];
-    if (r.src < 0 || r.src >= B || r.x0 < 0 || r.x0 >= r.x1 || r.x1 > Ws || r.y0 < 0 || r.y0 >= r.y1 || r.y1 > Hs)
-      return SGL_ERR_BAD_SHAPE;
-  }
+  for (int v = 0; v < V; ++v)
+    if (!sgl::view_box_ok(views[v], B, Hs, Ws)) return SGL_ERR_BAD_SHAPE;
   for (int v = 0; v < V; ++v) {
     const sgl_view& r = views[v];
     if (r.turns != 0 || r.keep_canvas != 0 || r.flip != 0) return SGL_ERR_UNSUPPORTED;

@@ -5,6 +5,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "siglip_hip.h"
+
 namespace sgl {
 
 enum DType : int {
@@ -24,6 +26,11 @@ hipError_t set_max_dynamic_lds_once(int bytes) {
       hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
   done = e == hipSuccess;
   return e;
+}
+
+// the box part of every sgl_view check (preprocess.hip, freq_features.hip): a source of the batch, a non-empty box inside it
+static inline bool view_box_ok(const sgl_view& r, int B, int Hs, int Ws) {
+  return r.src >= 0 && r.src < B && r.x0 >= 0 && r.x0 < r.x1 && r.x1 <= Ws && r.y0 >= 0 && r.y0 < r.y1 && r.y1 <= Hs;
 }
 
 // ---- GEMM epilogues (shared by the MFMA kernels and the strict-fp32 generic kernel) ----------------

@@ -11,8 +11,16 @@
 // is what torchvision Resize(antialias=True) runs in the reference's CPU transform (cifake...:1795-1797).  kornia (the
 // GPU transform) is not installed here: its result is "parity unpinned" (it blurs with a Gaussian before sampling).
 // HBM-bound; one thread = one operand element (coalesced bf16 stores along k), source taps come from L1/L2.
+//
+// Map: aa_axis / aa_w / resample_px   the one filter of every kernel      | OutLayout   where an output element goes
+//      preprocess_kernel, aug_* + preprocess_aug_kernel, preprocess_views_kernel   the three forward transforms
+//      AxisTables + views_bwd_tables_kernel + bwd_filter_sum<NC>          the tables and the sum of both adjoints
+//      preprocess_bwd_kernel, preprocess_views_bwd_kernel                 the adjoints (float source, NCHW output)
+//      check_args, views_check, dispatch_src_out, extern "C"              refusals, type dispatch, the entry points
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "common.hip.h"
 #include "kernels.h"
@@ -80,38 +88,56 @@ __device__ __forceinline__ float resample(const void* src, int b, int c, int oy,
   return resample_px([&](int y, int x) { return src_px<SRC_U8>(src, b, c, y, x, Hs, Ws); }, oy, ox, Hs, Ws, sy, sx);
 }
 
-// patch_major: out[(b*gh + gy)*gw + gx][k], k = c*P*P + ky*P + kx (k >= 3*P*P zero)   | else out[b][c][y][x] (NCHW)
-template <bool SRC_U8, typename TOut>
-__global__ __launch_bounds__(256) void preprocess_kernel(const void* __restrict__ src, TOut* __restrict__ out, int B,
-                                                         int Hs, int Ws, int S, int P, int Kp, int patch_major,
-                                                         float mean, float inv_std, const int* __restrict__ mix_index,
-                                                         float lam) {
-  const int g = S / P, K0 = 3 * P * P;
-  const size_t total = patch_major ? (size_t)B * g * g * Kp : (size_t)B * 3 * S * S;
-  const float sy = (float)Hs / (float)S, sx = (float)Ws / (float)S;
-  for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
-    int b, c, oy, ox;
-    bool live = true;
+// The two output layouts of the forward transforms, n = the image or view:
+// patch_major: out[(n*g + gy)*g + gx][k], k = c*P*P + ky*P + kx (k >= 3*P*P zero), g = S / P | else out[n][c][y][x]
+struct OutPx {
+  int n, c, oy, ox;
+  bool live;                                             // false: a K padding column, stored as zero
+};
+struct OutLayout {
+  int S, P, Kp, g, patch_major;                          // g = patch_major ? S / P : 0
+
+  __host__ __device__ size_t elems(int n) const { return patch_major ? (size_t)n * g * g * Kp : (size_t)n * 3 * S * S; }
+  __device__ __forceinline__ OutPx decode(size_t idx) const {
+    OutPx o;
+    o.live = true;
     if (patch_major) {
       const int k = (int)(idx % Kp);
       const size_t m = idx / Kp;
       const int gx = (int)(m % g), gy = (int)((m / g) % g);
-      b = (int)(m / ((size_t)g * g));
-      live = k < K0;
-      c = k / (P * P);
-      const int r = k - c * P * P;
-      oy = gy * P + r / P;
-      ox = gx * P + r % P;
+      o.n = (int)(m / ((size_t)g * g));
+      o.live = k < 3 * P * P;
+      o.c = k / (P * P);
+      const int r = k - o.c * P * P;
+      o.oy = gy * P + r / P;
+      o.ox = gx * P + r % P;
     } else {
-      ox = (int)(idx % S);
-      oy = (int)((idx / S) % S);
-      c = (int)((idx / ((size_t)S * S)) % 3);
-      b = (int)(idx / ((size_t)3 * S * S));
+      o.ox = (int)(idx % S);
+      o.oy = (int)((idx / S) % S);
+      o.c = (int)((idx / ((size_t)S * S)) % 3);
+      o.n = (int)(idx / ((size_t)3 * S * S));
     }
+    return o;
+  }
+  __device__ __forceinline__ size_t offset(int n, int c, int oy, int ox) const {   // the inverse of decode
+    if (patch_major) return (((size_t)n * g + oy / P) * g + ox / P) * Kp + (size_t)c * P * P + (oy % P) * P + (ox % P);
+    return (((size_t)n * 3 + c) * S + oy) * S + ox;
+  }
+};
+
+template <bool SRC_U8, typename TOut>
+__global__ __launch_bounds__(256) void preprocess_kernel(const void* __restrict__ src, TOut* __restrict__ out, int B,
+                                                         int Hs, int Ws, const OutLayout L, float mean, float inv_std,
+                                                         const int* __restrict__ mix_index, float lam) {
+  const size_t total = L.elems(B);
+  const float sy = (float)Hs / (float)L.S, sx = (float)Ws / (float)L.S;
+  for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
+    const OutPx o = L.decode(idx);
     float v = 0.f;
-    if (live) {
-      v = resample<SRC_U8>(src, b, c, oy, ox, Hs, Ws, sy, sx);
-      if (mix_index) v = lam * v + (1.0f - lam) * resample<SRC_U8>(src, mix_index[b], c, oy, ox, Hs, Ws, sy, sx);
+    if (o.live) {
+      v = resample<SRC_U8>(src, o.n, o.c, o.oy, o.ox, Hs, Ws, sy, sx);
+      if (mix_index)
+        v = lam * v + (1.0f - lam) * resample<SRC_U8>(src, mix_index[o.n], o.c, o.oy, o.ox, Hs, Ws, sy, sx);
       v = (v - mean) * inv_std;
     }
     Elem<TOut>::st(out + idx, v);
@@ -261,13 +287,12 @@ __global__ __launch_bounds__(256) void aug_mean_kernel(const void* __restrict__ 
 
 template <bool SRC_U8, typename TOut>
 __global__ __launch_bounds__(256) void preprocess_aug_kernel(const void* __restrict__ src, TOut* __restrict__ out, int B,
-                                                             int Hs, int Ws, int S, int P, int Kp, int patch_major,
-                                                             float mean, float inv_std,
-                                                             const AugSample* __restrict__ aug,
+                                                             int Hs, int Ws, const OutLayout L, float mean,
+                                                             float inv_std, const AugSample* __restrict__ aug,
                                                              const float* __restrict__ grey_mean) {
   // one thread = one output PIXEL (all three channels: the colour operators mix them)
-  const int g = patch_major ? S / P : 0;
-  const int side = patch_major ? g * P : S;             // pixels past the last whole patch are dropped ('valid' conv)
+  const int S = L.S;
+  const int side = L.patch_major ? L.g * L.P : S;       // pixels past the last whole patch are dropped ('valid' conv)
   const size_t total = (size_t)B * side * side;
   const float sy = (float)Hs / (float)S, sx = (float)Ws / (float)S;
   for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
@@ -277,15 +302,7 @@ __global__ __launch_bounds__(256) void preprocess_aug_kernel(const void* __restr
     aug_geo<SRC_U8>(src, b, oy, ox, Hs, Ws, S, sy, sx, a, rgb);
     aug_colour(rgb, a, grey_mean[b], false);
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const float v = (rgb[c] - mean) * inv_std;
-      size_t o;
-      if (patch_major)
-        o = (((size_t)b * g + oy / P) * g + ox / P) * Kp + (size_t)c * P * P + (oy % P) * P + (ox % P);
-      else
-        o = (((size_t)b * 3 + c) * S + oy) * S + ox;
-      Elem<TOut>::st(out + o, v);
-    }
+    for (int c = 0; c < 3; ++c) Elem<TOut>::st(out + L.offset(b, c, oy, ox), (rgb[c] - mean) * inv_std);
   }
 }
 
@@ -307,16 +324,13 @@ __global__ __launch_bounds__(256) void patch_pad_zero_kernel(TOut* __restrict__ 
 // The records travel by value in the kernel arguments (64 x 32 bytes of the 4 KB a launch may carry): no device table,
 // no copy, nothing to keep alive, graph-capturable.  Same thread mapping and store pattern as preprocess_kernel.
 // ---------------------------------------------------------------------------------------------------------------
-struct View {   // == sgl_view
-  int src, x0, y0, x1, y1, turns, keep_canvas, flip;
-};
 constexpr int kViewChunk = 64;
 struct ViewChunk {
-  View v[kViewChunk];
+  sgl_view v[kViewChunk];
 };
 
 // oriented extents of a record: an exact odd turn swaps them, a turn on the kept canvas does not
-__host__ __device__ __forceinline__ void view_extent(const View& r, int* oh, int* ow) {
+__host__ __device__ __forceinline__ void view_extent(const sgl_view& r, int* oh, int* ow) {
   const int w = r.x1 - r.x0, h = r.y1 - r.y0;
   const bool swap = (r.turns & 1) && !r.keep_canvas;
   *oh = swap ? w : h;
@@ -329,7 +343,7 @@ struct ViewMap {
   int ax, axx, axy, ay, ayx, ayy;
 };
 
-__device__ __forceinline__ ViewMap view_map(const View& r) {
+__device__ __forceinline__ ViewMap view_map(const sgl_view& r) {
   ViewMap m;
   m.src = r.src, m.x0 = r.x0, m.y0 = r.y0;
   const int w = m.w = r.x1 - r.x0, h = m.h = r.y1 - r.y0;
@@ -364,34 +378,17 @@ __device__ __forceinline__ float view_px(const void* src, const ViewMap& m, int 
 // out: the rows of this chunk's first view onward; layouts as preprocess_kernel with b = the view's index in the chunk
 template <bool SRC_U8, typename TOut>
 __global__ __launch_bounds__(256) void preprocess_views_kernel(const void* __restrict__ src, TOut* __restrict__ out,
-                                                               const ViewChunk chunk, int nv, int Hs, int Ws, int S, int P,
-                                                               int Kp, int patch_major, float mean, float inv_std) {
-  const int g = patch_major ? S / P : 0, K0 = 3 * P * P;
-  const size_t total = patch_major ? (size_t)nv * g * g * Kp : (size_t)nv * 3 * S * S;
+                                                               const ViewChunk chunk, int nv, int Hs, int Ws,
+                                                               const OutLayout L, float mean, float inv_std) {
+  const size_t total = L.elems(nv);
   for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
-    int v, c, oy, ox;
-    bool live = true;
-    if (patch_major) {
-      const int k = (int)(idx % Kp);
-      const size_t m = idx / Kp;
-      const int gx = (int)(m % g), gy = (int)((m / g) % g);
-      v = (int)(m / ((size_t)g * g));
-      live = k < K0;
-      c = k / (P * P);
-      const int r = k - c * P * P;
-      oy = gy * P + r / P;
-      ox = gx * P + r % P;
-    } else {
-      ox = (int)(idx % S);
-      oy = (int)((idx / S) % S);
-      c = (int)((idx / ((size_t)S * S)) % 3);
-      v = (int)(idx / ((size_t)3 * S * S));
-    }
+    const OutPx o = L.decode(idx);
     float val = 0.f;
-    if (live) {
-      const ViewMap m = view_map(chunk.v[v]);
-      const float sy = (float)m.oh / (float)S, sx = (float)m.ow / (float)S;
-      val = resample_px([&](int y, int x) { return view_px<SRC_U8>(src, m, c, y, x, Hs, Ws); }, oy, ox, m.oh, m.ow, sy, sx);
+    if (o.live) {
+      const ViewMap m = view_map(chunk.v[o.n]);
+      const float sy = (float)m.oh / (float)L.S, sx = (float)m.ow / (float)L.S;
+      val = resample_px([&](int y, int x) { return view_px<SRC_U8>(src, m, o.c, y, x, Hs, Ws); }, o.oy, o.ox, m.oh, m.ow,
+                        sy, sx);
       val = (val - mean) * inv_std;
     }
     Elem<TOut>::st(out + idx, val);
@@ -404,8 +401,8 @@ __global__ __launch_bounds__(256) void preprocess_views_kernel(const void* __res
 // so d_src[b] = Wy^T (lam G[b] + (1 - lam) sum_{j : mix[j] == b} G[j]) Wx / std with the SAME fp32 weights (aa_axis / aa_w).
 // Gather form: one thread = one source element, which sums the outputs whose taps include it; nothing is scattered, no
 // atomics, every element of d_src is stored exactly once, and the order of the sums is fixed (j, then oy, then ox).
-// A pre-pass writes two small tables per axis into caller scratch, so that the per-element loop neither normalises a
-// filter (up to 33 taps per output at ratio 16) nor searches:
+// A pre-pass (views_bwd_tables_kernel, for the one full-frame record) writes two small tables per axis into caller
+// scratch, so that the per-element loop neither normalises a filter (up to 33 taps per output at ratio 16) nor searches:
 //   AaAxis  [S]   the forward's filter of every output index
 //   SrcSpan [in]  the outputs [first, first + count) whose taps [lo, hi) include source index j.  lo and hi are
 //                 non-decreasing in the output index, so the set is one range; it is found by testing lo <= j < hi with
@@ -438,85 +435,73 @@ __device__ __forceinline__ SrcSpan src_span(int j, int in, int out, float scale)
   return s;
 }
 
-__host__ __device__ __forceinline__ size_t bwd_span_offset(int S) {   // the SrcSpan tables follow the two AaAxis tables
-  return (size_t)2 * S * sizeof(AaAxis);
+// One table set, for an oriented image of oh x ow resized to S x S: AaAxis[S] (y), AaAxis[S] (x), SrcSpan[oh], SrcSpan[ow]
+struct AxisTables {
+  AaAxis *ty, *tx;
+  SrcSpan *ry, *rx;
+};
+
+__host__ __device__ __forceinline__ size_t view_table_bytes(int oh, int ow, int S) {
+  if (oh == S && ow == S) return 0;                      // the copy shortcut reads no table
+  return (size_t)2 * S * sizeof(AaAxis) + ((size_t)oh + (size_t)ow) * sizeof(SrcSpan);
 }
 
-__global__ __launch_bounds__(256) void preprocess_bwd_tables_kernel(AaAxis* __restrict__ ty, AaAxis* __restrict__ tx,
-                                                                    SrcSpan* __restrict__ ry, SrcSpan* __restrict__ rx,
-                                                                    int Hs, int Ws, int S) {
-  const float sy = (float)Hs / (float)S, sx = (float)Ws / (float)S;
-  const int total = 2 * S + Hs + Ws;
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
-    if (i < S) ty[i] = aa_axis(i, Hs, sy);
-    else if (i < 2 * S) tx[i - S] = aa_axis(i - S, Ws, sx);
-    else if (i < 2 * S + Hs) ry[i - 2 * S] = src_span(i - 2 * S, Hs, S, sy);
-    else rx[i - 2 * S - Hs] = src_span(i - 2 * S - Hs, Ws, S, sx);
-  }
+__host__ __device__ __forceinline__ AxisTables axis_tables(char* base, int oh, int S) {
+  AxisTables t;
+  t.ty = reinterpret_cast<AaAxis*>(base);
+  t.tx = t.ty + S;
+  t.ry = reinterpret_cast<SrcSpan*>(t.tx + S);
+  t.rx = t.ry + oh;
+  return t;
 }
 
-// sum over the outputs of image j that read source element (y, x) of channel c: (Wy^T G[j, c] Wx)[y, x]
-__device__ __forceinline__ float bwd_filter_sum(const float* __restrict__ g, const AaAxis* __restrict__ ty,
-                                                const AaAxis* __restrict__ tx, SrcSpan py, SrcSpan px, int y, int x,
-                                                int S) {
-  float acc = 0.f;
+// sum over the outputs of one image that read source element (y, x), for NC channels (planes `plane` apart) side by
+// side: out[c] = (Wy^T G[c] Wx)[y, x].  Each weight is evaluated once per tap, then the row sums, then acc: the same
+// operations in the same order for every NC, and NC independent loads in flight per tap
+template <int NC>
+__device__ __forceinline__ void bwd_filter_sum(const float* __restrict__ g, size_t plane, const AxisTables& t, SrcSpan py,
+                                               SrcSpan px, int y, int x, int S, float* out) {
+  float acc[NC] = {};
   for (int oy = py.first; oy < py.first + py.count; ++oy) {
-    const AaAxis ay = ty[oy];
+    const AaAxis ay = t.ty[oy];
     const float* grow = g + (size_t)oy * S;
-    float row = 0.f;
+    float row[NC] = {};
     for (int ox = px.first; ox < px.first + px.count; ++ox) {
-      const AaAxis ax = tx[ox];
-      row += aa_w(ax, x - ax.lo) * grow[ox];
-    }
-    acc += aa_w(ay, y - ay.lo) * row;
-  }
-  return acc;
-}
-
-// bwd_filter_sum for the three channels of one pixel (planes `plane` apart): each weight is evaluated once, the three
-// sums run side by side with bwd_filter_sum's operations in bwd_filter_sum's order, so three loads are in flight per tap
-__device__ __forceinline__ void bwd_filter_sum3(const float* __restrict__ g, size_t plane, const AaAxis* __restrict__ ty,
-                                                const AaAxis* __restrict__ tx, SrcSpan py, SrcSpan px, int y, int x, int S,
-                                                float* out) {
-  float acc[3] = {0.f, 0.f, 0.f};
-  for (int oy = py.first; oy < py.first + py.count; ++oy) {
-    const AaAxis ay = ty[oy];
-    const float* grow = g + (size_t)oy * S;
-    float row[3] = {0.f, 0.f, 0.f};
-    for (int ox = px.first; ox < px.first + px.count; ++ox) {
-      const AaAxis ax = tx[ox];
+      const AaAxis ax = t.tx[ox];
       const float w = aa_w(ax, x - ax.lo);
 #pragma unroll
-      for (int c = 0; c < 3; ++c) row[c] += w * grow[c * plane + ox];
+      for (int c = 0; c < NC; ++c) row[c] += w * grow[c * plane + ox];
     }
     const float wy = aa_w(ay, y - ay.lo);
 #pragma unroll
-    for (int c = 0; c < 3; ++c) acc[c] += wy * row[c];
+    for (int c = 0; c < NC; ++c) acc[c] += wy * row[c];
   }
 #pragma unroll
-  for (int c = 0; c < 3; ++c) out[c] = acc[c];
+  for (int c = 0; c < NC; ++c) out[c] = acc[c];
 }
 
+// t: the tables of the full frame; t.ty == nullptr when Hs == S && Ws == S (the forward's copy shortcut)
 __global__ __launch_bounds__(256) void preprocess_bwd_kernel(const float* __restrict__ d_out, float* __restrict__ d_src,
                                                              int B, int Hs, int Ws, int S, float inv_std,
                                                              const int* __restrict__ mix_index, float lam,
-                                                             const AaAxis* __restrict__ ty, const AaAxis* __restrict__ tx,
-                                                             const SrcSpan* __restrict__ ry,
-                                                             const SrcSpan* __restrict__ rx) {
+                                                             const AxisTables t) {
   const size_t total = (size_t)B * 3 * Hs * Ws;
-  const bool copy = ty == nullptr;                       // Hs == S && Ws == S: the forward's copy shortcut
+  const bool copy = t.ty == nullptr;
   const size_t plane = (size_t)S * S;
   for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
     const int x = (int)(idx % Ws), y = (int)((idx / Ws) % Hs);
     const int c = (int)((idx / ((size_t)Hs * Ws)) % 3), b = (int)(idx / ((size_t)3 * Hs * Ws));
     SrcSpan py = {0, 0}, px = {0, 0};
     if (!copy) {
-      py = ry[y];
-      px = rx[x];
+      py = t.ry[y];
+      px = t.rx[x];
     }
     auto image = [&](int j) {
       const float* g = d_out + ((size_t)j * 3 + c) * plane;
-      return copy ? g[(size_t)y * S + x] : bwd_filter_sum(g, ty, tx, py, px, y, x, S);
+      float f;
+      if (copy) f = g[(size_t)y * S + x];
+      else bwd_filter_sum<1>(g, plane, t, py, px, y, x, S, &f);
+      return f;
     };
     float v = image(b);
     if (mix_index) {
@@ -541,22 +526,17 @@ __global__ __launch_bounds__(256) void preprocess_bwd_kernel(const float* __rest
 // wave a view with an odd turn reads G with stride S, 64 lines per load).  The record loop is wave-uniform and the
 // records are kernel arguments.  For every record of its image whose box holds (x, y) the thread
 // inverts view_map (a signed permutation plus offset) to the oriented pixel (Y, X), drops the term when that falls off
-// the kept canvas, and adds bwd_filter_sum (as bwd_filter_sum3) over the two SrcSpans of (Y, X); a view with
+// the kept canvas, and adds bwd_filter_sum<3> over the two SrcSpans of (Y, X); a view with
 // oh == ow == S reads G[v][c][Y][X] (the forward's copy shortcut).  Order per element: view ascending, then oy, then ox;
 // one multiply by 1 / std at the end.
 // V > 64: one launch per 64 records on the caller's stream; the first stores the partial sum, each later one loads it,
 // goes on adding in the same order and stores it back, the last one scales: the bits of one long loop over all V.
-// Tables: per view that is not a copy, AaAxis[S] (y), AaAxis[S] (x), SrcSpan[oh], SrcSpan[ow] in caller scratch at the
-// byte offset that travels next to the record; one pre-pass launch per 64 records writes them (aa_axis / src_span).
+// Tables: per view that is not a copy, one AxisTables set in caller scratch at the byte offset that travels next to the
+// record; one pre-pass launch per 64 records writes them (aa_axis / src_span).
 // ---------------------------------------------------------------------------------------------------------------
 struct ViewTableChunk {
   size_t off[kViewChunk];
 };
-
-__host__ __device__ __forceinline__ size_t view_table_bytes(int oh, int ow, int S) {
-  if (oh == S && ow == S) return 0;                      // the copy shortcut reads no table
-  return bwd_span_offset(S) + ((size_t)oh + (size_t)ow) * sizeof(SrcSpan);
-}
 
 // grid: (blocks over the 2 S + oh + ow entries, views of the chunk)
 __global__ __launch_bounds__(256) void views_bwd_tables_kernel(char* __restrict__ scratch, const ViewChunk chunk,
@@ -565,27 +545,23 @@ __global__ __launch_bounds__(256) void views_bwd_tables_kernel(char* __restrict_
   int oh, ow;
   view_extent(chunk.v[v], &oh, &ow);
   if (oh == S && ow == S) return;
-  char* base = scratch + tabs.off[v];
-  AaAxis* ty = reinterpret_cast<AaAxis*>(base);
-  AaAxis* tx = ty + S;
-  SrcSpan* ry = reinterpret_cast<SrcSpan*>(base + bwd_span_offset(S));
-  SrcSpan* rx = ry + oh;
+  const AxisTables t = axis_tables(scratch + tabs.off[v], oh, S);
   const float sy = (float)oh / (float)S, sx = (float)ow / (float)S;   // the forward's scales
   const int total = 2 * S + oh + ow;
   for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
-    if (i < S) ty[i] = aa_axis(i, oh, sy);
-    else if (i < 2 * S) tx[i - S] = aa_axis(i - S, ow, sx);
-    else if (i < 2 * S + oh) ry[i - 2 * S] = src_span(i - 2 * S, oh, S, sy);
-    else rx[i - 2 * S - oh] = src_span(i - 2 * S - oh, ow, S, sx);
+    if (i < S) t.ty[i] = aa_axis(i, oh, sy);
+    else if (i < 2 * S) t.tx[i - S] = aa_axis(i - S, ow, sx);
+    else if (i < 2 * S + oh) t.ry[i - 2 * S] = src_span(i - 2 * S, oh, S, sy);
+    else t.rx[i - 2 * S - oh] = src_span(i - 2 * S - oh, ow, S, sx);
   }
 }
 
 constexpr int kBwdTile = 16;   // 16 x 16 pixels per block: kBwdTile * kBwdTile == the block's 256 threads
 
-// d_out: the rows of this chunk's first view onward.  first: store (no load); last: scale by inv_std
+// d_out: the rows of this chunk's first view onward.  first: store (no load); last: scale by inv_std.  scratch is read only
 __global__ __launch_bounds__(256) void preprocess_views_bwd_kernel(const float* __restrict__ d_out,
                                                                    float* __restrict__ d_src,
-                                                                   const char* __restrict__ scratch,
+                                                                   char* __restrict__ scratch,
                                                                    const ViewChunk chunk, const ViewTableChunk tabs,
                                                                    int nv, int B, int Hs, int Ws, int S, int first,
                                                                    int last, float inv_std) {
@@ -602,7 +578,7 @@ __global__ __launch_bounds__(256) void preprocess_views_bwd_kernel(const float* 
 #pragma unroll
     for (int c = 0; c < 3; ++c) acc[c] = first ? 0.f : dst[c * src_plane];
     for (int v = 0; v < nv; ++v) {
-      const View& r = chunk.v[v];
+      const sgl_view& r = chunk.v[v];
       if (r.src != b || x < r.x0 || x >= r.x1 || y < r.y0 || y >= r.y1) continue;
       const ViewMap m = view_map(r);
       // cx = ax + axx X + axy Y, cy = ay + ayx X + ayy Y with (axx, ayy) or (axy, ayx) the +-1 pair: its own inverse
@@ -615,13 +591,9 @@ __global__ __launch_bounds__(256) void preprocess_views_bwd_kernel(const float* 
 #pragma unroll
         for (int c = 0; c < 3; ++c) acc[c] += g[c * plane + (size_t)Y * S + X];
       } else {
-        const char* base = scratch + tabs.off[v];
-        const AaAxis* ty = reinterpret_cast<const AaAxis*>(base);
-        const AaAxis* tx = ty + S;
-        const SrcSpan* ry = reinterpret_cast<const SrcSpan*>(base + bwd_span_offset(S));
-        const SrcSpan* rx = ry + m.oh;
+        const AxisTables tb = axis_tables(scratch + tabs.off[v], m.oh, S);
         float f[3];
-        bwd_filter_sum3(g, plane, ty, tx, ry[Y], rx[X], Y, X, S, f);
+        bwd_filter_sum<3>(g, plane, tb, tb.ry[Y], tb.rx[X], Y, X, S, f);
 #pragma unroll
         for (int c = 0; c < 3; ++c) acc[c] += f[c];
       }
@@ -632,11 +604,10 @@ __global__ __launch_bounds__(256) void preprocess_views_bwd_kernel(const float* 
 }
 
 // the record checks sgl_op_preprocess_views and its adjoint share: SGL_OK, SGL_ERR_BAD_SHAPE or SGL_ERR_UNSUPPORTED
-static int views_check(const View* rec, int V, int B, int Hs, int Ws, int S) {
+static int views_check(const sgl_view* rec, int V, int B, int Hs, int Ws, int S) {
   for (int v = 0; v < V; ++v) {
-    const View& r = rec[v];
-    if (r.src < 0 || r.src >= B || r.x0 < 0 || r.x0 >= r.x1 || r.x1 > Ws || r.y0 < 0 || r.y0 >= r.y1 || r.y1 > Hs ||
-        r.turns < 0 || r.turns > 3 || (r.keep_canvas | 1) != 1 || (r.flip | 1) != 1)
+    const sgl_view& r = rec[v];
+    if (!view_box_ok(r, B, Hs, Ws) || r.turns < 0 || r.turns > 3 || (r.keep_canvas | 1) != 1 || (r.flip | 1) != 1)
       return SGL_ERR_BAD_SHAPE;
   }
   for (int v = 0; v < V; ++v) {
@@ -647,6 +618,34 @@ static int views_check(const View* rec, int V, int B, int Hs, int Ws, int S) {
   return SGL_OK;
 }
 
+// the argument checks every entry point shares, in the order in which refusals win: shape, patch geometry, output dtype,
+// then (ratio: the source extents are what the filter reads) the 16x limit that keeps the tap loops short.  An entry point
+// without an output layout passes patch_major = 0 and SGL_DTYPE_F32
+static int check_args(int B, int Hs, int Ws, int S, float std, int patch_major, int P, int Kp, int out_dtype, bool ratio) {
+  if (B <= 0 || Hs <= 0 || Ws <= 0 || S <= 0 || std == 0.f) return SGL_ERR_BAD_SHAPE;
+  if (patch_major && (P <= 0 || S < P || Kp < 3 * P * P)) return SGL_ERR_BAD_SHAPE;
+  if (out_dtype != SGL_DTYPE_BF16 && out_dtype != SGL_DTYPE_F16 && out_dtype != SGL_DTYPE_F32) return SGL_ERR_UNSUPPORTED;
+  if (ratio && ((float)Hs / (float)S > 16.f || (float)Ws / (float)S > 16.f)) return SGL_ERR_UNSUPPORTED;
+  return SGL_OK;
+}
+
+// f(std::bool_constant<source is uint8 NHWC>, (TOut*)out) for the six (source type, output dtype) pairs
+template <typename F>
+static void dispatch_src_out(int src_is_u8, int out_dtype, void* out, F&& f) {
+  auto with_src = [&](auto u8) {
+    if (out_dtype == SGL_DTYPE_BF16) f(u8, static_cast<bf16*>(out));
+    else if (out_dtype == SGL_DTYPE_F16) f(u8, static_cast<f16*>(out));
+    else f(u8, static_cast<float*>(out));
+  };
+  if (src_is_u8) with_src(std::true_type{});
+  else with_src(std::false_type{});
+}
+
+static int capped_blocks(size_t total, int cap) {       // 256 threads per block, grid-stride above the cap
+  const size_t blocks = (total + 255) / 256;
+  return (int)(blocks < (size_t)cap ? blocks : (size_t)cap);
+}
+
 }  // namespace sgl
 
 extern "C" {
@@ -655,28 +654,16 @@ int sgl_op_preprocess(const void* src, int src_is_u8_nhwc, int B, int Hs, int Ws
                       int Kp, int patch_major, float mean, float std, const int* mix_index, float lam,
                       sgl_stream stream) {
   if (!src || !out) return SGL_ERR_NULL;
-  if (B <= 0 || Hs <= 0 || Ws <= 0 || S <= 0 || std == 0.f) return SGL_ERR_BAD_SHAPE;
-  if (patch_major && (P <= 0 || S < P || Kp < 3 * P * P)) return SGL_ERR_BAD_SHAPE;
-  if (out_dtype != SGL_DTYPE_BF16 && out_dtype != SGL_DTYPE_F16 && out_dtype != SGL_DTYPE_F32) return SGL_ERR_UNSUPPORTED;
-  if ((float)Hs / (float)S > 16.f || (float)Ws / (float)S > 16.f) return SGL_ERR_UNSUPPORTED;  // tap loops stay short
-  const int g = patch_major ? S / P : 0;
-  const size_t total = patch_major ? (size_t)B * g * g * Kp : (size_t)B * 3 * S * S;
-  const int blocks = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
+  if (const int st = sgl::check_args(B, Hs, Ws, S, std, patch_major, P, Kp, out_dtype, true)) return st;
+  const sgl::OutLayout L = {S, P, Kp, patch_major ? S / P : 0, patch_major};
+  const int blocks = sgl::capped_blocks(L.elems(B), 16384);
   hipStream_t s = (hipStream_t)stream;
   const float inv_std = 1.0f / std;
-#define SGL_PP(U8, T)                                                                                               \
-  hipLaunchKernelGGL((sgl::preprocess_kernel<U8, T>), dim3(blocks), dim3(256), 0, s, src, (T*)out, B, Hs, Ws, S, P, Kp, \
-                     patch_major, mean, inv_std, mix_index, lam)
-  if (src_is_u8_nhwc) {
-    if (out_dtype == SGL_DTYPE_BF16) SGL_PP(true, sgl::bf16);
-    else if (out_dtype == SGL_DTYPE_F16) SGL_PP(true, sgl::f16);
-    else SGL_PP(true, float);
-  } else {
-    if (out_dtype == SGL_DTYPE_BF16) SGL_PP(false, sgl::bf16);
-    else if (out_dtype == SGL_DTYPE_F16) SGL_PP(false, sgl::f16);
-    else SGL_PP(false, float);
-  }
-#undef SGL_PP
+  sgl::dispatch_src_out(src_is_u8_nhwc, out_dtype, out, [&](auto u8, auto* dst) {
+    using T = std::remove_pointer_t<decltype(dst)>;
+    hipLaunchKernelGGL((sgl::preprocess_kernel<decltype(u8)::value, T>), dim3(blocks), dim3(256), 0, s, src, dst, B, Hs, Ws,
+                       L, mean, inv_std, mix_index, lam);
+  });
   return hipGetLastError() == hipSuccess ? SGL_OK : SGL_ERR_HIP;
 }
 
@@ -688,55 +675,42 @@ size_t sgl_op_preprocess_views_scratch_bytes(int V, int S) {
 int sgl_op_preprocess_views(const void* src, int src_is_u8_nhwc, int B, int Hs, int Ws, const sgl_view* views, int V,
                             void* out, int out_dtype, int S, int P, int Kp, int patch_major, float mean, float std,
                             void* scratch, size_t scratch_bytes, sgl_stream stream) {
-  static_assert(sizeof(sgl_view) == sizeof(sgl::View) && sizeof(sgl_view) == 32, "record layout");
   static_assert(sizeof(sgl::ViewChunk) <= 2048, "a chunk of records must fit the kernel arguments");
   if (!src || !views || !out) return SGL_ERR_NULL;
-  if (B <= 0 || Hs <= 0 || Ws <= 0 || S <= 0 || V <= 0 || std == 0.f) return SGL_ERR_BAD_SHAPE;
-  if (patch_major && (P <= 0 || S < P || Kp < 3 * P * P)) return SGL_ERR_BAD_SHAPE;
-  const sgl::View* rec = reinterpret_cast<const sgl::View*>(views);
-  const int rec_status = sgl::views_check(rec, V, B, Hs, Ws, S);
+  if (V <= 0) return SGL_ERR_BAD_SHAPE;
+  // a bad record is a bad shape and wins over a bad dtype, which wins over a record's unsupported ratio
+  const int rec_status = sgl::views_check(views, V, B, Hs, Ws, S);
   if (rec_status == SGL_ERR_BAD_SHAPE) return rec_status;
-  if (out_dtype != SGL_DTYPE_BF16 && out_dtype != SGL_DTYPE_F16 && out_dtype != SGL_DTYPE_F32) return SGL_ERR_UNSUPPORTED;
+  if (const int st = sgl::check_args(B, Hs, Ws, S, std, patch_major, P, Kp, out_dtype, false)) return st;
   if (rec_status != SGL_OK) return rec_status;
   if (scratch_bytes < sgl_op_preprocess_views_scratch_bytes(V, S)) return SGL_ERR_WORKSPACE;   // 0 bytes: never taken
   (void)scratch;
-  const int g = patch_major ? S / P : 0;
-  const size_t per_view = patch_major ? (size_t)g * g * Kp : (size_t)3 * S * S;
+  const sgl::OutLayout L = {S, P, Kp, patch_major ? S / P : 0, patch_major};
   const size_t esize = out_dtype == SGL_DTYPE_F32 ? 4 : 2;
   hipStream_t s = (hipStream_t)stream;
   const float inv_std = 1.0f / std;
   for (int v0 = 0; v0 < V; v0 += sgl::kViewChunk) {      // one launch per 64 views
     const int nv = V - v0 < sgl::kViewChunk ? V - v0 : sgl::kViewChunk;
     sgl::ViewChunk chunk = {};
-    for (int v = 0; v < nv; ++v) chunk.v[v] = rec[v0 + v];
-    void* dst = reinterpret_cast<char*>(out) + (size_t)v0 * per_view * esize;
-    const size_t total = (size_t)nv * per_view;
-    const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);   // 256 CUs x 16, grid-stride
+    for (int v = 0; v < nv; ++v) chunk.v[v] = views[v0 + v];
+    const int blocks = sgl::capped_blocks(L.elems(nv), 4096);   // 256 CUs x 16, grid-stride
     if (blocks == 0) continue;                           // patch-major with S / P == 0 cannot happen (S >= P)
-#define SGL_PV(U8, T)                                                                                                \
-  hipLaunchKernelGGL((sgl::preprocess_views_kernel<U8, T>), dim3(blocks), dim3(256), 0, s, src, (T*)dst, chunk, nv, Hs, \
-                     Ws, S, P, Kp, patch_major, mean, inv_std)
-    if (src_is_u8_nhwc) {
-      if (out_dtype == SGL_DTYPE_BF16) SGL_PV(true, sgl::bf16);
-      else if (out_dtype == SGL_DTYPE_F16) SGL_PV(true, sgl::f16);
-      else SGL_PV(true, float);
-    } else {
-      if (out_dtype == SGL_DTYPE_BF16) SGL_PV(false, sgl::bf16);
-      else if (out_dtype == SGL_DTYPE_F16) SGL_PV(false, sgl::f16);
-      else SGL_PV(false, float);
-    }
-#undef SGL_PV
+    sgl::dispatch_src_out(src_is_u8_nhwc, out_dtype, reinterpret_cast<char*>(out) + L.elems(v0) * esize,
+                          [&](auto u8, auto* dst) {
+      using T = std::remove_pointer_t<decltype(dst)>;
+      hipLaunchKernelGGL((sgl::preprocess_views_kernel<decltype(u8)::value, T>), dim3(blocks), dim3(256), 0, s, src, dst,
+                         chunk, nv, Hs, Ws, L, mean, inv_std);
+    });
   }
   return hipGetLastError() == hipSuccess ? SGL_OK : SGL_ERR_HIP;
 }
 
 size_t sgl_op_preprocess_views_bwd_scratch_bytes(const sgl_view* views, int V, int S) {
   if (!views || V <= 0 || S <= 0) return 0;
-  const sgl::View* rec = reinterpret_cast<const sgl::View*>(views);
   size_t bytes = 0;
   for (int v = 0; v < V; ++v) {
     int oh, ow;
-    sgl::view_extent(rec[v], &oh, &ow);
+    sgl::view_extent(views[v], &oh, &ow);
     if (oh > 0 && ow > 0) bytes += sgl::view_table_bytes(oh, ow, S);   // an empty box is refused by the call itself
   }
   return bytes;
@@ -747,11 +721,9 @@ int sgl_op_preprocess_views_bwd(const float* d_out, int B, int Hs, int Ws, const
   static_assert(sizeof(sgl::ViewChunk) + sizeof(sgl::ViewTableChunk) <= 3072, "records and offsets travel as arguments");
   static_assert(sizeof(sgl::AaAxis) % 4 == 0 && sizeof(sgl::SrcSpan) % 4 == 0, "tables stay 4-byte aligned");
   if (!d_out || !views || !d_src) return SGL_ERR_NULL;
-  if (B <= 0 || Hs <= 0 || Ws <= 0 || S <= 0 || V <= 0 || std == 0.f) return SGL_ERR_BAD_SHAPE;
-  if ((long long)34 * S > 0x7fffffffLL) return SGL_ERR_BAD_SHAPE;   // 2 S + oh + ow entries of a view's tables in an int
-  const sgl::View* rec = reinterpret_cast<const sgl::View*>(views);
-  const int rec_status = sgl::views_check(rec, V, B, Hs, Ws, S);
-  if (rec_status != SGL_OK) return rec_status;
+  if (V <= 0 || (long long)34 * S > 0x7fffffffLL) return SGL_ERR_BAD_SHAPE;   // 2 S + oh + ow table entries in an int
+  if (const int st = sgl::check_args(B, Hs, Ws, S, std, 0, 0, 0, SGL_DTYPE_F32, false)) return st;
+  if (const int st = sgl::views_check(views, V, B, Hs, Ws, S)) return st;
   const size_t need = sgl_op_preprocess_views_bwd_scratch_bytes(views, V, S);
   if (need && !scratch) return SGL_ERR_NULL;
   if (scratch_bytes < need) return SGL_ERR_WORKSPACE;
@@ -766,7 +738,7 @@ int sgl_op_preprocess_views_bwd(const float* d_out, int B, int Hs, int Ws, const
     sgl::ViewTableChunk tabs = {};
     int entries = 0;                                     // the longest table of the chunk; 0: copies only
     for (int v = 0; v < nv; ++v) {
-      chunk.v[v] = rec[v0 + v];
+      chunk.v[v] = views[v0 + v];
       int oh, ow;
       sgl::view_extent(chunk.v[v], &oh, &ow);
       tabs.off[v] = off;
@@ -778,43 +750,38 @@ int sgl_op_preprocess_views_bwd(const float* d_out, int B, int Hs, int Ws, const
       hipLaunchKernelGGL(sgl::views_bwd_tables_kernel, dim3((unsigned)((entries + 255) / 256), (unsigned)nv), dim3(256), 0,
                          s, reinterpret_cast<char*>(scratch), chunk, tabs, S);
     hipLaunchKernelGGL(sgl::preprocess_views_bwd_kernel, dim3(blocks), dim3(256), 0, s,
-                       d_out + (size_t)v0 * 3 * S * S, d_src, reinterpret_cast<const char*>(scratch), chunk, tabs, nv, B,
-                       Hs, Ws, S, (int)(v0 == 0), (int)(v0 + nv == V), inv_std);
+                       d_out + (size_t)v0 * 3 * S * S, d_src, reinterpret_cast<char*>(scratch), chunk, tabs, nv, B, Hs, Ws,
+                       S, (int)(v0 == 0), (int)(v0 + nv == V), inv_std);
   }
   return hipGetLastError() == hipSuccess ? SGL_OK : SGL_ERR_HIP;
 }
 
 size_t sgl_op_preprocess_bwd_scratch_bytes(int B, int Hs, int Ws, int S) {
   if (B <= 0 || Hs <= 0 || Ws <= 0 || S <= 0) return 0;
-  if (Hs == S && Ws == S) return 0;                      // the copy shortcut reads no table
-  return sgl::bwd_span_offset(S) + ((size_t)Hs + (size_t)Ws) * sizeof(sgl::SrcSpan);
+  return sgl::view_table_bytes(Hs, Ws, S);
 }
 
 int sgl_op_preprocess_bwd(const float* d_out, int B, int Hs, int Ws, int S, float std, const int* mix_index, float lam,
                           float* d_src, void* scratch, size_t scratch_bytes, sgl_stream stream) {
   if (!d_out || !d_src) return SGL_ERR_NULL;
-  if (B <= 0 || Hs <= 0 || Ws <= 0 || S <= 0 || std == 0.f) return SGL_ERR_BAD_SHAPE;
-  if ((long long)2 * S + Hs + Ws > 0x7fffffffLL) return SGL_ERR_BAD_SHAPE;
-  if ((float)Hs / (float)S > 16.f || (float)Ws / (float)S > 16.f) return SGL_ERR_UNSUPPORTED;  // the forward's limit
+  if ((long long)2 * S + Hs + Ws > 0x7fffffffLL) return SGL_ERR_BAD_SHAPE;   // the tables' entries in an int
+  if (const int st = sgl::check_args(B, Hs, Ws, S, std, 0, 0, 0, SGL_DTYPE_F32, true)) return st;   // the forward's limit
   const size_t need = sgl_op_preprocess_bwd_scratch_bytes(B, Hs, Ws, S);
   if (need && !scratch) return SGL_ERR_NULL;
   if (scratch_bytes < need) return SGL_ERR_WORKSPACE;
   hipStream_t s = (hipStream_t)stream;
-  sgl::AaAxis *ty = nullptr, *tx = nullptr;
-  sgl::SrcSpan *ry = nullptr, *rx = nullptr;
-  if (need) {
-    ty = reinterpret_cast<sgl::AaAxis*>(scratch);
-    tx = ty + S;
-    ry = reinterpret_cast<sgl::SrcSpan*>(reinterpret_cast<char*>(scratch) + sgl::bwd_span_offset(S));
-    rx = ry + Hs;
+  sgl::AxisTables t = {};
+  if (need) {                                            // the tables of one view: the full frame, unturned, at offset 0
+    t = sgl::axis_tables(reinterpret_cast<char*>(scratch), Hs, S);
+    sgl::ViewChunk chunk = {};
+    chunk.v[0] = sgl_view{0, 0, 0, Ws, Hs, 0, 0, 0};
     const int entries = 2 * S + Hs + Ws;
-    hipLaunchKernelGGL(sgl::preprocess_bwd_tables_kernel, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, s, ty, tx,
-                       ry, rx, Hs, Ws, S);
+    hipLaunchKernelGGL(sgl::views_bwd_tables_kernel, dim3((unsigned)((entries + 255) / 256), 1u), dim3(256), 0, s,
+                       reinterpret_cast<char*>(scratch), chunk, sgl::ViewTableChunk{}, S);
   }
-  const size_t total = (size_t)B * 3 * Hs * Ws;
-  const int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);   // 256 CUs x 8 blocks, grid-stride
+  const int blocks = sgl::capped_blocks((size_t)B * 3 * Hs * Ws, 2048);   // 256 CUs x 8 blocks, grid-stride
   hipLaunchKernelGGL(sgl::preprocess_bwd_kernel, dim3(blocks), dim3(256), 0, s, d_out, d_src, B, Hs, Ws, S, 1.0f / std,
-                     mix_index, lam, ty, tx, ry, rx);
+                     mix_index, lam, t);
   return hipGetLastError() == hipSuccess ? SGL_OK : SGL_ERR_HIP;
 }
 
@@ -823,113 +790,25 @@ int sgl_op_preprocess_aug(const void* src, int src_is_u8_nhwc, int B, int Hs, in
                           float* grey_mean, sgl_stream stream) {
   static_assert(sizeof(sgl_aug_sample) == sizeof(sgl::AugSample) && sizeof(sgl_aug_sample) == 48, "table layout");
   if (!src || !out || !aug || !grey_mean) return SGL_ERR_NULL;
-  if (B <= 0 || Hs <= 0 || Ws <= 0 || S <= 0 || std == 0.f) return SGL_ERR_BAD_SHAPE;
-  if (patch_major && (P <= 0 || S < P || Kp < 3 * P * P)) return SGL_ERR_BAD_SHAPE;
-  if (out_dtype != SGL_DTYPE_BF16 && out_dtype != SGL_DTYPE_F16 && out_dtype != SGL_DTYPE_F32) return SGL_ERR_UNSUPPORTED;
-  if ((float)Hs / (float)S > 16.f || (float)Ws / (float)S > 16.f) return SGL_ERR_UNSUPPORTED;
+  if (const int st = sgl::check_args(B, Hs, Ws, S, std, patch_major, P, Kp, out_dtype, true)) return st;
   hipStream_t s = (hipStream_t)stream;
   const sgl::AugSample* tab = reinterpret_cast<const sgl::AugSample*>(aug);
   if (src_is_u8_nhwc)
     hipLaunchKernelGGL((sgl::aug_mean_kernel<true>), dim3((unsigned)B), dim3(256), 0, s, src, Hs, Ws, S, tab, grey_mean);
   else
     hipLaunchKernelGGL((sgl::aug_mean_kernel<false>), dim3((unsigned)B), dim3(256), 0, s, src, Hs, Ws, S, tab, grey_mean);
-  const int g = patch_major ? S / P : 0;
-  const int side = patch_major ? g * P : S;
-  const size_t total = (size_t)B * side * side;
-  const int blocks = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
+  const sgl::OutLayout L = {S, P, Kp, patch_major ? S / P : 0, patch_major};
+  const int side = patch_major ? L.g * P : S;
+  const int blocks = sgl::capped_blocks((size_t)B * side * side, 16384);
   const float inv_std = 1.0f / std;
-#define SGL_PA(U8, T)                                                                                                   \
-  do {                                                                                                                  \
-    if (patch_major && Kp > 3 * P * P)                                                                                  \
-      hipLaunchKernelGGL((sgl::patch_pad_zero_kernel<T>), dim3(1024), dim3(256), 0, s, (T*)out, (size_t)B * g * g,      \
-                         3 * P * P, Kp);                                                                                \
-    hipLaunchKernelGGL((sgl::preprocess_aug_kernel<U8, T>), dim3(blocks), dim3(256), 0, s, src, (T*)out, B, Hs, Ws, S, P, \
-                       Kp, patch_major, mean, inv_std, tab, grey_mean);                                                 \
-  } while (0)
-  if (src_is_u8_nhwc) {
-    if (out_dtype == SGL_DTYPE_BF16) SGL_PA(true, sgl::bf16);
-    else if (out_dtype == SGL_DTYPE_F16) SGL_PA(true, sgl::f16);
-    else SGL_PA(true, float);
-  } else {
-    if (out_dtype == SGL_DTYPE_BF16) SGL_PA(false, sgl::bf16);
-    else if (out_dtype == SGL_DTYPE_F16) SGL_PA(false, sgl::f16);
-    else SGL_PA(false, float);
-  }
-#undef SGL_PA
-  return hipGetLastError() == hipSuccess ? SGL_OK : SGL_ERR_HIP;
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------------------------------------------------
-// Video tail (hidf_video_classifier.py:304-316): per-frame embeddings (B*T, D) -> L2-normalise each frame -> mean over the T
-// frames of a clip -> (B, D).  One workgroup per clip; forward keeps 1/|f| per frame for the backward:
-//   out[b] = (1/T) sum_t f_t / |f_t|          d f_t = (g - fhat_t (fhat_t . g)) / (T |f_t|),  g = d out[b]
-// ---------------------------------------------------------------------------------------------------------------
-namespace sgl {
-
-__global__ __launch_bounds__(256) void l2norm_tmean_fwd_kernel(const float* __restrict__ f, float* __restrict__ out,
-                                                               float* __restrict__ inv_norm, int T, int D) {
-  extern __shared__ float acc[];   // [D]
-  __shared__ float red[4];
-  const int b = blockIdx.x;
-  for (int d = threadIdx.x; d < D; d += 256) acc[d] = 0.f;
-  __syncthreads();
-  for (int t = 0; t < T; ++t) {
-    const float* row = f + ((size_t)b * T + t) * D;
-    float s = 0.f;
-    for (int d = threadIdx.x; d < D; d += 256) s += row[d] * row[d];
-    s = wave_sum(s);
-    if (lane_id() == 0) red[wave_id()] = s;
-    __syncthreads();
-    const float inv = 1.0f / sqrtf((red[0] + red[1]) + (red[2] + red[3]));
-    if (threadIdx.x == 0) inv_norm[(size_t)b * T + t] = inv;
-    for (int d = threadIdx.x; d < D; d += 256) acc[d] += row[d] * inv;
-    __syncthreads();
-  }
-  const float it = 1.0f / (float)T;
-  for (int d = threadIdx.x; d < D; d += 256) out[(size_t)b * D + d] = acc[d] * it;
-}
-
-__global__ __launch_bounds__(256) void l2norm_tmean_bwd_kernel(const float* __restrict__ f,
-                                                               const float* __restrict__ inv_norm,
-                                                               const float* __restrict__ dout, float* __restrict__ df,
-                                                               int T, int D) {
-  __shared__ float red[4];
-  const int bt = blockIdx.x, b = bt / T;
-  const float* row = f + (size_t)bt * D;
-  const float* g = dout + (size_t)b * D;
-  const float inv = inv_norm[bt];
-  float s = 0.f;
-  for (int d = threadIdx.x; d < D; d += 256) s += row[d] * g[d];
-  s = wave_sum(s);
-  if (lane_id() == 0) red[wave_id()] = s;
-  __syncthreads();
-  const float dot = ((red[0] + red[1]) + (red[2] + red[3])) * inv;   // fhat . g
-  const float k = inv / (float)T;
-  for (int d = threadIdx.x; d < D; d += 256) df[(size_t)bt * D + d] = (g[d] - row[d] * inv * dot) * k;
-}
-
-}  // namespace sgl
-
-extern "C" {
-
-int sgl_op_l2norm_tmean_fwd(const float* f, float* out, float* inv_norm, int B, int T, int D, sgl_stream stream) {
-  if (!f || !out || !inv_norm) return SGL_ERR_NULL;
-  // D floats of dynamic LDS next to the kernel's 16 static bytes, inside the 64 KiB a launch gets without raising
-  // hipFuncAttributeMaxDynamicSharedMemorySize: D * 4 + 16 <= 65536
-  if (B <= 0 || T <= 0 || D <= 0 || D > 16380) return SGL_ERR_BAD_SHAPE;
-  hipLaunchKernelGGL(sgl::l2norm_tmean_fwd_kernel, dim3((unsigned)B), dim3(256), (size_t)D * sizeof(float),
-                     (hipStream_t)stream, f, out, inv_norm, T, D);
-  return hipGetLastError() == hipSuccess ? SGL_OK : SGL_ERR_HIP;
-}
-
-int sgl_op_l2norm_tmean_bwd(const float* f, const float* inv_norm, const float* dout, float* df, int B, int T, int D,
-                            sgl_stream stream) {
-  if (!f || !inv_norm || !dout || !df) return SGL_ERR_NULL;
-  if (B <= 0 || T <= 0 || D <= 0) return SGL_ERR_BAD_SHAPE;
-  hipLaunchKernelGGL(sgl::l2norm_tmean_bwd_kernel, dim3((unsigned)(B * T)), dim3(256), 0, (hipStream_t)stream, f, inv_norm,
-                     dout, df, T, D);
+  sgl::dispatch_src_out(src_is_u8_nhwc, out_dtype, out, [&](auto u8, auto* dst) {
+    using T = std::remove_pointer_t<decltype(dst)>;
+    if (patch_major && Kp > 3 * P * P)
+      hipLaunchKernelGGL((sgl::patch_pad_zero_kernel<T>), dim3(1024), dim3(256), 0, s, dst, (size_t)B * L.g * L.g, 3 * P * P,
+                         Kp);
+    hipLaunchKernelGGL((sgl::preprocess_aug_kernel<decltype(u8)::value, T>), dim3(blocks), dim3(256), 0, s, src, dst, B, Hs,
+                       Ws, L, mean, inv_std, tab, grey_mean);
+  });
   return hipGetLastError() == hipSuccess ? SGL_OK : SGL_ERR_HIP;
 }
 

@@ -393,7 +393,7 @@ def seg_eval_from_lowres(logit_lr: torch.Tensor, masks: torch.Tensor, has_mask: 
 # ---------------------------------------------------------------------------------------------------------
 class _L2NormTemporalMeanFn(torch.autograd.Function):
     """(B*T, D) frame embeddings -> per-frame L2-norm -> mean over the T frames of a clip -> (B, D), one HIP launch forward
-    and one backward (csrc/preprocess.hip) instead of norm / div / view / mean and their four backward kernels
+    and one backward (csrc/video_tail.hip) instead of norm / div / view / mean and their four backward kernels
     (hidf_video_classifier.py:308-316)."""
 
     @staticmethod

@@ -78,19 +78,37 @@ def _patch_geometry(config, size):
     return int(size or cfg.image_size), (P, (3 * P * P + 63) // 64 * 64)
 
 
+def _alloc_out(n, size, patch, dtype, dev):
+    """The output of ``n`` images or views and its ``(S, P, Kp, patch_major)`` arguments: ``patch`` None: the
+    (n,3,size,size) image tensor; ``(P, Kp)``: the patch GEMM's operand rows."""
+    if patch is None:
+        return torch.empty((n, 3, size, size), device=dev, dtype=dtype), (size, 1, 3, 0)
+    P, Kp = patch
+    return torch.empty((n * (size // P) ** 2, Kp), device=dev, dtype=dtype), (size, P, Kp, 1)
+
+
+def _grad_out(grad_out, rows: str) -> torch.Tensor:
+    """``grad_out`` checked as a CUDA (``rows``,3,S,S) tensor: its detached fp32 contiguous form."""
+    if not grad_out.is_cuda:
+        raise RuntimeError("the GPU input pipeline runs on CUDA tensors only (no CPU path)")
+    if grad_out.dim() != 4 or grad_out.shape[1] != 3 or grad_out.shape[2] != grad_out.shape[3]:
+        raise ValueError(f"grad_out must be ({rows},3,S,S), got {tuple(grad_out.shape)}")
+    return grad_out.detach().float().contiguous()
+
+
+def _scratch(nbytes, dev):
+    """``nbytes`` of device scratch, or None for none."""
+    return torch.empty(nbytes, device=dev, dtype=torch.uint8) if nbytes else None
+
+
 def _transform(images, size, patch, dtype, mean, std, mix_index=None, lam=1.0, params=None) -> torch.Tensor:
-    """The one launch behind the four public transforms.  ``patch`` None: the (B,3,size,size) image tensor; ``(P, Kp)``:
-    the patch GEMM's operand rows.  ``params`` None: sgl_op_preprocess (MixUp); a list of per-sample draws:
-    sgl_op_preprocess_aug."""
+    """The one launch behind the four public transforms; ``patch`` as in ``_alloc_out``.  ``params`` None: sgl_op_preprocess
+    (MixUp); a list of per-sample draws: sgl_op_preprocess_aug."""
     src, is_u8, B, Hs, Ws = _source(images)
     dev = src.device
     if params is not None and len(params) != B:
         raise ValueError("one augmentation record per image")
-    if patch is None:
-        out, layout = torch.empty((B, 3, size, size), device=dev, dtype=dtype), (size, 1, 3, 0)
-    else:
-        P, Kp = patch
-        out, layout = torch.empty((B * (size // P) ** 2, Kp), device=dev, dtype=dtype), (size, P, Kp, 1)
+    out, layout = _alloc_out(B, size, patch, dtype, dev)
     common = (src.data_ptr(), is_u8, B, Hs, Ws, out.data_ptr(), _lib.dtype_code(dtype), *layout, float(mean), float(std))
     if params is None:
         idx = _mix(mix_index, B, dev)
@@ -129,18 +147,14 @@ def resize_normalize_backward(grad_out: torch.Tensor, source_hw, mix_index: Opti
     gradient with respect to a float source of size ``source_hw = (Hs, Ws)`` (for a uint8 source: with respect to
     ``bytes / 255``).  The transform is linear, so no source values are needed; one ``sgl_op_preprocess_bwd``, a gather with
     a fixed summation order: bitwise reproducible.  ``mix_index`` / ``lam`` / ``std`` as given to the forward."""
-    if not grad_out.is_cuda:
-        raise RuntimeError("the GPU input pipeline runs on CUDA tensors only (no CPU path)")
-    if grad_out.dim() != 4 or grad_out.shape[1] != 3 or grad_out.shape[2] != grad_out.shape[3]:
-        raise ValueError(f"grad_out must be (B,3,S,S), got {tuple(grad_out.shape)}")
-    g = grad_out.detach().float().contiguous()
+    g = _grad_out(grad_out, "B")
     B, S = g.shape[0], g.shape[2]
     Hs, Ws = int(source_hw[0]), int(source_hw[1])
     dev = g.device
     idx = _mix(mix_index, B, dev)
     d_src = torch.empty((B, 3, Hs, Ws), device=dev, dtype=torch.float32)
     nbytes = _lib.load().sgl_op_preprocess_bwd_scratch_bytes(B, Hs, Ws, S)
-    scratch = torch.empty(nbytes, device=dev, dtype=torch.uint8) if nbytes else None
+    scratch = _scratch(nbytes, dev)
     _lib.call("sgl_op_preprocess_bwd", dev, g.data_ptr(), B, Hs, Ws, S, float(std), _lib.ptr(idx), float(lam),
               d_src.data_ptr(), _lib.ptr(scratch), nbytes)
     return d_src
@@ -289,18 +303,14 @@ def view_table(views, B: int, Hs: int, Ws: int):
 
 
 def _views_transform(images, views, size, patch, dtype, mean, std) -> torch.Tensor:
-    """The launches behind the two view transforms (one per 64 views): ``patch`` as in ``_transform``."""
+    """The launches behind the two view transforms (one per 64 views): ``patch`` as in ``_alloc_out``."""
     src, is_u8, B, Hs, Ws = _source(images)
     dev = src.device
     tab = view_table(views, B, Hs, Ws)
     V = len(tab)
-    if patch is None:
-        out, layout = torch.empty((V, 3, size, size), device=dev, dtype=dtype), (size, 1, 3, 0)
-    else:
-        P, Kp = patch
-        out, layout = torch.empty((V * (size // P) ** 2, Kp), device=dev, dtype=dtype), (size, P, Kp, 1)
+    out, layout = _alloc_out(V, size, patch, dtype, dev)
     nbytes = _lib.load().sgl_op_preprocess_views_scratch_bytes(V, size)
-    scratch = torch.empty(nbytes, device=dev, dtype=torch.uint8) if nbytes else None
+    scratch = _scratch(nbytes, dev)
     _lib.call("sgl_op_preprocess_views", dev, src.data_ptr(), is_u8, B, Hs, Ws, tab, V, out.data_ptr(),
               _lib.dtype_code(dtype), *layout, float(mean), float(std), _lib.ptr(scratch), nbytes)
     return out
@@ -312,20 +322,16 @@ def views_resize_normalize_backward(grad_out: torch.Tensor, views, source_shape,
     ``bytes / 255``), summed over the views of each source.  The transform is linear, so no source values are needed; one
     ``sgl_op_preprocess_views_bwd``, a gather with a fixed summation order: bitwise reproducible.  A source that no view
     names, and every pixel outside all boxes, gets exactly zero.  ``views`` / ``std`` as given to the forward."""
-    if not grad_out.is_cuda:
-        raise RuntimeError("the GPU input pipeline runs on CUDA tensors only (no CPU path)")
-    if grad_out.dim() != 4 or grad_out.shape[1] != 3 or grad_out.shape[2] != grad_out.shape[3]:
-        raise ValueError(f"grad_out must be (V,3,S,S), got {tuple(grad_out.shape)}")
+    g = _grad_out(grad_out, "V")
     B, Hs, Ws = (int(t) for t in source_shape)
     tab = view_table(views, B, Hs, Ws)
     V, S = len(tab), grad_out.shape[2]
     if grad_out.shape[0] != V:
         raise ValueError(f"grad_out has {grad_out.shape[0]} rows for {V} views")
-    g = grad_out.detach().float().contiguous()
     dev = g.device
     d_src = torch.empty((B, 3, Hs, Ws), device=dev, dtype=torch.float32)
     nbytes = _lib.load().sgl_op_preprocess_views_bwd_scratch_bytes(tab, V, S)
-    scratch = torch.empty(nbytes, device=dev, dtype=torch.uint8) if nbytes else None
+    scratch = _scratch(nbytes, dev)
     _lib.call("sgl_op_preprocess_views_bwd", dev, g.data_ptr(), B, Hs, Ws, tab, V, S, float(std), d_src.data_ptr(),
               _lib.ptr(scratch), nbytes)
     return d_src
@@ -577,7 +583,9 @@ class GpuTransform(nn.Module):
         """``data_augmentation=True`` (hidf_video_classifier.py ``--data_augmentation``, :2866-2874) inserts flip / rotation /
         colour jitter between resize and normalize while the module is in training mode; draws come from ``generator``.
         The plain branch is differentiable with respect to floating ``images`` that require grad (``resize_normalize``);
-        the augmentation branch refuses such a source."""
+        the augmentation branch refuses such a source.  The reference never puts its ``gpu_transform`` into eval mode, so
+        with ``--data_augmentation`` it augments validation batches too.  This module augments only in training mode, on
+        purpose: call ``.eval()`` for validation."""
         if self.data_augmentation and self.training:
             _refuse_grad(images, "GpuTransform(data_augmentation=True) in training mode")
             if mix_index is not None:

@@ -478,7 +478,7 @@ def pos_resize_bound(table, g0):
 
 
 # ===============================================================================================================
-# kernels outside the encoder (csrc/preprocess.hip, decoder.hip, decoder_tail.hip, optimizer.hip)
+# kernels outside the encoder (csrc/preprocess.hip, video_tail.hip, decoder.hip, decoder_tail.hip, optimizer.hip)
 #
 # Every bound below is derived: output rounding UNIT / TINY, fp32 accumulation from the number of addends the element
 # has (a sum of n fp32 terms in any order is off by at most n 2^-24 sum|terms|; where the kernel's order is fixed by the

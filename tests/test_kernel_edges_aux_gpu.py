@@ -1,6 +1,6 @@
-"""GPU tests of the HIP kernels OUTSIDE the encoder, through the C ABI (``sgl_op_*``): the input pipeline and the video
-tail (csrc/preprocess.hip), the depthwise 3x3 (csrc/decoder.hip), the decoder tail (csrc/decoder_tail.hip) and AdamW
-(csrc/optimizer.hip).
+"""GPU tests of the HIP kernels OUTSIDE the encoder, through the C ABI (``sgl_op_*``): the input pipeline
+(csrc/preprocess.hip), the video tail (csrc/video_tail.hip), the depthwise 3x3 (csrc/decoder.hip), the decoder tail
+(csrc/decoder_tail.hip) and AdamW (csrc/optimizer.hip).
 
 Same discipline as tests/test_kernel_edges_gpu.py: every output element is held to its own bound against a float64
 reference of the same operation on the same rounded inputs (tests/kernel_ref.py; the bounds are asserted against CPU
