@@ -52,6 +52,8 @@ template <> struct Elem<f16> {
   static __device__ __forceinline__ float ld(const f16* p) { return (float)*p; }
   static __device__ __forceinline__ void st(f16* p, float v) { *p = (f16)v; }
 };
+// float -> T for T in {float, bf16, f16}: round to nearest even, the conversion Elem<T>::st applies
+template <typename T> __device__ __forceinline__ T cvt_to(float x) { return (T)x; }
 
 // load / store NV (4 or 8) consecutive elements as float; pointers must be NV*sizeof(T)-aligned
 template <typename T, int NV> struct Vec;

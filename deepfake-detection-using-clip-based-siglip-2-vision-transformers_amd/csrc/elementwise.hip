@@ -1,6 +1,7 @@
 // HBM-bound helper kernels around the encoder GEMMs (gfx950): patch gather (im2col), weight-shadow casts,
 // bias-gradient column sums, position-table bicubic resize, and the 1-query attention-pool head.
 #include "common.hip.h"
+#include "shadow_tile.hip.h"
 #include "kernels.h"
 
 namespace sgl {
@@ -160,9 +161,11 @@ __device__ __forceinline__ void split_bf16(float x, bf16& hi, bf16& lo) {
   lo = (bf16)(x - (float)hi);
 }
 
-// dst [R][3*Cs] bf16 (Cs = C rounded up to 8, zero filled); b_side selects the B-operand segment order
-__global__ __launch_bounds__(256) void split3_rows_kernel(const float* __restrict__ src, int R, int C, int ld,
-                                                          bf16* __restrict__ dst, int Cs, int b_side) {
+// Row r of src (Cs = C rounded up to 8, zero filled) goes to dst + r * row_stride as hi, then at + seg_stride and
+// + 2 * seg_stride as (hi, lo) for an A operand and (lo, hi) for a B operand (b_side).
+__global__ __launch_bounds__(256) void split3_kernel(const float* __restrict__ src, int R, int C, int ld,
+                                                     bf16* __restrict__ dst, int Cs, size_t row_stride, size_t seg_stride,
+                                                     int b_side) {
   const int cpr = Cs >> 3;
   const size_t total = (size_t)R * cpr;
   const bool vec = ((ld & 3) == 0) && ((((uintptr_t)src) & 15) == 0);
@@ -185,60 +188,29 @@ __global__ __launch_bounds__(256) void split3_rows_kernel(const float* __restric
       hi[j] = h;
       lo[j] = l;
     }
-    bf16* dp = dst + (size_t)r * (3 * (size_t)Cs) + c0;
+    bf16* dp = dst + (size_t)r * row_stride + c0;
     *reinterpret_cast<bf16x8*>(dp) = hi;
-    *reinterpret_cast<bf16x8*>(dp + Cs) = b_side ? lo : hi;
-    *reinterpret_cast<bf16x8*>(dp + 2 * (size_t)Cs) = b_side ? hi : lo;
+    *reinterpret_cast<bf16x8*>(dp + seg_stride) = b_side ? lo : hi;
+    *reinterpret_cast<bf16x8*>(dp + 2 * seg_stride) = b_side ? hi : lo;
   }
 }
 
+static hipError_t split3(const float* src, int R, int C, int ld, void* dst, int Cs, size_t row_stride, size_t seg_stride,
+                         int b_side, hipStream_t s) {
+  const size_t total = (size_t)R * (Cs / 8);
+  if (total == 0) return hipSuccess;
+  const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
+  hipLaunchKernelGGL(split3_kernel, dim3(blocks), dim3(256), 0, s, src, R, C, ld, (bf16*)dst, Cs, row_stride, seg_stride,
+                     b_side);
+  return hipGetLastError();
+}
+// dst [R][3*Cs] bf16: the three segments side by side in each row
 hipError_t split3_rows(const float* src, int R, int C, int ld, void* dst, int Cs, int b_side, hipStream_t s) {
-  const size_t total = (size_t)R * (Cs / 8);
-  if (total == 0) return hipSuccess;
-  const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-  hipLaunchKernelGGL(split3_rows_kernel, dim3(blocks), dim3(256), 0, s, src, R, C, ld, (bf16*)dst, Cs, b_side);
-  return hipGetLastError();
+  return split3(src, R, C, ld, dst, Cs, 3 * (size_t)Cs, (size_t)Cs, b_side, s);
 }
-
-// dst [3*R][Cs] bf16: rows [0,R) hi, [R,2R) hi (A) / lo (B), [2R,3R) lo (A) / hi (B)
-__global__ __launch_bounds__(256) void split3_stack_kernel(const float* __restrict__ src, int R, int C, int ld,
-                                                           bf16* __restrict__ dst, int Cs, int b_side) {
-  const int cpr = Cs >> 3;
-  const size_t total = (size_t)R * cpr;
-  const bool vec = ((ld & 3) == 0) && ((((uintptr_t)src) & 15) == 0);
-  for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
-    const int r = (int)(idx / cpr), c0 = (int)(idx - (size_t)r * cpr) * 8;
-    const float* sp = src + (size_t)r * ld + c0;
-    float v[8];
-    if (vec && c0 + 8 <= C) {
-      Vec<float, 4>::ld(sp, v);
-      Vec<float, 4>::ld(sp + 4, v + 4);
-    } else {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = (c0 + j < C) ? sp[j] : 0.f;
-    }
-    bf16x8 hi, lo;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      bf16 h, l;
-      split_bf16(v[j], h, l);
-      hi[j] = h;
-      lo[j] = l;
-    }
-    bf16* dp = dst + (size_t)r * Cs + c0;
-    const size_t plane = (size_t)R * Cs;
-    *reinterpret_cast<bf16x8*>(dp) = hi;
-    *reinterpret_cast<bf16x8*>(dp + plane) = b_side ? lo : hi;
-    *reinterpret_cast<bf16x8*>(dp + 2 * plane) = b_side ? hi : lo;
-  }
-}
-
+// dst [3*R][Cs] bf16: the three segments as planes of R rows, one below the other
 hipError_t split3_stack(const float* src, int R, int C, int ld, void* dst, int Cs, int b_side, hipStream_t s) {
-  const size_t total = (size_t)R * (Cs / 8);
-  if (total == 0) return hipSuccess;
-  const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-  hipLaunchKernelGGL(split3_stack_kernel, dim3(blocks), dim3(256), 0, s, src, R, C, ld, (bf16*)dst, Cs, b_side);
-  return hipGetLastError();
+  return split3(src, R, C, ld, dst, Cs, (size_t)Cs, (size_t)R * Cs, b_side, s);
 }
 
 // ---- all weight shadows of one transformer block (or of the pooling head) in ONE launch -----------------------------------
@@ -247,11 +219,6 @@ hipError_t split3_stack(const float* src, int R, int C, int ld, void* dst, int C
 // 350 launches of 5-7 us per so400m step, 153 per base-224 step.  Here a block's matrices are walked in 64x64 tiles of their
 // PADDED destination (zeros outside the source), each tile read once as fp32 and written twice: row-major and, through an LDS
 // transpose, column-major, both with >= 128-byte row segments; one extra workgroup copies / pads the bias vectors.
-template <typename T> __device__ __forceinline__ T cj_cvt(float x);
-template <> __device__ __forceinline__ float cj_cvt<float>(float x) { return x; }
-template <> __device__ __forceinline__ bf16 cj_cvt<bf16>(float x) { return (bf16)x; }
-template <> __device__ __forceinline__ f16 cj_cvt<f16>(float x) { return (f16)x; }
-
 template <typename T>
 __global__ __launch_bounds__(256) void cast_job_kernel(CastJob job) {
   __shared__ float lds_raw[64 * 66];
@@ -274,7 +241,8 @@ __global__ __launch_bounds__(256) void cast_job_kernel(CastJob job) {
   const int tr = tile / m.tiles_c, tc = tile - tr * m.tiles_c;
   const int r0 = tr * 64, c0 = tc * 64;
   const int tx = t & 15, ty = t >> 4;
-  T* dst = reinterpret_cast<T*>(m.dst);
+  // the padded destination [Rp][Cp] is written whole: zeros outside the R x C source
+  const ShadowTile<T> sh{reinterpret_cast<T*>(m.dst), reinterpret_cast<T*>(m.dst_t), m.ldd, m.ldt, 0, m.Rp, m.Cp, 0, r0, c0, lt};
   const bool vsrc_ok = ((m.lds & 3) == 0) && ((((uintptr_t)m.src) & 15) == 0);
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
@@ -289,51 +257,9 @@ __global__ __launch_bounds__(256) void cast_job_kernel(CastJob job) {
         for (int j = 0; j < 4 && cc + j < m.C; ++j) v[j] = sp[j];
       }
     }
-    T o4[4] = {cj_cvt<T>(v[0]), cj_cvt<T>(v[1]), cj_cvt<T>(v[2]), cj_cvt<T>(v[3])};
-    if (dst && r < m.Rp && cc < m.Cp) {
-      T* d = dst + (size_t)r * m.ldd + cc;
-      if (cc + 3 < m.Cp && ((((uintptr_t)d) & (4 * sizeof(T) - 1)) == 0)) {
-        if constexpr (sizeof(T) == 2) {
-          u32x2 w;
-          __builtin_memcpy(&w, o4, 8);
-          *reinterpret_cast<u32x2*>(d) = w;
-        } else {
-          u32x4 w;
-          __builtin_memcpy(&w, o4, 16);
-          *reinterpret_cast<u32x4*>(d) = w;
-        }
-      } else {
-        for (int j = 0; j < 4 && cc + j < m.Cp; ++j) d[j] = o4[j];
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) lt[(ty + 16 * k) * 66 + tx * 4 + j] = o4[j];
+    sh.put(k, v);
   }
-  if (!m.dst_t) return;
-  __syncthreads();
-  // transposed copy [Cp][Rp]: output row = source column c0 + oc, 16 consecutive elements = source rows r0 + 16*seg ..
-  T* dt = reinterpret_cast<T*>(m.dst_t);
-  const int oc = t >> 2, seg = t & 3;
-  if (c0 + oc < m.Cp) {
-    const int rb = r0 + seg * 16;
-    T* drow = dt + (size_t)(c0 + oc) * m.ldt + rb;
-    T vals[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) vals[j] = lt[(seg * 16 + j) * 66 + oc];
-    if (rb + 15 < m.Rp && ((((uintptr_t)drow) & 15) == 0)) {
-      constexpr int PER = 16 / sizeof(T);
-#pragma unroll
-      for (int q = 0; q < 16 / PER; ++q) {
-        u32x4 w;
-        __builtin_memcpy(&w, &vals[q * PER], 16);
-        *reinterpret_cast<u32x4*>(drow + q * PER) = w;
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < 16; ++j)
-        if (rb + j < m.Rp) drow[j] = vals[j];
-    }
-  }
+  sh.put_transposed();
 }
 
 void cast_job_add(CastJob& job, const float* src, int R, int C, int lds_, void* dst, int Rp, int Cp, int ldd, void* dst_t,

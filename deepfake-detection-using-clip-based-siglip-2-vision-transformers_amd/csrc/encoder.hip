@@ -684,6 +684,85 @@ int sgl_query_sizes(const sgl_ctx* ctx, int B, int H, int W, int train, size_t* 
   return SGL_OK;
 }
 
+// ---- the placement table: where each master tensor's copies live in the shadow arena -------------------------------
+// The ONE statement of it.  sgl_prepare_weights_dirty builds its cast jobs from these records and sgl_adamw_bind_shadows
+// hands the same records to the optimizer (optimizer.hip, adamw_ex_kernel), so the two routes that write the arena
+// cannot disagree about an offset, a leading dimension or a padding.
+struct ShadowMat {
+  const float* master;   // fp32 [rows][cols], leading dimension lds
+  int rows, cols, lds;
+  int row0;              // the copies hold rows [row0, rows)
+  size_t dst, dst_t;     // byte offsets of the row-major copy [Rp][Cp] and of the transposed copy [Cp][Rp] (if ld_t != 0)
+  int ld, ld_t;          // their leading dimensions, in elements
+  int Rp, Cp;            // padded extents: zero outside the (rows - row0) x cols source
+};
+struct ShadowVec {       // fp32 copy of n elements, zero padded to np
+  const float* master;
+  int n;
+  size_t dst;
+  int np;
+};
+struct ShadowUnit {
+  ShadowMat m[6];
+  ShadowVec v[4];
+  int nm = 0, nv = 0;
+};
+
+// unit = block l >= 0, or -1: the globals (patch weight and, with the pooling head, its matrices).  MX mode keeps the
+// blocks' matrices as MX operands (quantize_mx, below): a block then has its bias vectors only.
+static ShadowUnit shadow_unit(const sgl_ctx* ctx, const sgl_weights* w, int unit) {
+  const int D = ctx->D, I = ctx->I, Ip = ctx->Ip;
+  const size_t es = ctx->es;
+  ShadowUnit u;
+  auto square = [&](const float* master, size_t dst, size_t dst_t, int ld_t) {   // [D][D] -> [D][D]
+    u.m[u.nm++] = {master, D, D, D, 0, dst, dst_t, D, ld_t, D, D};
+  };
+  auto mlp = [&](const float* fc1_w, size_t w1, size_t w1_t, const float* fc2_w, size_t w2, size_t w2_t,
+                 const float* fc1_b, size_t b1) {   // the intermediate dimension is padded to Ip
+    u.m[u.nm++] = {fc1_w, I, D, D, 0, w1, w1_t, D, Ip, Ip, D};
+    u.m[u.nm++] = {fc2_w, D, I, I, 0, w2, w2_t, Ip, D, D, Ip};
+    u.v[u.nv++] = {fc1_b, I, b1, Ip};
+  };
+  if (unit >= 0) {
+    const sgl_layer_weights& lw = w->layers[unit];
+    const ShadowLayer& sl = ctx->sh_layers[unit];
+    const float* qkv_w[3] = {lw.q_w, lw.k_w, lw.v_w};
+    const float* qkv_b[3] = {lw.q_b, lw.k_b, lw.v_b};
+    for (int j = 0; j < 3; ++j) {   // fused: [3D][D] row-major, [D][3D] transposed
+      if (!ctx->mx) square(qkv_w[j], sl.wqkv + (size_t)j * D * D * es, sl.wqkv_t + (size_t)j * D * es, 3 * D);
+      u.v[u.nv++] = {qkv_b[j], D, sl.bqkv + (size_t)j * D * 4, D};
+    }
+    if (ctx->mx) {
+      u.v[u.nv++] = {lw.fc1_b, I, sl.b1, Ip};
+      return u;
+    }
+    square(lw.o_w, sl.wo, sl.wo_t, D);
+    mlp(lw.fc1_w, sl.w1, sl.w1_t, lw.fc2_w, sl.w2, sl.w2_t, lw.fc1_b, sl.b1);
+    return u;
+  }
+  u.m[u.nm++] = {w->patch_w, D, ctx->K0, ctx->K0, 0, ctx->sh_wpatch, 0, ctx->Kp, 0, D, ctx->Kp};   // no transposed copy
+  if (ctx->cfg.use_head) {
+    // the probe's query never changes with the input: only the k / v rows [D, 3D) of in_proj_w have copies
+    u.m[u.nm++] = {w->in_proj_w, 3 * D, D, D, D, ctx->sh_hwkv, ctx->sh_hwkv_t, D, 2 * D, 2 * D, D};
+    square(w->out_proj_w, ctx->sh_hwo, ctx->sh_hwo_t, D);
+    mlp(w->head_fc1_w, ctx->sh_hw1, ctx->sh_hw1_t, w->head_fc2_w, ctx->sh_hw2, ctx->sh_hw2_t, w->head_fc1_b, ctx->sh_hb1);
+  }
+  return u;
+}
+
+// one launch per unit (elementwise.hip, cast_job_kernel): every matrix read once, written row-major and transposed
+static hipError_t cast_unit(const ShadowUnit& u, void* shadow, int dt, hipStream_t s) {
+  CastJob job;
+  for (int k = 0; k < u.nm; ++k) {
+    const ShadowMat& m = u.m[k];
+    cast_job_add(job, m.master + (size_t)m.row0 * m.lds, m.rows - m.row0, m.cols, m.lds, at(shadow, m.dst), m.Rp, m.Cp,
+                 m.ld, m.ld_t ? at(shadow, m.dst_t) : nullptr, m.ld_t);
+  }
+  for (int k = 0; k < u.nv; ++k)
+    cast_job_add_vec(job, u.v[k].master, u.v[k].n, reinterpret_cast<float*>(at(shadow, u.v[k].dst)), u.v[k].np);
+  return cast_job_run(job, dt, s);
+}
+
 // layer_dirty: L flags (NULL = every block); globals_dirty: patch embedding + pooling-head matrices.  Frozen-prefix
 // fine-tuning (Siglip2sidafrozen.py:757-768) changes 6 of 27 blocks per step: re-casting all of them every step was
 // 2.5 % of that config's step.
@@ -692,17 +771,13 @@ int sgl_prepare_weights_dirty(sgl_ctx* ctx, const sgl_weights* w, void* shadow, 
   if (!ctx || !w || !shadow || (ctx->L > 0 && !w->layers)) return SGL_ERR_NULL;
   if (shadow_bytes < ctx->sh_total) return SGL_ERR_WORKSPACE;
   hipStream_t s = (hipStream_t)stream;
-  const int D = ctx->D, I = ctx->I, Ip = ctx->Ip, dt = ctx->dt;
-  if (globals_dirty)
-    CK(cast_pad(w->patch_w, D, ctx->K0, ctx->K0, at(shadow, ctx->sh_wpatch), dt, D, ctx->Kp, ctx->Kp, s));
-  const size_t es = ctx->es;
   for (int l = 0; l < ctx->L; ++l) {
     if (layer_dirty && !layer_dirty[l]) continue;
-    const sgl_layer_weights& lw = w->layers[l];
-    const ShadowLayer& sl = ctx->sh_layers[l];
-    const float* qkv_w[3] = {lw.q_w, lw.k_w, lw.v_w};
-    const float* qkv_b[3] = {lw.q_b, lw.k_b, lw.v_b};
     if (ctx->mx) {   // each weight row quantized along its input dim, exactly as the activations are
+      const int D = ctx->D, I = ctx->I, Ip = ctx->Ip;
+      const sgl_layer_weights& lw = w->layers[l];
+      const ShadowLayer& sl = ctx->sh_layers[l];
+      const float* qkv_w[3] = {lw.q_w, lw.k_w, lw.v_w};
       const size_t Dp = ctx->Dp;
       for (int j = 0; j < 3; ++j)
         CK(quantize_mx(qkv_w[j], DT_F32, D, D, D, (int)Dp, at(shadow, sl.wqkv + (size_t)j * D * Dp),
@@ -714,36 +789,10 @@ int sgl_prepare_weights_dirty(sgl_ctx* ctx, const sgl_weights* w, void* shadow, 
         CK(hipMemsetAsync(at(shadow, sl.w1_s + (size_t)I * Dp / 32), 0, (size_t)(Ip - I) * Dp / 32, s));
       }
       CK(quantize_mx(lw.fc2_w, DT_F32, I, D, I, Ip, at(shadow, sl.w2), at(shadow, sl.w2_s), s));
-      CastJob job;
-      for (int j = 0; j < 3; ++j)
-        cast_job_add_vec(job, qkv_b[j], D, reinterpret_cast<float*>(at(shadow, sl.bqkv)) + (size_t)j * D, D);
-      cast_job_add_vec(job, lw.fc1_b, I, reinterpret_cast<float*>(at(shadow, sl.b1)), Ip);
-      CK(cast_job_run(job, dt, s));
-      continue;
     }
-    // one launch per block (elementwise.hip, cast_job_kernel): every matrix read once, written row-major and transposed
-    CastJob job;
-    for (int j = 0; j < 3; ++j) {
-      cast_job_add(job, qkv_w[j], D, D, D, at(shadow, sl.wqkv + (size_t)j * D * D * es), D, D, D,
-                   at(shadow, sl.wqkv_t + (size_t)j * D * es), 3 * D);
-      cast_job_add_vec(job, qkv_b[j], D, reinterpret_cast<float*>(at(shadow, sl.bqkv)) + (size_t)j * D, D);
-    }
-    cast_job_add(job, lw.o_w, D, D, D, at(shadow, sl.wo), D, D, D, at(shadow, sl.wo_t), D);
-    cast_job_add(job, lw.fc1_w, I, D, D, at(shadow, sl.w1), Ip, D, D, at(shadow, sl.w1_t), Ip);
-    cast_job_add(job, lw.fc2_w, D, I, I, at(shadow, sl.w2), D, Ip, Ip, at(shadow, sl.w2_t), D);
-    cast_job_add_vec(job, lw.fc1_b, I, reinterpret_cast<float*>(at(shadow, sl.b1)), Ip);
-    CK(cast_job_run(job, dt, s));
+    CK(cast_unit(shadow_unit(ctx, w, l), shadow, ctx->dt, s));
   }
-  if (ctx->cfg.use_head && globals_dirty) {
-    const float* kv_w = w->in_proj_w + (size_t)D * D;
-    CastJob job;
-    cast_job_add(job, kv_w, 2 * D, D, D, at(shadow, ctx->sh_hwkv), 2 * D, D, D, at(shadow, ctx->sh_hwkv_t), 2 * D);
-    cast_job_add(job, w->out_proj_w, D, D, D, at(shadow, ctx->sh_hwo), D, D, D, at(shadow, ctx->sh_hwo_t), D);
-    cast_job_add(job, w->head_fc1_w, I, D, D, at(shadow, ctx->sh_hw1), Ip, D, D, at(shadow, ctx->sh_hw1_t), Ip);
-    cast_job_add(job, w->head_fc2_w, D, I, I, at(shadow, ctx->sh_hw2), D, Ip, Ip, at(shadow, ctx->sh_hw2_t), D);
-    cast_job_add_vec(job, w->head_fc1_b, I, reinterpret_cast<float*>(at(shadow, ctx->sh_hb1)), Ip);
-    CK(cast_job_run(job, dt, s));
-  }
+  if (globals_dirty) CK(cast_unit(shadow_unit(ctx, w, -1), shadow, ctx->dt, s));
   return SGL_OK;
 }
 
@@ -751,59 +800,34 @@ int sgl_prepare_weights(sgl_ctx* ctx, const sgl_weights* w, void* shadow, size_t
   return sgl_prepare_weights_dirty(ctx, w, shadow, shadow_bytes, nullptr, 1, stream);
 }
 
-
-// Where each master tensor's copies live in the shadow arena (the destinations sgl_prepare_weights_dirty casts into),
-// matched by the master pointer: lets the optimizer write them in its own pass (optimizer.hip, adamw_ex_kernel).
+// Lets the optimizer write the copies in its own pass: every table entry whose .p is a master of the placement table
+// gets that record's destinations.
 int sgl_adamw_bind_shadows(const sgl_ctx* ctx, const sgl_weights* w, void* shadow, const sgl_adamw_tensor* table,
                            sgl_adamw_aux* aux, int ntensors) {
   if (!ctx || !w || !shadow || !table || !aux) return SGL_ERR_NULL;
   if (ctx->mx) return 0;   // MX shadows are re-quantized by sgl_prepare_weights_dirty (the mode does not train)
-  const int D = ctx->D, I = ctx->I, Ip = ctx->Ip;
-  const size_t es = ctx->es;
   int bound = 0;
-  auto mat = [&](const float* master, int rows, int cols, int row0, size_t off, int ld, size_t off_t, int ld_t,
-                 size_t elem_off = 0, size_t elem_off_t = 0) {
-    if (!master) return;
-    for (int i = 0; i < ntensors; ++i)
-      if (table[i].p == master) {
-        aux[i].dst = at(shadow, off) + elem_off * es;
-        aux[i].dst_t = ld_t ? at(shadow, off_t) + elem_off_t * es : nullptr;
+  for (int unit = -1; unit < (w->layers ? ctx->L : 0); ++unit) {
+    const ShadowUnit u = shadow_unit(ctx, w, unit);
+    for (int i = 0; i < ntensors; ++i) {
+      if (!table[i].p) continue;
+      for (int k = 0; k < u.nm; ++k) {
+        const ShadowMat& m = u.m[k];
+        if (table[i].p != m.master) continue;
+        aux[i].dst = at(shadow, m.dst);
+        aux[i].dst_t = m.ld_t ? at(shadow, m.dst_t) : nullptr;
         aux[i].dst_f32 = nullptr;
-        aux[i].ld = ld; aux[i].ld_t = ld_t; aux[i].rows = rows; aux[i].cols = cols; aux[i].row0 = row0;
+        aux[i].ld = m.ld; aux[i].ld_t = m.ld_t; aux[i].rows = m.rows; aux[i].cols = m.cols; aux[i].row0 = m.row0;
         aux[i].dtype = ctx->dt;
         ++bound;
       }
-  };
-  auto vec = [&](const float* master, size_t off, size_t elem_off) {
-    if (!master) return;
-    for (int i = 0; i < ntensors; ++i)
-      if (table[i].p == master) {
+      for (int k = 0; k < u.nv; ++k) {
+        if (table[i].p != u.v[k].master) continue;
         aux[i].dst = aux[i].dst_t = nullptr;
-        aux[i].dst_f32 = reinterpret_cast<float*>(at(shadow, off)) + elem_off;
+        aux[i].dst_f32 = reinterpret_cast<float*>(at(shadow, u.v[k].dst));
         ++bound;
       }
-  };
-  mat(w->patch_w, D, ctx->K0, 0, ctx->sh_wpatch, ctx->Kp, 0, 0);
-  for (int l = 0; l < ctx->L && w->layers; ++l) {
-    const sgl_layer_weights& lw = w->layers[l];
-    const ShadowLayer& sl = ctx->sh_layers[l];
-    const float* qkv_w[3] = {lw.q_w, lw.k_w, lw.v_w};
-    const float* qkv_b[3] = {lw.q_b, lw.k_b, lw.v_b};
-    for (int j = 0; j < 3; ++j) {
-      mat(qkv_w[j], D, D, 0, sl.wqkv, D, sl.wqkv_t, 3 * D, (size_t)j * D * D, (size_t)j * D);
-      vec(qkv_b[j], sl.bqkv, (size_t)j * D);
     }
-    mat(lw.o_w, D, D, 0, sl.wo, D, sl.wo_t, D);
-    mat(lw.fc1_w, I, D, 0, sl.w1, D, sl.w1_t, Ip);
-    mat(lw.fc2_w, D, I, 0, sl.w2, Ip, sl.w2_t, D);
-    vec(lw.fc1_b, sl.b1, 0);
-  }
-  if (ctx->cfg.use_head) {
-    mat(w->in_proj_w, 3 * D, D, D, ctx->sh_hwkv, D, ctx->sh_hwkv_t, 2 * D);
-    mat(w->out_proj_w, D, D, 0, ctx->sh_hwo, D, ctx->sh_hwo_t, D);
-    mat(w->head_fc1_w, I, D, 0, ctx->sh_hw1, D, ctx->sh_hw1_t, Ip);
-    mat(w->head_fc2_w, D, I, 0, ctx->sh_hw2, Ip, ctx->sh_hw2_t, D);
-    vec(w->head_fc1_b, ctx->sh_hb1, 0);
   }
   return bound;
 }

@@ -26,6 +26,7 @@
 #include <stdint.h>
 
 #include "common.hip.h"
+#include "shadow_tile.hip.h"
 #include "siglip_hip.h"
 
 namespace sgl {
@@ -36,43 +37,54 @@ __device__ __forceinline__ bool aligned16(const void* a, const void* b, const vo
   return ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c) | ((uintptr_t)d)) & 15) == 0;
 }
 
+// One 4096-element chunk (starting at `base`) of a tensor of n elements, walked by a 256-thread block: four 16-byte
+// accesses per thread, vec4(i) for a whole group of four elements at i, one(j) per element of the tensor's tail; element
+// by element, one(j), when the caller's pointers are not 16-byte aligned.
+template <typename Vec4, typename One>
+__device__ __forceinline__ void walk_chunk(uint64_t base, uint64_t n, bool aligned, Vec4 vec4, One one) {
+  if (aligned) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const uint64_t i = base + (uint64_t)(k * 256 + threadIdx.x) * 4;
+      if (i + 3 < n) {
+        vec4(i);
+      } else {
+        for (uint64_t j = i; j < n && j < i + 4; ++j) one(j);
+      }
+    }
+  } else {
+    for (int k = 0; k < 16; ++k) {
+      const uint64_t i = base + (uint64_t)k * 256 + threadIdx.x;
+      if (i < n) one(i);
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void grad_sqnorm_kernel(const sgl_adamw_tensor* __restrict__ T,
                                                           const int32_t* __restrict__ map,
                                                           float* __restrict__ partial) {
   __shared__ float red[4];
   const int ti = map[2 * blockIdx.x], ch = map[2 * blockIdx.x + 1];
   const float* g = T[ti].g;
-  const uint64_t n = T[ti].n;
-  const uint64_t base = (uint64_t)ch * OPT_CHUNK;
   float s = 0.f;
-  if (g) {
-    if ((((uintptr_t)g) & 15) == 0) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const uint64_t i = base + (uint64_t)(k * 256 + threadIdx.x) * 4;
-        if (i + 3 < n) {
-          const f32x4 x = *reinterpret_cast<const f32x4*>(g + i);
-          s += (x[0] * x[0] + x[1] * x[1]) + (x[2] * x[2] + x[3] * x[3]);
-        } else {
-          for (uint64_t j = i; j < n && j < i + 4; ++j) s += g[j] * g[j];
-        }
-      }
-    } else {
-      for (int k = 0; k < 16; ++k) {
-        const uint64_t i = base + (uint64_t)k * 256 + threadIdx.x;
-        if (i < n) s += g[i] * g[i];
-      }
-    }
-  }
+  if (g)
+    walk_chunk((uint64_t)ch * OPT_CHUNK, T[ti].n, (((uintptr_t)g) & 15) == 0,
+               [&](uint64_t i) {
+                 const f32x4 x = *reinterpret_cast<const f32x4*>(g + i);
+                 s += (x[0] * x[0] + x[1] * x[1]) + (x[2] * x[2] + x[3] * x[3]);
+               },
+               [&](uint64_t j) { s += g[j] * g[j]; });
   s = wave_sum(s);
   if (lane_id() == 0) red[wave_id()] = s;
   __syncthreads();
   if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-// out[0] = ||g||_2 ; out[1] = min(1, max_norm / (norm + 1e-6))   (torch.nn.utils.clip_grad_norm_)
-__global__ __launch_bounds__(1024) void grad_norm_finish_kernel(const float* __restrict__ partial, int n,
-                                                                float max_norm, float* __restrict__ out) {
+// out[0] = s*||g||_2 ; out[1] = s*min(1, max_norm / (s*norm + 1e-6)).  s = 1 is torch.nn.utils.clip_grad_norm_; s = 1/world
+// is the factor every gradient is multiplied by when the stored gradients are rank SUMS
+// (ddp.GradBucketReducer(average="defer")).
+__global__ __launch_bounds__(1024) void grad_norm_finish_kernel(const float* __restrict__ partial, int n, float max_norm,
+                                                                float gscale, float* __restrict__ out) {
   __shared__ double red[16];
   double s = 0.0;
   for (int i = threadIdx.x; i < n; i += 1024) s += (double)partial[i];
@@ -83,14 +95,14 @@ __global__ __launch_bounds__(1024) void grad_norm_finish_kernel(const float* __r
   if (threadIdx.x == 0) {
     double t = 0.0;
     for (int i = 0; i < 16; ++i) t += red[i];
-    const float norm = (float)sqrt(t);
+    const float norm = (float)sqrt(t) * gscale;
     out[0] = norm;
     float coef = 1.0f;
     if (max_norm > 0.f) {
       coef = max_norm / (norm + 1e-6f);
       if (coef > 1.0f) coef = 1.0f;
     }
-    out[1] = coef;
+    out[1] = coef * gscale;
   }
 }
 
@@ -111,47 +123,6 @@ __device__ __forceinline__ void adamw_one(float& p, float g, float& m, float& v,
   p = p - (lr * c.inv_bc1) * (m / denom);
 }
 
-__global__ __launch_bounds__(256) void adamw_kernel(const sgl_adamw_tensor* __restrict__ T,
-                                                    const int32_t* __restrict__ map, AdamConst c,
-                                                    const float* __restrict__ clip /* [2] or null */) {
-  const int ti = map[2 * blockIdx.x], ch = map[2 * blockIdx.x + 1];
-  const sgl_adamw_tensor t = T[ti];
-  if (!t.g) return;  // parameter without a gradient this step: untouched, as torch skips p.grad is None
-  const float gs = clip ? clip[1] : 1.0f;
-  const uint64_t base = (uint64_t)ch * OPT_CHUNK;
-  if (aligned16(t.p, t.g, t.m, t.v)) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const uint64_t i = base + (uint64_t)(k * 256 + threadIdx.x) * 4;
-      if (i + 3 < t.n) {
-        f32x4 p = *reinterpret_cast<const f32x4*>(t.p + i);
-        const f32x4 g = *reinterpret_cast<const f32x4*>(t.g + i);
-        f32x4 m = *reinterpret_cast<const f32x4*>(t.m + i);
-        f32x4 v = *reinterpret_cast<const f32x4*>(t.v + i);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          float pj = p[j], mj = m[j], vj = v[j];
-          adamw_one(pj, g[j] * gs, mj, vj, t.lr, t.weight_decay, c);
-          p[j] = pj;
-          m[j] = mj;
-          v[j] = vj;
-        }
-        *reinterpret_cast<f32x4*>(t.p + i) = p;
-        *reinterpret_cast<f32x4*>(t.m + i) = m;
-        *reinterpret_cast<f32x4*>(t.v + i) = v;
-      } else {
-        for (uint64_t j = i; j < t.n && j < i + 4; ++j) adamw_one(t.p[j], t.g[j] * gs, t.m[j], t.v[j], t.lr, t.weight_decay, c);
-      }
-    }
-  } else {
-    for (int k = 0; k < 16; ++k) {
-      const uint64_t i = base + (uint64_t)k * 256 + threadIdx.x;
-      if (i < t.n) adamw_one(t.p[i], t.g[i] * gs, t.m[i], t.v[i], t.lr, t.weight_decay, c);
-    }
-  }
-}
-
-
 // ---------------------------------------------------------------------------------------------------------------
 // AdamW + everything that must follow a parameter update, in the same pass over the parameter (SURVEY.md §8f row 3,
 // kernel work-list k11): the compute-dtype weight shadow the GEMMs read (row-major copy, zero-padded leading dimension),
@@ -162,17 +133,12 @@ __global__ __launch_bounds__(256) void adamw_kernel(const sgl_adamw_tensor* __re
 //
 // Matrices with a shadow are walked in 64x64 tiles (one tile per 256-thread block: 4 x 16-byte accesses per thread per
 // array, 256-byte row segments), the bf16 tile is transposed through LDS so that both copies are written in >= 128-byte
-// row segments.  Everything else uses the linear 4096-element chunks of adamw_kernel.
+// row segments.  Everything else is walked in linear 4096-element chunks.
 // ---------------------------------------------------------------------------------------------------------------
 struct GroupHyper {
   float lr[16], wd[16];
   int n;
 };
-
-template <typename T> __device__ __forceinline__ T cvt_out(float x);
-template <> __device__ __forceinline__ float cvt_out<float>(float x) { return x; }
-template <> __device__ __forceinline__ bf16 cvt_out<bf16>(float x) { return (bf16)x; }
-template <> __device__ __forceinline__ f16 cvt_out<f16>(float x) { return (f16)x; }
 
 template <typename T>
 __device__ __forceinline__ void adamw_tile(const sgl_adamw_tensor& t, const sgl_adamw_aux& a, int tile, float lr,
@@ -183,7 +149,9 @@ __device__ __forceinline__ void adamw_tile(const sgl_adamw_tensor& t, const sgl_
   const int r0 = tr * 64, c0 = tc * 64;
   const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
   const bool vec = ((cols & 3) == 0) && aligned16(t.p, t.g, t.m, t.v) && (!a.ema || ((((uintptr_t)a.ema) & 15) == 0));
-  T* dst = reinterpret_cast<T*>(a.dst);
+  // shadows hold the rows [row0, rows) of the parameter
+  const ShadowTile<T> sh{reinterpret_cast<T*>(a.dst), reinterpret_cast<T*>(a.dst_t), a.ld, a.ld_t, a.row0, rows, cols,
+                         a.row0, r0, c0, lt};
   // interior tiles: every load of the tile in flight before the first dependent instruction
   const bool interior = vec && (r0 + 64 <= rows) && (c0 + 64 <= cols);
   f32x4 P4[4], G4[4], M4[4], V4[4];
@@ -228,53 +196,10 @@ __device__ __forceinline__ void adamw_tile(const sgl_adamw_tensor& t, const sgl_
           if (a.ema) a.ema[i + j] = a.ema[i + j] * ema_decay + out[j] * (1.0f - ema_decay);
         }
       }
-      if (dst && r >= a.row0) {
-        T* d = dst + (size_t)(r - a.row0) * a.ld + cc;
-        if (cc + 3 < cols && ((((uintptr_t)d) & (4 * sizeof(T) - 1)) == 0)) {
-          T o4[4] = {cvt_out<T>(out[0]), cvt_out<T>(out[1]), cvt_out<T>(out[2]), cvt_out<T>(out[3])};
-          if constexpr (sizeof(T) == 2) {
-            u32x2 w;
-            __builtin_memcpy(&w, o4, 8);
-            *reinterpret_cast<u32x2*>(d) = w;
-          } else {
-            u32x4 w;
-            __builtin_memcpy(&w, o4, 16);
-            *reinterpret_cast<u32x4*>(d) = w;
-          }
-        } else {
-          for (int j = 0; j < 4 && cc + j < cols; ++j) d[j] = cvt_out<T>(out[j]);
-        }
-      }
     }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) lt[(ty + 16 * k) * 66 + tx * 4 + j] = cvt_out<T>(out[j]);
+    sh.put(k, out);
   }
-  if (!a.dst_t) return;
-  __syncthreads();
-  // transposed copy: output row = parameter column c0 + oc, 64 consecutive elements = parameter rows r0 .. r0+63
-  T* dt = reinterpret_cast<T*>(a.dst_t);
-  const int oc = threadIdx.x >> 2, seg = threadIdx.x & 3;   // 64 output rows x 4 segments of 16 elements
-  if (c0 + oc < cols) {
-    const int rb = r0 + seg * 16;
-    T* drow = dt + (size_t)(c0 + oc) * a.ld_t + (rb - a.row0);
-    T vals[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) vals[j] = lt[(seg * 16 + j) * 66 + oc];
-    if (rb >= a.row0 && rb + 15 < rows && ((((uintptr_t)drow) & 15) == 0)) {
-      // 16 consecutive elements of one output row: 16-byte stores
-      constexpr int PER = 16 / sizeof(T);
-#pragma unroll
-      for (int q = 0; q < 16 / PER; ++q) {
-        u32x4 w;
-        __builtin_memcpy(&w, &vals[q * PER], 16);
-        *reinterpret_cast<u32x4*>(drow + q * PER) = w;
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < 16; ++j)
-        if (rb + j < rows && rb + j >= a.row0) drow[j] = vals[j];
-    }
-  }
+  sh.put_transposed();
 }
 
 __global__ __launch_bounds__(256) void adamw_ex_kernel(const sgl_adamw_tensor* __restrict__ T,
@@ -285,7 +210,7 @@ __global__ __launch_bounds__(256) void adamw_ex_kernel(const sgl_adamw_tensor* _
   const int ti = map[2 * blockIdx.x], ch = map[2 * blockIdx.x + 1];
   const sgl_adamw_tensor t = T[ti];
   if (!t.g) return;
-  const sgl_adamw_aux a = A[ti];
+  const sgl_adamw_aux a = A ? A[ti] : sgl_adamw_aux{};   // no aux (sgl_op_adamw): no shadow, EMA or dst_f32
   const float gs = clip ? clip[1] : 1.0f;
   const float lr = (gh.n > 0 && a.group >= 0 && a.group < gh.n) ? gh.lr[a.group] : t.lr;
   const float wd = (gh.n > 0 && a.group >= 0 && a.group < gh.n) ? gh.wd[a.group] : t.weight_decay;
@@ -335,62 +260,32 @@ __global__ __launch_bounds__(256) void adamw_ex_kernel(const sgl_adamw_tensor* _
     }
     return;
   }
+  walk_chunk(base, t.n, vec,
+             [&](uint64_t i) {
+               f32x4 p = *reinterpret_cast<const f32x4*>(t.p + i);
+               const f32x4 g = *reinterpret_cast<const f32x4*>(t.g + i);
+               f32x4 m = *reinterpret_cast<const f32x4*>(t.m + i);
+               f32x4 v = *reinterpret_cast<const f32x4*>(t.v + i);
 #pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const uint64_t i = base + (uint64_t)(k * 256 + threadIdx.x) * 4;
-    if (vec && i + 3 < t.n) {
-      f32x4 p = *reinterpret_cast<const f32x4*>(t.p + i);
-      const f32x4 g = *reinterpret_cast<const f32x4*>(t.g + i);
-      f32x4 m = *reinterpret_cast<const f32x4*>(t.m + i);
-      f32x4 v = *reinterpret_cast<const f32x4*>(t.v + i);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        float pj = p[j], mj = m[j], vj = v[j];
-        adamw_one(pj, g[j] * gs, mj, vj, lr, wd, c);
-        p[j] = pj; m[j] = mj; v[j] = vj;
-      }
-      *reinterpret_cast<f32x4*>(t.p + i) = p;
-      *reinterpret_cast<f32x4*>(t.m + i) = m;
-      *reinterpret_cast<f32x4*>(t.v + i) = v;
-      if (a.dst_f32) *reinterpret_cast<f32x4*>(a.dst_f32 + i) = p;
-      if (a.ema) {
-        const f32x4 e = *reinterpret_cast<const f32x4*>(a.ema + i);
-        *reinterpret_cast<f32x4*>(a.ema + i) = e * ema_decay + p * (1.0f - ema_decay);
-      }
-    } else {
-      for (uint64_t j = i; j < t.n && j < i + 4; ++j) {
-        adamw_one(t.p[j], t.g[j] * gs, t.m[j], t.v[j], lr, wd, c);
-        if (a.dst_f32) a.dst_f32[j] = t.p[j];
-        if (a.ema) a.ema[j] = a.ema[j] * ema_decay + t.p[j] * (1.0f - ema_decay);
-      }
-    }
-  }
-}
-
-// out[0] = s*||g||_2 ; out[1] = s*min(1, max_norm / (s*norm + 1e-6)): the factor every gradient is multiplied by when the
-// stored gradients are rank SUMS and s = 1/world (ddp.GradBucketReducer(average="defer")); s = 1 is grad_norm_finish.
-__global__ __launch_bounds__(1024) void grad_norm_finish_scaled_kernel(const float* __restrict__ partial, int n,
-                                                                       float max_norm, float gscale,
-                                                                       float* __restrict__ out) {
-  __shared__ double red[16];
-  double s = 0.0;
-  for (int i = threadIdx.x; i < n; i += 1024) s += (double)partial[i];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t = 0.0;
-    for (int i = 0; i < 16; ++i) t += red[i];
-    const float norm = (float)sqrt(t) * gscale;
-    out[0] = norm;
-    float coef = 1.0f;
-    if (max_norm > 0.f) {
-      coef = max_norm / (norm + 1e-6f);
-      if (coef > 1.0f) coef = 1.0f;
-    }
-    out[1] = coef * gscale;
-  }
+               for (int j = 0; j < 4; ++j) {
+                 float pj = p[j], mj = m[j], vj = v[j];
+                 adamw_one(pj, g[j] * gs, mj, vj, lr, wd, c);
+                 p[j] = pj; m[j] = mj; v[j] = vj;
+               }
+               *reinterpret_cast<f32x4*>(t.p + i) = p;
+               *reinterpret_cast<f32x4*>(t.m + i) = m;
+               *reinterpret_cast<f32x4*>(t.v + i) = v;
+               if (a.dst_f32) *reinterpret_cast<f32x4*>(a.dst_f32 + i) = p;
+               if (a.ema) {
+                 const f32x4 e = *reinterpret_cast<const f32x4*>(a.ema + i);
+                 *reinterpret_cast<f32x4*>(a.ema + i) = e * ema_decay + p * (1.0f - ema_decay);
+               }
+             },
+             [&](uint64_t j) {
+               adamw_one(t.p[j], t.g[j] * gs, t.m[j], t.v[j], lr, wd, c);
+               if (a.dst_f32) a.dst_f32[j] = t.p[j];
+               if (a.ema) a.ema[j] = a.ema[j] * ema_decay + t.p[j] * (1.0f - ema_decay);
+             });
 }
 
 // shadow <- shadow*decay + p*(1-decay) for every table entry (p = .p, shadow = .m); the reference's
@@ -400,26 +295,13 @@ __global__ __launch_bounds__(256) void ema_kernel(const sgl_adamw_tensor* __rest
   const int ti = map[2 * blockIdx.x], ch = map[2 * blockIdx.x + 1];
   const float* p = T[ti].p;
   float* sh = T[ti].m;
-  const uint64_t n = T[ti].n;
-  const uint64_t base = (uint64_t)ch * OPT_CHUNK;
-  if (((((uintptr_t)p) | ((uintptr_t)sh)) & 15) == 0) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const uint64_t i = base + (uint64_t)(k * 256 + threadIdx.x) * 4;
-      if (i + 3 < n) {
-        const f32x4 x = *reinterpret_cast<const f32x4*>(p + i);
-        const f32x4 y = *reinterpret_cast<const f32x4*>(sh + i);
-        *reinterpret_cast<f32x4*>(sh + i) = y * decay + x * omd;
-      } else {
-        for (uint64_t j = i; j < n && j < i + 4; ++j) sh[j] = sh[j] * decay + p[j] * omd;
-      }
-    }
-  } else {
-    for (int k = 0; k < 16; ++k) {
-      const uint64_t i = base + (uint64_t)k * 256 + threadIdx.x;
-      if (i < n) sh[i] = sh[i] * decay + p[i] * omd;
-    }
-  }
+  walk_chunk((uint64_t)ch * OPT_CHUNK, T[ti].n, ((((uintptr_t)p) | ((uintptr_t)sh)) & 15) == 0,
+             [&](uint64_t i) {
+               const f32x4 x = *reinterpret_cast<const f32x4*>(p + i);
+               const f32x4 y = *reinterpret_cast<const f32x4*>(sh + i);
+               *reinterpret_cast<f32x4*>(sh + i) = y * decay + x * omd;
+             },
+             [&](uint64_t j) { sh[j] = sh[j] * decay + p[j] * omd; });
 }
 
 }  // namespace sgl
@@ -451,37 +333,30 @@ int64_t sgl_adamw_plan(const uint64_t* numel, int ntensors, int32_t* blockmap, i
   return nb;
 }
 
-int sgl_op_grad_norm(const sgl_adamw_tensor* table, const int32_t* blockmap, int64_t nblocks, float max_norm,
-                     float* partials, float* norm_and_coef, sgl_stream stream) {
-  if (!table || !blockmap || !partials || !norm_and_coef) return SGL_ERR_NULL;
-  if (nblocks < 0 || nblocks > 0x7fffffff) return SGL_ERR_BAD_SHAPE;
-  hipStream_t s = (hipStream_t)stream;
-  if (nblocks > 0) hipLaunchKernelGGL(sgl::grad_sqnorm_kernel, dim3((unsigned)nblocks), dim3(256), 0, s, table, blockmap, partials);
-  hipLaunchKernelGGL(sgl::grad_norm_finish_kernel, dim3(1), dim3(1024), 0, s, partials, (int)nblocks, max_norm,
-                     norm_and_coef);
-  return hipGetLastError() == hipSuccess ? SGL_OK : SGL_ERR_HIP;
-}
-
-
 int sgl_op_grad_norm_scaled(const sgl_adamw_tensor* table, const int32_t* blockmap, int64_t nblocks, float max_norm,
                             float grad_scale, float* partials, float* norm_and_coef, sgl_stream stream) {
   if (!table || !blockmap || !partials || !norm_and_coef) return SGL_ERR_NULL;
   if (nblocks < 0 || nblocks > 0x7fffffff) return SGL_ERR_BAD_SHAPE;
   hipStream_t s = (hipStream_t)stream;
   if (nblocks > 0) hipLaunchKernelGGL(sgl::grad_sqnorm_kernel, dim3((unsigned)nblocks), dim3(256), 0, s, table, blockmap, partials);
-  hipLaunchKernelGGL(sgl::grad_norm_finish_scaled_kernel, dim3(1), dim3(1024), 0, s, partials, (int)nblocks, max_norm,
+  hipLaunchKernelGGL(sgl::grad_norm_finish_kernel, dim3(1), dim3(1024), 0, s, partials, (int)nblocks, max_norm,
                      grad_scale, norm_and_coef);
   return hipGetLastError() == hipSuccess ? SGL_OK : SGL_ERR_HIP;
 }
 
-int sgl_op_adamw_ex(const sgl_adamw_tensor* table, const sgl_adamw_aux* aux, const int32_t* blockmap, int64_t nblocks,
-                    double beta1, double beta2, double eps, int step, const float* norm_and_coef,
-                    const float* group_lr_wd_host, int ngroups, double ema_decay, sgl_stream stream) {
-  if (!table || !aux || !blockmap) return SGL_ERR_NULL;
-  if (nblocks < 0 || nblocks > 0x7fffffff || step < 1 || ngroups < 0 || ngroups > 16) return SGL_ERR_BAD_SHAPE;
-  if (ngroups > 0 && !group_lr_wd_host) return SGL_ERR_NULL;
+int sgl_op_grad_norm(const sgl_adamw_tensor* table, const int32_t* blockmap, int64_t nblocks, float max_norm,
+                     float* partials, float* norm_and_coef, sgl_stream stream) {
+  return sgl_op_grad_norm_scaled(table, blockmap, nblocks, max_norm, 1.0f, partials, norm_and_coef, stream);
+}
+
+// aux may be NULL (sgl_op_adamw); the caller has checked the arguments
+static int launch_adamw(const sgl_adamw_tensor* table, const sgl_adamw_aux* aux, const int32_t* blockmap, int64_t nblocks,
+                        double beta1, double beta2, double eps, int step, const float* norm_and_coef,
+                        const float* group_lr_wd_host, int ngroups, double ema_decay, sgl_stream stream) {
   if (nblocks == 0) return SGL_OK;
   sgl::AdamConst c;
+  // every scalar is formed in double and rounded once, as torch does with its Python-float hyper-parameters
+  // (1 - 0.999f evaluated in fp32 is off by 1.3e-5 relative, which would show up in exp_avg_sq)
   c.omb1 = (float)(1.0 - beta1);
   c.beta2 = (float)beta2;
   c.omb2 = (float)(1.0 - beta2);
@@ -500,24 +375,22 @@ int sgl_op_adamw_ex(const sgl_adamw_tensor* table, const sgl_adamw_aux* aux, con
   return hipGetLastError() == hipSuccess ? SGL_OK : SGL_ERR_HIP;
 }
 
+int sgl_op_adamw_ex(const sgl_adamw_tensor* table, const sgl_adamw_aux* aux, const int32_t* blockmap, int64_t nblocks,
+                    double beta1, double beta2, double eps, int step, const float* norm_and_coef,
+                    const float* group_lr_wd_host, int ngroups, double ema_decay, sgl_stream stream) {
+  if (!table || !aux || !blockmap) return SGL_ERR_NULL;
+  if (nblocks < 0 || nblocks > 0x7fffffff || step < 1 || ngroups < 0 || ngroups > 16) return SGL_ERR_BAD_SHAPE;
+  if (ngroups > 0 && !group_lr_wd_host) return SGL_ERR_NULL;
+  return launch_adamw(table, aux, blockmap, nblocks, beta1, beta2, eps, step, norm_and_coef, group_lr_wd_host, ngroups,
+                      ema_decay, stream);
+}
+
+// the table's own lr / weight_decay per tensor; no shadow, EMA or dst_f32
 int sgl_op_adamw(const sgl_adamw_tensor* table, const int32_t* blockmap, int64_t nblocks, double beta1, double beta2,
                  double eps, int step, const float* norm_and_coef, sgl_stream stream) {
   if (!table || !blockmap) return SGL_ERR_NULL;
   if (nblocks < 0 || nblocks > 0x7fffffff || step < 1) return SGL_ERR_BAD_SHAPE;
-  if (nblocks == 0) return SGL_OK;
-  sgl::AdamConst c;
-  // every scalar is formed in double and rounded once, as torch does with its Python-float hyper-parameters
-  // (1 - 0.999f evaluated in fp32 is off by 1.3e-5 relative, which would show up in exp_avg_sq)
-  c.omb1 = (float)(1.0 - beta1);
-  c.beta2 = (float)beta2;
-  c.omb2 = (float)(1.0 - beta2);
-  c.eps = (float)eps;
-  const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-  c.inv_bc1 = (float)(1.0 / bc1);
-  c.inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
-  hipLaunchKernelGGL(sgl::adamw_kernel, dim3((unsigned)nblocks), dim3(256), 0, (hipStream_t)stream, table, blockmap, c,
-                     norm_and_coef);
-  return hipGetLastError() == hipSuccess ? SGL_OK : SGL_ERR_HIP;
+  return launch_adamw(table, nullptr, blockmap, nblocks, beta1, beta2, eps, step, norm_and_coef, nullptr, 0, 0.0, stream);
 }
 
 }  // extern "C"

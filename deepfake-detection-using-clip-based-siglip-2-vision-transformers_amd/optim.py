@@ -23,6 +23,21 @@ def _is_dense(t: torch.Tensor) -> bool:
     return t.is_contiguous() or (t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last))
 
 
+def _upload_plan(lib, table, numel, dev, members=None):
+    """ctypes tensor table + per-tensor element counts -> (device table, device block map, nblocks).  The block map lists
+    (tensor, 4096-element chunk) pairs over the tensors in ``members`` (indices into the table; None = all of them);
+    ``table`` None uploads no table (the caller keeps one)."""
+    members = tuple(range(len(numel))) if members is None else members
+    sub = (C.c_uint64 * len(members))(*[numel[i] for i in members])
+    nb = lib.sgl_adamw_plan(sub, len(members), None, 0)
+    bm = (C.c_int32 * (2 * max(nb, 1)))()
+    lib.sgl_adamw_plan(sub, len(members), bm, nb)
+    pairs = torch.frombuffer(bytearray(bytes(bm)), dtype=torch.int32).view(-1, 2).clone()
+    pairs[:, 0] = torch.tensor(members, dtype=torch.int32)[pairs[:, 0].long()] if nb else 0
+    dev_table = None if table is None else torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(dev)
+    return dev_table, pairs.contiguous().view(-1).to(dev), nb
+
+
 class FusedAdamW(torch.optim.Optimizer):
     """``torch.optim.AdamW`` semantics (decoupled weight decay, bias correction, same operation order) in one launch
     for all tensors.  ``max_grad_norm`` > 0 folds ``clip_grad_norm_(all parameters, max_grad_norm)`` into the step: the
@@ -153,13 +168,7 @@ class FusedAdamW(torch.optim.Optimizer):
         key = (numel, members)
         hit = self._plans.get(key)
         if hit is None:
-            sub = (C.c_uint64 * len(members))(*[numel[i] for i in members])
-            nb = lib.sgl_adamw_plan(sub, len(members), None, 0)
-            bm = (C.c_int32 * (2 * max(nb, 1)))()
-            lib.sgl_adamw_plan(sub, len(members), bm, nb)
-            pairs = torch.frombuffer(bytearray(bytes(bm)), dtype=torch.int32).view(-1, 2).clone()
-            pairs[:, 0] = torch.tensor(members, dtype=torch.int32)[pairs[:, 0].long()] if nb else 0
-            hit = (pairs.contiguous().view(-1).to(dev), nb)
+            hit = _upload_plan(lib, None, numel, dev, members)[1:]
             if len(self._plans) > 16:
                 self._plans.clear()
             self._plans[key] = hit
@@ -180,7 +189,6 @@ class FusedAdamW(torch.optim.Optimizer):
             raise RuntimeError("FusedAdamW: all parameters must live on one device")
         table, aux, chunks, encs = self._device_tables(lib, ents, dev)
         numel = tuple(p.numel() for p, _, _, _ in ents)
-        stream = torch.cuda.current_stream(dev).cuda_stream
         in_sync = [enc._shadows.units_in_sync() for enc in encs]
         # one AdamW launch per distinct (betas, eps, step): a single one for every trainer of the reference (one param
         # group, every trainable tensor receives a gradient every step); torch tracks the step per tensor, so do we
@@ -198,18 +206,16 @@ class FusedAdamW(torch.optim.Optimizer):
                 if "norm" not in self._bufs or self._bufs["partials"].numel() < max(nb, 1):
                     self._bufs["partials"] = torch.empty(max(nb, 1), device=dev, dtype=torch.float32)
                     self._bufs["norm"] = torch.zeros(2, device=dev, dtype=torch.float32)
-                _lib.check(lib.sgl_op_grad_norm_scaled(table.data_ptr(), bmap.data_ptr(), nb,
-                                                       float(self.max_grad_norm) if clip else 0.0, self.grad_scale,
-                                                       self._bufs["partials"].data_ptr(), self._bufs["norm"].data_ptr(),
-                                                       stream), "sgl_op_grad_norm_scaled")
+                _lib.call("sgl_op_grad_norm_scaled", dev, table.data_ptr(), bmap.data_ptr(), nb,
+                          float(self.max_grad_norm) if clip else 0.0, self.grad_scale,
+                          self._bufs["partials"].data_ptr(), self._bufs["norm"].data_ptr())
                 norm_ptr = self._bufs["norm"].data_ptr()
                 self.last_grad_norm = self._bufs["norm"][0]
             decay = float(self._ema.decay) if self._ema is not None else 0.0
             for (beta1, beta2, eps, step0), members in launches.items():
                 bmap, nb = self._plan(lib, chunks, tuple(members), dev)
-                _lib.check(lib.sgl_op_adamw_ex(table.data_ptr(), aux.data_ptr(), bmap.data_ptr(), nb, float(beta1),
-                                               float(beta2), float(eps), step0 + 1, norm_ptr, hyper,
-                                               len(self.param_groups), decay, stream), "sgl_op_adamw_ex")
+                _lib.call("sgl_op_adamw_ex", dev, table.data_ptr(), aux.data_ptr(), bmap.data_ptr(), nb, float(beta1),
+                          float(beta2), float(eps), step0 + 1, norm_ptr, hyper, len(self.param_groups), decay)
         for _, st, _, _ in ents:
             st["step"] += 1
         # the kernel wrote the parameters behind autograd's back: bump their version counters, which is what everything
@@ -233,12 +239,7 @@ def global_grad_norm(parameters) -> torch.Tensor:
         if not p.grad.is_cuda or p.grad.dtype != torch.float32 or not p.grad.is_contiguous():
             raise RuntimeError("global_grad_norm handles contiguous fp32 CUDA gradients only")
         e.p, e.g, e.m, e.v, e.n, e.lr, e.weight_decay = 0, p.grad.data_ptr(), 0, 0, p.numel(), 0.0, 0.0
-    numel = (C.c_uint64 * len(params))(*[p.numel() for p in params])
-    nb = lib.sgl_adamw_plan(numel, len(params), None, 0)
-    bm = (C.c_int32 * (2 * max(nb, 1)))()
-    lib.sgl_adamw_plan(numel, len(params), bm, nb)
-    table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
-    bmap = torch.frombuffer(bytearray(bytes(bm)), dtype=torch.int32).to(dev)
+    table, bmap, nb = _upload_plan(lib, arr, [p.numel() for p in params], dev)
     partials = torch.empty(max(nb, 1), device=dev, dtype=torch.float32)
     out = torch.zeros(2, device=dev, dtype=torch.float32)
     _lib.call("sgl_op_grad_norm", dev, table.data_ptr(), bmap.data_ptr(), nb, 0.0, partials.data_ptr(), out.data_ptr())
@@ -283,12 +284,7 @@ class ExponentialMovingAverage:
             arr = (_lib.SglAdamwTensor * len(ents))()
             for e, (pp, sp, n) in zip(arr, key):
                 e.p, e.g, e.m, e.v, e.n, e.lr, e.weight_decay = pp, 0, sp, 0, n, 0.0, 0.0
-            numel = (C.c_uint64 * len(ents))(*[k[2] for k in key])
-            nb = lib.sgl_adamw_plan(numel, len(ents), None, 0)
-            bm = (C.c_int32 * (2 * max(nb, 1)))()
-            lib.sgl_adamw_plan(numel, len(ents), bm, nb)
-            self._bufs = (torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev),
-                          torch.frombuffer(bytearray(bytes(bm)), dtype=torch.int32).to(dev), nb, dev)
+            self._bufs = _upload_plan(lib, arr, [k[2] for k in key], dev) + (dev,)
             self._key = key
         return self._bufs
 
