@@ -20,6 +20,8 @@
 // residual, head-major QKV scatter, ...) works on 8 consecutive columns per lane with 16-byte global accesses.
 //
 // Roofline: MFMA-bound (arithmetic intensity K/2... >> machine balance); algorithmic FLOPs = 2*M*N*K.
+#include <stdlib.h>
+
 #include "common.hip.h"
 #include "epilogue.hip.h"
 #include "kernels.h"
@@ -318,6 +320,11 @@ hipError_t gemm_nt256_f16(const void* A, int lda, const void* B, int ldb, int M,
                           const EpiParams& p, hipStream_t s);
 hipError_t gemm_tn256_f16(const void* A, int lda, const void* B, int ldb, int Mred, int N1, int N2, int m_per,
                           int splits, const EpiParams& p, hipStream_t s);
+// 384x192-tile NT kernel of the same file (EPI_STORE and EPI_RES_F32 only)
+hipError_t gemm_nt384_bf16(const void* A, int lda, const void* B, int ldb, int M, int N, int K, int epi, int out_dtype,
+                           const EpiParams& p, hipStream_t s);
+hipError_t gemm_nt384_f16(const void* A, int lda, const void* B, int ldb, int M, int N, int K, int epi, int out_dtype,
+                          const EpiParams& p, hipStream_t s);
 
 template <int EPI, typename TOut, typename TIn>
 static hipError_t launch_nt(const TIn* A, int lda, const TIn* B, int ldb, int M, int N, int K, const EpiParams& p,
@@ -336,9 +343,24 @@ static hipError_t gemm_nt_mfma(const void* A, int lda, const void* B, int ldb, i
   if ((lda % 8) || (ldb % 8) || (K % 8) || K <= 0) return hipErrorInvalidValue;
   if (epi != EPI_F32 && (N % 8)) return hipErrorInvalidValue;
   if ((size_t)M * lda * 2 >= (1ull << 32) || (size_t)N * ldb * 2 >= (1ull << 32)) return hipErrorInvalidValue;
-  if (M >= 2048 && N >= 256)
+  if (M >= 2048 && N >= 256) {
+    // Outputs whose width is a whole number of 192-column tiles but not of 256-column ones (the encoder's 1152: fc2 and
+    // the three plain-store dX GEMMs) take the 384x192 tile, which has no half-empty last column tile: 1,458 tiles of
+    // 1.125 x the work instead of 1,825 at the bench batch, same sums bit for bit.  Measured at M = 93,312 it is 6-7 %
+    // faster except with the fp32-residual epilogue at K = 1152 (out_proj: 308 against 310 us, inside the run-to-run
+    // spread: that launch is bound by its 860 MB of residual traffic, not by tiles), which therefore stays on the 256x256
+    // tile like everything else (N = 3456 with the QKV scatter, 4352, 768, ...).  SGL_NT_TILE=256|384 (developer switch,
+    // read once) forces one tile for every shape and epilogue it supports.
+    static const int tile_env = getenv("SGL_NT_TILE") ? atoi(getenv("SGL_NT_TILE")) : 0;
+    const bool can384 = epi == EPI_STORE || epi == EPI_RES_F32;
+    const bool pays384 = N % 192 == 0 && N % 256 != 0 && (epi == EPI_STORE || K >= 2048);
+    const bool want384 = tile_env == 384 || (tile_env != 256 && pays384);
+    if (can384 && want384)
+      return std::is_same<TIn, f16>::value ? gemm_nt384_f16(A, lda, B, ldb, M, N, K, epi, out_dtype, p, s)
+                                           : gemm_nt384_bf16(A, lda, B, ldb, M, N, K, epi, out_dtype, p, s);
     return std::is_same<TIn, f16>::value ? gemm_nt256_f16(A, lda, B, ldb, M, N, K, epi, out_dtype, p, s)
                                          : gemm_nt256_bf16(A, lda, B, ldb, M, N, K, epi, out_dtype, p, s);
+  }
   return dispatch_epilogue<TIn>(epi, out_dtype, [&](auto tag) {
     using T = decltype(tag);
     return launch_nt<T::epi, typename T::out, TIn>((const TIn*)A, lda, (const TIn*)B, ldb, M, N, K, p, s);

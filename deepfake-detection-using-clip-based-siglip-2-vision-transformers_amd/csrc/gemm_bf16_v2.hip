@@ -1,24 +1,28 @@
-// bf16 / fp16 MFMA GEMMs for gfx950 on a 256x256 output tile, K-step 64, 512 threads = 8 waves, operands streamed
-// global -> LDS by LDS-DMA (buffer_load_dwordx4 ... lds, 1 KiB per wave instruction, no VGPR staging), two LDS stages
-// (2 x 64 KiB).  The main loops gemm_nt6_kernel / gemm_tn6_kernel run anti-phase wave groups, four barrier-separated
-// slots per K-step (see the comment above them), and share the LDS images, tile order and epilogue below.
-// gemm_nt_bf16 / gemm_tn_bf16 (gemm_bf16.hip) send the shapes that fill the chip here, through gemm_nt256_bf16 /
-// gemm_tn256_bf16 at the end of this file.
+// bf16 / fp16 MFMA GEMMs for gfx950, K-step 64, 512 threads = 8 waves, operands streamed global -> LDS by LDS-DMA
+// (buffer_load_dwordx4 ... lds, 1 KiB per wave instruction, no VGPR staging), two LDS stages.  Tiles:
+//   256 x 256 (2 x 64 KiB)   gemm_nt6_kernel, gemm_tn6_kernel   waves 2 (rows) x 4 (columns), 128 x 64 each
+//   384 x 192 (2 x 72 KiB)   gemm_nt384_kernel                  waves 4 (rows) x 2 (columns),  96 x 96 each
+// All three main loops run anti-phase wave groups, four barrier-separated slots per K-step (see the comments above
+// them), and share the LDS images, tile order and epilogue code below.  gemm_nt_bf16 / gemm_tn_bf16 (gemm_bf16.hip)
+// send the shapes that fill the chip here, through gemm_nt256_* / gemm_nt384_* / gemm_tn256_* at the end of this file:
+// NT outputs whose width is a multiple of 192 but not of 256 (the encoder's 1152) with a plain-store epilogue, or the
+// fp32-residual one from K = 2048, take the 384 x 192 tile; every other NT shape and all of TN the 256 x 256 tile.
 //
 //   nt : C[M,N]   = A[M,K] · B[N,K]ᵀ           (forward projections, dX with transposed weight shadows)
 //   tn : C[N1,N2] (+)= Σ_m A[m,N1] · B[m,N2]    (dW; token index is the MFMA k index via ds_read_b64_tr_b16)
 //
-// Arithmetic intensity of the tile: 2*256*256*64 / (2*256*64*2 B) = 128 FLOP per LDS-staged byte (the 128x128
-// tile of gemm_bf16.hip has 64 and is L2->LDS bandwidth bound near 0.6-0.7 PFLOP/s on this chip).
+// Arithmetic intensity of both tiles: 2*256*256*64 / (2*256*64*2 B) = 2*384*192*64 / ((384+192)*64*2 B) = 128 FLOP per
+// LDS-staged byte (the 128x128 tile of gemm_bf16.hip has 64 and is L2->LDS bandwidth bound near 0.6-0.7 PFLOP/s on this chip).
 //
 // LDS-DMA writes lane-linear (wave-uniform base + lane*16), so the bank-conflict swizzles are applied to each
 // lane's SOURCE address and again on the fragment reads (same involution on both sides):
-//   NT image [256 rows][64 k]   128-B rows: slot s of row r holds source chunk s ^ (r & 7)
+//   NT image [rows][64 k]       128-B rows: slot s of row r holds source chunk s ^ (r & 7)
 //   TN image [64 m][256 n]      512-B rows: slot s of row m holds source chunk s ^ (2*(m&3) + 8*((m>>3)&1))
-// Wave w -> (wr, wc) = ((w>>1)&1, (w&1) + 2*(w>>2)): the two waves sharing a SIMD (w, w+4) sit in different column
-// halves.  In a half-empty last column tile (N = 1152 = 4.5 tiles) the waves of the empty half skip their
-// instructions (`active`) but still take part in every barrier, so the workgroup holds its CU for the whole K loop:
-// that tile takes as long as a full one (the skipped work saves power, not time).
+// 256 x 256: wave w -> (wr, wc) = ((w>>1)&1, (w&1) + 2*(w>>2)): the two waves sharing a SIMD (w, w+4) sit in different
+// column halves.  In a half-empty last column tile (0 < N % 256 <= 128) the waves of the
+// empty half skip their instructions (`active`) but still take part in every barrier, so the workgroup holds its CU for
+// the whole K loop: that tile takes as long as a full one (the skipped work saves power, not time).  That is why
+// N = 1152 = 4.5 tiles has the 384 x 192 tile.
 // blockIdx -> tile is XCD-aware (unit_of_block / tile_of_unit below): each XCD works through a contiguous chunk of
 // a grouped tile order, so its concurrent workgroups share A and B panels in its private L2.  Measured with
 // rocprofv3 FETCH_SIZE on the fc1 shape: the earlier "row panel per XCD" map fetched 6x the algorithmic bytes
@@ -40,6 +44,14 @@ constexpr int T_OP = T_BM * T_BK * 2;     // 32 KiB per operand per stage
 constexpr int T_STAGE = 2 * T_OP;         // 64 KiB
 constexpr int T_LDS = 2 * T_STAGE;        // 128 KiB
 constexpr int T_CT_LD = 260;              // fp32 epilogue staging stride (64 rows x 260 floats = 66,560 B)
+// 384 (M) x 192 (N) NT tile for outputs whose width divides by 192 but not by 256 (gemm_nt384_kernel)
+constexpr int W_BM = 384, W_BN = 192;
+constexpr int W_OPA = W_BM * T_BK * 2;    // 48 KiB of A per stage
+constexpr int W_OPB = W_BN * T_BK * 2;    // 24 KiB of B per stage
+constexpr int W_STAGE = W_OPA + W_OPB;    // 72 KiB
+constexpr int W_LDS = 2 * W_STAGE;        // 144 KiB of the 160
+constexpr int W_CT_LD = 196;              // fp32 epilogue staging stride (same bank phase as 260: 4 mod 64)
+constexpr int W_PB = 1;                   // 16-row blocks of every wave per epilogue pass (64 rows x 196 floats = 50,176 B)
 
 
 // accumulators -> LDS (64 rows at a time) -> row-contiguous chunks -> fused epilogue
@@ -239,6 +251,94 @@ __device__ __forceinline__ void store_tile256(char* smem, f32x4 (&acc)[8][4], in
       }
     }
   }
+}
+
+// The 384x192 tile's sibling of store_tile256 (EPI_STORE and EPI_RES_F32 only): waves are 4 (rows) x 2 (columns) with
+// 96 x 96 accumulators each, so a pass moves W_PB of every wave's six 16-row blocks = 64 * W_PB tile rows through a
+// [64 * W_PB][W_CT_LD] fp32 staging image, and the workgroup then walks the image's 16-byte chunks in row-major order
+// (chunk t + 512 q for thread t), so a wave store covers whole 768-byte (fp32) / 384-byte (16-bit) output rows.  192 / NV
+// chunks per row do not divide 512, so a thread's column changes with q, but with period 3 (1536 is a multiple of the
+// chunks per row): bias and column checks exist three times per thread.  Same request order as store_tile256: the
+// residual of pass + 1 is asked for before this pass's stores (in-order vmcnt, see there).
+template <int EPI, typename TOut>
+__device__ __forceinline__ void store_tile384(char* smem, f32x4 (&acc)[6][6], int wr, int wc, int lane, int t, int m0,
+                                              int n0, int M, int N, const EpiParams& p) {
+  static_assert(EPI == EPI_STORE || EPI == EPI_RES_F32, "other epilogues stay on the 256x256 tile");
+  float* ct = reinterpret_cast<float*>(smem);
+  const int g = lane >> 4, c16 = lane & 15;
+  constexpr int NV = (sizeof(TOut) == 4) ? 4 : 8;
+  constexpr int CPR = W_BN / NV;             // chunks per row: 48 / 24
+  constexpr int WROWS = 16 * W_PB;           // rows a wave contributes per pass
+  constexpr int QN = 4 * WROWS * CPR / 512;  // chunks per thread and pass
+  constexpr int NPASS = 6 / W_PB;
+  static_assert(4 * WROWS * W_CT_LD * 4 <= W_LDS && (4 * WROWS * CPR) % 512 == 0 && 1536 % CPR == 0 && 6 % W_PB == 0,
+                "staging image");
+  int tcol[3];
+  bool col_ok[3];
+#pragma unroll
+  for (int h = 0; h < 3; ++h) {
+    tcol[h] = ((t + 512 * h) % CPR) * NV;
+    col_ok[h] = n0 + tcol[h] < N;
+  }
+  float bias[3][NV];
+  if constexpr (EPI == EPI_RES_F32) {
+#pragma unroll
+    for (int h = 0; h < 3; ++h) {
+#pragma unroll
+      for (int j = 0; j < NV; ++j) bias[h][j] = 0.f;
+      if (col_ok[h]) Vec<float, NV>::ld(p.bias + n0 + tcol[h], bias[h]);
+    }
+  }
+  // staging row q of a pass holds tile row (q / WROWS) * 96 + pass * WROWS + q % WROWS
+#define SGL_CT384_GROW(q) (m0 + ((q) / WROWS) * 96 + pass * WROWS + ((q) % WROWS))
+  u32x4 pre[2][QN];
+  auto load_pre = [&](int pass, u32x4 (&dst)[QN]) {
+    if constexpr (EPI == EPI_RES_F32) {
+#pragma unroll
+      for (int q = 0; q < QN; ++q) {
+        const int h = q % 3;
+        const int grow = SGL_CT384_GROW((t + 512 * q) / CPR);
+        dst[q] = (grow < M && col_ok[h]) ? *reinterpret_cast<const u32x4*>(p.res + (size_t)grow * p.ldr + n0 + tcol[h])
+                                         : u32x4{0u, 0u, 0u, 0u};
+      }
+    }
+  };
+  load_pre(0, pre[0]);
+#pragma unroll
+  for (int pass = 0; pass < NPASS; ++pass) {
+    if (pass + 1 < NPASS) load_pre(pass + 1, pre[(pass + 1) & 1]);
+    // pass 0: every wave has drained its trailing DMA units (vmcnt(0) in the kernel); later: the previous pass's chunk
+    // reads are done
+    SGL_LDS_BARRIER();
+#pragma unroll
+    for (int i2 = 0; i2 < W_PB; ++i2)
+#pragma unroll
+      for (int j = 0; j < 6; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          ct[(wr * WROWS + i2 * 16 + g * 4 + r) * W_CT_LD + wc * 96 + j * 16 + c16] = acc[W_PB * pass + i2][j][r];
+    SGL_LDS_BARRIER();
+#pragma unroll
+    for (int q = 0; q < QN; ++q) {
+      const int h = q % 3;
+      const int row = (t + 512 * q) / CPR;
+      const int grow = SGL_CT384_GROW(row);
+      const int gcol = n0 + tcol[h];
+      if (grow < M && col_ok[h]) {
+        float v[NV];
+        Vec<float, NV>::ld(ct + row * W_CT_LD + tcol[h], v);
+        if constexpr (EPI == EPI_RES_F32) {
+          const f32x4 r = __builtin_bit_cast(f32x4, pre[pass & 1][q]);
+#pragma unroll
+          for (int j = 0; j < NV; ++j) v[j] = r[j] + (v[j] + bias[h][j]);
+          Vec<float, NV>::st_nt(reinterpret_cast<float*>(p.out) + (size_t)grow * p.ldo + gcol, v);
+        } else {
+          epi_apply<EPI, TOut, NV>(p, grow, gcol, N, v);
+        }
+      }
+    }
+  }
+#undef SGL_CT384_GROW
 }
 
 // blockIdx -> work unit.  Workgroups are dealt round-robin to the 8 XCDs (blockIdx % 8 labels the XCD group), each
@@ -468,6 +568,169 @@ __global__ __launch_bounds__(512, 2) void gemm_nt6_kernel(const TIn* __restrict_
 }
 
 // ------------------------------------------------------------------------------------------------------
+// NT on a 384 (M) x 192 (N) tile, for outputs 1152 wide: 1152 = 6 x 192, so there is no half-empty column tile, and at
+// the bench batch 93,312 = 243 x 384 rows give 1,458 tiles of 1.125 x the work where the 256x256 tile runs 1,825.
+// Wave w -> (wr, wc) = (w & 3, w >> 2): 96 x 96 per wave = 6 x 6 MFMA blocks (0.33 fragment reads per MFMA against
+// 0.375), the two waves of a SIMD (w, w + 4) sit in different column halves.  LDS image, anti-phase groups, slot macros
+// and the schedule are those of gemm_nt6_kernel with units of THREE wave-instructions per wave instead of two: the
+// global->LDS stream moves 24-KiB units in the fixed round-robin order
+//     A0(t) = rows 0-47 of every wave row,  B(t) = all 192 columns,  A1(t) = rows 48-95 of every wave row,  A0(t+1), ...
+// Per wave and K-step t:
+//     R1(t): 18 fragment reads (A0 = row blocks 0-2, B = column blocks 0-5, both k-halves)  + DMA unit A1(t+1)
+//     M1(t): A0 x B   36 MFMAs (k-half 0 of all 18 accumulators, then k-half 1)
+//     R2(t):  6 fragment reads (A1 = row blocks 3-5)                                       + DMA units A0(t+2), B(t+2)
+//     M2(t): A1 x B   36 MFMAs
+// G0 runs R1 in slot 4t, G1 in slot 4t+1.  Every accumulator sees K-steps ascending, k-half 0 then 1, in one MFMA chain:
+// bit for bit the sums of gemm_nt6_kernel.  Every read slot ends with s_waitcnt vmcnt(9) (three younger units may stay
+// in flight): after R1(t) these are A0(t+1), B(t+1), A1(t+1), so A1(t) has landed for R2(t); after R2(t) they are A1(t+1),
+// A0(t+2), B(t+2), so A0(t+1) and B(t+1) have landed for R1(t+1).  Invariants, as in gemm_nt6_kernel: (a) a unit is issued
+// at least 4 slots before the wait that publishes it; (b) both groups have passed that wait and a barrier before anyone
+// reads it; (c) a unit is issued only after both groups finished (lgkmcnt(0) + barrier) reading the unit it overwrites:
+// A1(t+1) over A1(t-1), last read in slot 4t-1, issued from slot 4t; A0/B(t+2) over A0/B(t), last read in slot 4t+1,
+// issued from slot 4t+2; (d) every wave passes 4 barriers per K-step + 2 whatever its `active` state or group.
+// Operands are reached only through the two bounded buffer descriptors (rows past M / N and k past K come back as
+// zeros), so ragged M, N and K need no branches; N need not divide by 192 for correctness.
+// Two other schedules were measured at M = 93,312, N = 1152, K = 4352 (256x256 tile: 766 us): splitting the K-step by
+// k-half (12 fragments live instead of 18, 12 + 12 reads) frees a stage only as a whole, so all nine DMA instructions of
+// a wave fall into one slot, three slots before their wait: 900 us; this schedule: 711 us; this schedule with A1(t+1)
+// issued from the MFMA slot that runs beside the other group's R1: 749 us.
+template <int EPI, typename TOut, typename TIn>
+__global__ __launch_bounds__(512, 2) void gemm_nt384_kernel(const TIn* __restrict__ A, int lda,
+                                                            const TIn* __restrict__ B, int ldb, int M, int N, int K,
+                                                            int tiles_m, int tiles_n, int band_h, EpiParams p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  SGL_TL_STAMP(tl0);
+  const int ntiles = tiles_m * tiles_n;
+  int tile_m, tile_n;
+  if (band_h < 0) {
+    if (!tile_of_local(blockIdx.x & 7, blockIdx.x >> 3, tiles_m, tiles_n, -band_h, tile_m, tile_n)) return;
+  } else {
+    const int unit = unit_of_block(blockIdx.x, (ntiles + 7) >> 3);
+    if (unit >= ntiles) return;  // whole block exits together
+    tile_of_unit(unit, tiles_m, tiles_n, tile_m, tile_n, band_h);
+  }
+  const int t = threadIdx.x, lane = t & 63;
+  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int wr = w & 3, wc = w >> 2, grp = w >> 2;
+  const int m0 = tile_m * W_BM, n0 = tile_n * W_BN;
+  const int rows_a = (M - m0 < W_BM) ? M - m0 : W_BM;
+  const int rows_b = (N - n0 < W_BN) ? N - n0 : W_BN;
+  const u32x4 da = pp_desc(A + (size_t)m0 * lda, (uint32_t)(((size_t)(rows_a - 1) * lda + K) * 2));
+  const u32x4 db = pp_desc(B + (size_t)n0 * ldb, (uint32_t)(((size_t)(rows_b - 1) * ldb + K) * 2));
+  const uint32_t lds0 = (uint32_t)(size_t)((SGL_LDS char*)smem);
+
+  // DMA plan: unit u in {A0, B, A1} is 24 instructions of 8 image rows, 3 per wave.  Piece 3w + q of A0 / A1 covers rows
+  // 96 * (piece / 6) + 8 * (piece % 6) (+ 48 for A1): the first / second 48 rows of every wave row; of B rows 8 * piece.
+  const int drow = lane >> 3, dchunk = (lane & 7) ^ drow;
+  uint32_t voff[3][3], ldst[3][3];
+#pragma unroll
+  for (int u = 0; u < 3; ++u)
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+      const int piece = 3 * w + q;
+      const bool isA = u != 1;
+      const int r0 = isA ? 96 * (piece / 6) + 8 * (piece % 6) + (u == 2 ? 48 : 0) : 8 * piece;
+      const int row = r0 + drow;
+      voff[u][q] = (row < (isA ? rows_a : rows_b)) ? (uint32_t)(row * (isA ? lda : ldb) + dchunk * 8) * 2u : SGL_OOB;
+      ldst[u][q] = lds0 + (isA ? 0 : W_OPA) + (uint32_t)r0 * 128u;
+    }
+  const int nk = (K + T_BK - 1) / T_BK;
+  auto issue = [&](int u, int kt) {  // unit u of K-step kt (K-steps past the end: all lanes out of range -> zeros)
+    const int k0 = kt * T_BK;
+    const bool kok = (kt < nk) && (k0 + dchunk * 8 < K);
+    const uint32_t sb = (uint32_t)((kt & 1) * W_STAGE);
+#pragma unroll
+    for (int q = 0; q < 3; ++q)
+      pp_dma16(u != 1 ? da : db, ldst[u][q] + sb, (kok && voff[u][q] != SGL_OOB) ? voff[u][q] + (uint32_t)k0 * 2u : SGL_OOB);
+  };
+#define SGL_W_END_READ9()                                               \
+  do {                                                                  \
+    asm volatile("s_waitcnt vmcnt(9) lgkmcnt(0)" ::: "memory");         \
+    __builtin_amdgcn_sched_barrier(0);                                  \
+    __builtin_amdgcn_s_barrier();                                       \
+    __builtin_amdgcn_sched_barrier(0);                                  \
+  } while (0)
+
+  const int frow = lane & 15, fg = lane >> 4, fsw = frow & 7;
+  const uint32_t fa_base = (uint32_t)((wr * 96 + frow) * 128);
+  const uint32_t fb_base = (uint32_t)(W_OPA + (wc * 96 + frow) * 128);
+  const uint32_t c0 = (uint32_t)(((0 + fg) ^ fsw) << 4), c1 = (uint32_t)(((4 + fg) ^ fsw) << 4);
+  const bool active = (n0 + wc * 96 < N) && (m0 + wr * 96 < M);
+
+  f32x4 acc[6][6];
+#pragma unroll
+  for (int i = 0; i < 6; ++i)
+#pragma unroll
+    for (int j = 0; j < 6; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  issue(0, 0); issue(1, 0); issue(2, 0);
+  issue(0, 1); issue(1, 1);
+  SGL_W_END_READ9();                 // A0(0), B(0) of every wave have landed
+  if (grp == 1) SGL_PP_END_MFMA();   // G1 runs one slot behind G0 from here on
+
+  lo_x8<TIn> fa[6], fb[12];
+  for (int kt = 0; kt < nk; ++kt) {
+    const char* base = smem + (kt & 1) * W_STAGE;
+    const char* pa = base + fa_base;
+    const char* pb = base + fb_base;
+    // ---- R1: A0 (row blocks 0-2), B (column blocks 0-5), both k-halves
+    if (active) {
+#pragma unroll
+      for (int f = 0; f < 12; ++f) fb[f] = *reinterpret_cast<const lo_x8<TIn>*>(pb + (f % 6) * 2048 + ((f / 6) ? c1 : c0));
+#pragma unroll
+      for (int f = 0; f < 6; ++f) fa[f] = *reinterpret_cast<const lo_x8<TIn>*>(pa + (f % 3) * 2048 + ((f / 3) ? c1 : c0));
+    }
+    issue(2, kt + 1);
+    SGL_W_END_READ9();
+    if (active) {
+      __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+          for (int j = 0; j < 6; ++j) acc[i][j] = mfma_16x16x32(fa[3 * h + i], fb[6 * h + j], acc[i][j]);
+      __builtin_amdgcn_s_setprio(0);
+    }
+    SGL_PP_END_MFMA();
+    // ---- R2: A1 (row blocks 3-5)
+    if (active) {
+#pragma unroll
+      for (int f = 0; f < 6; ++f) fa[f] = *reinterpret_cast<const lo_x8<TIn>*>(pa + (3 + f % 3) * 2048 + ((f / 3) ? c1 : c0));
+    }
+    issue(0, kt + 2); issue(1, kt + 2);
+    SGL_W_END_READ9();
+    if (active) {
+      __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+          for (int j = 0; j < 6; ++j) acc[3 + i][j] = mfma_16x16x32(fa[3 * h + i], fb[6 * h + j], acc[3 + i][j]);
+      __builtin_amdgcn_s_setprio(0);
+    }
+    SGL_PP_END_MFMA();
+  }
+  if (grp == 0) SGL_PP_END_MFMA();   // G0 waits for G1's last slot
+#undef SGL_W_END_READ9
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // trailing (all-zero) units must land before the LDS is reused
+#ifdef SGL_TIMELINE
+  if (p.atomic == 77) return;   // developer build only (SGL_NT6_SKIP_EPI): main loop without its epilogue
+#endif
+  SGL_TL_STAMP(tl1);
+  store_tile384<EPI, TOut>(smem, acc, wr, wc, lane, t, m0, n0, M, N, p);
+#ifdef SGL_TIMELINE
+  SGL_TL_STAMP(tl2);
+  if (t == 0) {
+    atomicAdd(&g_nt6_tl[0], tl1 - tl0);
+    atomicAdd(&g_nt6_tl[1], tl2 - tl1);
+    atomicAdd(&g_nt6_tl[2], 1ull);
+  }
+#endif
+}
+
+// ------------------------------------------------------------------------------------------------------
 // TN (dW), four slots per K-step of 64 tokens, split by K-HALF: the token index is the MFMA k index, so the first 32
 // image rows of both operands feed the first 32 MFMAs (every accumulator once) and the last 32 rows the other 32.
 //     R1(t): k-half 0 fragments (8 A + 4 B, two transposed reads each) + DMA units U2(t+1), U3(t+1)
@@ -665,6 +928,60 @@ hipError_t gemm_nt256_bf16(const void* A, int lda, const void* B, int ldb, int M
 hipError_t gemm_nt256_f16(const void* A, int lda, const void* B, int ldb, int M, int N, int K, int epi, int out_dtype,
                           const EpiParams& p, hipStream_t s) {
   return gemm_nt256<f16>(A, lda, B, ldb, M, N, K, epi, out_dtype, p, s);
+}
+
+// 384x192 tile: same tile orders and SGL_BAND switch as launch_nt256, counted in 384x192 tiles (B-stationary by default:
+// an XCD walks its 30-31 row tiles with all six column tiles of an output 1152 wide in one column group)
+template <int EPI, typename TOut, typename TIn>
+static hipError_t launch_nt384(const TIn* A, int lda, const TIn* B, int ldb, int M, int N, int K, const EpiParams& p,
+                               hipStream_t s) {
+  const hipError_t e = set_max_dynamic_lds_once<&gemm_nt384_kernel<EPI, TOut, TIn>>(W_LDS);
+  if (e != hipSuccess) return e;
+  const int tiles_m = (M + W_BM - 1) / W_BM, tiles_n = (N + W_BN - 1) / W_BN;
+  static const int band_env = getenv("SGL_BAND") ? atoi(getenv("SGL_BAND")) : 0;
+  const int band_h = band_env != 0 ? band_env : -8;
+  const int grid = band_h < 0 ? 8 * (((tiles_m + 7) / 8) * tiles_n) : ((tiles_m * tiles_n + 7) / 8) * 8;
+  EpiParams pp = p;
+#ifdef SGL_TIMELINE   // measurement builds only (make TIMELINE=1): the product library never skips an epilogue
+  static const bool skip_epi = getenv("SGL_NT6_SKIP_EPI") != nullptr;
+  if (skip_epi) pp.atomic = 77;
+#endif
+  hipLaunchKernelGGL((gemm_nt384_kernel<EPI, TOut, TIn>), dim3(grid), dim3(512), W_LDS, s, A, lda, B, ldb, M, N, K,
+                     tiles_m, tiles_n, band_h, pp);
+#ifdef SGL_TIMELINE
+  if (getenv("SGL_TIMELINE")) {   // synchronises: measurement builds only
+    unsigned long long h[4];
+    (void)hipStreamSynchronize(s);
+    (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_nt6_tl), sizeof(h));
+    if (h[2])
+      fprintf(stderr, "[timeline] gemm_nt384 EPI %d M=%d N=%d K=%d: %llu tiles, main loop %.0f, epilogue %.0f cycles per tile\n", EPI,
+              M, N, K, h[2], (double)h[0] / h[2], (double)h[1] / h[2]);
+    memset(h, 0, sizeof(h));
+    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_nt6_tl), h, sizeof(h));
+  }
+#endif
+  return hipGetLastError();
+}
+
+// EPI_STORE (16-bit or fp32 output) and EPI_RES_F32 only: gemm_nt_mfma (gemm_bf16.hip) sends nothing else here
+template <typename TIn>
+static hipError_t gemm_nt384(const void* A, int lda, const void* B, int ldb, int M, int N, int K, int epi, int out_dtype,
+                             const EpiParams& p, hipStream_t s) {
+  const TIn* a = (const TIn*)A;
+  const TIn* b = (const TIn*)B;
+  if (epi == EPI_RES_F32) return launch_nt384<EPI_RES_F32, float, TIn>(a, lda, b, ldb, M, N, K, p, s);
+  if (epi != EPI_STORE) return hipErrorInvalidValue;
+  if (out_dtype == (std::is_same<TIn, f16>::value ? DT_F16 : DT_BF16))
+    return launch_nt384<EPI_STORE, TIn, TIn>(a, lda, b, ldb, M, N, K, p, s);
+  return launch_nt384<EPI_STORE, float, TIn>(a, lda, b, ldb, M, N, K, p, s);
+}
+hipError_t gemm_nt384_bf16(const void* A, int lda, const void* B, int ldb, int M, int N, int K, int epi, int out_dtype,
+                           const EpiParams& p, hipStream_t s) {
+  return gemm_nt384<bf16>(A, lda, B, ldb, M, N, K, epi, out_dtype, p, s);
+}
+hipError_t gemm_nt384_f16(const void* A, int lda, const void* B, int ldb, int M, int N, int K, int epi, int out_dtype,
+                          const EpiParams& p, hipStream_t s) {
+  return gemm_nt384<f16>(A, lda, B, ldb, M, N, K, epi, out_dtype, p, s);
 }
 
 template <typename TIn>
