@@ -15,6 +15,103 @@
 
 namespace sgl {
 
+// The value arithmetic and the stores of the four epilogues that have operands besides an optional bias, on NV
+// consecutive columns of one row.  The caller supplies the operands and the destinations: epi_apply below loads and
+// addresses per chunk; the staged epilogue of gemm_bf16_v2.hip loads the bias once per thread, requests the residual /
+// pre-activation one pass ahead and keeps the column part of the QKV address per thread.
+template <int NV>
+__device__ __forceinline__ void epi_res_f32(float* v, const float* bias, const float* r, float* dst) {
+#pragma unroll
+  for (int j = 0; j < NV; ++j) v[j] = r[j] + (v[j] + bias[j]);
+  Vec<float, NV>::st_nt(dst, v);
+}
+// dst_u (inside p.out) is written only when p.out is given: the pre-activation u (or gelu'(u),
+// EpiParams::gelu_grad_form) is only read by the backward GELU'; inference and frozen blocks pass out == nullptr
+template <typename TOut, int NV>
+__device__ __forceinline__ void epi_bias_gelu(const EpiParams& p, float* v, const float* bias, TOut* dst_u, TOut* dst_act) {
+  float a[NV];
+  if (p.out && p.gelu_grad_form) {   // training, derivative form: out := gelu'(u)
+#pragma unroll
+    for (int j = 0; j < NV; ++j) gelu_tanh_both(v[j] + bias[j], a[j], v[j]);
+  } else {
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+      v[j] += bias[j];
+      a[j] = gelu_tanh(v[j]);
+    }
+  }
+  if (p.out) Vec<TOut, NV>::st_nt(dst_u, v);
+  Vec<TOut, NV>::st_nt(dst_act, a);
+}
+// row -> (b, n) = (row / tokens, row % tokens) without the ~35-instruction integer division (16 of them per thread and
+// tile otherwise): float reciprocal estimate, then one exact correction step (rows < 2^22)
+__device__ __forceinline__ void qkv_split_row(int row, int tokens, int& b, int& n) {
+  b = (int)((float)row * __builtin_amdgcn_rcpf((float)tokens));
+  n = row - b * tokens;
+  if (n < 0) { b -= 1; n += tokens; }
+  else if (n >= tokens) { b += 1; n -= tokens; }
+}
+// pad_chunks: NV-chunks of zeros behind the head's last data chunk, the pad columns [head_dim, head_dim_pad).
+// head_dim % 8 == 0 and head_dim_pad = round_up(head_dim, 16), so the pad is 0 or 8 elements, i.e. whole NV-chunks:
+// vector stores (scalar 2-byte stores here cost the QKV GEMM ~15 %)
+template <typename TOut, int NV>
+__device__ __forceinline__ void epi_qkv(float* v, const float* bias, TOut* dst, int pad_chunks) {
+#pragma unroll
+  for (int j = 0; j < NV; ++j) v[j] += bias[j];
+  Vec<TOut, NV>::st_nt(dst, v);
+  if (pad_chunks) {
+    float z[NV];
+#pragma unroll
+    for (int j = 0; j < NV; ++j) z[j] = 0.f;
+    for (int k = 1; k <= pad_chunks; ++k) Vec<TOut, NV>::st_nt(dst + k * NV, z);
+  }
+}
+// u: the saved pre-activation, or gelu'(u) itself with EpiParams::gelu_grad_form; leaves the stored values in v
+template <typename TOut, int NV>
+__device__ __forceinline__ void epi_gelu_bwd(const EpiParams& p, float* v, const float* u, TOut* dst) {
+  if (p.gelu_grad_form) {
+#pragma unroll
+    for (int j = 0; j < NV; ++j) v[j] *= u[j];
+  } else {
+#pragma unroll
+    for (int j = 0; j < NV; ++j) v[j] *= gelu_tanh_grad(u[j]);
+  }
+  Vec<TOut, NV>::st_nt(dst, v);
+}
+
+// Workgroup barrier that orders LDS traffic only: raw s_barrier + lgkmcnt(0).  __syncthreads() would also emit vmcnt(0)
+// and make the caller wait for its global stores to be acknowledged (microseconds under load); they stay in flight.
+__device__ __forceinline__ void lds_barrier() {
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");
+}
+
+// Fused bias gradient of EPI_GELU_BWD, after the chunk loop of a workgroup of NT threads on a tile BN columns wide: every
+// thread owns the same NV columns in all its chunks (NT % (BN / NV) == 0) and has their sums over its rows in csum.  Folds
+// the NT / (BN / NV) row groups through LDS (ct: at least NT * NV floats, free to overwrite) and gives one value per
+// column to p.colsum (EpiParams: stored per 128-row block when colsum_ld > 0, added atomically otherwise).
+template <int NT, int BN, int NV>
+__device__ __forceinline__ void epi_colsum_fold(float* ct, const float (&csum)[NV], int t, int m0, int n0, int N,
+                                                const EpiParams& p) {
+  constexpr int CPR = BN / NV, GROUPS = NT / CPR;
+  static_assert(NT % CPR == 0 && BN <= NT, "one fixed column set per thread, one thread per column");
+  if (!p.colsum) return;
+  lds_barrier();
+#pragma unroll
+  for (int j = 0; j < NV; ++j) ct[(t / CPR) * BN + (t % CPR) * NV + j] = csum[j];
+  lds_barrier();
+  if (t < BN && n0 + t < N) {
+    float s = 0.f;
+#pragma unroll
+    for (int gI = 0; gI < GROUPS; ++gI) s += ct[gI * BN + t];
+    if (p.colsum_ld > 0)
+      p.colsum[(size_t)(m0 >> 7) * p.colsum_ld + n0 + t] = s;
+    else
+      atomicAdd(p.colsum + n0 + t, s);
+  }
+}
+
 template <int EPI, typename TOut, int NV>
 __device__ __forceinline__ void epi_apply(const EpiParams& p, int row, int col, int N, float* v) {
   if constexpr (EPI == EPI_STORE) {
@@ -28,58 +125,32 @@ __device__ __forceinline__ void epi_apply(const EpiParams& p, int row, int col, 
     }
     Vec<TOut, NV>::st_nt(reinterpret_cast<TOut*>(p.out) + (size_t)row * p.ldo + col, v);
   } else if constexpr (EPI == EPI_BIAS_GELU) {
-    float b[NV], a[NV];
+    float b[NV];
     Vec<float, NV>::ld(p.bias + col, b);
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-      v[j] += b[j];
-      if (p.out && p.gelu_grad_form) gelu_tanh_both(v[j], a[j], v[j]);   // v := gelu'(u)
-      else a[j] = gelu_tanh(v[j]);
-    }
-    // the pre-activation u (or gelu'(u), gelu_grad_form) is only read by the backward GELU': inference and frozen blocks
-    // pass out == nullptr
-    if (p.out) Vec<TOut, NV>::st_nt(reinterpret_cast<TOut*>(p.out) + (size_t)row * p.ldo + col, v);
-    Vec<TOut, NV>::st_nt(reinterpret_cast<TOut*>(p.out2) + (size_t)row * p.ldo2 + col, a);
+    epi_bias_gelu<TOut, NV>(p, v, b, reinterpret_cast<TOut*>(p.out) + (size_t)row * p.ldo + col,
+                            reinterpret_cast<TOut*>(p.out2) + (size_t)row * p.ldo2 + col);
   } else if constexpr (EPI == EPI_RES_F32) {
     float b[NV], r[NV];
     Vec<float, NV>::ld(p.bias + col, b);
     Vec<float, NV>::ld(p.res + (size_t)row * p.ldr + col, r);
-#pragma unroll
-    for (int j = 0; j < NV; ++j) v[j] = r[j] + (v[j] + b[j]);
-    Vec<float, NV>::st_nt(reinterpret_cast<float*>(p.out) + (size_t)row * p.ldo + col, v);
+    epi_res_f32<NV>(v, b, r, reinterpret_cast<float*>(p.out) + (size_t)row * p.ldo + col);
   } else if constexpr (EPI == EPI_QKV) {
     const int dm = p.heads * p.head_dim;
     const int which = col / dm;
     const int hc = col - which * dm;
     const int h = hc / p.head_dim;
     const int d = hc - h * p.head_dim;
-    // row / tokens without the ~35-instruction integer division (16 of them per thread and tile otherwise): float
-    // reciprocal estimate, then one exact correction step (rows < 2^22)
-    int b = (int)((float)row * __builtin_amdgcn_rcpf((float)p.tokens));
-    int n = row - b * p.tokens;
-    if (n < 0) { b -= 1; n += p.tokens; }
-    else if (n >= p.tokens) { b += 1; n -= p.tokens; }
+    int b, n;
+    qkv_split_row(row, p.tokens, b, n);
     float bb[NV];
     Vec<float, NV>::ld(p.bias + col, bb);
-#pragma unroll
-    for (int j = 0; j < NV; ++j) v[j] += bb[j];
     TOut* dst = reinterpret_cast<TOut*>(p.out) +
                 ((((size_t)which * p.batch + b) * p.heads + h) * p.tokens + n) * p.head_dim_pad + d;
-    Vec<TOut, NV>::st_nt(dst, v);
-    if (d + NV == p.head_dim) {
-      // zero the pad columns [head_dim, head_dim_pad): head_dim % 8 == 0 and head_dim_pad = round_up(head_dim, 16), so the
-      // pad is 0 or 8 elements, i.e. whole NV-chunks: vector stores (scalar 2-byte stores here cost the QKV GEMM ~15 %)
-      float z[NV];
-#pragma unroll
-      for (int j = 0; j < NV; ++j) z[j] = 0.f;
-      for (int j = p.head_dim; j + NV <= p.head_dim_pad; j += NV) Vec<TOut, NV>::st_nt(dst + (j - d), z);
-    }
+    epi_qkv<TOut, NV>(v, bb, dst, (d + NV == p.head_dim) ? (p.head_dim_pad - p.head_dim) / NV : 0);
   } else if constexpr (EPI == EPI_GELU_BWD) {
     float u[NV];
     Vec<TOut, NV>::ld(reinterpret_cast<const TOut*>(p.aux) + (size_t)row * p.ldaux + col, u);
-#pragma unroll
-    for (int j = 0; j < NV; ++j) v[j] *= p.gelu_grad_form ? u[j] : gelu_tanh_grad(u[j]);
-    Vec<TOut, NV>::st_nt(reinterpret_cast<TOut*>(p.out) + (size_t)row * p.ldo + col, v);
+    epi_gelu_bwd<TOut, NV>(p, v, u, reinterpret_cast<TOut*>(p.out) + (size_t)row * p.ldo + col);
   } else if constexpr (EPI == EPI_POS_F32) {
     float b[NV], e[NV];
     Vec<float, NV>::ld(p.bias + col, b);

@@ -93,24 +93,7 @@ __device__ __forceinline__ void store_tile(char* smem, f32x4 (&acc)[4][4], int w
       }
     }
   }
-  if constexpr (EPI == EPI_GELU_BWD) {
-    if (p.colsum) {  // fused bias gradient (see gemm_bf16_v2.hip)
-      __syncthreads();
-      constexpr int GROUPS = 256 / CPR;
-#pragma unroll
-      for (int j = 0; j < NV; ++j) ct[(t / CPR) * G_BN + (t % CPR) * NV + j] = csum[j];
-      __syncthreads();
-      if (t < G_BN && n0 + t < N) {
-        float s = 0.f;
-#pragma unroll
-        for (int gI = 0; gI < GROUPS; ++gI) s += ct[gI * G_BN + t];
-        if (p.colsum_ld > 0)
-          p.colsum[(size_t)(m0 >> 7) * p.colsum_ld + n0 + t] = s;
-        else
-          atomicAdd(p.colsum + n0 + t, s);
-      }
-    }
-  }
+  if constexpr (EPI == EPI_GELU_BWD) epi_colsum_fold<256, G_BN, NV>(ct, csum, t, m0, n0, N, p);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -311,21 +294,6 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const TIn* __restrict__
 // ------------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------------
-// 256x256-tile LDS-DMA kernels (gemm_bf16_v2.hip), used whenever the problem is large enough to fill the chip
-hipError_t gemm_nt256_bf16(const void* A, int lda, const void* B, int ldb, int M, int N, int K, int epi, int out_dtype,
-                           const EpiParams& p, hipStream_t s);
-hipError_t gemm_tn256_bf16(const void* A, int lda, const void* B, int ldb, int Mred, int N1, int N2, int m_per,
-                           int splits, const EpiParams& p, hipStream_t s);
-hipError_t gemm_nt256_f16(const void* A, int lda, const void* B, int ldb, int M, int N, int K, int epi, int out_dtype,
-                          const EpiParams& p, hipStream_t s);
-hipError_t gemm_tn256_f16(const void* A, int lda, const void* B, int ldb, int Mred, int N1, int N2, int m_per,
-                          int splits, const EpiParams& p, hipStream_t s);
-// 384x192-tile NT kernel of the same file (EPI_STORE and EPI_RES_F32 only)
-hipError_t gemm_nt384_bf16(const void* A, int lda, const void* B, int ldb, int M, int N, int K, int epi, int out_dtype,
-                           const EpiParams& p, hipStream_t s);
-hipError_t gemm_nt384_f16(const void* A, int lda, const void* B, int ldb, int M, int N, int K, int epi, int out_dtype,
-                          const EpiParams& p, hipStream_t s);
-
 template <int EPI, typename TOut, typename TIn>
 static hipError_t launch_nt(const TIn* A, int lda, const TIn* B, int ldb, int M, int N, int K, const EpiParams& p,
                             hipStream_t s) {
@@ -355,11 +323,8 @@ static hipError_t gemm_nt_mfma(const void* A, int lda, const void* B, int ldb, i
     const bool can384 = epi == EPI_STORE || epi == EPI_RES_F32;
     const bool pays384 = N % 192 == 0 && N % 256 != 0 && (epi == EPI_STORE || K >= 2048);
     const bool want384 = tile_env == 384 || (tile_env != 256 && pays384);
-    if (can384 && want384)
-      return std::is_same<TIn, f16>::value ? gemm_nt384_f16(A, lda, B, ldb, M, N, K, epi, out_dtype, p, s)
-                                           : gemm_nt384_bf16(A, lda, B, ldb, M, N, K, epi, out_dtype, p, s);
-    return std::is_same<TIn, f16>::value ? gemm_nt256_f16(A, lda, B, ldb, M, N, K, epi, out_dtype, p, s)
-                                         : gemm_nt256_bf16(A, lda, B, ldb, M, N, K, epi, out_dtype, p, s);
+    if (can384 && want384) return gemm_nt384<TIn>(A, lda, B, ldb, M, N, K, epi, out_dtype, p, s);
+    return gemm_nt256<TIn>(A, lda, B, ldb, M, N, K, epi, out_dtype, p, s);
   }
   return dispatch_epilogue<TIn>(epi, out_dtype, [&](auto tag) {
     using T = decltype(tag);
@@ -431,8 +396,7 @@ static hipError_t gemm_tn_mfma(const void* A, int lda, const void* B, int ldb, i
     const int max_sp = Mred / 1024 > 0 ? Mred / 1024 : 1;
     if (sp > max_sp) sp = max_sp;
     return tn_split_k(Mred, N1, N2, sp, p, s, split_ws, split_ws_bytes, [&](int m_per, int nsplit, const EpiParams& q) {
-      return std::is_same<TIn, f16>::value ? gemm_tn256_f16(A, lda, B, ldb, Mred, N1, N2, m_per, nsplit, q, s)
-                                           : gemm_tn256_bf16(A, lda, B, ldb, Mred, N1, N2, m_per, nsplit, q, s);
+      return gemm_tn256<TIn>(A, lda, B, ldb, Mred, N1, N2, m_per, nsplit, q, s);
     });
   }
   return tn_split_k(Mred, N1, N2, splits, p, s, split_ws, split_ws_bytes, [&](int m_per, int nsplit, const EpiParams& q) {

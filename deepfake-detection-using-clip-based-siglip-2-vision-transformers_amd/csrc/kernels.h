@@ -187,6 +187,18 @@ hipError_t gemm_nt_f16(const void* A, int lda, const void* B, int ldb, int M, in
                        const EpiParams& p, hipStream_t s);
 hipError_t gemm_tn_f16(const void* A, int lda, const void* B, int ldb, int Mred, int N1, int N2, int splits,
                        const EpiParams& p, hipStream_t s, float* split_ws = nullptr, size_t split_ws_bytes = 0);
+// The LDS-DMA kernels of gemm_bf16_v2.hip, which the four above send the shapes that fill the chip to; TIn = bf16 or f16
+// (instantiated there).  gemm_nt384 takes EPI_STORE and EPI_RES_F32 only (hipErrorInvalidValue otherwise); gemm_tn256
+// runs `splits` ranges of m_per tokens (EpiParams::split_stride / atomic say where a split's tile goes).
+template <typename TIn>
+hipError_t gemm_nt256(const void* A, int lda, const void* B, int ldb, int M, int N, int K, int epi, int out_dtype,
+                      const EpiParams& p, hipStream_t s);
+template <typename TIn>
+hipError_t gemm_nt384(const void* A, int lda, const void* B, int ldb, int M, int N, int K, int epi, int out_dtype,
+                      const EpiParams& p, hipStream_t s);
+template <typename TIn>
+hipError_t gemm_tn256(const void* A, int lda, const void* B, int ldb, int Mred, int N1, int N2, int m_per, int splits,
+                      const EpiParams& p, hipStream_t s);
 
 // ---- attention.hip -------------------------------------------------------------------------------------
 // q,k,v: ld_qkv > 0: token-major [B*N][ld_qkv] column blocks (head h of row r at r*ld_qkv + h*dh; the QKV projection's

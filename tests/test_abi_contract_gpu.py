@@ -710,7 +710,7 @@ def test_package_refuses_546px_before_any_launch(pkg, hiplib, mode):
 
 
 # =====================================================================================================================
-# f. bf16x3 at >= 2048 tokens: the two gemm_nt6_kernel<0|4, float, bfloat16> instantiations
+# f. bf16x3 at >= 2048 tokens: the fp32-output gemm_nt6_kernel<Tile, 0 | 4, float, bfloat16> instantiations (0 on both tiles)
 # =====================================================================================================================
 def test_bf16x3_2187_tokens_vs_oracle(pkg, oracle, hiplib):
     B, H, W = 3, 384, 384

@@ -1,4 +1,4 @@
-"""GPU tests of the 384x192-tile NT GEMM (gemm_nt384_kernel), through the C ABI (``sgl_op_gemm_nt``).
+"""GPU tests of the 384x192-tile NT GEMM (gemm_nt6_kernel on the NtTile384 geometry), through the C ABI (``sgl_op_gemm_nt``).
 
 The dispatch sends an NT GEMM there when M >= 2048, N % 192 == 0, N % 256 != 0 and the epilogue is EPI_STORE, or EPI_RES_F32
 with K >= 2048 (at smaller K the residual launch is bound by its memory traffic and the tile does not pay).
