@@ -65,8 +65,13 @@ namespace {
 
 constexpr int kMaxLayers = 128;
 
-// splits * N1 * N2 * 4 bytes with tiles*splits <= 256 workgroups of 256x256 outputs: never more than 64 MiB
+// Slabs of the split-K dW GEMMs: splits * N1 * N2 * 4 bytes.  64 MiB holds every plan of the 256x256 tile (tiles*splits <=
+// 256 tiles of 256x256 floats); tn_plan (kernels.h) takes the best plan whose slabs fit, which on the 384x192 tile is 12
+// splits instead of 14 for out_proj dW at the bench batch (14 slabs of 1152 x 1152 are 71 MiB).  The size is part of what
+// sgl_query_sizes reports and stays as it is.
 constexpr size_t kSplitWsBytes = (size_t)256 * 256 * 256 * 4;
+static_assert(tn_plan_is(93312, 1152, 1152, kSplitWsBytes, 384, 12), "out_proj dW in the encoder's workspace");
+static_assert(tn_plan_is(93312, 3456, 1152, kSplitWsBytes, 384, 4), "QKV dW in the encoder's workspace");
 
 // one of q / k / v of a whole batch, head-major [B][H][N][DP]
 inline size_t head_bytes(const sgl_ctx* c, int B, int N) { return (size_t)B * c->H * N * c->DP * c->es; }

@@ -340,6 +340,12 @@ hipError_t gemm_nt_f16(const void* A, int lda, const void* B, int ldb, int M, in
   return gemm_nt_mfma<f16>(A, lda, B, ldb, M, N, K, epi, out_dtype, p, s);
 }
 
+// whether a TN output with these parameters can be written as private slabs and summed by reduce_splits()
+static bool tn_slabs_ok(const EpiParams& p, int N2, const float* split_ws) {
+  return p.alpha == 1.0f && !p.bias && (N2 % 4 == 0) && (p.ldo % 4 == 0) &&
+         ((((uintptr_t)p.out) | ((uintptr_t)split_ws)) & 15) == 0;
+}
+
 // Split the token reduction of a TN GEMM into `splits` ranges of m_per rows (m_per a multiple of G_BK) and run
 // launch(m_per, splits, params).  With a workspace that holds every split's slab the splits store private slabs and
 // reduce_splits() sums them in a fixed order (deterministic, and ~4x cheaper than the atomic epilogue); otherwise they
@@ -355,8 +361,7 @@ static hipError_t tn_split_k(int Mred, int N1, int N2, int splits, const EpiPara
   splits = (Mred + m_per - 1) / m_per;
   if (splits > 1) {
     const size_t slab = (size_t)N1 * N2;
-    if (split_ws && (size_t)splits * slab * sizeof(float) <= split_ws_bytes && p.alpha == 1.0f && !p.bias &&
-        (N2 % 4 == 0) && (p.ldo % 4 == 0) && ((((uintptr_t)out) | ((uintptr_t)split_ws)) & 15) == 0) {
+    if (split_ws && (size_t)splits * slab * sizeof(float) <= split_ws_bytes && tn_slabs_ok(p, N2, split_ws)) {
       EpiParams q = p;
       q.out = split_ws;
       q.ldo = N2;
@@ -388,14 +393,17 @@ static hipError_t gemm_tn_mfma(const void* A, int lda, const void* B, int ldb, i
     return hipSuccess;
   }
   if (N1 >= 512 && N2 >= 512 && Mred >= 2048) {
-    // 256x256 tiles, one workgroup per CU (128 KiB LDS): split the token reduction so that tiles*splits <= 256 (a single
-    // full round), but keep at least 1024 tokens per split
-    const int tiles = ((N1 + 255) / 256) * ((N2 + 255) / 256);
-    int sp = 256 / tiles;
-    if (sp < 1) sp = 1;
-    const int max_sp = Mred / 1024 > 0 ? Mred / 1024 : 1;
-    if (sp > max_sp) sp = max_sp;
-    return tn_split_k(Mred, N1, N2, sp, p, s, split_ws, split_ws_bytes, [&](int m_per, int nsplit, const EpiParams& q) {
+    // One workgroup per CU (128 / 144 KiB of LDS) in a single round: tn_plan (kernels.h) chooses the tile and the split of
+    // the token reduction.  The slabs of the plan must fit the scratch; if there is no scratch, the output cannot take
+    // slabs (tn_split_k) or not even two slabs fit, the plan is made without that limit and the splits add with atomics.
+    // SGL_TN_TILE=256|384 (developer switch, read once) allows one geometry only.
+    static const int tile_env = getenv("SGL_TN_TILE") ? atoi(getenv("SGL_TN_TILE")) : 0;
+    const int tile = (tile_env == 256 || tile_env == 384) ? tile_env : 0;
+    const bool slabs_ok = split_ws && tn_slabs_ok(p, N2, split_ws);
+    TnPlan plan = tn_plan(Mred, N1, N2, slabs_ok ? split_ws_bytes : 0, tile);
+    if (plan.splits == 1) plan = tn_plan(Mred, N1, N2, ~(size_t)0, tile);
+    return tn_split_k(Mred, N1, N2, plan.splits, p, s, split_ws, split_ws_bytes, [&](int m_per, int nsplit, const EpiParams& q) {
+      if (plan.tile == 384) return gemm_tn384<TIn>(A, lda, B, ldb, Mred, N1, N2, m_per, nsplit, q, s);
       return gemm_tn256<TIn>(A, lda, B, ldb, Mred, N1, N2, m_per, nsplit, q, s);
     });
   }

@@ -1,11 +1,11 @@
 // bf16 / fp16 MFMA GEMMs for gfx950, K-step 64, 512 threads = 8 waves, operands streamed global -> LDS by LDS-DMA
 // (buffer_load_dwordx4 ... lds, 1 KiB per wave instruction, no VGPR staging), two LDS stages.  Two kernels:
 //   gemm_nt6_kernel<Tile, ...>   NT on a tile geometry: NtTile256 (256 x 256) or NtTile384 (384 x 192), see the structs
-//   gemm_tn6_kernel              TN on the 256 x 256 geometry
+//   gemm_tn6_kernel<Tile, ...>   TN on the same two geometries
 // Both main loops run anti-phase wave groups, four barrier-separated slots per K-step (see the comments above them),
 // and share the LDS images, the tile order and one staged epilogue (store_tile_pp).  gemm_nt_bf16 / gemm_tn_bf16
-// (gemm_bf16.hip) send the shapes that fill the chip here, through gemm_nt256 / gemm_nt384 / gemm_tn256 at the end of
-// this file, and hold the rule that chooses the NT tile.
+// (gemm_bf16.hip) send the shapes that fill the chip here, through gemm_nt256 / gemm_nt384 / gemm_tn256 / gemm_tn384 at the
+// end of this file, and hold the rules that choose the tile (and, for TN, the split).
 //
 //   nt : C[M,N]   = A[M,K] · B[N,K]ᵀ           (forward projections, dX with transposed weight shadows)
 //   tn : C[N1,N2] (+)= Σ_m A[m,N1] · B[m,N2]    (dW; token index is the MFMA k index via ds_read_b64_tr_b16)
@@ -16,7 +16,7 @@
 // LDS-DMA writes lane-linear (wave-uniform base + lane*16), so the bank-conflict swizzles are applied to each
 // lane's SOURCE address and again on the fragment reads (same involution on both sides):
 //   NT image [rows][64 k]       128-B rows: slot s of row r holds source chunk s ^ (r & 7)
-//   TN image [64 m][256 n]      512-B rows: slot s of row m holds source chunk s ^ (2*(m&3) + 8*((m>>3)&1))
+//   TN image [64 m][BM or BN n] 512-, 768- or 384-B rows: slot s of row m holds source chunk s ^ tn_swz(m), see gemm_tn6_kernel
 // blockIdx -> tile is XCD-aware (unit_of_block / tile_of_unit below): each XCD works through a contiguous chunk of
 // a grouped tile order, so its concurrent workgroups share A and B panels in its private L2.  Measured with
 // rocprofv3 FETCH_SIZE on the fc1 shape: the earlier "row panel per XCD" map fetched 6x the algorithmic bytes
@@ -75,12 +75,13 @@ struct NtTile256 : NtTileShape<256, 256, 8, 4> {
 // 384 x 192 (2 x 72 KiB): waves 4 (rows) x 2 (columns), 96 x 96 each (0.33 fragment reads per MFMA against 0.375), the
 // two waves of a SIMD again in different column halves.  For outputs 1152 = 6 x 192 wide there is no half-empty column
 // tile, and at the bench batch 93,312 = 243 x 384 rows give 1,458 tiles of 1.125 x the work where NtTile256 runs 1,825.
-// N need not divide by 192 for correctness.  EPI_STORE and EPI_RES_F32 only: nothing else is sent here.
+// N need not divide by 192 for correctness.  EPI_STORE and EPI_RES_F32 (NT), EPI_F32 (the TN kernel's slabs and atomics)
+// only: nothing else is sent here.
 struct NtTile384 : NtTileShape<384, 192, 6, 6> {
   static __device__ __forceinline__ int wr(int w) { return w & 3; }
   static __device__ __forceinline__ int wc(int w) { return w >> 2; }
   static __device__ __forceinline__ int b_row(int w, int q) { return 8 * (3 * w + q); }
-  static constexpr bool takes(int epi) { return epi == EPI_STORE || epi == EPI_RES_F32; }
+  static constexpr bool takes(int epi) { return epi == EPI_STORE || epi == EPI_RES_F32 || epi == EPI_F32; }
 };
 
 constexpr int gcd_of(int a, int b) { return b == 0 ? a : gcd_of(b, a % b); }
@@ -303,6 +304,11 @@ __device__ __forceinline__ u32x4 pp_desc(const void* base, uint32_t bytes) {
   u32x4 d = {(uint32_t)q, (uint32_t)(q >> 32) & 0xffffu, bytes, 0x00020000u};
   return d;
 }
+// a descriptor whose words the compiler cannot prove wave-uniform (it must sit in SGPRs for the "s" operand above)
+__device__ __forceinline__ u32x4 pp_desc_sgpr(u32x4 d) {
+  return u32x4{(uint32_t)__builtin_amdgcn_readfirstlane((int)d[0]), (uint32_t)__builtin_amdgcn_readfirstlane((int)d[1]),
+               (uint32_t)__builtin_amdgcn_readfirstlane((int)d[2]), (uint32_t)__builtin_amdgcn_readfirstlane((int)d[3])};
+}
 // end of a read slot: all but the NI youngest DMA instructions of this wave have landed, its fragment reads are done
 template <int NI>
 __device__ __forceinline__ void pp_end_read() {
@@ -487,20 +493,53 @@ __global__ __launch_bounds__(512, 2) void gemm_nt6_kernel(const TIn* __restrict_
 }
 
 // ------------------------------------------------------------------------------------------------------
-// TN (dW) on the NtTile256 geometry, four slots per K-step of 64 tokens, split by K-HALF: the token index is the MFMA k
-// index, so the first 32 image rows of both operands feed the first 32 MFMAs (every accumulator once) and the last 32
-// rows the other 32.
-//     R1(t): k-half 0 fragments (8 A + 4 B, two transposed reads each) + DMA units U2(t+1), U3(t+1)
-//     M1(t): 32 MFMAs      R2(t): k-half 1 fragments + DMA units U0(t+2), U1(t+2)      M2(t): 32 MFMAs
-// units: U0 = A image rows 0-31, U1 = B rows 0-31, U2 = A rows 32-63, U3 = B rows 32-63 (16 KiB, two instructions per
-// wave each: four younger units may stay in flight behind pp_end_read<8>).
-template <typename TIn>
+// TN (dW) on a tile geometry G, four slots per K-step of 64 tokens, split by K-HALF: the token index is the MFMA k
+// index, so the first 32 image rows of both operands feed the first MI MJ MFMAs (every accumulator once) and the last
+// 32 rows the other MI MJ.
+//     R1(t): k-half 0 fragments (MI of A + MJ of B, two transposed reads each) + DMA unit H1(t+1)
+//     M1(t): MI MJ MFMAs      R2(t): k-half 1 fragments + DMA unit H0(t+2)      M2(t): MI MJ MFMAs
+// Unit Hh = image rows 32h..32h+31 of A, then of B.  Both images are token rows of RA = 2 BM and RB = 2 BN bytes, a
+// k-half of them HA = BM/16 and HB = BN/16 contiguous KiB, one DMA instruction each: wave w moves A pieces PA w + q
+// (PA = HA/8) and B pieces PB w + q (PB = HB/8); where HB is 8 PB + 4 (the 192-wide image: 12 pieces) the four waves of
+// group h also move piece 8 PB + (w & 3) of Hh.  Every wave then issues the same NI = 2 PA + 2 PB (+ 1) instructions per
+// K-step, in whichever two slots, and every read slot ends with vmcnt(NI): behind the unit it publishes a wave has
+// issued exactly the two younger units, one of each k-half, i.e. NI instructions (pipeline start: H0(0), H1(0), H0(1)
+// issued, the same wait publishes H0(0)).  Invariants (a)-(d) of the NT loop hold with "unit" = Hh.
+// Swizzle (tn_swz, chunks of 16 B): a 32-lane half of a transposed read touches 8 token rows {8g + q} x 32 B, which
+// must fall into 8 different 32-B bank groups of the 256-B bank row.  Rows of 0 mod 256 bytes (512: 256 columns, 768:
+// 384 columns) all start on bank 0: slot s of row m holds chunk s ^ (2 (m & 3) + 8 ((m >> 3) & 1)), closed inside every
+// 256 B of the row.  Rows of 128 mod 256 bytes (384: 192 columns) already alternate between the two halves of the bank
+// row with m & 1, and the pattern must stay inside 128 B: chunk s ^ (2 ((m >> 1) & 1) + 4 ((m >> 3) & 1)).
+//              tile       MI x MJ   HA  HB   PA  PB(+1)  NI = vmcnt   reads per slot   MFMAs per slot   LDS
+//   NtTile256  256 x 256  8 x 4     16  16   2   2       8            24               32               128 KiB
+//   NtTile384  384 x 192  6 x 6     24  12   3   1 + 1   9            24               36               144 KiB
+// Every accumulator sees K-steps ascending, k-half 0 then 1, in one MFMA chain on either geometry: with equal split
+// boundaries the tiles agree bit for bit (tests/test_gemm_tn_384_gpu.py).
+template <int ROWB>
+__device__ __forceinline__ int tn_swz(int m) {
+  static_assert(ROWB % 128 == 0, "the patterns are closed inside 256 / 128 bytes of a row");
+  if constexpr (ROWB % 256 == 0) return 2 * (m & 3) + 8 * ((m >> 3) & 1);
+  else return 2 * ((m >> 1) & 1) + 4 * ((m >> 3) & 1);
+}
+
+// Units are numbered split-major, tile2 fastest inside a split; an XCD runs a chunk of ~32 consecutive units at once
+// (unit_of_block).  On a grid with few row tiles (fc2 dW: 5 x 17 tiles) that chunk is 1.9 x 17 tiles, 19-20 operand
+// column slices through one L2 where 17 x 5 gives 11-12, and FETCH_SIZE shows it (+34 %); running the shorter grid side
+// fastest removes the extra fills but moves no launch time out of its run-to-run band, so the
+// order stays as it is.
+template <typename G, typename TIn>
 __global__ __launch_bounds__(512, 2) void gemm_tn6_kernel(const TIn* __restrict__ A, int lda,
                                                           const TIn* __restrict__ B, int ldb, int Mred, int N1, int N2,
                                                           int m_per_split, int nsplits, int tiles_1, int tiles_2,
                                                           EpiParams p) {
-  using G = NtTile256;
   extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int MI = G::MI, MJ = G::MJ;
+  constexpr int RA = 2 * G::BM, RB = 2 * G::BN;            // bytes of a token row of the A / B image
+  constexpr int HA = G::BM / 16, HB = G::BN / 16;          // 1-KiB pieces of a k-half
+  constexpr int PA = HA / 8, PB = HB / 8;
+  constexpr bool BX = (HB % 8) != 0;                       // four pieces over: one more for each wave of group h
+  constexpr int NI = 2 * PA + 2 * PB + (BX ? 1 : 0);
+  static_assert(HA % 8 == 0 && (HB % 8 == 0 || HB % 8 == 4), "pieces of a k-half over 8 waves (+ one wave group)");
   const int ntiles = tiles_1 * tiles_2;
   const int nunits = ntiles * nsplits;
   const int unit = unit_of_block(blockIdx.x, (nunits + 7) >> 3);
@@ -514,63 +553,75 @@ __global__ __launch_bounds__(512, 2) void gemm_tn6_kernel(const TIn* __restrict_
   const int m_begin = split * m_per_split;
   const int m_end = (m_begin + m_per_split < Mred) ? m_begin + m_per_split : Mred;
   const int rows = m_end - m_begin;
-  const u32x4 da = pp_desc(A + (size_t)m_begin * lda, (uint32_t)((size_t)rows * lda * 2));
-  const u32x4 db = pp_desc(B + (size_t)m_begin * ldb, (uint32_t)((size_t)rows * ldb * 2));
+  const u32x4 da = pp_desc_sgpr(pp_desc(A + (size_t)m_begin * lda, (uint32_t)((size_t)rows * lda * 2)));
+  const u32x4 db = pp_desc_sgpr(pp_desc(B + (size_t)m_begin * ldb, (uint32_t)((size_t)rows * ldb * 2)));
   const uint32_t lds0 = (uint32_t)(size_t)((SGL_LDS char*)smem);
 
-  // DMA plan: unit u = 2*khalf + operand; wave w moves image rows 32*khalf + 4w + {0..3}, 2 rows (1 KiB) per
-  // instruction; slot s of row m holds source chunk s ^ (2*(m&3) + 8*((m>>3)&1)) (the image of the header comment)
-  const int dr2 = lane >> 5, dslot = lane & 31;
-  uint32_t voff[4][2], ldst[4][2];
+  // DMA plan: lane l of piece c of unit Hh writes image bytes 1024 c + 16 l of the k-half, i.e. slot s of token row
+  // 32 h + r, and fetches the chunk that the swizzle puts there
+  uint32_t voffA[2][PA], ldsA[2][PA], voffB[2][PB + 1], ldsB[2][PB + 1];
 #pragma unroll
-  for (int u = 0; u < 4; ++u)
+  for (int h = 0; h < 2; ++h) {
 #pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const int r0 = 32 * (u >> 1) + 4 * w + 2 * q;
-      const int row = r0 + dr2;
-      const int chunk = dslot ^ (2 * (row & 3) + 8 * ((row >> 3) & 1));
-      const bool isA = (u & 1) == 0;
-      const int col = (isA ? n1_0 : n2_0) + chunk * 8;
-      const int lim = isA ? N1 : N2;
-      const int ld = isA ? lda : ldb;
-      voff[u][q] = (col < lim) ? (uint32_t)(row * ld + col) * 2u : SGL_OOB;
-      ldst[u][q] = lds0 + (isA ? 0 : G::OPA) + (uint32_t)r0 * 512u;
+    for (int q = 0; q < PA; ++q) {
+      const int piece = PA * w + q, pos = 1024 * piece + 16 * lane;
+      const int row = 32 * h + pos / RA, chunk = ((pos % RA) >> 4) ^ tn_swz<RA>(row);
+      const int col = n1_0 + chunk * 8;
+      voffA[h][q] = (col < N1) ? (uint32_t)(row * lda + col) * 2u : SGL_OOB;
+      ldsA[h][q] = lds0 + (uint32_t)(h * 32 * RA + 1024 * piece);
     }
-  auto issue = [&](int u, int kt) {  // rows past the split's range are out of range for the descriptor -> zeros
+#pragma unroll
+    for (int q = 0; q < PB + 1; ++q) {
+      const int piece = (q < PB) ? PB * w + q : 8 * PB + (w & 3), pos = 1024 * piece + 16 * lane;
+      const int row = 32 * h + pos / RB, chunk = ((pos % RB) >> 4) ^ tn_swz<RB>(row);
+      const int col = n2_0 + chunk * 8;
+      voffB[h][q] = (col < N2) ? (uint32_t)(row * ldb + col) * 2u : SGL_OOB;
+      ldsB[h][q] = lds0 + (uint32_t)(G::OPA + h * 32 * RB + 1024 * piece);
+    }
+  }
+  auto issue = [&](int h, int kt) {  // rows past the split's range are out of range for the descriptor -> zeros
     const uint32_t r0 = (uint32_t)kt * T_BK;
     const uint32_t sb = (uint32_t)((kt & 1) * G::STAGE);
-    const bool isA = (u & 1) == 0;
-    const u32x4 d = isA ? da : db;
-    const uint32_t adv = r0 * (uint32_t)(isA ? lda : ldb) * 2u;
+    const uint32_t adva = r0 * (uint32_t)lda * 2u, advb = r0 * (uint32_t)ldb * 2u;
 #pragma unroll
-    for (int q = 0; q < 2; ++q) pp_dma16(d, ldst[u][q] + sb, voff[u][q] == SGL_OOB ? SGL_OOB : voff[u][q] + adv);
+    for (int q = 0; q < PA; ++q) pp_dma16(da, ldsA[h][q] + sb, voffA[h][q] == SGL_OOB ? SGL_OOB : voffA[h][q] + adva);
+#pragma unroll
+    for (int q = 0; q < PB; ++q) pp_dma16(db, ldsB[h][q] + sb, voffB[h][q] == SGL_OOB ? SGL_OOB : voffB[h][q] + advb);
+    if constexpr (BX) {
+      if (grp == h) pp_dma16(db, ldsB[h][PB] + sb, voffB[h][PB] == SGL_OOB ? SGL_OOB : voffB[h][PB] + advb);
+    }
   };
 
+  // fragment block i (16 columns = 32 B) of this wave: token row 8 fg + fq (and + 4), 8 B at column block + 4 fp
   const int fg = lane >> 4, fq = (lane >> 2) & 3, fp = lane & 3;
-  const uint32_t swz = (uint32_t)(32 * fq + 128 * (fg & 1));
-  const uint32_t frow = (uint32_t)((8 * fg + fq) * 512);
-  const uint32_t fa_col = ((uint32_t)(wr * 256 + 8 * fp)) ^ swz;
-  const uint32_t fb_col = ((uint32_t)(wc * 128 + 8 * fp)) ^ swz;
+  const int fm = 8 * fg + fq;
+  uint32_t fa_off[MI], fb_off[MJ];
+#pragma unroll
+  for (int i = 0; i < MI; ++i)
+    fa_off[i] = (uint32_t)(fm * RA) + ((uint32_t)(wr * G::WM * 2 + i * 32 + 8 * fp) ^ (uint32_t)(16 * tn_swz<RA>(fm)));
+#pragma unroll
+  for (int j = 0; j < MJ; ++j)
+    fb_off[j] = (uint32_t)(G::OPA + fm * RB) + ((uint32_t)(wc * G::WN * 2 + j * 32 + 8 * fp) ^ (uint32_t)(16 * tn_swz<RB>(fm)));
   const bool active = (n2_0 + wc * G::WN < N2) && (n1_0 + wr * G::WM < N1);
 
-  f32x4 acc[G::MI][G::MJ];
+  f32x4 acc[MI][MJ];
 #pragma unroll
-  for (int i = 0; i < 8; ++i)
+  for (int i = 0; i < MI; ++i)
 #pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < MJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   const int nk = (rows + T_BK - 1) / T_BK;
-  issue(0, 0); issue(1, 0); issue(2, 0); issue(3, 0);
-  issue(0, 1); issue(1, 1);
-  pp_end_read<8>();                  // U0(0), U1(0) of every wave have landed
+  issue(0, 0); issue(1, 0);
+  issue(0, 1);
+  pp_end_read<NI>();                 // H0(0) of every wave has landed
   if (grp == 1) SGL_PP_END_MFMA();   // G1 runs one slot behind G0 from here on
 
-#define SGL_TR6(ptr) \
-  __builtin_shufflevector(lds_read_tr16<TIn>(ptr), lds_read_tr16<TIn>((ptr) + 4 * 512), 0, 1, 2, 3, 4, 5, 6, 7)
-  lo_x8<TIn> fa[8], fb[4];
+#define SGL_TR6(ptr, rowb) \
+  __builtin_shufflevector(lds_read_tr16<TIn>(ptr), lds_read_tr16<TIn>((ptr) + 4 * (rowb)), 0, 1, 2, 3, 4, 5, 6, 7)
+  lo_x8<TIn> fa[MI], fb[MJ];
 #ifdef SGL_TIMELINE
   // per-phase cycle sums of this wave over the main loop: [0] issue fragment reads + DMA, [1] wait for them (lgkmcnt/vmcnt),
-  // [2] barrier after the read slot, [3] 32 MFMAs, [4] barrier after the MFMA slot
+  // [2] barrier after the read slot, [3] the slot's MFMAs, [4] barrier after the MFMA slot
   unsigned long long tlp[5] = {0, 0, 0, 0, 0};
 #define SGL_TLP(i) do { const unsigned long long n_ = __builtin_readcyclecounter(); tlp[i] += n_ - tl_last; tl_last = n_; } while (0)
   unsigned long long tl_last = __builtin_readcyclecounter();
@@ -578,39 +629,39 @@ __global__ __launch_bounds__(512, 2) void gemm_tn6_kernel(const TIn* __restrict_
 #define SGL_TLP(i)
 #endif
   for (int kt = 0; kt < nk; ++kt) {
-    const char* base = smem + (kt & 1) * G::STAGE + frow;
+    const char* base = smem + (kt & 1) * G::STAGE;
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       if (active) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) fb[j] = SGL_TR6(base + G::OPA + h * 32 * 512 + (fb_col ^ (uint32_t)(j * 32)));
+        for (int j = 0; j < MJ; ++j) fb[j] = SGL_TR6(base + h * 32 * RB + fb_off[j], RB);
 #pragma unroll
-        for (int i = 0; i < 8; ++i) fa[i] = SGL_TR6(base + h * 32 * 512 + (fa_col ^ (uint32_t)(i * 32)));
+        for (int i = 0; i < MI; ++i) fa[i] = SGL_TR6(base + h * 32 * RA + fa_off[i], RA);
       }
-      if (h == 0) { issue(2, kt + 1); issue(3, kt + 1); }
-      else { issue(0, kt + 2); issue(1, kt + 2); }
+      if (h == 0) issue(1, kt + 1);
+      else issue(0, kt + 2);
 #ifdef SGL_TIMELINE
       SGL_TLP(0);
-      asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
+      asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" :: "n"(NI) : "memory");
       SGL_TLP(1);
       __builtin_amdgcn_sched_barrier(0);
       __builtin_amdgcn_s_barrier();
       __builtin_amdgcn_sched_barrier(0);
       SGL_TLP(2);
 #else
-      pp_end_read<8>();
+      pp_end_read<NI>();
 #endif
       if (active) {
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-        for (int i = 0; i < 8; ++i)
+        for (int i = 0; i < MI; ++i)
 #pragma unroll
-          for (int j = 0; j < 4; ++j)
+          for (int j = 0; j < MJ; ++j)
             acc[i][j] = mfma_16x16x32(fa[i], fb[j], acc[i][j]);
         __builtin_amdgcn_s_setprio(0);
       }
 #ifdef SGL_TIMELINE
-      asm volatile("s_nop 0" ::"v"(acc[0][0]), "v"(acc[7][3]));
+      asm volatile("s_nop 0" ::"v"(acc[0][0]), "v"(acc[MI - 1][MJ - 1]));
       SGL_TLP(3);
 #endif
       SGL_PP_END_MFMA();
@@ -705,27 +756,36 @@ hipError_t gemm_nt384(const void* A, int lda, const void* B, int ldb, int M, int
   return gemm_nt_pp<NtTile384, TIn>(A, lda, B, ldb, M, N, K, epi, out_dtype, p, s);
 }
 
-template <typename TIn>
-hipError_t gemm_tn256(const void* A, int lda, const void* B, int ldb, int Mred, int N1, int N2, int m_per, int splits,
-                      const EpiParams& p, hipStream_t s) {
-  using G = NtTile256;
-  const hipError_t e = set_max_dynamic_lds_once<&gemm_tn6_kernel<TIn>>(G::LDS);
+template <typename G, typename TIn>
+static hipError_t launch_tn_pp(const void* A, int lda, const void* B, int ldb, int Mred, int N1, int N2, int m_per,
+                               int splits, const EpiParams& p, hipStream_t s) {
+  const hipError_t e = set_max_dynamic_lds_once<&gemm_tn6_kernel<G, TIn>>(G::LDS);
   if (e != hipSuccess) return e;
   const int tiles_1 = (N1 + G::BM - 1) / G::BM, tiles_2 = (N2 + G::BN - 1) / G::BN;
   const int grid = ((tiles_1 * tiles_2 * splits + 7) / 8) * 8;
-  hipLaunchKernelGGL(gemm_tn6_kernel<TIn>, dim3(grid), dim3(512), G::LDS, s, (const TIn*)A, lda, (const TIn*)B, ldb, Mred,
-                     N1, N2, m_per, splits, tiles_1, tiles_2, p);
+  hipLaunchKernelGGL((gemm_tn6_kernel<G, TIn>), dim3(grid), dim3(512), G::LDS, s, (const TIn*)A, lda, (const TIn*)B, ldb,
+                     Mred, N1, N2, m_per, splits, tiles_1, tiles_2, p);
 #ifdef SGL_TIMELINE
   timeline_report(s, g_tn6_tl, [&](const unsigned long long* h) {
     for (int g = 0; g < 2; ++g)
       if (h[g * 6 + 5])
-        fprintf(stderr, "[timeline] gemm_tn6 N1=%d N2=%d Mred=%d splits=%d group %d, cycles per slot pair (read slot + MFMA slot): issue "
-                "reads+DMA %.0f, wait %.0f, barrier %.0f, 32 MFMAs %.0f, barrier %.0f\n", N1, N2, Mred, splits, g,
+        fprintf(stderr, "[timeline] gemm_tn6 %dx%d N1=%d N2=%d Mred=%d splits=%d group %d, cycles per slot pair (read slot + MFMA slot): "
+                "issue reads+DMA %.0f, wait %.0f, barrier %.0f, %d MFMAs %.0f, barrier %.0f\n", G::BM, G::BN, N1, N2, Mred, splits, g,
                 (double)h[g * 6 + 0] / h[g * 6 + 5], (double)h[g * 6 + 1] / h[g * 6 + 5], (double)h[g * 6 + 2] / h[g * 6 + 5],
-                (double)h[g * 6 + 3] / h[g * 6 + 5], (double)h[g * 6 + 4] / h[g * 6 + 5]);
+                G::MI * G::MJ, (double)h[g * 6 + 3] / h[g * 6 + 5], (double)h[g * 6 + 4] / h[g * 6 + 5]);
   });
 #endif
   return hipGetLastError();
+}
+template <typename TIn>
+hipError_t gemm_tn256(const void* A, int lda, const void* B, int ldb, int Mred, int N1, int N2, int m_per, int splits,
+                      const EpiParams& p, hipStream_t s) {
+  return launch_tn_pp<NtTile256, TIn>(A, lda, B, ldb, Mred, N1, N2, m_per, splits, p, s);
+}
+template <typename TIn>
+hipError_t gemm_tn384(const void* A, int lda, const void* B, int ldb, int Mred, int N1, int N2, int m_per, int splits,
+                      const EpiParams& p, hipStream_t s) {
+  return launch_tn_pp<NtTile384, TIn>(A, lda, B, ldb, Mred, N1, N2, m_per, splits, p, s);
 }
 
 #define SGL_INSTANTIATE_PP(TIn)                                                                                        \
@@ -734,6 +794,8 @@ hipError_t gemm_tn256(const void* A, int lda, const void* B, int ldb, int Mred, 
   template hipError_t gemm_nt384<TIn>(const void*, int, const void*, int, int, int, int, int, int, const EpiParams&,   \
                                       hipStream_t);                                                                    \
   template hipError_t gemm_tn256<TIn>(const void*, int, const void*, int, int, int, int, int, int, const EpiParams&,   \
+                                      hipStream_t);                                                                    \
+  template hipError_t gemm_tn384<TIn>(const void*, int, const void*, int, int, int, int, int, int, const EpiParams&,   \
                                       hipStream_t);
 SGL_INSTANTIATE_PP(bf16)
 SGL_INSTANTIATE_PP(f16)

@@ -178,8 +178,9 @@ hipError_t gemm_nt_bf16(const void* A, int lda, const void* B, int ldb, int M, i
 // out[r*ldo + c] (+)= sum_s ws[s*stride + r*N2 + c]   (fixed summation order)
 hipError_t reduce_splits(const float* ws, int splits, size_t stride, int N1, int N2, float* out, int ldo, int accumulate,
                          hipStream_t s);
-// split_ws (optional device scratch): when given and large enough, the splits of the 256x256-tile kernel write private
-// slabs and reduce_splits() sums them (bitwise reproducible); otherwise they add into `out` with fp32 atomics.
+// split_ws (optional device scratch): when given, the splits of the LDS-DMA kernels write private slabs and
+// reduce_splits() sums them (bitwise reproducible); the plan (tn_plan) is the best one whose slabs fit it.  Without
+// scratch, or with room for no second slab, the splits add into `out` with fp32 atomics.
 hipError_t gemm_tn_bf16(const void* A, int lda, const void* B, int ldb, int Mred, int N1, int N2, int splits,
                         const EpiParams& p, hipStream_t s, float* split_ws = nullptr, size_t split_ws_bytes = 0);
 // fp16-operand forms of the two (DT_F16): same kernels, tiles and dispatch; 16-bit outputs are fp16 (out_dtype DT_F16)
@@ -188,8 +189,8 @@ hipError_t gemm_nt_f16(const void* A, int lda, const void* B, int ldb, int M, in
 hipError_t gemm_tn_f16(const void* A, int lda, const void* B, int ldb, int Mred, int N1, int N2, int splits,
                        const EpiParams& p, hipStream_t s, float* split_ws = nullptr, size_t split_ws_bytes = 0);
 // The LDS-DMA kernels of gemm_bf16_v2.hip, which the four above send the shapes that fill the chip to; TIn = bf16 or f16
-// (instantiated there).  gemm_nt384 takes EPI_STORE and EPI_RES_F32 only (hipErrorInvalidValue otherwise); gemm_tn256
-// runs `splits` ranges of m_per tokens (EpiParams::split_stride / atomic say where a split's tile goes).
+// (instantiated there).  gemm_nt384 takes EPI_STORE and EPI_RES_F32 only (hipErrorInvalidValue otherwise); gemm_tn256 /
+// gemm_tn384 run `splits` ranges of m_per tokens (EpiParams::split_stride / atomic say where a split's tile goes).
 template <typename TIn>
 hipError_t gemm_nt256(const void* A, int lda, const void* B, int ldb, int M, int N, int K, int epi, int out_dtype,
                       const EpiParams& p, hipStream_t s);
@@ -199,6 +200,51 @@ hipError_t gemm_nt384(const void* A, int lda, const void* B, int ldb, int M, int
 template <typename TIn>
 hipError_t gemm_tn256(const void* A, int lda, const void* B, int ldb, int Mred, int N1, int N2, int m_per, int splits,
                       const EpiParams& p, hipStream_t s);
+template <typename TIn>
+hipError_t gemm_tn384(const void* A, int lda, const void* B, int ldb, int Mred, int N1, int N2, int m_per, int splits,
+                      const EpiParams& p, hipStream_t s);
+
+// Tile and split of a TN GEMM on the LDS-DMA kernels (N1, N2 >= 512, Mred >= 2048).  The launch is one round of at most
+// 256 workgroups, one per CU, so its time is the work of one workgroup: tile area x token rows per split.  Among the
+// 256 x 256 and 384 x 192 tiles and every split count with tiles x splits <= 256, at least 1024 rows per split and
+// (beyond one split) slabs of splits x N1 x N2 floats inside `ws_bytes`, the plan minimises that product; ties go to the
+// 256 x 256 tile and to fewer splits.  One split is always allowed, whatever the tile count.  `tile` = 256 / 384
+// considers that geometry only.
+struct TnPlan {
+  int tile, splits, m_per;   // m_per: rows per split, a multiple of 64; `splits` ranges of it cover Mred
+};
+constexpr TnPlan tn_plan(int Mred, int N1, int N2, size_t ws_bytes, int tile = 0) {
+  TnPlan best = {0, 0, 0};
+  long best_cost = 0;
+  for (int g = 0; g < 2; ++g) {
+    const int bm = g ? 384 : 256, bn = g ? 192 : 256, area8 = g ? 9 : 8;   // tile area in eighths of 256 x 256
+    if (tile != 0 && tile != bm) continue;
+    const int tiles = ((N1 + bm - 1) / bm) * ((N2 + bn - 1) / bn);
+    for (int sp = 1; sp == 1 || (tiles * sp <= 256 && Mred / sp >= 1024); ++sp) {
+      if (sp > 1 && (size_t)sp * N1 * N2 * sizeof(float) > ws_bytes) break;
+      const int m_per = ((Mred + sp - 1) / sp + 63) / 64 * 64;
+      const long cost = (long)area8 * m_per;
+      if (best.tile == 0 || cost < best_cost) {
+        best = {bm, (Mred + m_per - 1) / m_per, m_per};
+        best_cost = cost;
+      }
+    }
+  }
+  return best;
+}
+constexpr bool tn_plan_is(int Mred, int N1, int N2, size_t ws_bytes, int tile, int splits) {
+  const TnPlan p = tn_plan(Mred, N1, N2, ws_bytes);
+  return (tile == 0 || p.tile == tile) && p.splits == splits;
+}
+// the bench batch's four dW shapes with a scratch that limits no plan (kTnSlabBytes), and the launches whose digests
+// tests/test_gemm_pp_digests_gpu.py records (their split boundaries must not move)
+constexpr size_t kTnSlabBytes = (size_t)256 * 384 * 192 * 4;   // tiles x splits <= 256 tiles of at most 384 x 192 floats
+static_assert(tn_plan_is(93312, 1152, 1152, kTnSlabBytes, 384, 14), "out_proj dW");
+static_assert(tn_plan_is(93312, 3456, 1152, kTnSlabBytes, 384, 4), "QKV dW");
+static_assert(tn_plan_is(93312, 4304, 1152, kTnSlabBytes, 256, 3), "fc1 dW");
+static_assert(tn_plan_is(93312, 1152, 4304, kTnSlabBytes, 256, 3), "fc2 dW");
+static_assert(tn_plan_is(4133, 520, 1152, kTnSlabBytes, 0, 4) && tn_plan(4133, 520, 1152, kTnSlabBytes).m_per == 1088, "digest case");
+static_assert(tn_plan_is(2048, 512, 512, kTnSlabBytes, 256, 2) && tn_plan(2048, 512, 512, kTnSlabBytes).m_per == 1024, "digest case");
 
 // ---- attention.hip -------------------------------------------------------------------------------------
 // q,k,v: ld_qkv > 0: token-major [B*N][ld_qkv] column blocks (head h of row r at r*ld_qkv + h*dh; the QKV projection's
