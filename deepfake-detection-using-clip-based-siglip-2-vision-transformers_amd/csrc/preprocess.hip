@@ -16,6 +16,7 @@
 //      preprocess_kernel, aug_* + preprocess_aug_kernel, preprocess_views_kernel   the three forward transforms
 //      AxisTables + views_bwd_tables_kernel + bwd_filter_sum<NC>          the tables and the sum of both adjoints
 //      preprocess_bwd_kernel, preprocess_views_bwd_kernel                 the adjoints (float source, NCHW output)
+//      aug_hue_bwd, aug_colour_bwd, aug_bwd_*_kernel                      the adjoint of the augmenting transform
 //      check_args, views_check, dispatch_src_out, extern "C"              refusals, type dispatch, the entry points
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -235,26 +236,31 @@ __device__ __forceinline__ void aug_geo(const void* src, int b, int oy, int ox, 
   }
 }
 
+// one operator of the colour chain on rgb, in place: the one place its arithmetic is written (the adjoint recomputes with it)
+__device__ __forceinline__ void aug_colour_op(float* rgb, const AugSample& a, int op, float grey_mean) {
+  if (op == 0) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) rgb[c] = aug_clamp01(rgb[c] * a.brightness);
+  } else if (op == 1) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) rgb[c] = aug_clamp01((rgb[c] - grey_mean) * a.contrast + grey_mean);
+  } else if (op == 2) {
+    const float g = aug_grey(rgb);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) rgb[c] = aug_clamp01((rgb[c] - g) * a.saturation + g);
+  } else {
+    aug_hue(rgb, a.hue);
+  }
+}
+
 // colour chain on rgb; stop_before_contrast: evaluate only the operators in front of the contrast step (mean pre-pass)
 __device__ __forceinline__ void aug_colour(float* rgb, const AugSample& a, float grey_mean, bool stop_before_contrast) {
   if (a.order[0] < 0) return;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const int op = a.order[k];
-    if (op == 0) {
-#pragma unroll
-      for (int c = 0; c < 3; ++c) rgb[c] = aug_clamp01(rgb[c] * a.brightness);
-    } else if (op == 1) {
-      if (stop_before_contrast) return;
-#pragma unroll
-      for (int c = 0; c < 3; ++c) rgb[c] = aug_clamp01((rgb[c] - grey_mean) * a.contrast + grey_mean);
-    } else if (op == 2) {
-      const float g = aug_grey(rgb);
-#pragma unroll
-      for (int c = 0; c < 3; ++c) rgb[c] = aug_clamp01((rgb[c] - g) * a.saturation + g);
-    } else {
-      aug_hue(rgb, a.hue);
-    }
+    if (op == 1 && stop_before_contrast) return;
+    aug_colour_op(rgb, a, op, grey_mean);
   }
 }
 
@@ -603,6 +609,300 @@ __global__ __launch_bounds__(256) void preprocess_views_bwd_kernel(const float* 
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Adjoint of preprocess_aug_kernel<., float>(patch_major = 0) with respect to the source: the one non-linear transform
+// of this file (clamps, a per-image mean, RGB <-> HSV).  Nothing of the forward is saved: a thread owns one output
+// pixel, recomputes T = rotate(flip(resize(src))) (aug_geo) and the colour chain with the forward's own expressions,
+// keeps the input of every operator in registers and walks the chain back.  Where the forward is not differentiable
+// the rules are those of torch.autograd on oracle/preprocess_oracle.py: a clamp passes the gradient at its bounds
+// (inclusive), max / min give it to the lowest channel index among ties, a where() differentiates the selected branch,
+// floor / fmod / comparisons / the sector index contribute nothing.
+//   aug_bwd_grey_kernel    the grey level in front of the contrast step, one thread per pixel: aug_mean_kernel's terms,
+//                          stored in the not yet used d_T
+//   aug_bwd_grey_mean_kernel   aug_mean_kernel's own sum over the stored terms, one block per image: the same additions in
+//                          the same order, so m[b] has the forward's bits (tests/test_aug_bwd_gpu.py) and the recomputed
+//                          chain clamps where the forward did, in 0.3 ms where the forward's pre-pass, whose one block
+//                          per image also evaluates the terms, takes 7 ms (B = 128, 224 x 224 -> 384)
+//   aug_bwd_colour<MEAN>   pass A: reverse the operators behind the contrast step, sum ghat = g [0 <= u <= 1] over the
+//                          block's pixels and channels, one partial per block (wave_sum, then the four waves in order)
+//   aug_bwd_fold_kernel    the partials of image b in a fixed order -> (sum ghat) / S^2, the contrast mean term
+//   aug_bwd_colour<FULL>   pass B: the full reverse -> d_T; an image that is not rotated is stored straight into d_R
+//                          (mirrored back when flipped: a permutation, one store per element)
+//   aug_bwd_rotate_kernel  rotated images only, the transpose of the bilinear taps as a gather: an intermediate pixel u
+//                          receives from the outputs whose sample point lies within one pixel of it, which are among
+//                          the 5 x 5 outputs round M^T (u - ctr) + ctr (a rigid rotation needs 3 x 3: the sample points
+//                          of the receivers lie within sqrt 2 of u).  Each candidate is tested with the forward's own
+//                          floor and weights; taps outside the image never had a weight.  Order: oy, then ox
+//   preprocess_bwd_kernel  d_R -> d_src, the resize adjoint above (tables, copy shortcut, the one multiply by 1 / std)
+// No atomics, every sum in a fixed order, d_src written by one plain store per element.
+// ---------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool aug_in01(float u) { return u >= 0.f && u <= 1.f; }
+
+// the vector-Jacobian product of aug_hue at c: g (cotangent of the result) -> cotangent of c, in place
+__device__ __forceinline__ void aug_hue_bwd(const float* c, float shift, float* g) {
+  const float r = c[0], gr = c[1], b = c[2];
+  const float maxc = fmaxf(r, fmaxf(gr, b)), minc = fminf(r, fminf(gr, b));
+  const bool eq = maxc == minc;
+  const float cr = maxc - minc;
+  const float d1 = eq ? 1.0f : maxc;
+  const float sat = cr / d1;
+  const float crd = eq ? 1.0f : cr;
+  const float rc = (maxc - r) / crd, gc = (maxc - gr) / crd, bc = (maxc - b) / crd;
+  const bool mr = maxc == r, mg = maxc == gr && maxc != r, mb = maxc != gr && maxc != r;
+  const float hr = mr ? (bc - gc) : 0.f;
+  const float hg = mg ? (2.0f + rc - bc) : 0.f;
+  const float hb = mb ? (4.0f + gc - rc) : 0.f;
+  float h = (hr + hg + hb) / 6.0f + 1.0f;
+  h = h - floorf(h);
+  h = h + shift;
+  h = h - floorf(h);
+  const float v = maxc;
+  const float h6 = h * 6.0f;
+  const float fi = floorf(h6);
+  const float f = h6 - fi;
+  const int i = (int)fi % 6;
+  const float up = v * (1.0f - sat), uq = v * (1.0f - f * sat), ut = v * (1.0f - (1.0f - f) * sat);
+  float gv = 0.f, gp = 0.f, gq = 0.f, gt = 0.f;
+  switch (i) {
+    case 0: gv = g[0]; gt = g[1]; gp = g[2]; break;
+    case 1: gq = g[0]; gv = g[1]; gp = g[2]; break;
+    case 2: gp = g[0]; gv = g[1]; gt = g[2]; break;
+    case 3: gp = g[0]; gq = g[1]; gv = g[2]; break;
+    case 4: gt = g[0]; gp = g[1]; gv = g[2]; break;
+    default: gv = g[0]; gp = g[1]; gq = g[2]; break;
+  }
+  gp = aug_in01(up) ? gp : 0.f;
+  gq = aug_in01(uq) ? gq : 0.f;
+  gt = aug_in01(ut) ? gt : 0.f;
+  float g_max = gv + gp * (1.0f - sat) + gq * (1.0f - f * sat) + gt * (1.0f - (1.0f - f) * sat);
+  const float g_sat = -v * (gp + gq * f + gt * (1.0f - f));
+  const float g_h = v * sat * (gt - gq);                 // f = 6 h - i and h = (hr + hg + hb) / 6 + ...: d f / d (hr + hg + hb) = 1
+  float g_cr = g_sat / d1;
+  if (!eq) g_max -= g_sat * sat / d1;
+  float g_rc = 0.f, g_gc = 0.f, g_bc = 0.f;
+  if (mr) g_bc += g_h, g_gc -= g_h;
+  if (mg) g_rc += g_h, g_bc -= g_h;
+  if (mb) g_gc += g_h, g_rc -= g_h;
+  const float icrd = 1.0f / crd;
+  g_max += (g_rc + g_gc + g_bc) * icrd;
+  if (!eq) g_cr -= (g_rc * rc + g_gc * gc + g_bc * bc) * icrd;
+  g_max += g_cr;
+  const float g_min = -g_cr;
+  const int imax = mr ? 0 : (maxc == gr ? 1 : 2);
+  const int imin = minc == r ? 0 : (minc == gr ? 1 : 2);
+  g[0] = -g_rc * icrd + (imax == 0 ? g_max : 0.f) + (imin == 0 ? g_min : 0.f);
+  g[1] = -g_gc * icrd + (imax == 1 ? g_max : 0.f) + (imin == 1 ? g_min : 0.f);
+  g[2] = -g_bc * icrd + (imax == 2 ? g_max : 0.f) + (imin == 2 ? g_min : 0.f);
+}
+
+// The colour chain forward from rgb = T (aug_colour_op, keeping every operator's input), then its reverse on g.  to_contrast: stop at the
+// contrast step and return the sum over the channels of ghat (0 when the record has none); else g becomes the cotangent
+// of T, with mean_term = (sum over the image of ghat) / S^2
+__device__ __forceinline__ float aug_colour_bwd(const float* rgb, const AugSample& a, float grey_mean, float mean_term,
+                                                bool to_contrast, float* g) {
+  if (a.order[0] < 0) return 0.f;
+  float x[4][3];
+  float c[3] = {rgb[0], rgb[1], rgb[2]};
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) x[k][ch] = c[ch];
+    aug_colour_op(c, a, a.order[k], grey_mean);
+  }
+  const float w[3] = {0.299f, 0.587f, 0.114f};
+#pragma unroll
+  for (int k = 3; k >= 0; --k) {
+    const int op = a.order[k];
+    const float* xi = x[k];
+    if (op == 0) {
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) g[ch] = aug_in01(xi[ch] * a.brightness) ? a.brightness * g[ch] : 0.f;
+    } else if (op == 1) {
+      float gh[3];
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) gh[ch] = aug_in01((xi[ch] - grey_mean) * a.contrast + grey_mean) ? g[ch] : 0.f;
+      if (to_contrast) return (gh[0] + gh[1]) + gh[2];
+      const float m = (1.0f - a.contrast) * mean_term;
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) g[ch] = a.contrast * gh[ch] + m * w[ch];
+    } else if (op == 2) {
+      const float gy = aug_grey(xi);
+      float gh[3];
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) gh[ch] = aug_in01((xi[ch] - gy) * a.saturation + gy) ? g[ch] : 0.f;
+      const float s = (1.0f - a.saturation) * ((gh[0] + gh[1]) + gh[2]);
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) g[ch] = a.saturation * gh[ch] + s * w[ch];
+    } else {
+      aug_hue_bwd(xi, a.hue, g);
+    }
+  }
+  return 0.f;
+}
+
+__device__ __forceinline__ bool aug_has_contrast(const AugSample& a) {
+  bool need = false;
+  if (a.order[0] >= 0)
+    for (int k = 0; k < 4; ++k) need = need || a.order[k] == 1;
+  return need;
+}
+__device__ __forceinline__ bool aug_rotates(const AugSample& a) { return !(a.sin_a == 0.f && a.cos_a == 1.f); }
+
+// grey[b][p]: aug_mean_kernel's term of pixel p, for the images with a contrast step (the others' planes stay unwritten
+// and unread).  Grid as aug_bwd_colour_kernel
+template <bool SRC_U8>
+__global__ __launch_bounds__(256) void aug_bwd_grey_kernel(const void* __restrict__ src, int Hs, int Ws, int S, int nblk,
+                                                           const AugSample* __restrict__ aug, float* __restrict__ grey) {
+  const int b = (int)(blockIdx.x / (unsigned)nblk);
+  const size_t plane = (size_t)S * S;
+  const size_t p = (size_t)(blockIdx.x % (unsigned)nblk) * 256 + threadIdx.x;
+  const AugSample a = aug[b];
+  if (!aug_has_contrast(a) || p >= plane) return;
+  const float sy = (float)Hs / (float)S, sx = (float)Ws / (float)S;
+  float rgb[3];
+  aug_geo<SRC_U8>(src, b, (int)(p / S), (int)(p % S), Hs, Ws, S, sy, sx, a, rgb);
+  aug_colour(rgb, a, 0.f, true);
+  grey[(size_t)b * plane + p] = aug_grey(rgb);
+}
+
+// aug_mean_kernel with its terms read back: thread t adds pixels t, t + 256, ... in order, then the same tree
+__global__ __launch_bounds__(256) void aug_bwd_grey_mean_kernel(const float* __restrict__ grey, int S,
+                                                                const AugSample* __restrict__ aug,
+                                                                float* __restrict__ grey_mean) {
+  __shared__ float red[4];
+  const int b = blockIdx.x;
+  if (!aug_has_contrast(aug[b])) {
+    if (threadIdx.x == 0) grey_mean[b] = 0.f;
+    return;
+  }
+  const size_t plane = (size_t)S * S;
+  const float* g = grey + (size_t)b * plane;
+  float acc = 0.f;
+  for (size_t i = threadIdx.x; i < plane; i += 256) acc += g[i];
+  acc = wave_sum(acc);
+  if (lane_id() == 0) red[wave_id()] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) grey_mean[b] = ((red[0] + red[1]) + (red[2] + red[3])) / (float)(S * S);
+}
+
+// Passes A (MEAN_PASS) and B.  grid: nblk = ceil(S^2 / 256) blocks per image, image b = blockIdx.x / nblk: a block never
+// straddles two images.  A: partial[blockIdx.x] = the block's sum of ghat.  B: d_T (rotated images) or d_R (the others)
+template <bool SRC_U8, bool MEAN_PASS>
+__global__ __launch_bounds__(256) void aug_bwd_colour_kernel(const void* __restrict__ src,
+                                                             const float* __restrict__ d_out, int Hs, int Ws, int S,
+                                                             int nblk, const AugSample* __restrict__ aug,
+                                                             const float* __restrict__ grey_mean,
+                                                             const float* __restrict__ mean_term,
+                                                             float* __restrict__ partial, float* __restrict__ d_T,
+                                                             float* __restrict__ d_R) {
+  __shared__ float red[4];
+  const int b = (int)(blockIdx.x / (unsigned)nblk);
+  const size_t plane = (size_t)S * S;
+  const size_t p = (size_t)(blockIdx.x % (unsigned)nblk) * 256 + threadIdx.x;
+  const AugSample a = aug[b];
+  if (MEAN_PASS && !aug_has_contrast(a)) {               // block-uniform
+    if (threadIdx.x == 0) partial[blockIdx.x] = 0.f;
+    return;
+  }
+  const float sy = (float)Hs / (float)S, sx = (float)Ws / (float)S;
+  float acc = 0.f;
+  if (p < plane) {
+    const int oy = (int)(p / S), ox = (int)(p % S);
+    const float* go = d_out + (size_t)b * 3 * plane + p;
+    float g[3] = {go[0], go[plane], go[2 * plane]};
+    if (a.order[0] >= 0) {                               // the chain is the identity otherwise: nothing to recompute
+      float rgb[3];
+      aug_geo<SRC_U8>(src, b, oy, ox, Hs, Ws, S, sy, sx, a, rgb);
+      acc = aug_colour_bwd(rgb, a, grey_mean[b], MEAN_PASS ? 0.f : mean_term[b], MEAN_PASS, g);
+    }
+    if (!MEAN_PASS) {
+      const bool rot = aug_rotates(a);
+      const int xr = (!rot && a.flip != 0.f) ? S - 1 - ox : ox;
+      float* dst = (rot ? d_T : d_R) + (size_t)b * 3 * plane + (size_t)oy * S + xr;
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) dst[ch * plane] = g[ch];
+    }
+  }
+  if (MEAN_PASS) {
+    acc = wave_sum(acc);
+    if (lane_id() == 0) red[wave_id()] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+  }
+}
+
+// one block per image: mean_term[b] = (partial[b * nblk + 0 .. nblk) summed: thread t takes t, t + 256, ..., then the tree) / S^2
+__global__ __launch_bounds__(256) void aug_bwd_fold_kernel(const float* __restrict__ partial, int nblk, int S,
+                                                           float* __restrict__ mean_term) {
+  __shared__ float red[4];
+  const int b = blockIdx.x;
+  float acc = 0.f;
+  for (int i = threadIdx.x; i < nblk; i += 256) acc += partial[(size_t)b * nblk + i];
+  acc = wave_sum(acc);
+  if (lane_id() == 0) red[wave_id()] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) mean_term[b] = ((red[0] + red[1]) + (red[2] + red[3])) / ((float)S * (float)S);
+}
+
+// d_R[b] = flip^T rotate^T d_T[b] for the rotated images; the blocks of the others leave at once (pass B stored their d_R)
+__global__ __launch_bounds__(256) void aug_bwd_rotate_kernel(const float* __restrict__ d_T, float* __restrict__ d_R, int S,
+                                                             int nblk, const AugSample* __restrict__ aug) {
+  const int b = (int)(blockIdx.x / (unsigned)nblk);
+  const size_t plane = (size_t)S * S;
+  const size_t p = (size_t)(blockIdx.x % (unsigned)nblk) * 256 + threadIdx.x;
+  const AugSample a = aug[b];
+  if (!aug_rotates(a) || p >= plane) return;
+  const int uy = (int)(p / S), ux = (int)(p % S);
+  const float ctr = 0.5f * (float)(S - 1);
+  // the output whose sample point is u, up to rounding: o = M^T (u - ctr) + ctr
+  const float du = (float)ux - ctr, dv = (float)uy - ctr;
+  const float lim = (float)S + 4.0f;                      // keeps the window's integers small whatever the record holds
+  const int cx = (int)rintf(fminf(fmaxf(a.cos_a * du + a.sin_a * dv + ctr, -4.0f), lim));
+  const int cy = (int)rintf(fminf(fmaxf(a.cos_a * dv - a.sin_a * du + ctr, -4.0f), lim));
+  const float* gT = d_T + (size_t)b * 3 * plane;
+  float acc[3] = {0.f, 0.f, 0.f};
+  for (int oy = cy - 2; oy <= cy + 2; ++oy) {
+    if (oy < 0 || oy >= S) continue;
+    for (int ox = cx - 2; ox <= cx + 2; ++ox) {
+      if (ox < 0 || ox >= S) continue;
+      const float dx = (float)ox - ctr, dy = (float)oy - ctr;          // aug_geo's expressions from here on
+      const float xs = a.cos_a * dx - a.sin_a * dy + ctr;
+      const float ys = a.sin_a * dx + a.cos_a * dy + ctr;
+      const float x0f = floorf(xs), y0f = floorf(ys);
+      const int jx = ux - (int)x0f, jy = uy - (int)y0f;
+      if (jx < 0 || jx > 1 || jy < 0 || jy > 1) continue;
+      const float fx = xs - x0f, fy = ys - y0f;
+      const float w = (jy ? fy : 1.0f - fy) * (jx ? fx : 1.0f - fx);
+      if (w == 0.f) continue;
+      const float* gp = gT + (size_t)oy * S + ox;
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) acc[ch] += w * gp[ch * plane];
+    }
+  }
+  float* dst = d_R + (size_t)b * 3 * plane + (size_t)uy * S + (a.flip != 0.f ? S - 1 - ux : ux);
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) dst[ch * plane] = acc[ch];
+}
+
+// scratch of sgl_op_preprocess_aug_bwd: [resize tables][grey_mean B][mean_term B][partial B nblk][d_T B 3 S S][d_R B 3 S S]
+struct AugBwdScratch {
+  size_t tables, grey_mean, mean_term, partial, d_T, d_R, bytes;
+  int nblk;
+};
+static AugBwdScratch aug_bwd_scratch(int B, int Hs, int Ws, int S) {
+  AugBwdScratch s;
+  const size_t plane = (size_t)S * S, img = (size_t)B * 3 * plane * sizeof(float);
+  s.nblk = (int)((plane + 255) / 256);
+  s.tables = 0;
+  s.grey_mean = view_table_bytes(Hs, Ws, S);
+  s.mean_term = s.grey_mean + (size_t)B * sizeof(float);
+  s.partial = s.mean_term + (size_t)B * sizeof(float);
+  s.d_T = s.partial + (size_t)B * s.nblk * sizeof(float);
+  s.d_R = s.d_T + img;
+  s.bytes = s.d_R + img;
+  return s;
+}
+
 // the record checks sgl_op_preprocess_views and its adjoint share: SGL_OK, SGL_ERR_BAD_SHAPE or SGL_ERR_UNSUPPORTED
 static int views_check(const sgl_view* rec, int V, int B, int Hs, int Ws, int S) {
   for (int v = 0; v < V; ++v) {
@@ -809,6 +1109,58 @@ int sgl_op_preprocess_aug(const void* src, int src_is_u8_nhwc, int B, int Hs, in
     hipLaunchKernelGGL((sgl::preprocess_aug_kernel<decltype(u8)::value, T>), dim3(blocks), dim3(256), 0, s, src, dst, B, Hs,
                        Ws, L, mean, inv_std, tab, grey_mean);
   });
+  return hipGetLastError() == hipSuccess ? SGL_OK : SGL_ERR_HIP;
+}
+
+size_t sgl_op_preprocess_aug_bwd_scratch_bytes(int B, int Hs, int Ws, int S) {
+  if (B <= 0 || Hs <= 0 || Ws <= 0 || S <= 0) return 0;
+  return sgl::aug_bwd_scratch(B, Hs, Ws, S).bytes;
+}
+
+int sgl_op_preprocess_aug_bwd(const float* d_out, const void* src, int src_is_u8_nhwc, int B, int Hs, int Ws, int S,
+                              float std, const sgl_aug_sample* aug, float* d_src, void* scratch, size_t scratch_bytes,
+                              sgl_stream stream) {
+  if (!d_out || !src || !aug || !d_src || !scratch) return SGL_ERR_NULL;
+  if (const int st = sgl::check_args(B, Hs, Ws, S, std, 0, 0, 0, SGL_DTYPE_F32, true)) return st;   // the forward's limit
+  if ((long long)2 * S + Hs + Ws > 0x7fffffffLL) return SGL_ERR_BAD_SHAPE;   // the tables' entries in an int
+  const sgl::AugBwdScratch L = sgl::aug_bwd_scratch(B, Hs, Ws, S);
+  // B nblk is one block index; S * S stays an int, as in the forward's pre-pass
+  if ((unsigned long long)B * (unsigned long long)L.nblk > 0x7fffffffULL || S > 46340) return SGL_ERR_BAD_SHAPE;
+  if (scratch_bytes < L.bytes) return SGL_ERR_WORKSPACE;
+  hipStream_t s = (hipStream_t)stream;
+  char* base = reinterpret_cast<char*>(scratch);
+  float* grey_mean = reinterpret_cast<float*>(base + L.grey_mean);
+  float* mean_term = reinterpret_cast<float*>(base + L.mean_term);
+  float* partial = reinterpret_cast<float*>(base + L.partial);
+  float* d_T = reinterpret_cast<float*>(base + L.d_T);
+  float* d_R = reinterpret_cast<float*>(base + L.d_R);
+  const sgl::AugSample* tab = reinterpret_cast<const sgl::AugSample*>(aug);
+  const dim3 grid((unsigned)((size_t)B * L.nblk)), block(256);
+  auto passes = [&](auto u8) {
+    constexpr bool U8 = decltype(u8)::value;
+    hipLaunchKernelGGL((sgl::aug_bwd_grey_kernel<U8>), grid, block, 0, s, src, Hs, Ws, S, L.nblk, tab, d_T);   // d_T is free
+    hipLaunchKernelGGL(sgl::aug_bwd_grey_mean_kernel, dim3((unsigned)B), block, 0, s, d_T, S, tab, grey_mean);   // until pass B
+    hipLaunchKernelGGL((sgl::aug_bwd_colour_kernel<U8, true>), grid, block, 0, s, src, d_out, Hs, Ws, S, L.nblk, tab,
+                       grey_mean, mean_term, partial, d_T, d_R);
+    hipLaunchKernelGGL(sgl::aug_bwd_fold_kernel, dim3((unsigned)B), block, 0, s, partial, L.nblk, S, mean_term);
+    hipLaunchKernelGGL((sgl::aug_bwd_colour_kernel<U8, false>), grid, block, 0, s, src, d_out, Hs, Ws, S, L.nblk, tab,
+                       grey_mean, mean_term, partial, d_T, d_R);
+  };
+  if (src_is_u8_nhwc) passes(std::true_type{});
+  else passes(std::false_type{});
+  hipLaunchKernelGGL(sgl::aug_bwd_rotate_kernel, grid, block, 0, s, d_T, d_R, S, L.nblk, tab);
+  sgl::AxisTables t = {};
+  if (sgl::view_table_bytes(Hs, Ws, S)) {                // as sgl_op_preprocess_bwd: the full frame's tables at offset 0
+    t = sgl::axis_tables(base + L.tables, Hs, S);
+    sgl::ViewChunk chunk = {};
+    chunk.v[0] = sgl_view{0, 0, 0, Ws, Hs, 0, 0, 0};
+    const int entries = 2 * S + Hs + Ws;
+    hipLaunchKernelGGL(sgl::views_bwd_tables_kernel, dim3((unsigned)((entries + 255) / 256), 1u), block, 0, s, base, chunk,
+                       sgl::ViewTableChunk{}, S);
+  }
+  const int blocks = sgl::capped_blocks((size_t)B * 3 * Hs * Ws, 2048);
+  hipLaunchKernelGGL(sgl::preprocess_bwd_kernel, dim3(blocks), block, 0, s, d_R, d_src, B, Hs, Ws, S, 1.0f / std,
+                     (const int*)nullptr, 1.0f, t);
   return hipGetLastError() == hipSuccess ? SGL_OK : SGL_ERR_HIP;
 }
 

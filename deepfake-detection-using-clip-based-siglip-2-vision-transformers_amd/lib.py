@@ -182,6 +182,8 @@ def load():
     _sig(lib, "sgl_op_preprocess_bwd_scratch_bytes", sz, [i, i, i, i])
     _sig(lib, "sgl_op_preprocess_bwd", i, [_fp, i, i, i, i, f, _fp, f, _fp, _fp, sz, _fp])
     _sig(lib, "sgl_op_preprocess_aug", i, [_fp, i, i, i, i, _fp, i, i, i, i, i, f, f, _fp, _fp, _fp])
+    _sig(lib, "sgl_op_preprocess_aug_bwd_scratch_bytes", sz, [i, i, i, i])
+    _sig(lib, "sgl_op_preprocess_aug_bwd", i, [_fp, _fp, i, i, i, i, i, f, _fp, _fp, _fp, sz, _fp])
     _sig(lib, "sgl_op_preprocess_views_scratch_bytes", sz, [i, i])
     _sig(lib, "sgl_op_preprocess_views", i, [_fp, i, i, i, i, C.POINTER(SglView), i, _fp, i, i, i, i, i, f, f, _fp, sz,
                                              _fp])

@@ -15,6 +15,11 @@ reference's CPU transform ``Resize + ToTensor`` produces).  Resampling is torch'
 reference's CPU transform, cifake…:1795-1797); kornia itself is not installed here, so equality with ``K.Resize`` is
 "parity unpinned".  CUDA only: there is no CPU path.
 
+Training side (hidf_video_classifier.py ``--data_augmentation``): ``augment_resize_normalize`` / ``GpuTransform(...,
+data_augmentation=True)`` insert flip, rotation and colour jitter between resize and normalise; with ``differentiable=True``
+they are differentiable with respect to a float source (one ``sgl_op_preprocess_aug_bwd``, which recomputes the colour
+chain per pixel and walks it back; ``augment_resize_normalize_backward`` is the VJP as a function).
+
 Inference side (appv3.py ``detect_core``): ``View`` / ``detect_views`` + ``views_to_patch_operand`` build the app's 9 crops, its
 90-degree rotated view and its 4 x 4 grid cells, 42 encoder rows per image, in one pass of ``sgl_op_preprocess_views``.
 ``views_resize_normalize(differentiable=True)`` is differentiable with respect to a float source (one
@@ -126,8 +131,8 @@ def _wants_grad(images) -> bool:
 
 
 def _refuse_grad(images, what: str, views: bool = False) -> None:
-    """Everything but ``resize_normalize`` and ``views_resize_normalize(differentiable=True)`` has no backward: refuse
-    rather than return a silently missing gradient.  ``views``: name the differentiable route of the view transforms."""
+    """Everything but ``resize_normalize`` and the ``differentiable=True`` routes of ``views_resize_normalize`` and
+    ``augment_resize_normalize`` has no backward: refuse rather than return a silently missing gradient.  ``views``: name the differentiable route of the view transforms."""
     if images.is_cuda and _wants_grad(images):
         if views:
             raise RuntimeError(
@@ -136,9 +141,11 @@ def _refuse_grad(images, what: str, views: bool = False) -> None:
                 "preprocess.views_resize_normalize(images, views, size, differentiable=True) and pass its result to the "
                 "encoder as pixel_values=, or detach the images / run under torch.no_grad()")
         raise RuntimeError(
-            f"{what} is not differentiable with respect to its source images (the colour operators and the patch-operand "
-            "layout have no backward); use preprocess.resize_normalize(images, size), which is, and pass its result to "
-            "the encoder as pixel_values=, or detach the images / run under torch.no_grad()")
+            f"{what} is not differentiable with respect to its source images as called (the patch-operand layout has no "
+            "backward, and the augmenting transform is differentiable only on request); use "
+            "preprocess.resize_normalize(images, size), which is, or preprocess.augment_resize_normalize(images, size, "
+            "params, differentiable=True) / GpuTransform(..., differentiable=True), and pass the result to the encoder as "
+            "pixel_values=, or detach the images / run under torch.no_grad()")
 
 
 def resize_normalize_backward(grad_out: torch.Tensor, source_hw, mix_index: Optional[torch.Tensor] = None,
@@ -239,12 +246,65 @@ def augment_table(params: list, device) -> torch.Tensor:
     return torch.frombuffer(buf, dtype=torch.uint8).to(device)
 
 
+def augment_resize_normalize_backward(grad_out: torch.Tensor, images: torch.Tensor, params: list,
+                                      std: float = 0.5) -> torch.Tensor:
+    """The vector-Jacobian product of ``augment_resize_normalize`` as a function: ``grad_out`` (B,3,S,S) -> fp32
+    (B,3,Hs,Ws), the gradient with respect to the source (for a uint8 NHWC source: with respect to ``bytes / 255``).  The
+    colour chain is not linear, so the call takes the source ``images`` and the draws ``params`` the forward had; nothing
+    else is kept: one ``sgl_op_preprocess_aug_bwd`` recomputes the chain per pixel and walks it back (clamps pass the
+    gradient at their bounds, ties of max / min go to the lowest channel: ``torch.autograd``'s rules).  No atomics, a
+    fixed summation order: bitwise reproducible."""
+    g = _grad_out(grad_out, "B")
+    src, is_u8, B, Hs, Ws = _source(images.detach())
+    if src.device != g.device:
+        raise ValueError("grad_out and images must live on the same device")
+    if len(params) != B or g.shape[0] != B:
+        raise ValueError("one augmentation record and one grad_out row per image")
+    S = g.shape[2]
+    dev = g.device
+    tab = augment_table(params, dev)
+    d_src = torch.empty((B, 3, Hs, Ws), device=dev, dtype=torch.float32)
+    nbytes = _lib.load().sgl_op_preprocess_aug_bwd_scratch_bytes(B, Hs, Ws, S)
+    scratch = _scratch(nbytes, dev)
+    _lib.call("sgl_op_preprocess_aug_bwd", dev, g.data_ptr(), src.data_ptr(), is_u8, B, Hs, Ws, S, float(std),
+              tab.data_ptr(), d_src.data_ptr(), _lib.ptr(scratch), nbytes)
+    return d_src
+
+
+class _AugmentResizeNormalize(torch.autograd.Function):
+    """``augment_resize_normalize(differentiable=True)`` for a source that requires grad: the same forward launch, one
+    ``sgl_op_preprocess_aug_bwd`` backward.  The source and the draws are kept (the chain is not linear; autograd refuses
+    the backward if the source was modified in place in between); nothing else is saved."""
+
+    @staticmethod
+    def forward(ctx, images, size, params, mean, std, dtype):
+        ctx.save_for_backward(images)
+        ctx.args = (params, std)
+        return _transform(images.detach(), size, None, dtype, mean, std, params=params)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        (images,) = ctx.saved_tensors
+        params, std = ctx.args
+        d_src = augment_resize_normalize_backward(grad_out, images.detach(), params, std)
+        return d_src.to(images.dtype), None, None, None, None, None
+
+
 def augment_resize_normalize(images: torch.Tensor, size: int, params: list, mean: float = 0.5, std: float = 0.5,
-                             dtype: torch.dtype = torch.float32) -> torch.Tensor:
+                             dtype: torch.dtype = torch.float32, differentiable: bool = False) -> torch.Tensor:
     """(B,3,size,size) = Normalize(ColorJitter(Rotation(Flip(Resize(images))))) with the given per-sample draws: the tensor
     the video trainer's augmenting GPU transform returns, in one pass over the pixels (plus a per-image mean pre-pass for
-    the contrast operator)."""
-    _refuse_grad(images, "augment_resize_normalize")
+    the contrast operator).  ``differentiable=True`` makes it differentiable with respect to a floating ``images`` that
+    requires grad (any float dtype, any strides; the same launch, so the same bits): ``images.grad`` arrives in the
+    source's dtype, shape and strides; ``create_graph=True`` is not supported.  Without it such a source is refused, as
+    before.  uint8 sources have no gradient of their own: see ``augment_resize_normalize_backward``."""
+    if differentiable:
+        params = list(params)
+        if images.is_cuda and _wants_grad(images):
+            return _AugmentResizeNormalize.apply(images, size, params, mean, std, dtype)
+    else:
+        _refuse_grad(images, "augment_resize_normalize")
     return _transform(images, size, None, dtype, mean, std, params=params)
 
 
@@ -574,22 +634,26 @@ class GpuTransform(nn.Module):
     hidf_video_classifier.py:2874-2878) as one module; ``forward(images, mix_index=None, lam=1.0)``."""
 
     def __init__(self, resolution: int, mean: float = 0.5, std: float = 0.5, data_augmentation: bool = False,
-                 generator: Optional[torch.Generator] = None):
+                 generator: Optional[torch.Generator] = None, differentiable: bool = False):
         super().__init__()
         self.resolution, self.mean, self.std = int(resolution), float(mean), float(std)
         self.data_augmentation, self.generator = bool(data_augmentation), generator
+        self.differentiable = bool(differentiable)
 
     def forward(self, images, mix_index=None, lam: float = 1.0):
         """``data_augmentation=True`` (hidf_video_classifier.py ``--data_augmentation``, :2866-2874) inserts flip / rotation /
         colour jitter between resize and normalize while the module is in training mode; draws come from ``generator``.
         The plain branch is differentiable with respect to floating ``images`` that require grad (``resize_normalize``);
-        the augmentation branch refuses such a source.  The reference never puts its ``gpu_transform`` into eval mode, so
+        the augmentation branch refuses such a source unless the module was built with ``differentiable=True``
+        (``augment_resize_normalize(differentiable=True)``).  The reference never puts its ``gpu_transform`` into eval mode, so
         with ``--data_augmentation`` it augments validation batches too.  This module augments only in training mode, on
         purpose: call ``.eval()`` for validation."""
         if self.data_augmentation and self.training:
-            _refuse_grad(images, "GpuTransform(data_augmentation=True) in training mode")
+            if not self.differentiable:
+                _refuse_grad(images, "GpuTransform(data_augmentation=True) in training mode")
             if mix_index is not None:
                 raise ValueError("MixUp and the augmentation branch belong to different trainers; use one of them")
             params = sample_augmentation(images.shape[0], self.generator)
-            return augment_resize_normalize(images, self.resolution, params, self.mean, self.std)
+            return augment_resize_normalize(images, self.resolution, params, self.mean, self.std,
+                                            differentiable=self.differentiable)
         return resize_normalize(images, self.resolution, self.mean, self.std, mix_index, lam)

@@ -570,6 +570,37 @@ typedef struct sgl_aug_sample {
 int sgl_op_preprocess_aug(const void* src, int src_is_u8_nhwc, int B, int Hs, int Ws, void* out, int out_dtype, int S,
                           int P, int Kp, int patch_major, float mean, float std, const sgl_aug_sample* aug,
                           float* grey_mean, sgl_stream stream);
+/* The adjoint of sgl_op_preprocess_aug(patch_major = 0) with respect to its source (new symbols; sgl_abi_version() stays
+ * 3, sgl_aug_sample is unchanged): d_out fp32 (B,3,S,S) NCHW, the gradient with respect to the transform's output ->
+ * d_src fp32 (B,3,Hs,Ws) NCHW, the gradient with respect to a float source (for a uint8 NHWC source: with respect to
+ * byte / 255; the result is NCHW either way).  The transform is not linear (clamps, the contrast step's per-image mean,
+ * RGB <-> HSV), so the call takes the source and the records the forward had.  Nothing of the forward is saved: per
+ * output pixel the resized, mirrored and rotated RGB and the colour chain are recomputed with the forward's own
+ * arithmetic, and the chain is walked back: brightness f g [0 <= x f <= 1]; contrast, with ghat = g [0 <= u <= 1],
+ * c ghat + (1 - c) w (sum of ghat over the image's pixels and channels) / S^2, w = (0.299, 0.587, 0.114); saturation
+ * s ghat + (1 - s) w (sum of ghat over the pixel's channels); hue, the vector-Jacobian product of the operator above line
+ * by line; then the transpose of the rotation's bilinear taps (taps outside the image dropped), the mirror undone, and
+ * the resize adjoint of sgl_op_preprocess_bwd (tables, copy shortcut), where 1 / std is applied, once.  mean does not
+ * enter.  Where the forward is not differentiable the result is what torch.autograd returns for
+ * oracle/preprocess_oracle.py: a clamp passes the gradient at its bounds (0 and 1 inclusive); max and min over the
+ * channels give it to the lowest channel index among ties; a select differentiates the selected branch only; floor, the
+ * fraction of the hue, comparisons and the hue sector contribute nothing (so a white pixel with hue 0.2 and cotangent
+ * (1, 2, 3) has gradient (6, 0, 0)).  A record's (cos_a, sin_a) must be a rotation (cos^2 + sin^2 = 1) and its order a
+ * permutation or order[0] < 0, as the forward documents them.
+ * No atomics: the contrast sum is per-block partials folded per image in a fixed order, the rotation's transpose is a
+ * gather; d_src is always overwritten, every element, by one plain store; two calls on the same inputs give the same bits.
+ * The caller's stream only, no allocation, no copy, no host synchronisation.
+ * scratch: sgl_op_preprocess_aug_bwd_scratch_bytes() bytes of device memory, 4-byte aligned: the resize tables of
+ * sgl_op_preprocess_bwd_scratch_bytes(), 2 B floats (the grey means, the contrast mean terms), B ceil(S^2 / 256) floats
+ * (partials) and two fp32 (B,3,S,S) images (the gradients in front of and behind the rotation).  The size function
+ * returns 0 for a dimension < 1.
+ * Refused before anything is enqueued, d_src untouched: d_out, src, aug, d_src or scratch NULL SGL_ERR_NULL; std == 0 or
+ * a dimension < 1 SGL_ERR_BAD_SHAPE; Hs > 16 * S or Ws > 16 * S SGL_ERR_UNSUPPORTED (the forward's limit); scratch_bytes
+ * too small SGL_ERR_WORKSPACE. */
+size_t sgl_op_preprocess_aug_bwd_scratch_bytes(int B, int Hs, int Ws, int S);
+int sgl_op_preprocess_aug_bwd(const float* d_out, const void* src, int src_is_u8_nhwc, int B, int Hs, int Ws, int S,
+                              float std, const sgl_aug_sample* aug, float* d_src, void* scratch, size_t scratch_bytes,
+                              sgl_stream stream);
 
 /* Video tail (hidf_video_classifier.py:304-316): per-frame embeddings f (B*T, D) fp32 -> each frame L2-normalised ->
  * mean over the T frames of a clip -> out (B, D); inv_norm (B*T) keeps 1/|f_t| for the backward
