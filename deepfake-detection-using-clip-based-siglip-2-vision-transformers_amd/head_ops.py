@@ -1,6 +1,7 @@
 """The HIP-backed operations of the heads: autograd Functions over the ``sgl_op_*`` kernels and, for each, ONE dispatcher that
 holds the rule for when the kernel is eligible and the torch composition used when it is not: ``linear_tokens``,
-``depthwise3x3``, ``gate_mul``, ``bce_dice_loss_from_lowres``, ``seg_eval_from_lowres``, ``l2norm_temporal_mean``.  Every launch goes through
+``depthwise3x3``, ``gate_mul``, ``bce_dice_loss_from_lowres``, ``combined_loss_from_lowres``, ``seg_eval_from_lowres``,
+``l2norm_temporal_mean``.  Every launch goes through
 ``lib.call`` (guard and stream of the device the operands live on).  ``heads.py`` holds the modules and losses built on these.
 """
 from __future__ import annotations
@@ -320,6 +321,82 @@ def bce_dice_loss_from_lowres(logit_lr: torch.Tensor, masks: torch.Tensor, has_m
     if has_mask is None:
         has_mask = torch.ones(logit_lr.shape[0], dtype=torch.bool, device=logit_lr.device)
     return _SegLossFromLowresFn.apply(logit_lr, masks, has_mask, float(bce_w), float(dice_w), float(eps))
+
+
+_FOCAL_ALPHA = 0.25       # focal_loss's alpha at the reference's call site (Siglip2sidafrozen.py:155; gamma = 2 is the kernel's)
+
+
+def seg_terms_mask(focal_w: float, boundary_w: float, morph_w: float) -> int:
+    """The `terms` bits of sgl_op_seg_loss_ex_*: an optional per-pixel term is computed only when its weight is non-zero."""
+    return ((_lib.SEG_TERM_FOCAL if focal_w != 0 else 0) | (_lib.SEG_TERM_BOUNDARY if boundary_w != 0 else 0)
+            | (_lib.SEG_TERM_TV if morph_w != 0 else 0))
+
+
+class _CombinedLossFromLowresFn(torch.autograd.Function):
+    """`combined_segmentation_loss(F.interpolate(logit_lr, (S,S), 'bilinear'), masks)` over the images flagged in `sel`, the
+    enhanced counterpart of `_SegLossFromLowresFn` (same operands, same fold, no host synchronisation, an empty selection
+    gives 0): sgl_op_seg_loss_ex_fwd / _bwd."""
+
+    @staticmethod
+    def forward(ctx, logit_lr, masks, sel, weights, eps, smooth):
+        bce_w, focal_w, dice_w, boundary_w, iou_w, morph_w = weights
+        B, g = logit_lr.shape[0], logit_lr.shape[-1]
+        S = masks.shape[-1]
+        terms = seg_terms_mask(focal_w, boundary_w, morph_w)
+        lr = logit_lr.detach().reshape(B, g, g).float().contiguous()
+        t = masks.reshape(B, S, S).float().contiguous()
+        chunks = _lib.load().sgl_op_seg_loss_chunks(S)
+        partial = torch.empty(B, chunks, 8, device=lr.device, dtype=torch.float32)
+        _lib.call("sgl_op_seg_loss_ex_fwd", lr.device, lr.data_ptr(), t.data_ptr(), partial.data_ptr(), B, g, S, terms,
+                  _FOCAL_ALPHA)
+        sums = partial.sum(1)                                   # (B, 8), fixed order
+        w = sel.to(torch.float32)
+        n = w.sum()
+        nz = (n > 0).to(torch.float32)
+        n1 = n.clamp(min=1.0)
+        npix, npairs = n1 * float(S * S), n1 * float(S * (S - 1))
+        inter, psum, tsum = sums[:, 1], sums[:, 2], sums[:, 3]
+        bce = (sums[:, 0] * w).sum() / npix
+        focal = (sums[:, 4] * w).sum() / npix
+        boundary = (sums[:, 5] * w).sum() / npix
+        dice = 1.0 - (2.0 * inter / (psum + tsum + eps) * w).sum() / n1
+        iou = 1.0 - (inter / (psum + tsum - inter + smooth) * w).sum() / n1
+        morph = ((sums[:, 6] + sums[:, 7]) * w).sum() / npairs
+        loss = (bce_w * bce + focal_w * focal + dice_w * dice + boundary_w * boundary + iou_w * iou + morph_w * morph) * nz
+        ctx.save_for_backward(lr, t, sums, w, n1, nz)
+        ctx.cfg = (B, g, S, terms, weights, eps, smooth, logit_lr.shape, logit_lr.dtype)
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        lr, t, sums, w, n1, nz = ctx.saved_tensors
+        B, g, S, terms, (bce_w, focal_w, dice_w, boundary_w, iou_w, morph_w), eps, smooth, shape, dtype = ctx.cfg
+        up = dloss.float() * nz
+        per_px, per_img, per_pair = up * w / (n1 * float(S * S)), up * w / n1, up * w / (n1 * float(S * (S - 1)))
+        coef = torch.stack([bce_w * per_px, -dice_w * per_img, focal_w * per_px, boundary_w * per_px, -iou_w * per_img,
+                            morph_w * per_pair], dim=1).contiguous()
+        dlr = torch.empty_like(lr)
+        _lib.call("sgl_op_seg_loss_ex_bwd", lr.device, lr.data_ptr(), t.data_ptr(), sums.contiguous().data_ptr(),
+                  coef.data_ptr(), dlr.data_ptr(), B, g, S, terms, _FOCAL_ALPHA, float(eps), float(smooth))
+        return dlr.reshape(shape).to(dtype), None, None, None, None, None
+
+
+@torch.compiler.disable
+def combined_loss_from_lowres(logit_lr: torch.Tensor, masks: torch.Tensor, has_mask: torch.Tensor = None,
+                              bce_w: float = 0.4, focal_w: float = 0.3, dice_w: float = 0.5, boundary_w: float = 0.4,
+                              iou_w: float = 0.4, morph_w: float = 0.2, eps: float = 1e-6,
+                              smooth: float = 1e-6) -> torch.Tensor:
+    """`combined_segmentation_loss(upsample(logit_lr)[has_mask], masks[has_mask])` (Siglip2sidafrozen.py:142-172, the
+    `--use_enhanced_loss` branch of the train step) from the (B,1,g,g) logits of `SegFormerMaskDecoder(...,
+    return_lowres=True)`; CUDA only (HIP kernels), fp32 statistics, the (B,1,S,S) logits are never formed.  A term whose
+    weight is zero is not computed.  `smooth` is `iou_loss`'s."""
+    if not logit_lr.is_cuda:
+        raise RuntimeError("combined_loss_from_lowres runs on the GPU (HIP kernels); use combined_segmentation_loss on CPU "
+                           "tensors")
+    if has_mask is None:
+        has_mask = torch.ones(logit_lr.shape[0], dtype=torch.bool, device=logit_lr.device)
+    weights = tuple(float(v) for v in (bce_w, focal_w, dice_w, boundary_w, iou_w, morph_w))
+    return _CombinedLossFromLowresFn.apply(logit_lr, masks, has_mask, weights, float(eps), float(smooth))
 
 
 def check_cuts(cuts) -> None:

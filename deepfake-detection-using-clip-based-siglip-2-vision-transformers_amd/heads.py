@@ -22,8 +22,8 @@ import torch.nn.functional as F
 
 from .config import isqrt_exact
 from . import lib as _lib
-from .head_ops import (bce_dice_loss_from_lowres, depthwise3x3, gate_mul, l2norm_temporal_mean, linear_tokens,
-                       seg_eval_from_lowres)
+from .head_ops import (bce_dice_loss_from_lowres, combined_loss_from_lowres, depthwise3x3, gate_mul,
+                       l2norm_temporal_mean, linear_tokens, seg_eval_from_lowres)
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -140,14 +140,23 @@ class SigLIP2MTL(nn.Module):
         return cls_logit, seg_logits
 
     def training_loss(self, pixel_values, y_class, masks, has_mask, lam_seg: float = 1.0, bce_w: float = 1.0,
-                      dice_w: float = 0.5):
+                      dice_w: float = 0.5, enhanced: bool = False, focal_w: float = 0.3, boundary_w: float = 0.4,
+                      iou_w: float = 0.4, morph_w: float = 0.2):
         """The SID train-step loss (Siglip2sidafrozen.py:1375-1389: CE + lam * BCE/Dice on the samples with a mask) with the
         decoder tail fused for HBM: low-res logits -> loss directly.  ``bce_w`` / ``dice_w`` are the epoch-scheduled
         ``current_bce_w`` / ``current_dice_w`` the reference passes to ``bce_dice_loss`` (Siglip2sidafrozen.py:1340-1351,
-        1389).  Returns (loss, cls_logit, seg_logits_lowres)."""
+        1389).  ``enhanced=True`` is the ``--use_enhanced_loss`` branch (:1379-1384): the segmentation term is
+        ``combined_segmentation_loss`` with ``focal_w`` / ``boundary_w`` / ``morph_w`` = ``args.*`` and ``iou_w`` =
+        ``current_iou_w`` (after the IoU-focused rescale of :1343-1351), again from the low-res logits
+        (``combined_loss_from_lowres``); the four extra keywords are ignored otherwise.
+        Returns (loss, cls_logit, seg_logits_lowres)."""
         cls_logit, seg_lr = self.forward(pixel_values, return_lowres=True)
-        loss = F.cross_entropy(cls_logit.float(), y_class) + lam_seg * bce_dice_loss_from_lowres(
-            seg_lr, masks, has_mask, bce_w=bce_w, dice_w=dice_w)
+        if enhanced:
+            seg = combined_loss_from_lowres(seg_lr, masks, has_mask, bce_w=bce_w, focal_w=focal_w, dice_w=dice_w,
+                                            boundary_w=boundary_w, iou_w=iou_w, morph_w=morph_w)
+        else:
+            seg = bce_dice_loss_from_lowres(seg_lr, masks, has_mask, bce_w=bce_w, dice_w=dice_w)
+        loss = F.cross_entropy(cls_logit.float(), y_class) + lam_seg * seg
         return loss, cls_logit, seg_lr
 
 

@@ -15,6 +15,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "siglip_hip.h")
 SGL_DTYPE_F32, SGL_DTYPE_BF16, SGL_DTYPE_BF16X3, SGL_DTYPE_F16, SGL_DTYPE_MXFP8 = 0, 1, 2, 3, 5   # 4 is unassigned
 SGL_DTYPE_U8 = 6               # storage type of mask bytes (sgl_op_seg_eval targets), never a compute dtype
 SEG_EVAL_AUC_BINS = 4096       # SGL_SEG_EVAL_AUC_BINS
+SEG_TERM_FOCAL, SEG_TERM_BOUNDARY, SEG_TERM_TV = 1, 2, 4   # SGL_SEG_TERM_*: optional terms of sgl_op_seg_loss_ex_*
 SGL_RECOMPUTE_NONE, SGL_RECOMPUTE_BLOCKS = 0, 1   # sgl_create_ex activation policies
 EPI_STORE, EPI_BIAS_GELU, EPI_RES_F32, EPI_QKV, EPI_GELU_BWD, EPI_POS_F32, EPI_F32 = range(7)
 STATUS = {0: "ok", -1: "bad shape", -2: "unsupported configuration", -3: "buffer too small", -4: "HIP error",
@@ -198,6 +199,8 @@ def load():
     _sig(lib, "sgl_op_seg_loss_chunks", i, [i])
     _sig(lib, "sgl_op_seg_loss_fwd", i, [_fp, _fp, _fp, i, i, i, _fp])
     _sig(lib, "sgl_op_seg_loss_bwd", i, [_fp, _fp, _fp, _fp, _fp, i, i, i, f, _fp])
+    _sig(lib, "sgl_op_seg_loss_ex_fwd", i, [_fp, _fp, _fp, i, i, i, i, f, _fp])
+    _sig(lib, "sgl_op_seg_loss_ex_bwd", i, [_fp, _fp, _fp, _fp, _fp, i, i, i, i, f, f, f, _fp])
     _sig(lib, "sgl_op_seg_eval_auc_bins", i, [])
     _sig(lib, "sgl_op_seg_eval", i, [_fp, _fp, i, _fp, _fp, i, _fp, _fp, i, i, i, _fp])
     _lib = lib

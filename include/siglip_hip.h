@@ -635,6 +635,45 @@ int sgl_op_seg_loss_fwd(const float* logits_lr, const float* targets, float* par
 int sgl_op_seg_loss_bwd(const float* logits_lr, const float* targets, const float* sums, const float* coef,
                         float* dlogits_lr, int B, int g, int S, float eps, sgl_stream stream);
 
+/* combined_segmentation_loss (:69-172, the --use_enhanced_loss branch of the train step at :1379-1386) from the same
+ * operands: BCE + focal + Dice + boundary-weighted BCE + IoU + the smoothness form of the morphological term (the branches
+ * taken without Kornia).  z, p = sigmoid(z) and bce_px = max(z,0) - z t + log(1 + exp(-|z|)) of an output pixel are formed
+ * exactly as by sgl_op_seg_loss_fwd.  n = images with a mask, N = n S^2.
+ *   focal     alpha_t q^2 bce_px,  q = p + t - 2 p t,  alpha_t = alpha t + (1 - alpha)(1 - t)  (gamma = 2), mean over N
+ *             d/dz = alpha_t (2 q (1 - 2t) p(1-p) bce_px + q^2 (p - t)) / N
+ *   boundary  (1 + 3 beta) bce_px,  beta = [s > 0] - [s == 9],  s = fp32 sum of the nine zero-padded 3x3 neighbours of t in
+ *             row-major order (dilate - erode, exact for {0,1} masks), mean over N;  d/dz = (1 + 3 beta)(p - t) / N
+ *   iou       1 - I / U per image, U = sum p + sum t - I + smooth, I = sum p t, mean over n
+ *             d/dz = -p(1-p) (t U - I (1 - t)) / (n U^2)
+ *   morph     mean |p[x+1] - p[x]| + mean |p[y+1] - p[y]|, each over n S (S-1) pairs
+ *             d/dz = p(1-p) (sum over the <= 4 neighbours of sign(p - p_nb)) / (n S (S-1)),  sign(0) = 0
+ * terms: SGL_SEG_TERM_* bits selecting the three optional per-pixel computations.  Without a bit its sums are written as 0,
+ *        its coefficient is not read as a term, and the work behind it (the 3x3 mask neighbourhood, the neighbour sigmoids)
+ *        is not done.  BCE, Dice and IoU are always available.  Another bit -> SGL_ERR_UNSUPPORTED.
+ * fwd: partial[b][chunk][8] = {sum bce_px, sum p t, sum p, sum t, sum focal, sum boundary, sum |dp/dx|, sum |dp/dy|} over 8
+ *      output rows (chunks = sgl_op_seg_loss_chunks(S)); the vertical pair (i, i+1) belongs to the chunk of row i.
+ * bwd: sums[b][8] = the chunks of image b folded by the caller in a fixed order (I, sum p, sum t are read);
+ *      coef[b][6] = {c_bce, c_dice, c_focal, c_boundary, c_iou, c_tv} = upstream * weight * {1/N, -1/n, 1/N, 1/N, -1/n,
+ *      1/(n S (S-1))}, all 0 for an image without a mask;
+ *      dlogits_lr[b] = transposed interpolation of
+ *        c_bce (p - t) + c_dice p(1-p)(2 t D - 2 I)/D^2 + c_focal alpha_t (2 q (1-2t) p(1-p) bce_px + q^2 (p - t))
+ *        + c_boundary (1 + 3 beta)(p - t) + c_iou p(1-p)(t U - I (1-t))/U^2 + c_tv p(1-p) sum_nb sign(p - p_nb),
+ *      D = sum p + sum t + eps; gathered per low-res pixel in a fixed order, no atomics, no scratch: bitwise reproducible.
+ * Where both taps of an axis are the same logit (the clamped last rows / columns) the weight is taken as 0, so z there is
+ * that logit itself rather than l (1 - w) + l w (at most an ulp apart).  Two output pixels whose taps and weights coincide
+ * (all clamped border rows / columns, g = 1) therefore hold bit-equal p: their smoothness term and its gradient are exact
+ * zeros, as in exact arithmetic.
+ * Refused before anything is enqueued, nothing written: a NULL pointer -> SGL_ERR_NULL; B or g <= 0, S < 2 (the mean over
+ * S - 1 pairs is undefined), g > 4096, S > 2048 (rows of p staged in LDS) -> SGL_ERR_BAD_SHAPE. */
+#define SGL_SEG_TERM_FOCAL 1
+#define SGL_SEG_TERM_BOUNDARY 2
+#define SGL_SEG_TERM_TV 4
+int sgl_op_seg_loss_ex_fwd(const float* logits_lr, const float* targets, float* partial, int B, int g, int S, int terms,
+                           float alpha, sgl_stream stream);
+int sgl_op_seg_loss_ex_bwd(const float* logits_lr, const float* targets, const float* sums, const float* coef,
+                           float* dlogits_lr, int B, int g, int S, int terms, float alpha, float eps, float smooth,
+                           sgl_stream stream);
+
 /* The localisation metrics of the validation loop (:183-240 dice_iou_from_logits / sweep_mask_thresholds, :1078-1106
  * PixelAUCBuffer) as integer counts, again straight from the low-resolution logit map, in one pass and without a host
  * synchronisation.  Per output pixel of every selected image:
