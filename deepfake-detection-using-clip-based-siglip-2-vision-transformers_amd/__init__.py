@@ -9,4 +9,4 @@ from .encoder import (SiglipVisionModelHIP, OpenClipStyleEncoder, create_model_a
 from .ddp import GradBucketReducer  # noqa: F401
 from .head_ops import seg_eval_from_lowres  # noqa: F401
 from .heads import MaskMetrics  # noqa: F401
-from .optim import FusedAdamW, global_grad_norm, ExponentialMovingAverage  # noqa: F401
+from .optim import FusedAdamW, GradScaler, global_grad_norm, ExponentialMovingAverage  # noqa: F401

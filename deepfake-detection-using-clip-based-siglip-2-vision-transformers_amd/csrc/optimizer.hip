@@ -18,6 +18,12 @@
 //     p <- p * (1 - lr*wd);  m <- m + (g - m)*(1 - b1);  v <- v*b2 + g*g*(1 - b2)
 //     p <- p - (lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
 //
+// Under torch.amp.GradScaler (scaler.unscale_ / scaler.step around the two calls above, Siglip2sidafrozen.py:1390-1397,
+// cifake_binary_classifier.py:831-841, hidf_video_classifier.py:388-402) the same three launches take the loss scale and
+// the scaler's found-inf flag from device memory (sgl_op_grad_norm_amp, sgl_op_adamw_amp): gradients are unscaled as they
+// are read, an overflowing step is skipped and counted on the device, and a one-thread launch forms the bias corrections
+// of the effective step.  The *_amp entry points share every device function with the plain ones.
+//
 // HBM-bound: 28 algorithmic bytes per parameter (read p,g,m,v; write p,m,v), +4 for the norm pass.
 // Work decomposition: the host plan (sgl_adamw_plan) cuts every tensor into 4096-element chunks and lists
 // (tensor, chunk) pairs; a 256-thread block takes one pair, 16 elements per thread as four 16-byte accesses.
@@ -60,50 +66,121 @@ __device__ __forceinline__ void walk_chunk(uint64_t base, uint64_t n, bool align
   }
 }
 
-__global__ __launch_bounds__(256) void grad_sqnorm_kernel(const sgl_adamw_tensor* __restrict__ T,
-                                                          const int32_t* __restrict__ map,
-                                                          float* __restrict__ partial) {
-  __shared__ float red[4];
+// Sum of squares of one chunk, folded over the block in a fixed order; the result is valid in thread 0.  AMP: every
+// gradient is multiplied by `inv` (1 / the loss scale) BEFORE it is squared, so a scaled gradient that is finite never
+// overflows in its square (exact for the power-of-two scales GradScaler produces).
+template <bool AMP>
+__device__ __forceinline__ float chunk_sqnorm(const sgl_adamw_tensor* __restrict__ T, const int32_t* __restrict__ map,
+                                              float inv, float* red /*[4]*/) {
   const int ti = map[2 * blockIdx.x], ch = map[2 * blockIdx.x + 1];
   const float* g = T[ti].g;
   float s = 0.f;
   if (g)
     walk_chunk((uint64_t)ch * OPT_CHUNK, T[ti].n, (((uintptr_t)g) & 15) == 0,
                [&](uint64_t i) {
-                 const f32x4 x = *reinterpret_cast<const f32x4*>(g + i);
+                 f32x4 x = *reinterpret_cast<const f32x4*>(g + i);
+                 if (AMP) x = x * inv;
                  s += (x[0] * x[0] + x[1] * x[1]) + (x[2] * x[2] + x[3] * x[3]);
                },
-               [&](uint64_t j) { s += g[j] * g[j]; });
+               [&](uint64_t j) {
+                 float x = g[j];
+                 if (AMP) x = x * inv;
+                 s += x * x;
+               });
   s = wave_sum(s);
   if (lane_id() == 0) red[wave_id()] = s;
   __syncthreads();
-  if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+  return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-// out[0] = s*||g||_2 ; out[1] = s*min(1, max_norm / (s*norm + 1e-6)).  s = 1 is torch.nn.utils.clip_grad_norm_; s = 1/world
-// is the factor every gradient is multiplied by when the stored gradients are rank SUMS
-// (ddp.GradBucketReducer(average="defer")).
-__global__ __launch_bounds__(1024) void grad_norm_finish_kernel(const float* __restrict__ partial, int n, float max_norm,
-                                                                float gscale, float* __restrict__ out) {
-  __shared__ double red[16];
+__global__ __launch_bounds__(256) void grad_sqnorm_kernel(const sgl_adamw_tensor* __restrict__ T,
+                                                          const int32_t* __restrict__ map,
+                                                          float* __restrict__ partial) {
+  __shared__ float red[4];
+  const float s = chunk_sqnorm<false>(T, map, 1.0f, red);
+  if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+__global__ __launch_bounds__(256) void grad_sqnorm_amp_kernel(const sgl_adamw_tensor* __restrict__ T,
+                                                              const int32_t* __restrict__ map,
+                                                              const float* __restrict__ amp_scale,
+                                                              float* __restrict__ partial) {
+  __shared__ float red[4];
+  const float inv = amp_scale ? 1.0f / amp_scale[0] : 1.0f;
+  const float s = chunk_sqnorm<true>(T, map, inv, red);
+  if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+// The block partials folded in double in a fixed order by a 1024-thread block; the total is valid in thread 0.
+__device__ __forceinline__ double fold_partials(const float* __restrict__ partial, int n, double* red /*[16]*/) {
   double s = 0.0;
   for (int i = threadIdx.x; i < n; i += 1024) s += (double)partial[i];
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
   __syncthreads();
-  if (threadIdx.x == 0) {
-    double t = 0.0;
+  double t = 0.0;
+  if (threadIdx.x == 0)
     for (int i = 0; i < 16; ++i) t += red[i];
-    const float norm = (float)sqrt(t) * gscale;
-    out[0] = norm;
-    float coef = 1.0f;
-    if (max_norm > 0.f) {
-      coef = max_norm / (norm + 1e-6f);
-      if (coef > 1.0f) coef = 1.0f;
-    }
-    out[1] = coef * gscale;
+  return t;
+}
+
+// norm = s*||g||_2 ; coef = s*min(1, max_norm / (s*norm + 1e-6)).  s = 1 is torch.nn.utils.clip_grad_norm_; s = 1/world
+// is the factor every gradient is multiplied by when the stored gradients are rank SUMS
+// (ddp.GradBucketReducer(average="defer")).
+__device__ __forceinline__ void norm_and_clip(double sumsq, float max_norm, float gscale, float& norm, float& coef) {
+  norm = (float)sqrt(sumsq) * gscale;
+  coef = 1.0f;
+  if (max_norm > 0.f) {
+    coef = max_norm / (norm + 1e-6f);
+    if (coef > 1.0f) coef = 1.0f;
   }
+  coef = coef * gscale;
+}
+
+__global__ __launch_bounds__(1024) void grad_norm_finish_kernel(const float* __restrict__ partial, int n, float max_norm,
+                                                                float gscale, float* __restrict__ out) {
+  __shared__ double red[16];
+  const double t = fold_partials(partial, n, red);
+  if (threadIdx.x == 0) {
+    float norm, coef;
+    norm_and_clip(t, max_norm, gscale, norm, coef);
+    out[0] = norm;
+    out[1] = coef;
+  }
+}
+
+// The AMP finish: the partials are sums of (g/scale)^2, so out[0] is the TRUE norm; out[1] carries 1/scale as its last
+// factor, so that g_scaled * out[1] has the bits of g_true * (coef * s) for a power-of-two scale.  One thread decides
+// whether the step is skipped and counts it.
+__global__ __launch_bounds__(1024) void grad_norm_finish_amp_kernel(const float* __restrict__ partial, int n,
+                                                                    float max_norm, float gscale,
+                                                                    const float* __restrict__ amp_scale,
+                                                                    const float* __restrict__ found_inf_in,
+                                                                    float* __restrict__ out,
+                                                                    sgl_amp_state* __restrict__ state) {
+  __shared__ double red[16];
+  const double t = fold_partials(partial, n, red);
+  if (threadIdx.x == 0) {
+    const float inv = amp_scale ? 1.0f / amp_scale[0] : 1.0f;
+    float norm, coef;
+    norm_and_clip(t, max_norm, gscale, norm, coef);
+    out[0] = norm;
+    out[1] = coef * inv;
+    const bool found = (found_inf_in && found_inf_in[0] != 0.f) || !isfinite(t);
+    state->found_inf = found ? 1.0f : 0.0f;
+    if (found) state->skipped = state->skipped + 1;
+  }
+}
+
+// Bias corrections of the EFFECTIVE step (calls minus skipped steps), once per launch: the formulas of launch_adamw.
+__global__ void amp_bias_correction_kernel(sgl_amp_state* __restrict__ state, int step, double beta1, double beta2) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  int t = step - state->skipped;
+  if (t < 1) t = 1;
+  const double bc1 = 1.0 - pow(beta1, (double)t), bc2 = 1.0 - pow(beta2, (double)t);
+  state->inv_bc1 = (float)(1.0 / bc1);
+  state->inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
 }
 
 struct AdamConst {
@@ -202,11 +279,21 @@ __device__ __forceinline__ void adamw_tile(const sgl_adamw_tensor& t, const sgl_
   sh.put_transposed();
 }
 
+// AMP (sgl_op_adamw_amp, the step under a GradScaler; `state` is NULL otherwise): a step the norm launch marked as
+// overflowed stores nothing, and the bias corrections are those of the effective step, read from the device state
+// (amp_bias_correction_kernel).
+template <bool AMP>
 __global__ __launch_bounds__(256) void adamw_ex_kernel(const sgl_adamw_tensor* __restrict__ T,
                                                        const sgl_adamw_aux* __restrict__ A,
                                                        const int32_t* __restrict__ map, AdamConst c, GroupHyper gh,
-                                                       const float* __restrict__ clip, float ema_decay) {
+                                                       const float* __restrict__ clip, float ema_decay,
+                                                       const sgl_amp_state* __restrict__ state) {
   __shared__ float lds_tile[64 * 66];
+  if (AMP) {
+    if (state->found_inf != 0.f) return;
+    c.inv_bc1 = state->inv_bc1;
+    c.inv_sqrt_bc2 = state->inv_sqrt_bc2;
+  }
   const int ti = map[2 * blockIdx.x], ch = map[2 * blockIdx.x + 1];
   const sgl_adamw_tensor t = T[ti];
   if (!t.g) return;
@@ -349,10 +436,27 @@ int sgl_op_grad_norm(const sgl_adamw_tensor* table, const int32_t* blockmap, int
   return sgl_op_grad_norm_scaled(table, blockmap, nblocks, max_norm, 1.0f, partials, norm_and_coef, stream);
 }
 
-// aux may be NULL (sgl_op_adamw); the caller has checked the arguments
+int sgl_op_grad_norm_amp(const sgl_adamw_tensor* table, const int32_t* blockmap, int64_t nblocks, float max_norm,
+                         float world_scale, const float* amp_scale, const float* found_inf_in, float* partials,
+                         float* norm_and_coef, sgl_amp_state* state, sgl_stream stream) {
+  if (!table || !blockmap || !partials || !norm_and_coef || !state) return SGL_ERR_NULL;
+  if (nblocks < 0 || nblocks > 0x7fffffff) return SGL_ERR_BAD_SHAPE;
+  if ((((uintptr_t)amp_scale) | ((uintptr_t)found_inf_in) | ((uintptr_t)state)) & 3) return SGL_ERR_BAD_SHAPE;
+  hipStream_t s = (hipStream_t)stream;
+  if (nblocks > 0)
+    hipLaunchKernelGGL(sgl::grad_sqnorm_amp_kernel, dim3((unsigned)nblocks), dim3(256), 0, s, table, blockmap, amp_scale,
+                       partials);
+  hipLaunchKernelGGL(sgl::grad_norm_finish_amp_kernel, dim3(1), dim3(1024), 0, s, partials, (int)nblocks, max_norm,
+                     world_scale, amp_scale, found_inf_in, norm_and_coef, state);
+  return hipGetLastError() == hipSuccess ? SGL_OK : SGL_ERR_HIP;
+}
+
+// aux may be NULL (sgl_op_adamw); state NULL is the plain step, otherwise the GradScaler one; the caller has checked the
+// arguments
 static int launch_adamw(const sgl_adamw_tensor* table, const sgl_adamw_aux* aux, const int32_t* blockmap, int64_t nblocks,
                         double beta1, double beta2, double eps, int step, const float* norm_and_coef,
-                        const float* group_lr_wd_host, int ngroups, double ema_decay, sgl_stream stream) {
+                        const float* group_lr_wd_host, int ngroups, double ema_decay, sgl_amp_state* state,
+                        sgl_stream stream) {
   if (nblocks == 0) return SGL_OK;
   sgl::AdamConst c;
   // every scalar is formed in double and rounded once, as torch does with its Python-float hyper-parameters
@@ -370,8 +474,16 @@ static int launch_adamw(const sgl_adamw_tensor* table, const sgl_adamw_aux* aux,
     gh.lr[i] = i < ngroups ? group_lr_wd_host[2 * i] : 0.f;
     gh.wd[i] = i < ngroups ? group_lr_wd_host[2 * i + 1] : 0.f;
   }
-  hipLaunchKernelGGL(sgl::adamw_ex_kernel, dim3((unsigned)nblocks), dim3(256), 0, (hipStream_t)stream, table, aux,
-                     blockmap, c, gh, norm_and_coef, (float)ema_decay);
+  if (state) {
+    // the effective step is known on the device only: its bias corrections replace c's in the kernel
+    hipLaunchKernelGGL(sgl::amp_bias_correction_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, state, step, beta1,
+                       beta2);
+    hipLaunchKernelGGL(sgl::adamw_ex_kernel<true>, dim3((unsigned)nblocks), dim3(256), 0, (hipStream_t)stream, table, aux,
+                       blockmap, c, gh, norm_and_coef, (float)ema_decay, (const sgl_amp_state*)state);
+  } else {
+    hipLaunchKernelGGL(sgl::adamw_ex_kernel<false>, dim3((unsigned)nblocks), dim3(256), 0, (hipStream_t)stream, table, aux,
+                       blockmap, c, gh, norm_and_coef, (float)ema_decay, (const sgl_amp_state*)nullptr);
+  }
   return hipGetLastError() == hipSuccess ? SGL_OK : SGL_ERR_HIP;
 }
 
@@ -382,7 +494,19 @@ int sgl_op_adamw_ex(const sgl_adamw_tensor* table, const sgl_adamw_aux* aux, con
   if (nblocks < 0 || nblocks > 0x7fffffff || step < 1 || ngroups < 0 || ngroups > 16) return SGL_ERR_BAD_SHAPE;
   if (ngroups > 0 && !group_lr_wd_host) return SGL_ERR_NULL;
   return launch_adamw(table, aux, blockmap, nblocks, beta1, beta2, eps, step, norm_and_coef, group_lr_wd_host, ngroups,
-                      ema_decay, stream);
+                      ema_decay, nullptr, stream);
+}
+
+int sgl_op_adamw_amp(const sgl_adamw_tensor* table, const sgl_adamw_aux* aux, const int32_t* blockmap, int64_t nblocks,
+                     double beta1, double beta2, double eps, int step, const float* norm_and_coef,
+                     const float* group_lr_wd_host, int ngroups, double ema_decay, sgl_amp_state* state,
+                     sgl_stream stream) {
+  if (!table || !aux || !blockmap || !state) return SGL_ERR_NULL;
+  if (nblocks < 0 || nblocks > 0x7fffffff || step < 1 || ngroups < 0 || ngroups > 16) return SGL_ERR_BAD_SHAPE;
+  if (((uintptr_t)state) & 3) return SGL_ERR_BAD_SHAPE;
+  if (ngroups > 0 && !group_lr_wd_host) return SGL_ERR_NULL;
+  return launch_adamw(table, aux, blockmap, nblocks, beta1, beta2, eps, step, norm_and_coef, group_lr_wd_host, ngroups,
+                      ema_decay, state, stream);
 }
 
 // the table's own lr / weight_decay per tensor; no shadow, EMA or dst_f32
@@ -390,7 +514,8 @@ int sgl_op_adamw(const sgl_adamw_tensor* table, const int32_t* blockmap, int64_t
                  double eps, int step, const float* norm_and_coef, sgl_stream stream) {
   if (!table || !blockmap) return SGL_ERR_NULL;
   if (nblocks < 0 || nblocks > 0x7fffffff || step < 1) return SGL_ERR_BAD_SHAPE;
-  return launch_adamw(table, nullptr, blockmap, nblocks, beta1, beta2, eps, step, norm_and_coef, nullptr, 0, 0.0, stream);
+  return launch_adamw(table, nullptr, blockmap, nblocks, beta1, beta2, eps, step, norm_and_coef, nullptr, 0, 0.0, nullptr,
+                      stream);
 }
 
 }  // extern "C"

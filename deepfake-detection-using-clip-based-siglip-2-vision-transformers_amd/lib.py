@@ -62,6 +62,11 @@ class SglAdamwAux(C.Structure):
                 ("reserved", C.c_int)]
 
 
+class SglAmpState(C.Structure):
+    _fields_ = [("found_inf", C.c_float), ("skipped", C.c_int32), ("inv_bc1", C.c_float), ("inv_sqrt_bc2", C.c_float),
+                ("reserved", C.c_int32 * 4)]
+
+
 class SglCastMat(C.Structure):
     _fields_ = [("src", _fp), ("dst", _fp), ("dst_t", _fp)] + [(n, C.c_int) for n in ("R", "C", "lds", "Rp", "Cp", "ldd",
                                                                                     "ldt")]
@@ -176,6 +181,9 @@ def load():
     _sig(lib, "sgl_op_grad_norm_scaled", i, [_fp, _fp, i64, f, f, _fp, _fp, _fp])
     _sig(lib, "sgl_op_adamw_ex", i, [_fp, _fp, _fp, i64, C.c_double, C.c_double, C.c_double, i, _fp,
                                      C.POINTER(C.c_float), i, C.c_double, _fp])
+    _sig(lib, "sgl_op_grad_norm_amp", i, [_fp, _fp, i64, f, f, _fp, _fp, _fp, _fp, _fp, _fp])
+    _sig(lib, "sgl_op_adamw_amp", i, [_fp, _fp, _fp, i64, C.c_double, C.c_double, C.c_double, i, _fp,
+                                      C.POINTER(C.c_float), i, C.c_double, _fp, _fp])
     _sig(lib, "sgl_op_dwconv3x3", i, [_fp, i, _fp, _fp, _fp, i, i, i, i, i, _fp])
     _sig(lib, "sgl_op_dwconv3x3_wgrad_scratch_bytes", sz, [i, i, i, i])
     _sig(lib, "sgl_op_dwconv3x3_wgrad", i, [_fp, _fp, i, _fp, i, _fp, sz, i, i, i, i, _fp])

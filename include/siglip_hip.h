@@ -756,7 +756,49 @@ int sgl_op_grad_norm_scaled(const sgl_adamw_tensor* table, const int32_t* blockm
 int sgl_op_adamw_ex(const sgl_adamw_tensor* table, const sgl_adamw_aux* aux, const int32_t* blockmap, int64_t nblocks,
                     double beta1, double beta2, double eps, int step, const float* norm_and_coef,
                     const float* group_lr_wd_host, int ngroups, double ema_decay, sgl_stream stream);
-/* Weight EMA of the CiFake trainer (ExponentialMovingAverage.update, cifake_binary_classifier.py:222-225):
+/* ---- the same step tail under torch.amp.GradScaler (scaler.scale(loss).backward(); scaler.step(opt); scaler.update(),
+ * Siglip2sidafrozen.py:1276,1390-1397, cifake_binary_classifier.py:831-841, hidf_video_classifier.py:388-402) ------
+ * The gradients in the table are loss-scaled; the scale and the scaler's inf flag are DEVICE values, and so is the
+ * decision to skip the step: no unscale pass, no host synchronisation.  Caller-owned device state, 32 bytes, 4-byte
+ * aligned, zero it once (hipMemset) before the first call: */
+typedef struct {
+  float found_inf;      /* 1.0f when this step is skipped, else 0.0f; written by sgl_op_grad_norm_amp (a float, so that it
+                           can be handed to GradScaler.update() as the found-inf tensor it sums) */
+  int32_t skipped;      /* running count of skipped steps */
+  float inv_bc1;        /* 1 / (1 - beta1^t)       of the last sgl_op_adamw_amp launch, t = step - skipped */
+  float inv_sqrt_bc2;   /* 1 / sqrt(1 - beta2^t) */
+  int32_t reserved[4];
+} sgl_amp_state;
+/* sgl_op_grad_norm_scaled for loss-scaled gradients.  amp_scale[0] is the loss scale (NULL = 1), found_inf_in[0] != 0
+ * says the caller already found an inf / NaN (NULL = 0); both are device pointers.  Every gradient is multiplied by
+ * inv = 1/amp_scale[0] BEFORE it is squared (a finite scaled gradient then never overflows in its square; exact for the
+ * power-of-two scales GradScaler produces); block and final summation order are sgl_op_grad_norm's.  Writes
+ *   norm_and_coef[0] = world_scale * ||g/scale||                             the TRUE norm
+ *   norm_and_coef[1] = (min(1, max_norm/([0] + 1e-6)) * world_scale) * inv   (max_norm <= 0: (world_scale) * inv), so that
+ *                      for a power-of-two scale g_scaled*[1] has the bits g_true*[1] has in sgl_op_grad_norm_scaled
+ *   state->found_inf = 1 when found_inf_in[0] != 0 or the sum of squares is not finite, else 0; when 1, also
+ *                      state->skipped += 1.
+ * A not-finite sum is an inf or NaN gradient, or a true norm beyond fp32's range (the block sums are fp32, so from about
+ * 1.8e19 up), where torch's own clip coefficient would already be 0 or NaN: such a step is skipped too.
+ * nblocks == 0 is allowed (the sum is 0: only found_inf_in decides).  Refused before anything is enqueued: table,
+ * blockmap, partials, norm_and_coef or state NULL -> SGL_ERR_NULL; nblocks < 0 or > 2^31-1, or amp_scale, found_inf_in or
+ * state not 4-byte aligned -> SGL_ERR_BAD_SHAPE. */
+int sgl_op_grad_norm_amp(const sgl_adamw_tensor* table, const int32_t* blockmap, int64_t nblocks, float max_norm,
+                         float world_scale, const float* amp_scale, const float* found_inf_in, float* partials,
+                         float* norm_and_coef, sgl_amp_state* state, sgl_stream stream);
+/* sgl_op_adamw_ex that obeys `state`: with state->found_inf == 1 every block returns before its first store (parameters,
+ * exp_avg, exp_avg_sq, dst / dst_t, dst_f32 and ema keep their bits).  The host cannot know how many steps were skipped
+ * without a synchronisation, so `step` >= 1 counts CALLS; the effective step is t = max(1, step - state->skipped), and
+ * its bias corrections are formed on the device in double and rounded to float (the host formulas of sgl_op_adamw_ex)
+ * by a one-thread launch in front of the update, which leaves them in state->inv_bc1 / inv_sqrt_bc2.
+ * Refused before anything is enqueued: table, aux, blockmap or state NULL, or group_lr_wd_host NULL with ngroups > 0
+ * -> SGL_ERR_NULL; nblocks < 0 or > 2^31-1, step < 1, ngroups outside [0, 16], state not 4-byte aligned ->
+ * SGL_ERR_BAD_SHAPE. */
+int sgl_op_adamw_amp(const sgl_adamw_tensor* table, const sgl_adamw_aux* aux, const int32_t* blockmap, int64_t nblocks,
+                     double beta1, double beta2, double eps, int step, const float* norm_and_coef,
+                     const float* group_lr_wd_host, int ngroups, double ema_decay, sgl_amp_state* state,
+                     sgl_stream stream);
+/* Weight EMA of the CiFake trainer (ExponentialMovingAverage.update,cifake_binary_classifier.py:222-225):
  * shadow = shadow*decay + p*(1-decay) for every table entry, with p = entry.p (read only) and shadow = entry.m. */
 int sgl_op_ema(const sgl_adamw_tensor* table, const int32_t* blockmap, int64_t nblocks, double decay,
                sgl_stream stream);
