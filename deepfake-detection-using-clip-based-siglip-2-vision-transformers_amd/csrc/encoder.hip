@@ -1389,6 +1389,44 @@ int sgl_op_attn_bwd(int dtype, const void* q, const void* k, const void* v, cons
   return SGL_OK;
 }
 
+int sgl_op_attn_probs(int dtype, const void* q, const void* k, const float* lse, float* out, int B, int H, int N,
+                      int head_dim, int head_dim_pad, int mode, sgl_stream stream) {
+  if (!q || !k || !lse || !out) return SGL_ERR_NULL;
+  if (B < 1 || H < 1 || N < 1 || head_dim < 1 || head_dim_pad < 1 || head_dim > head_dim_pad) return SGL_ERR_BAD_SHAPE;
+  if (dtype != DT_F32 && dtype != DT_BF16 && dtype != DT_F32_MFMA && dtype != DT_F16) return SGL_ERR_UNSUPPORTED;
+  if (mode != SGL_ATTN_PROBS_FULL && mode != SGL_ATTN_PROBS_HEAD_MEAN) return SGL_ERR_UNSUPPORTED;
+  if (!attn_probs_shape_ok(dtype, B, H, N, head_dim, head_dim_pad)) return SGL_ERR_BAD_SHAPE;
+  CKV(attn_probs(q, k, lse, out, dtype, B, H, N, head_dim, head_dim_pad, mode, (hipStream_t)stream));
+  return SGL_OK;
+}
+
+int sgl_attention_probs(sgl_ctx* ctx, int B, int H, int W, const void* saved, size_t saved_bytes, int layer, int mode,
+                        float* out, size_t out_bytes, sgl_stream stream) {
+  if (!ctx || !saved || !out) return SGL_ERR_NULL;
+  if (!train_shape_ok(ctx, B, H, W) || layer < 0 || layer > ctx->L) return SGL_ERR_BAD_SHAPE;
+  if (ctx->recompute || ctx->mx || (layer == ctx->L && !ctx->cfg.use_head)) return SGL_ERR_UNSUPPORTED;
+  if (mode != SGL_ATTN_PROBS_FULL && mode != SGL_ATTN_PROBS_HEAD_MEAN) return SGL_ERR_UNSUPPORTED;
+  const Layout lay(ctx, B, H, W, true);
+  const size_t N = (size_t)lay.N, heads = mode == SGL_ATTN_PROBS_FULL ? (size_t)ctx->H : 1;
+  const size_t need = (size_t)B * heads * N * (layer == ctx->L ? 1 : N) * sizeof(float);
+  if (saved_bytes < lay.saved_total || out_bytes < need) return SGL_ERR_WORKSPACE;
+  const char* act = reinterpret_cast<const char*>(saved);
+  hipStream_t s = (hipStream_t)stream;
+  if (layer == ctx->L) {   // the pooling head kept its probe probabilities [B][heads][N]
+    const float* probs = reinterpret_cast<const float*>(act + lay.a_probs);
+    if (mode == SGL_ATTN_PROBS_FULL)
+      CK(copy_f32(probs, out, (size_t)B * ctx->H * N, s));
+    else
+      CK(probs_head_mean(probs, out, B, ctx->H, lay.N, s));
+    return SGL_OK;
+  }
+  const char* lb = act + lay.layer_base(layer);
+  const char* q = lb + lay.r_qkv;
+  CK(attn_probs(q, q + head_bytes(ctx, B, lay.N), reinterpret_cast<const float*>(lb + lay.r_lse), out,
+                ctx->split ? DT_F32_MFMA : ctx->dt, B, ctx->H, lay.N, ctx->dh, ctx->DP, mode, s));
+  return SGL_OK;
+}
+
 int sgl_op_colsum(int dtype, const void* in, int ld, int M, int N, float* out, int accumulate, float* scratch,
                   size_t scratch_bytes, sgl_stream stream) {
   if (scratch_bytes < (size_t)colsum_chunks(M) * N * 4) return SGL_ERR_WORKSPACE;

@@ -257,4 +257,15 @@ hipError_t attn_bwd(const void* q, const void* k, const void* v, const void* out
                     const float* lse, int dtype, void* dqkv, float* delta, float* reserved, int B, int H, int N,
                     int dh, int DP, int ld_qkv, hipStream_t s);
 
+// ---- attention_probs.hip -------------------------------------------------------------------------------
+// out[b,h,i,j] = exp2(S_ij * c - lse_i * log2e) from head-major q, k [B][H][N][DP] and the forward's lse [B][H][N]: the P
+// the backward kernels rebuild.  mode SGL_ATTN_PROBS_FULL: out (B,H,N,N); SGL_ATTN_PROBS_HEAD_MEAN: out (B,N,N), heads
+// summed in ascending order in registers.  fp32 out, plain stores only, inputs const.  hipErrorInvalidValue for an unknown
+// dtype / mode, a shape attn_probs_shape_ok refuses or 16-bit operands that are not 16-byte aligned.
+bool attn_probs_shape_ok(int dtype, int B, int H, int N, int dh, int DP);
+hipError_t attn_probs(const void* q, const void* k, const float* lse, float* out, int dtype, int B, int H, int N, int dh,
+                      int DP, int mode, hipStream_t s);
+// out [B][N] = (sum_h probs[b][h][n]) / H, heads in ascending order (the pooling head's probe map, head mean)
+hipError_t probs_head_mean(const float* probs, float* out, int B, int H, int N, hipStream_t s);
+
 }  // namespace sgl

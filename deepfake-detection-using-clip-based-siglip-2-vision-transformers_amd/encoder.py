@@ -4,6 +4,7 @@ hand-written gfx950 kernels in ``libsiglip_hip.so``.
 Surface H (HuggingFace-style; ``Siglip2sidafrozen.py:753,757-768,771,787-793``):
     ``SiglipVisionModelHIP.from_pretrained(path_or_name)``, ``model(pixel_values=..., output_hidden_states=True,
     interpolate_pos_encoding=True)`` → ``.pooler_output`` / ``.last_hidden_state`` / ``.hidden_states``;
+    ``output_attentions=True`` → ``.attentions`` / ``.pooling_attention`` (detached), ``model.attention_rollout(x)``;
     ``.config.hidden_size``; ``.vision_model.embeddings`` / ``.vision_model.encoder.layers[i]`` for freezing;
     ``state_dict`` keys equal HF ``SiglipVisionModel`` keys.
 Surface O (open_clip-style; ``cifake_binary_classifier.py:625-638,721``, ``hidf_video_classifier.py:259-273,307``):
@@ -111,6 +112,9 @@ class VisionModelOutput:
     last_hidden_state: torch.Tensor
     pooler_output: Optional[torch.Tensor]
     hidden_states: Optional[Tuple[torch.Tensor, ...]] = None
+    # output_attentions=True only (after the fields above, so positional construction and indexing keep their meaning)
+    attentions: Optional[Tuple[torch.Tensor, ...]] = None
+    pooling_attention: Optional[torch.Tensor] = None
 
     def __getitem__(self, i):
         return (self.last_hidden_state, self.pooler_output, self.hidden_states)[i]
@@ -259,10 +263,77 @@ class SiglipVisionModelHIP(nn.Module):
         return super().load_state_dict(dict(state_dict), strict=strict, **kw)
 
     def forward(self, pixel_values=None, output_hidden_states: bool = False, interpolate_pos_encoding: bool = False,
-                hidden_state_ids=None, patches=None, **_):
+                hidden_state_ids=None, patches=None, output_attentions: bool = False, attention_layers=None,
+                attention_heads: str = "all", **_):
         """Traceable by Dynamo: everything device-side happens inside ``torch.ops.siglip_hip.encoder_fwd``.
         ``patches`` (a ``preprocess.PatchOperand``) replaces ``pixel_values``: the resized + normalised images already
-        in the patch GEMM's operand layout, so neither an fp32 (B,3,S,S) tensor nor the im2col pass exists."""
+        in the patch GEMM's operand layout, so neither an fp32 (B,3,S,S) tensor nor the im2col pass exists.
+
+        ``output_attentions=True`` adds ``.attentions``: one fp32 tensor per block of ``attention_layers`` (default: every
+        block, as HF), (B,heads,N,N) each, or (B,N,N), the mean over heads, with ``attention_heads="mean"`` (all full maps
+        of so400m@384 are 27 x 34 MB per image: ask for the layers, or the mean, you need), and ``.pooling_attention``: the
+        pooling head's probe attention (B,heads,N), or (B,N) with ``"mean"``, when the model has its head.  The maps are
+        recomputed by a HIP kernel from the q, k and log-sum-exp the saving forward keeps; every other output, and every
+        gradient, is bit-identical to the same call without the flag.  Unlike HF's, the maps are DETACHED: no gradient
+        flows through them.  Works in every grad mode (under ``no_grad`` the call runs the saving forward and drops the
+        arena afterwards); not on a ``recompute=True`` model and not with ``compute_dtype="mxfp8"`` (RuntimeError).  The
+        call is a graph break under ``torch.compile``; without the flag nothing changes."""
+        if output_attentions:
+            return self._forward_with_attentions(pixel_values, output_hidden_states, interpolate_pos_encoding,
+                                                 hidden_state_ids, patches, attention_layers, attention_heads)
+        return self._run(pixel_values, output_hidden_states, interpolate_pos_encoding, hidden_state_ids, patches)[0]
+
+    def _attention_request(self, attention_layers, attention_heads):
+        """(block indices, head_mean) of an ``output_attentions=True`` call, checked before any device work."""
+        L = self.config.num_hidden_layers
+        if self._recompute:
+            raise RuntimeError("output_attentions=True on a recompute=True model: recompute keeps no per-block q, k to "
+                               "rebuild the maps from; use a model without recompute for attention maps")
+        if self.compute_dtype in INFERENCE_ONLY:
+            raise RuntimeError(f"output_attentions=True with compute_dtype={self.compute_dtype!r}: the inference-only mode "
+                               "has no saving forward; use compute_dtype='bf16' / 'fp16' / 'bf16x3' / 'fp32' for attention maps")
+        if attention_heads not in ("all", "mean"):
+            raise ValueError(f"attention_heads must be 'all' or 'mean', got {attention_heads!r}")
+        layers = list(range(L)) if attention_layers is None else [int(i) for i in attention_layers]
+        for i in layers:
+            if not -L <= i < L:
+                raise RuntimeError(f"attention_layers entry {i} is out of range for {L} blocks; valid: {-L} .. {L - 1} "
+                                   "(the pooling head's map is .pooling_attention)")
+        return [i % L for i in layers], attention_heads == "mean"
+
+    @torch.compiler.disable
+    def _forward_with_attentions(self, pixel_values, output_hidden_states, interpolate_pos_encoding, hidden_state_ids,
+                                 patches, attention_layers, attention_heads):
+        layers, head_mean = self._attention_request(attention_layers, attention_heads)
+        out, saved, (B, H, W) = self._run(pixel_values, output_hidden_states, interpolate_pos_encoding, hidden_state_ids,
+                                          patches, keep_arena=True)
+        maps = encoder_ops.attention_maps(self, saved, B, H, W, layers + ([self.config.num_hidden_layers]
+                                                                        if self.use_head else []), head_mean)
+        out.attentions = tuple(maps[:len(layers)])
+        out.pooling_attention = maps[-1] if self.use_head else None
+        return out
+
+    def attention_rollout(self, pixel_values, residual: float = 0.5, interpolate_pos_encoding: bool = True):
+        """Attention rollout (``heads.attention_rollout``) of every block's head-mean map, read through the pooling head's
+        probe attention: one relevance value per patch, (B, gh, gw), detached.  One saving forward; the per-head (B,H,N,N)
+        maps are never materialised."""
+        from .heads import attention_rollout
+        if not self.use_head:
+            raise RuntimeError("attention_rollout reads the rollout through the pooling head's probe attention and this "
+                               "model has none; use heads.attention_rollout(model(..., output_attentions=True, "
+                               "attention_heads='mean').attentions) for the (B,N,N) rollout")
+        with torch.no_grad():
+            out = self(pixel_values=pixel_values, interpolate_pos_encoding=interpolate_pos_encoding,
+                       output_attentions=True, attention_heads="mean")
+            r = attention_rollout(out.attentions, residual, pooling=out.pooling_attention)
+        P = self.config.patch_size
+        return r.view(r.shape[0], pixel_values.shape[-2] // P, pixel_values.shape[-1] // P)
+
+    def _run(self, pixel_values, output_hidden_states, interpolate_pos_encoding, hidden_state_ids, patches,
+             keep_arena: bool = False):
+        """The forward proper: (output, activation arena or None, (B, H, W)).  keep_arena (output_attentions): a call that
+        would not train runs the saving forward all the same (no block keeps its GELU pre-activation: first = L), so the
+        arena exists; a training call already has it."""
         layout, img_h, img_w = 0, 0, 0
         if patches is not None:
             if pixel_values is not None:
@@ -301,12 +372,18 @@ class SiglipVisionModelHIP(nn.Module):
         if train and not want_px and not any(p.requires_grad for p in params[:self._table.n_emb]):
             first = next((e.block for e, p in zip(self._table.entries, params) if p.requires_grad and e.block is not None),
                          L)
-        outs = torch.ops.siglip_hip.encoder_fwd(pixel_values, params, self._handle, train,
+        save = train
+        if keep_arena and not train:
+            save, first = True, L
+        outs = torch.ops.siglip_hip.encoder_fwd(pixel_values, params, self._handle, save,
                                                 bool(interpolate_pos_encoding), self.use_head, uniq, first, layout, img_h,
                                                 img_w, train and self._recompute)
         pooled = outs[0] if self.use_head else None
         hs = tuple(outs[2 + uniq.index(i)] for i in tap_ids) if tap_ids else None
-        return VisionModelOutput(last_hidden_state=outs[1], pooler_output=pooled, hidden_states=hs)
+        out = VisionModelOutput(last_hidden_state=outs[1], pooler_output=pooled, hidden_states=hs)
+        if not keep_arena:
+            return out, None, None
+        return out, outs[-2], encoder_ops._input_geometry(self.config, pixel_values, layout, img_h, img_w)[:3]
 
     # ---- plumbing ----------------------------------------------------------------------------------------
     _RUNTIME = ("_table", "_contexts", "_shadows", "_grads", "_handle")

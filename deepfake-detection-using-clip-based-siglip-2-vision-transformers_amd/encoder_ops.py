@@ -327,3 +327,28 @@ def _encoder_backward(ctx, grads):
 
 
 encoder_fwd.register_autograd(_encoder_backward, setup_context=_encoder_setup_context)
+
+
+def attention_maps(mod, saved: torch.Tensor, B: int, H: int, W: int, layers: Sequence[int], head_mean: bool):
+    """sgl_attention_probs for each entry of ``layers`` (block index, or L for the pooling head) on the activation arena
+    ``saved`` of a saving forward of ``mod`` at (B, H, W): fresh fp32 tensors, (B,heads,N,N) / (B,heads,N) each, without
+    the heads dimension when ``head_mean``.  The arena is only read.  Not a custom op (a graph break under torch.compile):
+    the tensors are outside autograd."""
+    lib = _lib.load()
+    cfg = mod.config
+    L, heads = cfg.num_hidden_layers, cfg.num_attention_heads
+    N = _geometry(cfg, H, W, B)[3]
+    dev = saved.device
+    mode = _lib.ATTN_PROBS_HEAD_MEAN if head_mean else _lib.ATTN_PROBS_FULL
+    lead = (B,) if head_mean else (B, heads)
+    outs = []
+    with torch.cuda.device(dev):
+        ctx = mod._contexts.get(False)
+        stream = _lib.current_stream_handle(dev)
+        for l in layers:
+            out = torch.empty(lead + ((N,) if l == L else (N, N)), dtype=torch.float32, device=dev)
+            st = lib.sgl_attention_probs(ctx, B, H, W, saved.data_ptr(), saved.numel(), int(l), mode, out.data_ptr(),
+                                         out.numel() * 4, stream)
+            _lib.check(st, f"sgl_attention_probs[{l}]", ctx)
+            outs.append(out)
+    return outs

@@ -163,6 +163,32 @@ class SigLIP2MTL(nn.Module):
 # ---------------------------------------------------------------------------------------------------------
 # binary heads on the pooled embedding
 # ---------------------------------------------------------------------------------------------------------
+def attention_rollout(attentions, residual: float = 0.5, pooling: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Attention rollout (Abnar & Zuidema 2020) of a ViT's per-block attention maps, e.g. the ``.attentions`` of
+    ``SiglipVisionModelHIP(..., output_attentions=True)``, first block first.  Per block: the head mean A of a (B,H,N,N)
+    tensor (a (B,N,N) one is taken as is), mixed with the residual path, ``(1 - residual) * A + residual * I``, rows
+    renormalised; the rollout is the product of those matrices, last block leftmost: (B,N,N) in fp32.  With ``pooling``
+    (the pooling head's probe attention, (B,H,N) or its head mean (B,N)) the result is ``pooling @ rollout``: (B,N), one
+    relevance value per patch.  Plain torch (``bmm``)."""
+    R = None
+    for A in attentions:
+        A = A.float()
+        if A.dim() == 4:
+            A = A.mean(1)
+        eye = torch.eye(A.shape[-1], dtype=A.dtype, device=A.device)
+        At = (1.0 - residual) * A + residual * eye
+        At = At / At.sum(-1, keepdim=True)
+        R = At if R is None else torch.bmm(At, R)
+    if R is None:
+        raise ValueError("attention_rollout needs at least one attention map")
+    if pooling is None:
+        return R
+    p = pooling.float()
+    if p.dim() == 3:
+        p = p.mean(1)
+    return torch.bmm(p.unsqueeze(1), R).squeeze(1)
+
+
 def l2_normalize(f: torch.Tensor, eps: float = 0.0) -> torch.Tensor:
     """`f / f.norm(dim=-1, keepdim=True)` (cifake_binary_classifier.py:728, hidf_video_classifier.py:308);
     eps=1e-6 is the `train_fusion_head_only.py:106` form."""

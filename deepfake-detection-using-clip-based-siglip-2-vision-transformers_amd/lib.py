@@ -17,6 +17,7 @@ SGL_DTYPE_U8 = 6               # storage type of mask bytes (sgl_op_seg_eval tar
 SEG_EVAL_AUC_BINS = 4096       # SGL_SEG_EVAL_AUC_BINS
 SEG_TERM_FOCAL, SEG_TERM_BOUNDARY, SEG_TERM_TV = 1, 2, 4   # SGL_SEG_TERM_*: optional terms of sgl_op_seg_loss_ex_*
 SGL_RECOMPUTE_NONE, SGL_RECOMPUTE_BLOCKS = 0, 1   # sgl_create_ex activation policies
+ATTN_PROBS_FULL, ATTN_PROBS_HEAD_MEAN = 0, 1      # SGL_ATTN_PROBS_*: modes of sgl_op_attn_probs / sgl_attention_probs
 EPI_STORE, EPI_BIAS_GELU, EPI_RES_F32, EPI_QKV, EPI_GELU_BWD, EPI_POS_F32, EPI_F32 = range(7)
 STATUS = {0: "ok", -1: "bad shape", -2: "unsupported configuration", -3: "buffer too small", -4: "HIP error",
           -5: "null pointer"}
@@ -154,6 +155,8 @@ def load():
     _sig(lib, "sgl_op_gemm_tn_ws", i, [i, _fp, i, _fp, i, i, i, i, i, _fp, i, i, _fp, sz, _fp])
     _sig(lib, "sgl_op_attn_fwd", i, [i, _fp, _fp, _fp, _fp, _fp, i, i, i, i, i, i, _fp])
     _sig(lib, "sgl_op_attn_bwd", i, [i, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, i, i, i, i, i, i, _fp])
+    _sig(lib, "sgl_op_attn_probs", i, [i, _fp, _fp, _fp, _fp, i, i, i, i, i, i, _fp])
+    _sig(lib, "sgl_attention_probs", i, [C.c_void_p, i, i, i, _fp, sz, i, i, _fp, sz, _fp])
     _sig(lib, "sgl_op_colsum", i, [i, _fp, i, i, i, _fp, i, _fp, sz, _fp])
     _sig(lib, "sgl_op_im2col", i, [_fp, i, _fp, i, i, i, i, i, i, _fp])
     _sig(lib, "sgl_op_col2im", i, [_fp, i, i, i, i, i, _fp, i, _fp])

@@ -4,6 +4,7 @@
  * nn.Module obtained from third-party libraries:
  *   surface H  self.encoder(pixel_values=..., output_hidden_states=True, interpolate_pos_encoding=True)
  *              -> .pooler_output / .last_hidden_state / .hidden_states        Siglip2sidafrozen.py:753,787-793
+ *              (+ output_attentions=True -> .attentions / .pooling_attention: sgl_attention_probs below)
  *   surface O  backbone.encode_image(x) -> (B, D)                             cifake_binary_classifier.py:721,
  *                                                                             hidf_video_classifier.py:307
  * The entry points below are what a binding for that path binds instead of the HuggingFace / open_clip ViT:
@@ -311,6 +312,33 @@ int sgl_op_attn_fwd(int dtype, const void* q, const void* k, const void* v, void
 int sgl_op_attn_bwd(int dtype, const void* q, const void* k, const void* v, const void* out, const void* dout,
                     const float* lse, void* dqkv, float* delta_scratch, int B, int H, int N, int head_dim,
                     int head_dim_pad, int ld_qkv, sgl_stream stream);
+/* ---- attention maps (new symbols; sgl_abi_version() stays 3: nothing existing changed) --------------------------------
+ * The attention probabilities of a block, recomputed from what a forward leaves behind: q, k head-major
+ * [B][H][N][head_dim_pad] with zero pad columns (the ld_qkv == 0 layout above; 16-bit operands 16-byte aligned) and the
+ * lse [B][H][N] sgl_op_attn_fwd wrote (natural log of the row sum of exp(q.k / sqrt(head_dim))).
+ *   out[b,h,i,j] = exp2(S_ij * c - lse_i * log2 e),  c = log2 e / sqrt(head_dim)
+ * which is the P the backward kernels differentiate: lse is used as given and rows are NOT renormalised.
+ * mode SGL_ATTN_PROBS_FULL: out fp32 (B,H,N,N).  SGL_ATTN_PROBS_HEAD_MEAN: out fp32 (B,N,N), the mean over heads, summed in
+ * ascending head order in registers (the per-head maps never exist in memory).  dtype as sgl_op_attn_fwd.  Every input is
+ * const; every element of out is written by exactly one plain store (no atomics): two calls give the same bits.
+ * Errors, before anything is enqueued: q / k / lse / out NULL -> SGL_ERR_NULL; a dimension < 1, head_dim > head_dim_pad
+ * or a head_dim / head_dim_pad sgl_op_attn_fwd refuses for that dtype -> SGL_ERR_BAD_SHAPE; an unknown dtype or mode, or
+ * misaligned 16-bit operands -> SGL_ERR_UNSUPPORTED. */
+enum { SGL_ATTN_PROBS_FULL = 0, SGL_ATTN_PROBS_HEAD_MEAN = 1 };
+int sgl_op_attn_probs(int dtype, const void* q, const void* k, const float* lse, float* out, int B, int H, int N,
+                      int head_dim, int head_dim_pad, int mode, sgl_stream stream);
+/* Attention maps of the encoder, read out of the activation arena `saved` that a saving forward (sgl_forward* with saved
+ * != NULL) of the same (B, H, W) left on a plain context.  The arena is const here and stays bit-identical: a backward
+ * may follow.  layer in [0, L): block `layer`, through sgl_op_attn_probs on the q, k, lse the block kept, with the
+ * context's attention dtype; out fp32 (B,heads,N,N) (FULL) or (B,N,N) (HEAD_MEAN).  layer == L: the pooling head's probe
+ * attention, from the probabilities its forward kept; out (B,heads,N) (FULL, a copy) or (B,N) (HEAD_MEAN, heads summed in
+ * ascending order, then divided by heads).
+ * Errors, in this order, before anything is enqueued: ctx / saved / out NULL -> SGL_ERR_NULL; a shape a training forward
+ * refuses, or layer outside [0, L] -> SGL_ERR_BAD_SHAPE; a recompute context (it keeps no per-block q, k), an
+ * SGL_DTYPE_MXFP8 context, layer == L without the head, or an unknown mode -> SGL_ERR_UNSUPPORTED; saved_bytes below what
+ * sgl_query_sizes(train = 1) reports, or out_bytes below the result -> SGL_ERR_WORKSPACE. */
+int sgl_attention_probs(sgl_ctx* ctx, int B, int H, int W, const void* saved, size_t saved_bytes, int layer, int mode,
+                        float* out, size_t out_bytes, sgl_stream stream);
 int sgl_op_colsum(int dtype, const void* in, int ld, int M, int N, float* out, int accumulate, float* scratch,
                   size_t scratch_bytes, sgl_stream stream);
 int sgl_op_im2col(const float* pixels, int channels_last, void* out, int out_dtype, int B, int H, int W, int P, int Kp,
