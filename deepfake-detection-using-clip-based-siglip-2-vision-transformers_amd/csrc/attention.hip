@@ -24,17 +24,9 @@
 // 14·N²·dh; the extra recompute buys determinism and no dQ atomics).
 #include <stdlib.h>
 
-#include "common.hip.h"
-#include "kernels.h"
+#include "attention.hip.h"
 
 namespace sgl {
-
-hipError_t attn_f32_fwd(const float*, const float*, const float*, float*, float*, int, int, int, int, int, int, hipStream_t);
-hipError_t attn_f32_bwd(const float*, const float*, const float*, const float*, const float*, const float*, float*,
-                        float*, int, int, int, int, int, int, hipStream_t);
-hipError_t attn_ref_fwd(const float*, const float*, const float*, float*, float*, int, int, int, int, int, int, hipStream_t);
-hipError_t attn_ref_bwd(const float*, const float*, const float*, const float*, const float*, const float*, float*,
-                        float*, int, int, int, int, int, int, hipStream_t);
 
 template <int DP>
 struct AttnCfg {
@@ -44,6 +36,12 @@ struct AttnCfg {
   static constexpr int RSTR = DP * 2 + 16;    // row-read image stride: odd multiple of 16 B -> b128 conflict-free
   static constexpr int TSTR = 192;            // transposed-read image stride: 4 rows x 64 B cover all 64 banks
   static constexpr int DSTR = 208;            // dual-use image (row reads + transposed reads), 96 columns
+  // dynamic LDS of the three kernels (the STAGE / IMG arithmetic of their bodies): 1 KiB per DMA instruction of an image
+  static constexpr int DIMG = (32 * (DSTR / 16) + 63) / 64 * 1024;   // 32-row dual-use image
+  static constexpr int RIMG = (32 * (RSTR / 16) + 63) / 64 * 1024;   // 32-row row-read image
+  static constexpr int SMEM_FWD = 2 * (64 * RSTR + 64 * TSTR);       // two stages of a 64-key K image + V image
+  static constexpr int SMEM_KV = 3 * (2 * DIMG + 32 * 8);            // three stages of Q image, dO image, 32 {lse, delta} pairs
+  static constexpr int SMEM_Q = 3 * (DIMG + RIMG);                   // three stages of K image + V image
 };
 
 __device__ __forceinline__ u32x4 a_ldg(__amdgpu_buffer_rsrc_t r, uint32_t off) {
@@ -89,27 +87,6 @@ __device__ __forceinline__ bool head_block(int nb, int BH, int& bh, int& xb) {
   return bh < BH;
 }
 static inline dim3 head_grid(int nb, int BH) { return dim3((unsigned)(8 * ((BH + 7) / 8) * nb)); }
-
-// Where head `hd` of batch `b` lives in a q/k/v source: byte stride between token rows, data chunks per row, buffer extent.
-struct HeadSrc {
-  uint32_t rowbytes, nc, bytes;
-  size_t base;   // element offset of (token 0, column 0) of this head
-};
-__device__ __forceinline__ HeadSrc head_src(int ld, int b, int hd, int H, int N, int dh, int DP) {
-  HeadSrc r;
-  if (ld > 0) {
-    r.rowbytes = (uint32_t)ld * 2u;
-    r.nc = (uint32_t)dh / 8u;
-    r.bytes = (uint32_t)(((size_t)(N - 1) * ld + dh) * 2);
-    r.base = (size_t)b * N * ld + (size_t)hd * dh;
-  } else {
-    r.rowbytes = (uint32_t)DP * 2u;
-    r.nc = (uint32_t)DP / 8u;
-    r.bytes = (uint32_t)((size_t)N * DP * 2);
-    r.base = ((size_t)b * H + hd) * (size_t)N * DP;
-  }
-  return r;
-}
 
 #define MFMA32(a, b, c) mfma_32x32x16((a), (b), (c))
 
@@ -530,7 +507,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_q_kernel(const T* __restrict_
   constexpr int KIMG = NIK * 1024, VIMG = NIV * 1024, STAGE = KIMG + VIMG;
   constexpr int NSLOT = NIK + NIV;
   static_assert(NSLOT <= 16, "at most four DMA slots per wave");
-  constexpr float LOG2E = 1.4426950408889634f;
+  constexpr float LOG2E = kLog2e;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int t = threadIdx.x, lane = t & 63;
   const int w = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -709,111 +686,87 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_q_kernel(const T* __restrict_
 }
 
 // ======================================================================================================
-// launchers
+// host front: the shape contract and the launchers
 // ======================================================================================================
-template <typename T, int DP>
-static hipError_t fwd_launch(const T* q, const T* k, const T* v, T* out, float* lse, int B, int H, int N,
-                             int dh, int ld, hipStream_t s) {
-  using C = AttnCfg<DP>;
-  constexpr int smem = 2 * (64 * C::RSTR + 64 * C::TSTR);
-  const float scale = 1.0f / sqrtf((float)dh);
-  if (ld > 0)
-    hipLaunchKernelGGL((attn_fwd_kernel<T, DP, true>), head_grid((N + 127) / 128, B * H), dim3(256), smem, s, q, k, v, out, lse,
-                       B, H, N, dh, ld, scale * 1.4426950408889634f, scale);
-  else
-    hipLaunchKernelGGL((attn_fwd_kernel<T, DP, false>), head_grid((N + 127) / 128, B * H), dim3(256), smem, s, q, k, v, out,
-                       lse, B, H, N, dh, 0, scale * 1.4426950408889634f, scale);
-  return hipGetLastError();
-}
-
-template <typename T, int DP>
-static hipError_t bwd_launch(const T* q, const T* k, const T* v, const T* out, const T* dout,
-                             const float* lse, T* dqkv, float* delta, int B, int H, int N, int dh, int ld,
-                             hipStream_t s) {
-  using C = AttnCfg<DP>;
-  const float scale = 1.0f / sqrtf((float)dh);
-  const float c = scale * 1.4426950408889634f;
-  // dQ first: it also computes delta and leaves the {-lse*log2e, -delta*scale} pairs in `delta` for the dK/dV kernel
-  constexpr int smem_kv = 3 * (2 * ((32 * (C::DSTR / 16) + 63) / 64) * 1024 + 32 * 8);
-  constexpr int smem_q = 3 * (((32 * (C::DSTR / 16) + 63) / 64) + ((32 * (C::RSTR / 16) + 63) / 64)) * 1024;
-  const dim3 grid = head_grid((N + 127) / 128, B * H), block(256);
-  if (ld > 0)
-    hipLaunchKernelGGL((attn_bwd_q_kernel<T, DP, true>), grid, block, smem_q, s, q, k, v, out, dout, lse, delta, dqkv, B, H, N,
-                       dh, ld, c, scale);
-  else
-    hipLaunchKernelGGL((attn_bwd_q_kernel<T, DP, false>), grid, block, smem_q, s, q, k, v, out, dout, lse, delta, dqkv, B, H, N,
-                       dh, 0, c, scale);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  if (ld > 0)
-    hipLaunchKernelGGL((attn_bwd_kv_kernel<T, DP, true>), grid, block, smem_kv, s, q, k, v, dout, delta, dqkv, B, H, N, dh, ld, c,
-                       scale);
-  else
-    hipLaunchKernelGGL((attn_bwd_kv_kernel<T, DP, false>), grid, block, smem_kv, s, q, k, v, dout, delta, dqkv, B, H, N, dh, 0,
-                       c, scale);
-  return hipGetLastError();
-}
-
-static bool attn_shape_ok(int N, int dh, int DP, int H, int ld) {
-  if (dh % 8 || DP != ((dh + 15) / 16) * 16) return false;
-  if (DP != 16 && DP != 32 && DP != 48 && DP != 64 && DP != 80 && DP != 96) return false;
-  if (ld < 0 || (ld > 0 && (ld % 8 || ld < H * dh))) return false;          // 16-byte aligned token rows
-  if ((size_t)N * (ld > 0 ? ld : DP) * 2 >= (1ull << 31)) return false;
-  if ((size_t)N * H * dh * 2 >= (1ull << 31)) return false;
+bool attn_shape_ok(int dtype, int B, int H, int N, int dh, int DP, int ld, AttnPass pass) {
+  const bool probs = pass == ATTN_PROBS, strict = dtype == DT_F32, f32m = dtype == DT_F32_MFMA;
+  const bool lo = !strict && !f32m;
+  if (probs && (B < 1 || H < 1 || N < 1 || dh < 1 || dh > DP)) return false;
+  // head dim: the strict route stages a row in 128 floats; fp32 MFMA keeps 96 / 2 k-steps in registers and fetches float4;
+  // the 16-bit kernels take 16-byte chunks and the padded widths they are instantiated for
+  if (strict) {
+    if (dh > 128) return false;
+  } else {
+    if (dh % 8) return false;
+    if (f32m && (dh > 96 || DP < dh || DP % 4)) return false;
+    if (lo && (DP != ((dh + 15) / 16) * 16 || !attn_dp_ok(DP))) return false;
+    // token rows: all heads of a token, 16-byte aligned
+    if (ld < 0 || (ld > 0 && (ld % (lo ? 8 : 4) || ld < H * dh))) return false;
+  }
+  if (f32m && N <= 0) return false;
+  if (lo) {   // 32-bit byte offsets into one head's q/k/v rows and into one image's out / dout / dqkv rows
+    if ((size_t)N * (ld > 0 ? ld : DP) * 2 >= (1ull << 31)) return false;
+    if (!probs && (size_t)N * H * dh * 2 >= (1ull << 31)) return false;
+  }
+  if (strict && !probs && attn_ref_lds(N, pass == ATTN_BWD ? 2 : 1, pass == ATTN_BWD ? 2 : 1) > 160 * 1024) return false;
+  if (probs) {   // workgroups of the FULL launch (the larger one): a 1-D grid
+    const size_t wgs = strict ? (size_t)((N + 3) / 4) * ((N + 63) / 64) : (size_t)((N + 127) / 128) * ((N + 127) / 128);
+    if (wgs * (size_t)B * (size_t)H >= (1ull << 31)) return false;
+  }
   return true;
 }
 
 hipError_t attn_fwd(const void* q, const void* k, const void* v, int dtype, void* out, float* lse, int B, int H, int N,
                     int dh, int DP, int ld, hipStream_t s) {
   if (B * H == 0 || N == 0) return hipSuccess;
+  if (!attn_shape_ok(dtype, B, H, N, dh, DP, ld, ATTN_FWD)) return hipErrorInvalidValue;
   if (dtype == DT_F32)
     return attn_ref_fwd((const float*)q, (const float*)k, (const float*)v, (float*)out, lse, B, H, N, dh, DP, ld, s);
   if (dtype == DT_F32_MFMA)
     return attn_f32_fwd((const float*)q, (const float*)k, (const float*)v, (float*)out, lse, B, H, N, dh, DP, ld, s);
-  if (!attn_shape_ok(N, dh, DP, H, ld)) return hipErrorInvalidValue;
-  if ((((uintptr_t)q) | ((uintptr_t)k) | ((uintptr_t)v)) & 15) return hipErrorInvalidValue;
-#define SGL_F(T, DPV) \
-  case DPV: return fwd_launch<T, DPV>((const T*)q, (const T*)k, (const T*)v, (T*)out, lse, B, H, N, dh, ld, s);
-  if (dtype == DT_F16) {
-    switch (DP) {
-      SGL_F(f16, 16) SGL_F(f16, 32) SGL_F(f16, 48) SGL_F(f16, 64) SGL_F(f16, 80) SGL_F(f16, 96)
-    }
-    return hipErrorInvalidValue;
-  }
-  switch (DP) {
-    SGL_F(bf16, 16) SGL_F(bf16, 32) SGL_F(bf16, 48) SGL_F(bf16, 64) SGL_F(bf16, 80) SGL_F(bf16, 96)
-  }
-#undef SGL_F
-  return hipErrorInvalidValue;
+  if (!attn_aligned16(q, k, v)) return hipErrorInvalidValue;
+  const AttnScales sc = attn_scales(dh);
+  return dispatch_attn(dtype, DP, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    constexpr int DPV = decltype(tag)::dp;
+    return with_bool(ld > 0, [&](auto tok) {
+      hipLaunchKernelGGL((attn_fwd_kernel<T, DPV, tok.value>), head_grid((N + 127) / 128, B * H), dim3(256),
+                         AttnCfg<DPV>::SMEM_FWD, s, (const T*)q, (const T*)k, (const T*)v, (T*)out, lse, B, H, N, dh,
+                         tok.value ? ld : 0, sc.c, sc.scale);
+      return hipGetLastError();
+    });
+  });
 }
 
 hipError_t attn_bwd(const void* q, const void* k, const void* v, const void* out, const void* dout, const float* lse,
-                    int dtype, void* dqkv, float* delta, float* /*unused*/, int B, int H, int N, int dh, int DP,
-                    int ld, hipStream_t s) {
+                    int dtype, void* dqkv, float* delta, int B, int H, int N, int dh, int DP, int ld, hipStream_t s) {
   if (B * H == 0 || N == 0) return hipSuccess;
+  if (!attn_shape_ok(dtype, B, H, N, dh, DP, ld, ATTN_BWD)) return hipErrorInvalidValue;
   if (dtype == DT_F32)
     return attn_ref_bwd((const float*)q, (const float*)k, (const float*)v, (const float*)out, (const float*)dout, lse,
                         (float*)dqkv, delta, B, H, N, dh, DP, ld, s);
   if (dtype == DT_F32_MFMA)
     return attn_f32_bwd((const float*)q, (const float*)k, (const float*)v, (const float*)out, (const float*)dout, lse,
                         (float*)dqkv, delta, B, H, N, dh, DP, ld, s);
-  if (!attn_shape_ok(N, dh, DP, H, ld)) return hipErrorInvalidValue;
-  if ((((uintptr_t)q) | ((uintptr_t)k) | ((uintptr_t)v)) & 15) return hipErrorInvalidValue;
-#define SGL_B(T, DPV)                                                                                  \
-  case DPV:                                                                                            \
-    return bwd_launch<T, DPV>((const T*)q, (const T*)k, (const T*)v, (const T*)out, (const T*)dout, lse, \
-                              (T*)dqkv, delta, B, H, N, dh, ld, s);
-  if (dtype == DT_F16) {
-    switch (DP) {
-      SGL_B(f16, 16) SGL_B(f16, 32) SGL_B(f16, 48) SGL_B(f16, 64) SGL_B(f16, 80) SGL_B(f16, 96)
-    }
-    return hipErrorInvalidValue;
-  }
-  switch (DP) {
-    SGL_B(bf16, 16) SGL_B(bf16, 32) SGL_B(bf16, 48) SGL_B(bf16, 64) SGL_B(bf16, 80) SGL_B(bf16, 96)
-  }
-#undef SGL_B
-  return hipErrorInvalidValue;
+  if (!attn_aligned16(q, k, v)) return hipErrorInvalidValue;
+  const AttnScales sc = attn_scales(dh);
+  return dispatch_attn(dtype, DP, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    constexpr int DPV = decltype(tag)::dp;
+    using C = AttnCfg<DPV>;
+    return with_bool(ld > 0, [&](auto tok) {
+      const dim3 grid = head_grid((N + 127) / 128, B * H), block(256);
+      const int ldk = tok.value ? ld : 0;
+      // dQ first: it also computes delta and leaves the {-lse*log2e, -delta*scale} pairs in `delta` for the dK/dV kernel
+      hipLaunchKernelGGL((attn_bwd_q_kernel<T, DPV, tok.value>), grid, block, C::SMEM_Q, s, (const T*)q, (const T*)k,
+                         (const T*)v, (const T*)out, (const T*)dout, lse, delta, (T*)dqkv, B, H, N, dh, ldk, sc.c, sc.scale);
+      const hipError_t e = hipGetLastError();
+      if (e != hipSuccess) return e;
+      hipLaunchKernelGGL((attn_bwd_kv_kernel<T, DPV, tok.value>), grid, block, C::SMEM_KV, s, (const T*)q, (const T*)k,
+                         (const T*)v, (const T*)dout, delta, (T*)dqkv, B, H, N, dh, ldk, sc.c, sc.scale);
+      return hipGetLastError();
+    });
+  });
 }
 
 }  // namespace sgl

@@ -16,8 +16,7 @@
 // barriers (B = 32 per layer: forward 2.48 -> 1.65 ms, dQ 4.74 -> 2.09 ms, dK/dV 5.38 -> 2.79 ms against synchronous scalar
 // staging; 47 TFLOP/s of fp32 MFMA in the forward.  Strict mode is not the benchmarked path: no LDS-DMA, no anti-phase).
 // q,k,v: fp32, head-major [B][H][N][DP] (ld = 0) or token-major column blocks (ld > 0), as attention_ref.hip.
-#include "common.hip.h"
-#include "kernels.h"
+#include "attention.hip.h"
 
 namespace sgl {
 
@@ -26,12 +25,6 @@ namespace sgl {
 constexpr int AF_MAXD = 96;          // head_dim <= 96 (3 output tiles of 32)
 constexpr int AF_RS = AF_MAXD + 1;   // LDS row stride in floats (odd: the 32 rows of a column read hit 32 banks)
 constexpr int AF_TILE = 32 * AF_RS;  // one staged 32-row tile
-
-__device__ __forceinline__ size_t af_base(int ld, int b, int h, int H, int N, int dh, int DP, int& rs) {
-  if (ld > 0) { rs = ld; return (size_t)b * N * ld + (size_t)h * dh; }
-  rs = DP;
-  return ((size_t)b * H + h) * (size_t)N * DP;
-}
 
 // Tile staging: rows [r0, r0+32) x dh of a row-major source (row stride rs floats, 16-byte aligned rows) are fetched as
 // float4 into registers one tile AHEAD (the loads fly under the current tile's MFMAs) and written to the LDS tile between two
@@ -71,7 +64,7 @@ __global__ __launch_bounds__(256) void attn_f32_fwd_kernel(const float* __restri
   const int li = lane & 31, hh = lane >> 5;
   const int bh = blockIdx.y, h = bh % H, b = bh / H;
   int rs;
-  const size_t hb = af_base(ld, b, h, H, N, dh, DP, rs);
+  const size_t hb = head_rows(ld, b, h, H, N, dh, DP, rs);
   const int q = blockIdx.x * 128 + w * 32 + li;
   const int ks = (dh + 1) / 2;             // k-steps over the head dim (dh is a multiple of 8)
   const int ndt = (dh + 31) / 32;          // 32-row tiles of Oᵀ
@@ -110,7 +103,7 @@ __global__ __launch_bounds__(256) void attn_f32_fwd_kernel(const float* __restri
     float mx = -INFINITY;
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
-      const int key = k0 + 8 * (i >> 2) + 4 * hh + (i & 3);
+      const int key = k0 + ctile_row(i, hh);
       s16[i] = (key < N) ? s16[i] * scale : -INFINITY;
       mx = fmaxf(mx, s16[i]);
     }
@@ -132,7 +125,7 @@ __global__ __launch_bounds__(256) void attn_f32_fwd_kernel(const float* __restri
         for (int i = 0; i < 16; ++i) o[dt][i] *= alpha;
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-          const int krow = 8 * (i >> 2) + 4 * hh + (i & 3);
+          const int krow = ctile_row(i, hh);
           o[dt] = MFMA_F32(vtile[krow * AF_RS + dt * 32 + li], s16[i], o[dt]);
         }
       }
@@ -172,7 +165,7 @@ __global__ __launch_bounds__(256) void attn_f32_bwd_q_kernel(const float* __rest
   const int bh = blockIdx.y, h = bh % H, b = bh / H;
   const int D = H * dh;
   int rs;
-  const size_t hb = af_base(ld, b, h, H, N, dh, DP, rs);
+  const size_t hb = head_rows(ld, b, h, H, N, dh, DP, rs);
   const int q = blockIdx.x * 128 + w * 32 + li;
   const int ks = (dh + 1) / 2, ndt = (dh + 31) / 32, dpad = ndt * 32;
   float qf[AF_MAXD / 2], dof[AF_MAXD / 2];
@@ -220,7 +213,7 @@ __global__ __launch_bounds__(256) void attn_f32_bwd_q_kernel(const float* __rest
       }
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
-      const int key = k0 + 8 * (i >> 2) + 4 * hh + (i & 3);
+      const int key = k0 + ctile_row(i, hh);
       const float p = (key < N) ? expf(S[i] * scale - Lq) : 0.f;
       dP[i] = p * (dP[i] - dl) * scale;
     }
@@ -229,7 +222,7 @@ __global__ __launch_bounds__(256) void attn_f32_bwd_q_kernel(const float* __rest
       if (dt < ndt) {
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-          const int krow = 8 * (i >> 2) + 4 * hh + (i & 3);
+          const int krow = ctile_row(i, hh);
           dq[dt] = MFMA_F32(ktile[krow * AF_RS + dt * 32 + li], dP[i], dq[dt]);
         }
       }
@@ -266,7 +259,7 @@ __global__ __launch_bounds__(256) void attn_f32_bwd_kv_kernel(const float* __res
   const int bh = blockIdx.y, h = bh % H, b = bh / H;
   const int D = H * dh;
   int rs;
-  const size_t hb = af_base(ld, b, h, H, N, dh, DP, rs);
+  const size_t hb = head_rows(ld, b, h, H, N, dh, DP, rs);
   const int key = blockIdx.x * 128 + w * 32 + li;
   const int ks = (dh + 1) / 2, ndt = (dh + 31) / 32, dpad = ndt * 32;
   float kf[AF_MAXD / 2], vf[AF_MAXD / 2];
@@ -313,7 +306,7 @@ __global__ __launch_bounds__(256) void attn_f32_bwd_kv_kernel(const float* __res
     // S[i], dP[i]: query row 8*(i>>2) + 4*hh + (i&3) of the tile, key = this lane's key
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
-      const int qr = 8 * (i >> 2) + 4 * hh + (i & 3);
+      const int qr = ctile_row(i, hh);
       const float p = (q0 + qr < N && key < N) ? expf(S[i] * scale - lrow[qr]) : 0.f;
       S[i] = p;
       dP[i] = p * (dP[i] - drow[qr]) * scale;
@@ -323,7 +316,7 @@ __global__ __launch_bounds__(256) void attn_f32_bwd_kv_kernel(const float* __res
       if (dt < ndt) {
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-          const int qr = 8 * (i >> 2) + 4 * hh + (i & 3);
+          const int qr = ctile_row(i, hh);
           dv[dt] = MFMA_F32(dotile[qr * AF_RS + dt * 32 + li], S[i], dv[dt]);
           dk[dt] = MFMA_F32(qtile[qr * AF_RS + dt * 32 + li], dP[i], dk[dt]);
         }
@@ -354,27 +347,18 @@ __global__ __launch_bounds__(256) void attn_f32_bwd_kv_kernel(const float* __res
 }
 
 // ======================================================================================================
-static bool af_shape_ok(int N, int dh, int DP, int H, int ld) {
-  if (dh % 8 || dh > AF_MAXD || DP < dh || DP % 4) return false;
-  if (ld < 0 || (ld > 0 && (ld < H * dh || ld % 4))) return false;   // float4 row fetches
-  return N > 0;
-}
-
 hipError_t attn_f32_fwd(const float* q, const float* k, const float* v, float* out, float* lse, int B, int H, int N,
                         int dh, int DP, int ld, hipStream_t s) {
-  if (!af_shape_ok(N, dh, DP, H, ld)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(attn_f32_fwd_kernel, dim3((N + 127) / 128, B * H), dim3(256), 0, s, q, k, v, out, lse, H, N, dh, DP,
-                     ld, 1.0f / sqrtf((float)dh));
+                     ld, attn_scales(dh).scale);
   return hipGetLastError();
 }
 
-// delta: scratch of B*H*N floats (the caller's 2*B*H*N buffer is more than enough)
 hipError_t attn_f32_bwd(const float* q, const float* k, const float* v, const float* out, const float* dout,
                         const float* lse, float* dqkv, float* delta, int B, int H, int N, int dh, int DP, int ld,
                         hipStream_t s) {
-  if (!af_shape_ok(N, dh, DP, H, ld)) return hipErrorInvalidValue;
   const dim3 grid((N + 127) / 128, B * H), block(256);
-  const float scale = 1.0f / sqrtf((float)dh);
+  const float scale = attn_scales(dh).scale;
   hipLaunchKernelGGL(attn_f32_bwd_q_kernel, grid, block, 0, s, q, k, v, out, dout, lse, dqkv, delta, H, N, dh, DP, ld, scale);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;

@@ -3,19 +3,9 @@
 // TF:models/siglip/modeling_siglip.py:227-247.  Not a performance path; the bf16 path is attention.hip.
 // q,k,v fp32: token-major [B*N][ld] column blocks of the QKV projection's output (ld > 0; head h of row r at r*ld + h*dh)
 // or, ld = 0, head-major [B][H][N][DP]; out / dout token-major [B*N][H*dh]; dqkv token-major [B*N][3*H*dh].
-#include "common.hip.h"
-#include "kernels.h"
+#include "attention.hip.h"
 
 namespace sgl {
-
-constexpr int AR_MAXD = 2;  // dh <= 128
-
-// element offset of (token 0, column 0) of head (b, h) and the element stride between its token rows
-__device__ __forceinline__ size_t ar_base(int ld, int b, int h, int H, int N, int dh, int DP, int& rs) {
-  if (ld > 0) { rs = ld; return (size_t)b * N * ld + (size_t)h * dh; }
-  rs = DP;
-  return ((size_t)b * H + h) * (size_t)N * DP;
-}
 
 __global__ __launch_bounds__(256) void attn_ref_fwd_kernel(const float* __restrict__ Q, const float* __restrict__ K,
                                                            const float* __restrict__ V, float* __restrict__ out,
@@ -29,7 +19,7 @@ __global__ __launch_bounds__(256) void attn_ref_fwd_kernel(const float* __restri
   const int i = blockIdx.x * 4 + w;
   if (i >= N) return;
   int rs;
-  const size_t hb = ar_base(ld, b, h, H, N, dh, DP, rs);
+  const size_t hb = head_rows(ld, b, h, H, N, dh, DP, rs);
   const float* Qb = Q + hb + (size_t)i * rs;
   const float* Kb = K + hb;
   const float* Vb = V + hb;
@@ -80,7 +70,7 @@ __global__ __launch_bounds__(256) void attn_ref_bwd_q_kernel(const float* __rest
   if (i >= N) return;
   const int D = H * dh;
   int rs;
-  const size_t hb = ar_base(ld, b, h, H, N, dh, DP, rs);
+  const size_t hb = head_rows(ld, b, h, H, N, dh, DP, rs);
   const float* Qb = Q + hb + (size_t)i * rs;
   const float* Kb = K + hb;
   const float* Vb = V + hb;
@@ -135,7 +125,7 @@ __global__ __launch_bounds__(256) void attn_ref_bwd_kv_kernel(const float* __res
   if (j >= N) return;
   const int D = H * dh;
   int rs;
-  const size_t hb = ar_base(ld, b, h, H, N, dh, DP, rs);
+  const size_t hb = head_rows(ld, b, h, H, N, dh, DP, rs);
   const float* Qb = Q + hb;
   const float* Kr = K + hb + (size_t)j * rs;
   const float* Vr = V + hb + (size_t)j * rs;
@@ -171,13 +161,16 @@ __global__ __launch_bounds__(256) void attn_ref_bwd_kv_kernel(const float* __res
   }
 }
 
+// The dynamic-LDS limit is raised on every call: it depends on N (attn_shape_ok keeps it within the 160 KiB of a CU).
+template <typename K>
+static hipError_t ar_allow_lds(K kernel, size_t bytes) {
+  return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+}
+
 hipError_t attn_ref_fwd(const float* q, const float* k, const float* v, float* out, float* lse, int B, int H, int N,
                         int dh, int DP, int ld, hipStream_t s) {
-  if (dh > 128) return hipErrorInvalidValue;
-  const size_t smem = (size_t)4 * (N + 128) * sizeof(float);
-  if (smem > 160 * 1024) return hipErrorInvalidValue;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_ref_fwd_kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+  const size_t smem = attn_ref_lds(N, 1, 1);
+  const hipError_t e = ar_allow_lds(&attn_ref_fwd_kernel, smem);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(attn_ref_fwd_kernel, dim3((N + 3) / 4, B * H), dim3(256), smem, s, q, k, v, out, lse, H, N, dh,
                      DP, ld);
@@ -187,15 +180,10 @@ hipError_t attn_ref_fwd(const float* q, const float* k, const float* v, float* o
 hipError_t attn_ref_bwd(const float* q, const float* k, const float* v, const float* out, const float* dout,
                         const float* lse, float* dqkv, float* delta, int B, int H, int N, int dh, int DP, int ld,
                         hipStream_t s) {
-  if (dh > 128) return hipErrorInvalidValue;
-  const size_t smem_q = (size_t)4 * (N + 256) * sizeof(float);
-  const size_t smem_kv = (size_t)4 * (2 * N + 256) * sizeof(float);
-  if (smem_kv > 160 * 1024) return hipErrorInvalidValue;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_ref_bwd_q_kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_q);
+  const size_t smem_q = attn_ref_lds(N, 1, 2), smem_kv = attn_ref_lds(N, 2, 2);
+  hipError_t e = ar_allow_lds(&attn_ref_bwd_q_kernel, smem_q);
   if (e != hipSuccess) return e;
-  e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_ref_bwd_kv_kernel),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_kv);
+  e = ar_allow_lds(&attn_ref_bwd_kv_kernel, smem_kv);
   if (e != hipSuccess) return e;
   dim3 grid((N + 3) / 4, B * H), block(256);
   hipLaunchKernelGGL(attn_ref_bwd_q_kernel, grid, block, smem_q, s, q, k, v, out, dout, lse, dqkv, delta, H, N, dh, DP,

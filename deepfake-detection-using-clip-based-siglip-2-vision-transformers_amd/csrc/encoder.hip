@@ -1054,7 +1054,7 @@ int attn_backward(const Call& c, const sgl_layer_weights& lw, const sgl_layer_gr
   if (lg.o_w) CK(c.gemm_tn(gbuf, D, lb + lay.r_attn, D, M, D, D, lg.o_w, D, acc, true));
   CK(attn_bwd(q, q + c.head_bytes(), q + 2 * c.head_bytes(), lb + lay.r_attn, dattn,
               reinterpret_cast<const float*>(lb + lay.r_lse), ctx->split ? DT_F32_MFMA : dt, dqkv, c.wsf(lay.w_delta),
-              nullptr, lay.B, ctx->H, lay.N, ctx->dh, ctx->DP, 0, s));
+              lay.B, ctx->H, lay.N, ctx->dh, ctx->DP, 0, s));
   float* gw[3] = {lg.q_w, lg.k_w, lg.v_w};
   float* gb[3] = {lg.q_b, lg.k_b, lg.v_b};
   // when the caller laid the three gradients out back to back (the Python host does), q/k/v are one GEMM
@@ -1384,8 +1384,7 @@ int sgl_op_attn_fwd(int dtype, const void* q, const void* k, const void* v, void
 int sgl_op_attn_bwd(int dtype, const void* q, const void* k, const void* v, const void* out, const void* dout,
                     const float* lse, void* dqkv, float* delta_scratch, int B, int H, int N, int head_dim,
                     int head_dim_pad, int ld_qkv, sgl_stream stream) {
-  CKV(attn_bwd(q, k, v, out, dout, lse, dtype, dqkv, delta_scratch, nullptr, B, H, N, head_dim, head_dim_pad, ld_qkv,
-               (hipStream_t)stream));
+  CKV(attn_bwd(q, k, v, out, dout, lse, dtype, dqkv, delta_scratch, B, H, N, head_dim, head_dim_pad, ld_qkv, (hipStream_t)stream));
   return SGL_OK;
 }
 

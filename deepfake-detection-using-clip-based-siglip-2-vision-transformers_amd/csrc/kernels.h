@@ -143,6 +143,8 @@ hipError_t pos_resize_bwd(const float* dout, int gh, int gw, float* dtable, int 
 hipError_t copy_f32(const float* src, float* dst, size_t n, hipStream_t s);
 hipError_t cast_f32(const float* src, void* dst, int dst_dtype, size_t n, hipStream_t s);
 hipError_t add_f32(const float* a, const float* b, float* out, size_t n, hipStream_t s);  // b may be null
+
+// ---- attention_pool.hip ------------------------------------------------------------------------------
 // attention-pool (1 query per image): q [H*dh] fp32, K/V head-major [B][H][N][DP]
 // One workgroup per (image, head) keeps, in the default 64 KiB LDS window, one fp32 partial per 8-column chunk of every
 // token (the region is reused for the output fold, hence its floor of 256 * 8 floats), the N probabilities (backward: the
@@ -246,7 +248,7 @@ static_assert(tn_plan_is(93312, 1152, 4304, kTnSlabBytes, 256, 3), "fc2 dW");
 static_assert(tn_plan_is(4133, 520, 1152, kTnSlabBytes, 0, 4) && tn_plan(4133, 520, 1152, kTnSlabBytes).m_per == 1088, "digest case");
 static_assert(tn_plan_is(2048, 512, 512, kTnSlabBytes, 256, 2) && tn_plan(2048, 512, 512, kTnSlabBytes).m_per == 1024, "digest case");
 
-// ---- attention.hip -------------------------------------------------------------------------------------
+// ---- attention.hip (attention.hip.h: the shape contract, dispatch and addressing its translation units share) ----
 // q,k,v: ld_qkv > 0: token-major [B*N][ld_qkv] column blocks (head h of row r at r*ld_qkv + h*dh; the QKV projection's
 // plain output, q/k/v = its three D-wide column blocks); ld_qkv == 0: head-major [B][H][N][DP] with zero pad columns.
 // out: token-major [B*N][H*dh]; lse: [B][H][N] (natural log units)
@@ -254,14 +256,15 @@ hipError_t attn_fwd(const void* q, const void* k, const void* v, int dtype, void
                     int N, int dh, int DP, int ld_qkv, hipStream_t s);
 // dout: token-major [B*N][H*dh] (T); dqkv: token-major [B*N][3*H*dh] (T); delta: scratch of 2*B*H*N floats
 hipError_t attn_bwd(const void* q, const void* k, const void* v, const void* out, const void* dout,
-                    const float* lse, int dtype, void* dqkv, float* delta, float* reserved, int B, int H, int N,
-                    int dh, int DP, int ld_qkv, hipStream_t s);
+                    const float* lse, int dtype, void* dqkv, float* delta, int B, int H, int N, int dh, int DP,
+                    int ld_qkv, hipStream_t s);
 
 // ---- attention_probs.hip -------------------------------------------------------------------------------
 // out[b,h,i,j] = exp2(S_ij * c - lse_i * log2e) from head-major q, k [B][H][N][DP] and the forward's lse [B][H][N]: the P
 // the backward kernels rebuild.  mode SGL_ATTN_PROBS_FULL: out (B,H,N,N); SGL_ATTN_PROBS_HEAD_MEAN: out (B,N,N), heads
 // summed in ascending order in registers.  fp32 out, plain stores only, inputs const.  hipErrorInvalidValue for an unknown
-// dtype / mode, a shape attn_probs_shape_ok refuses or 16-bit operands that are not 16-byte aligned.
+// dtype / mode, a shape attn_probs_shape_ok (= attn_shape_ok of attention.hip.h for the probs pass) refuses or 16-bit
+// operands that are not 16-byte aligned.
 bool attn_probs_shape_ok(int dtype, int B, int H, int N, int dh, int DP);
 hipError_t attn_probs(const void* q, const void* k, const float* lse, float* out, int dtype, int B, int H, int N, int dh,
                       int DP, int mode, hipStream_t s);

@@ -217,7 +217,8 @@ def test_bad_shapes_are_err_bad_shape(host, cfg_name):
 
 
 # The pooling head keeps one fp32 partial per 8-column chunk of every token of an image in the 64 KiB LDS window
-# (csrc/kernels.h pool_attn_max_tokens): N <= floor(16376 / (DP / 8 + 1)) forward, floor(16376 / (DP / 8 + 2)) backward.
+# (csrc/kernels.h pool_attn_max_tokens; the kernels are in csrc/attention_pool.hip): N <= floor(16376 / (DP / 8 + 1))
+# forward, floor(16376 / (DP / 8 + 2)) backward.
 # hostile: head dimension 72, DP 80 (so400m's), patch 14 -> 1488 / 1364 tokens; tiny: head dimension 16, DP 16, patch 16
 # -> 5458 / 4094.  (grid, train, accepted): squares either side of each limit, then rectangles just over it (and one exactly at it).
 POOL_LIMIT_CASES = {

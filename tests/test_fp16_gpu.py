@@ -20,6 +20,7 @@ import pytest
 import torch
 
 import golden_util as gu
+from attn_util import attn_reference, run_attention
 
 pytestmark = pytest.mark.gpu
 
@@ -179,40 +180,15 @@ def test_gemm_tn_ws_f16(lib, Mred, N1, N2):
     assert relerr(outs[0], 2 * ref) < TOL_F32_OUT
 
 
-def attn_reference(q, k, v, dout):
-    q, k, v = (t.float().clone().requires_grad_(True) for t in (q, k, v))
-    s = (q @ k.transpose(-1, -2)) * q.shape[-1] ** -0.5
-    o = torch.softmax(s, dim=-1) @ v
-    o.backward(dout.float())
-    return o.detach(), torch.logsumexp(s, dim=-1).detach(), q.grad, k.grad, v.grad
-
-
-def run_attention(lib, dtype, qkv, dout_tok, B, H, N, dh, layout):
+def attention_errors(lib, dtype, qkv, dout_tok, B, H, N, dh, layout):
+    """relerr of O, dQ, dK, dV and the largest |lse| error against fp32 eager + autograd on the same rounded inputs."""
     tdt = {BF16: torch.bfloat16, F16: torch.float16}[dtype]
-    DP = (dh + 15) // 16 * 16
-    D = H * dh
-    x = torch.zeros(3, B, H, N, DP, device="cuda", dtype=tdt)
-    x[..., :dh] = qkv.to(tdt)
-    if layout == "token":
-        ld = 3 * D + 8
-        tok = torch.full((B * N, ld), float("nan"), device="cuda", dtype=tdt)
-        tok[:, :3 * D] = x[..., :dh].permute(1, 3, 0, 2, 4).reshape(B * N, 3 * D)
-        ptrs = [P(tok) + j * D * tok.element_size() for j in range(3)]
-    else:
-        ld, ptrs = 0, [P(x[0]), P(x[1]), P(x[2])]
-    dout = dout_tok.to(tdt)
-    out = torch.full((B * N, D), float("nan"), device="cuda", dtype=tdt)
-    lse = torch.empty(B, H, N, device="cuda")
-    ok(lib.sgl_op_attn_fwd(dtype, ptrs[0], ptrs[1], ptrs[2], P(out), P(lse), B, H, N, dh, DP, ld, stream()))
-    dqkv = torch.full((B * N, 3 * D), float("nan"), device="cuda", dtype=tdt)
-    delta = torch.empty(2, B, H, N, device="cuda")
-    ok(lib.sgl_op_attn_bwd(dtype, ptrs[0], ptrs[1], ptrs[2], P(out), P(dout), P(lse), P(dqkv), P(delta), B, H, N, dh,
-                           DP, ld, stream()))
-    ref = attn_reference(x[0][..., :dh], x[1][..., :dh], x[2][..., :dh], dout.view(B, N, H, dh).permute(0, 2, 1, 3))
-    got = dqkv.view(B, N, 3, H, dh).permute(2, 0, 3, 1, 4).float()
-    o_tok = ref[0].permute(0, 2, 1, 3).reshape(B * N, D)
-    return dict(out=relerr(out, o_tok), lse=(lse - ref[1]).abs().max().item(), dq=relerr(got[0], ref[2]),
-                dk=relerr(got[1], ref[3]), dv=relerr(got[2], ref[4]))
+    q, k, v = qkv.to(tdt)
+    dout = dout_tok.to(tdt).view(B, N, H, dh).permute(0, 2, 1, 3)
+    out, lse, dq, dk, dv = run_attention(lib, dtype, layout, q, k, v, dout)
+    ref = attn_reference(q, k, v, dout)
+    return dict(out=relerr(out, ref[0]), lse=(lse - ref[1]).abs().max().item(), dq=relerr(dq, ref[2]),
+                dk=relerr(dk, ref[3]), dv=relerr(dv, ref[4]))
 
 
 @pytest.mark.parametrize("B,H,N,dh", [(2, 16, 729, 72), (1, 12, 196, 64), (2, 2, 9, 72), (1, 2, 130, 32)])
@@ -223,8 +199,8 @@ def test_attention_f16_fwd_bwd(lib, B, H, N, dh, layout):
     torch.manual_seed(N + dh)
     qkv = torch.randn(3, B, H, N, dh, device="cuda") * 1.2
     dout = torch.randn(B * N, H * dh, device="cuda")
-    e16 = run_attention(lib, F16, qkv, dout, B, H, N, dh, layout)
-    eb = run_attention(lib, BF16, qkv, dout, B, H, N, dh, layout)
+    e16 = attention_errors(lib, F16, qkv, dout, B, H, N, dh, layout)
+    eb = attention_errors(lib, BF16, qkv, dout, B, H, N, dh, layout)
     print(f"[attn fp16 {B},{H},{N},{dh} {layout}] " + ", ".join(f"{k} {e16[k]:.2e} (bf16 {eb[k]:.2e})" for k in e16))
     assert e16["out"] < 3e-3 and e16["lse"] < 2e-3
     for k in ("dq", "dk", "dv"):

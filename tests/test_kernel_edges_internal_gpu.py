@@ -1,6 +1,6 @@
 """GPU tests of the HIP kernels only the encoder calls, through the thin ``sgl_op_*`` entry points at the end of
 csrc/encoder.hip: the pooling head's one-query attention, the position-table resize backward, the weight-shadow casts,
-the bf16x3 operand splits, and the small sums and copies (csrc/elementwise.hip, csrc/layernorm.hip).
+the bf16x3 operand splits, and the small sums and copies (csrc/attention_pool.hip, csrc/elementwise.hip, csrc/layernorm.hip).
 
 Same discipline as tests/test_kernel_edges_gpu.py and tests/test_kernel_edges_aux_gpu.py: every output element against a
 float64 reference of the same operation on the same rounded inputs (tests/kernel_ref.py; tests/test_kernel_ref_host.py
