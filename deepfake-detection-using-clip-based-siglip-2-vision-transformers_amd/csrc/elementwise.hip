@@ -518,6 +518,23 @@ hipError_t add_f32(const float* a, const float* b, float* out, size_t n, hipStre
 }
 hipError_t copy_f32(const float* src, float* dst, size_t n, hipStream_t s) { return add_f32(src, nullptr, dst, n, s); }
 
+// dst[i] (+)= |0 * src[i]|: +0 where src[i] is finite, NaN where it is inf or NaN.  For a gradient that is zero in real
+// arithmetic and is therefore never summed (the k_proj bias): it still has to turn non-finite when the pass it belongs to
+// did, so that an overflowing step is seen in every gradient ("Non-finite values").
+__global__ __launch_bounds__(256) void zero_unless_nonfinite_kernel(const float* __restrict__ src, float* __restrict__ dst,
+                                                                    int n, int accumulate) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const float z = fabsf(src[i] * 0.f);
+  dst[i] = accumulate ? dst[i] + z : z;
+}
+hipError_t zero_unless_nonfinite(const float* src, float* dst, int n, int accumulate, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(zero_unless_nonfinite_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src, dst, n,
+                     accumulate);
+  return hipGetLastError();
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void cast_f32_kernel(const float* __restrict__ a, T* __restrict__ out, size_t n) {
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256)

@@ -72,6 +72,9 @@ constexpr int kMaxLayers = 128;
 constexpr size_t kSplitWsBytes = (size_t)256 * 256 * 256 * 4;
 static_assert(tn_plan_is(93312, 1152, 1152, kSplitWsBytes, 384, 12), "out_proj dW in the encoder's workspace");
 static_assert(tn_plan_is(93312, 3456, 1152, kSplitWsBytes, 384, 4), "QKV dW in the encoder's workspace");
+// tests/test_nonfinite_gpu.py holds the scratch-less 2048 x 512 x 512 route to a float64 bound, not to bits, because its
+// splits add with fp32 atomics: that rests on the plan splitting this shape
+static_assert(tn_plan(2048, 512, 512, ~(size_t)0).splits > 1, "2048 x 512 x 512 dW without scratch: more than one split");
 
 // one of q / k / v of a whole batch, head-major [B][H][N][DP]
 inline size_t head_bytes(const sgl_ctx* c, int B, int N) { return (size_t)B * c->H * N * c->DP * c->es; }
@@ -1067,13 +1070,24 @@ int attn_backward(const Call& c, const sgl_layer_weights& lw, const sgl_layer_gr
   // Bias gradients of the three projections = column sums of dQ, dK, dV over all tokens.  Only dQ's needs a pass:
   //   sum_n dK[n,:] = sum_q Q[q,:] * scale * (sum_n dS[q,n]) and sum_n dS[q,n] = sum_n P (dP - delta) = delta - delta = 0:
   //     the k_proj bias has NO gradient (softmax is invariant to a per-query shift of the scores) — exact zeros here,
-  //     rounding noise around zero in the reference;
+  //     rounding noise around zero in the reference.  The reference's noise is NaN when dS is not finite, though, and an
+  //     overflowing pass has to show in every gradient: a non-finite dS or q makes every column sum of dQ = dS K
+  //     non-finite, so the zeros are written as 0 * (the column sums of dQ): +0 from finite sums, NaN otherwise;
   //   sum_n dV[n,:] = sum_q dO[q,:] * (sum_n P[q,n]) = sum_q dO[q,:] = colsum(dY) * W_o, and colsum(dY) is the out_proj bias
   //     gradient the LayerNorm backward above already produced (gsum): a 1152-vector times W_o instead of a read of dV.
   // (One column-sum pass over a third of dqkv instead of all of it: 116 -> ~40 us per block at B = 128.)
   if (gb[0]) RET(c.bias_grad(dqkv, 3 * D, M, D, D, gb[0], acc));
-  if (gb[1] && !acc) CK(hipMemsetAsync(gb[1], 0, (size_t)D * 4, s));
   if (gb[2]) CK(vecmat_f32(gsum, lw.o_w, D, D, c.wsf(lay.w_cspart), gb[2], acc, s));
+  if (gb[1]) {
+    // without a q_proj bias gradient the column sums of dQ go to gsum: its last reader in this block was the line above,
+    // and the LN1 backward that follows rewrites it before anything reads it again
+    const float* qsum = gb[0];
+    if (!qsum) {
+      RET(c.bias_grad(dqkv, 3 * D, M, D, D, gsum, 0));
+      qsum = gsum;
+    }
+    CK(zero_unless_nonfinite(qsum, gb[1], D, acc, s));
+  }
   return SGL_OK;
 }
 

@@ -143,6 +143,8 @@ hipError_t pos_resize_bwd(const float* dout, int gh, int gw, float* dtable, int 
 hipError_t copy_f32(const float* src, float* dst, size_t n, hipStream_t s);
 hipError_t cast_f32(const float* src, void* dst, int dst_dtype, size_t n, hipStream_t s);
 hipError_t add_f32(const float* a, const float* b, float* out, size_t n, hipStream_t s);  // b may be null
+// dst[i] (+)= +0 where src[i] is finite, NaN where it is not
+hipError_t zero_unless_nonfinite(const float* src, float* dst, int n, int accumulate, hipStream_t s);
 
 // ---- attention_pool.hip ------------------------------------------------------------------------------
 // attention-pool (1 query per image): q [H*dh] fp32, K/V head-major [B][H][N][DP]

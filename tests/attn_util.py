@@ -107,16 +107,17 @@ def launch_attention(lib, dtype, layout, q, k, v, dout, exact_extent=False):
     return st_f, st_b, out, lse, dqkv
 
 
-def run_attention(lib, dtype, layout, q, k, v, dout, exact_extent=False):
+def run_attention(lib, dtype, layout, q, k, v, dout, exact_extent=False, written=True):
     """launch_attention with both calls accepted and every guard band checked.  Returns O, lse, dQ, dK, dV as
-    [B, H, N, dh] (lse [B, H, N])."""
+    [B, H, N, dh] (lse [B, H, N]).  written=False (inputs that hold a NaN on purpose) leaves out the check that no NaN of
+    the pre-filled bodies survived; the guard bands are checked all the same."""
     B, H, N, dh = q.shape
     st_f, st_b, out, lse, dqkv = launch_attention(lib, dtype, layout, q, k, v, dout, exact_extent)
     ok(st_f)
     ok(st_b)
-    out.check("attention forward out")
-    lse.check("attention forward lse")
-    dqkv.check("attention backward dqkv")
+    out.check("attention forward out", written)
+    lse.check("attention forward lse", written)
+    dqkv.check("attention backward dqkv", written)
     O = out.got().view(B, N, H, dh).permute(0, 2, 1, 3)
     g = dqkv.got().view(B, N, 3, H, dh).permute(2, 0, 3, 1, 4)
     return O, lse.got().view(B, H, N), g[0], g[1], g[2]

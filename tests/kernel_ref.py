@@ -1190,9 +1190,10 @@ def split3_layout(x, Cs, b_side, stacked):
 
 def split3_special_values():
     """+-0, fp32 subnormals, bf16 rounding ties (round to even both ways), values next to ties, the largest fp32 that does
-    not round to a bf16 infinity, and its neighbours."""
+    not round to a bf16 infinity, and its neighbours; then NaN and +-inf (hi keeps the class, lo = x - hi is NaN)."""
     bits = [0x00000000, 0x80000000, 0x00000001, 0x807FFFFF, 0x00400000, 0x3F808000, 0x3F818000, 0x3F808001, 0x3F807FFF,
-            0xBF818000, 0x7F7F7FFF, 0xFF7F7FFF, 0x7F7F0000, 0x7F7E8000, 0x00800000, 0x00808000, 0x3EAAAAAB, 0x4B7FFFFF]
+            0xBF818000, 0x7F7F7FFF, 0xFF7F7FFF, 0x7F7F0000, 0x7F7E8000, 0x00800000, 0x00808000, 0x3EAAAAAB, 0x4B7FFFFF,
+            0x7FC00000, 0x7F800000, 0xFF800000]
     return torch.tensor(bits, dtype=torch.int64).to(torch.int32).view(torch.float32)
 
 

@@ -18,6 +18,7 @@ import torch
 import kernel_ref as kr
 from attn_util import DEV, Guarded, P, check_attention, ok, rup, stream, tdt_of  # noqa: F401  (re-exported)
 from kernel_ref import BF16, BF16X3, EPS32, F16, F32
+from op_runners import gemm_nt, padded, run_gemm_nt, run_gemm_nt_qkv, run_gemm_tn, run_layernorm  # noqa: F401  (re-exported)
 
 pytestmark = pytest.mark.gpu
 LO = [BF16, F16]
@@ -38,22 +39,9 @@ def randn(g, *shape):
     return torch.randn(*shape, device=DEV, generator=g)
 
 
-def padded(t, ld, fill=float("nan")):
-    """[rows, w] -> the same values as the first w columns of a [rows, ld] matrix whose slack holds `fill`."""
-    out = torch.full((t.shape[0], ld), fill, device=t.device, dtype=t.dtype)
-    out[:, :t.shape[1]] = t
-    return out
-
-
 # =========================================================================================================
 # GEMM NT
 # =========================================================================================================
-def gemm_nt(lib, dtype, A, lda, B, ldb, M, N, K, epi, out, ldo, out2=None, ldo2=0, bias=None, res=None, ldr=0, aux=None,
-            ldaux=0, pos=None, pos_rows=1, tokens=1, heads=1, hd=8, hdp=8, batch=1):
-    return lib.sgl_op_gemm_nt(dtype, P(A), lda, P(B), ldb, M, N, K, epi, out, ldo, out2, ldo2, P(bias), P(res), ldr,
-                              P(aux), ldaux, P(pos), pos_rows, tokens, heads, hd, hdp, batch, stream())
-
-
 def nt_operands(dtype, M, N, K, seed):
     """A [M, K], B [N, K] in the operand dtype inside matrices whose leading dimension is 8 above K, NaN in the slack."""
     g = gen(seed)
@@ -72,23 +60,14 @@ def check_nt_epilogue(lib, dtype, M, N, K, epi, seed=0):
     f32_out = epi in (2, 5, 6)
     odt = torch.float32 if f32_out else tdt
     u, tiny = kr.UNIT[odt], kr.TINY[odt]
-    ldo = N + 8
-    out = Guarded(M, N, ldo, odt)
-    out2 = res = aux = pos = None
-    kw = {}
-    if epi == 1:
-        out2 = Guarded(M, N, N + 16, odt)
-        kw = dict(out2=out2.ptr, ldo2=N + 16)
+    res = aux = pos = None
     if epi == 2:
         res = padded(randn(g, M, N), N + 8)
-        kw = dict(res=res, ldr=N + 8)
     if epi == 4:
         aux = padded((randn(g, M, N) * 1.5).to(odt), N + 24)
-        kw = dict(aux=aux, ldaux=N + 24)
     if epi == 5:
         pos = randn(g, 37, N)
-        kw = dict(pos=pos, pos_rows=37)
-    ok(gemm_nt(lib, dtype, A, K + 8, B, K + 8, M, N, K, epi, out.ptr, ldo, bias=None if epi == 4 else bias, **kw))
+    out, out2 = run_gemm_nt(lib, dtype, M, N, K, epi, A, B, None if epi == 4 else bias, res, aux, pos)
     what = f"NT {kr.DT_NAME[dtype]} M={M} N={N} K={K} epi={epi}"
     out.check(what)
     if out2 is not None:
@@ -196,9 +175,7 @@ def test_gemm_nt_qkv_scatter_guard(lib, dtype, batch, tokens, heads, hd):
     A = padded(randn(g, M, K).to(tdt), K + 8)
     B = padded((randn(g, N, K) / math.sqrt(K)).to(tdt), K + 8)
     bias = randn(g, N)
-    out = Guarded(3 * batch * heads * tokens, hdp, hdp, tdt)
-    ok(gemm_nt(lib, dtype, A, K + 8, B, K + 8, M, N, K, 3, out.ptr, 0, bias=bias, tokens=tokens, heads=heads, hd=hd,
-               hdp=hdp, batch=batch))
+    out = run_gemm_nt_qkv(lib, dtype, A, B, bias, batch, tokens, heads, hd, hdp)
     what = f"QKV {kr.DT_NAME[dtype]} hd={hd} M={M}"
     out.check(what)
     ref, bound, _ = kr.gemm_ref(A[:, :K], B[:, :K], K, kr.UNIT[tdt], [bias[None, :].expand(M, N)], kr.TINY[tdt])
@@ -220,13 +197,7 @@ def check_tn(lib, dtype, Mred, N1, N2, splits=1, accumulate=0, ws_bytes=None, se
     A = padded(randn(g, rows, N1).to(tdt), lda)
     B = padded(randn(g, rows, N2).to(tdt), ldb)
     prior = randn(g, N1, N2) * 3 if accumulate else None
-    out = Guarded(N1, N2, ldo, torch.float32, prior=prior)
-    if ws_bytes is None:
-        ok(lib.sgl_op_gemm_tn(dtype, P(A), lda, P(B), ldb, Mred, N1, N2, splits, out.ptr, ldo, accumulate, stream()))
-    else:
-        ws = torch.empty(max(ws_bytes, 16), device=DEV, dtype=torch.uint8)
-        ok(lib.sgl_op_gemm_tn_ws(dtype, P(A), lda, P(B), ldb, Mred, N1, N2, splits, out.ptr, ldo, accumulate, P(ws),
-                                 ws_bytes, stream()))
+    out = run_gemm_tn(lib, dtype, A, B, Mred, N1, N2, ldo, splits, accumulate, prior, ws_bytes)
     what = f"TN {kr.DT_NAME[dtype]} Mred={Mred} N1={N1} N2={N2} acc={accumulate}"
     out.check(what)
     ref, bound = kr.gemm_tn_ref(A[:Mred, :N1], B[:Mred, :N2], Mred, prior)
@@ -356,28 +327,17 @@ def check_layernorm(lib, x, odt_code, seed=0, dres=True, dgamma=True, dbeta=True
     odt = tdt_of(odt_code)
     u = kr.UNIT[odt]
     gam, bet = randn(g, D) * 0.2 + 1, randn(g, D) * 0.1
-    y = Guarded(M, D, D, odt)
-    mean = Guarded(1, M, M, torch.float32)
-    rstd = Guarded(1, M, M, torch.float32)
-    ok(lib.sgl_op_layernorm_fwd(P(x), P(gam), P(bet), y.ptr, odt_code, mean.ptr, rstd.ptr, M, D, 1e-6, stream()))
     what = f"LayerNorm M={M} D={D} {kr.DT_NAME[odt_code]}"
-    for t, n in ((y, "y"), (mean, "mean"), (rstd, "rstd")):
-        t.check(f"{what} {n}")
-    mu_k, rs_k = mean.got()[0], rstd.got()[0]
     dy_code = odt_code if dy_code is None else dy_code
     lp_code = odt_code if lp_code is None else lp_code
     lpt = tdt_of(lp_code)
     dy = randn(g, M, D).to(tdt_of(dy_code))
     dr = randn(g, M, D) if dres else None
-    dx = Guarded(M, D, D, torch.float32)
-    dxlp = Guarded(M, D, D, lpt)
-    dg = Guarded(1, D, D, torch.float32) if dgamma else None
-    db = Guarded(1, D, D, torch.float32) if dbeta else None
-    nblk = max(1, min(768, (M + 3) // 4))
-    scratch = torch.empty(nblk * 3 * D, device=DEV)
-    ok(lib.sgl_op_layernorm_bwd(P(dy), dy_code, P(x), mean.ptr, rstd.ptr, P(gam), P(dr), dx.ptr, dxlp.ptr, lp_code,
-                                dg.ptr if dg else None, db.ptr if db else None, P(scratch), scratch.numel() * 4, M, D,
-                                stream()))
+    o = run_layernorm(lib, x, gam, bet, dy, dr, odt_code, dy_code, lp_code, dgamma, dbeta)
+    y, mean, rstd, dx, dxlp, dg, db = (o[n] for n in ("y", "mean", "rstd", "dx", "dx_lp", "dgamma", "dbeta"))
+    for t, n in ((y, "y"), (mean, "mean"), (rstd, "rstd")):
+        t.check(f"{what} {n}")
+    mu_k, rs_k = mean.got()[0], rstd.got()[0]
     dx.check(what + " dx")
     dxlp.check(what + " dx_lp")
     dg_ref = torch.zeros(D, device=DEV, dtype=torch.float64)
