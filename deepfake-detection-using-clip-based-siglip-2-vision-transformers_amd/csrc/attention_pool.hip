@@ -217,4 +217,58 @@ hipError_t pool_attn_bwd(const float* q, const void* K, const void* V, int dtype
   });
 }
 
+// The probe row's counterpart of attention_grad_probs.hip: da[b,h,n] = sum_d dout[b,h*dh+d] * V[b,h,n,d] (one FMA chain,
+// d ascending, over the dh real columns: V's pad is never read), combined with the probabilities the forward kept.
+// One thread per output element; MEAN sums the heads in ascending order and divides once.  Plain stores, inputs const.
+template <typename T, bool MEAN>
+__global__ __launch_bounds__(256) void pool_attn_grad_probs_kernel(const T* __restrict__ V, const float* __restrict__ probs,
+                                                                   const float* __restrict__ dout,
+                                                                   float* __restrict__ out, int H, int N, int dh, int DP,
+                                                                   size_t total, float heads, int kind) {
+  const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const size_t n = idx % (size_t)N, z = idx / (size_t)N;
+  const int nh = MEAN ? H : 1;
+  float acc = 0.f;
+  for (int hd = 0; hd < nh; ++hd) {
+    const size_t bh = MEAN ? z * H + hd : z;
+    const float* go = dout + bh * (size_t)dh;   // [B][H*dh]: head (b, h) starts at (b*H + h) * dh
+    const T* vr = V + (bh * (size_t)N + n) * (size_t)DP;
+    float da = 0.f;
+    for (int c = 0; c < dh; c += 8) {
+      float vv[8];
+      Vec<T, 8>::ld(vr + c, vv);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) da = fmaf(go[c + j], vv[j], da);
+    }
+    float x = da;
+    if (kind != SGL_ATTN_GRAD_DP) {
+      x = probs[bh * (size_t)N + n] * da;
+      if (kind == SGL_ATTN_GRAD_RELEVANCE) x = x > 0.f ? x : (x != x ? x : 0.f);
+    }
+    acc += x;
+  }
+  if constexpr (MEAN) acc /= heads;
+  out[idx] = acc;
+}
+
+hipError_t pool_attn_grad_probs(const void* V, int dtype, const float* probs, const float* dout, float* out, int B, int H,
+                                int N, int dh, int DP, int kind, int mode, hipStream_t s) {
+  if (B < 1 || H < 1 || N < 1 || dh < 8 || DP % 8 || dh % 8 || dh > DP) return hipErrorInvalidValue;
+  if (mode != SGL_ATTN_PROBS_FULL && mode != SGL_ATTN_PROBS_HEAD_MEAN) return hipErrorInvalidValue;
+  if (kind != SGL_ATTN_GRAD_DP && kind != SGL_ATTN_GRAD_PDP && kind != SGL_ATTN_GRAD_RELEVANCE) return hipErrorInvalidValue;
+  const size_t total = (size_t)B * (mode ? 1 : H) * N;
+  if ((total + 255) / 256 >= (1ull << 31)) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)((total + 255) / 256));
+  return pool_dispatch(dtype, [&](auto elem) {
+    using T = decltype(elem);
+    if (mode)
+      hipLaunchKernelGGL((pool_attn_grad_probs_kernel<T, true>), grid, dim3(256), 0, s, (const T*)V, probs, dout, out, H, N,
+                         dh, DP, total, (float)H, kind);
+    else
+      hipLaunchKernelGGL((pool_attn_grad_probs_kernel<T, false>), grid, dim3(256), 0, s, (const T*)V, probs, dout, out, H,
+                         N, dh, DP, total, (float)H, kind);
+  });
+}
+
 }  // namespace sgl

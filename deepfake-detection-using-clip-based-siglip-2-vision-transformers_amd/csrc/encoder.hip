@@ -920,10 +920,29 @@ int sgl_forward_slots(sgl_ctx* ctx, const sgl_weights* w, const void* shadow, co
 // -------------------------------------------------------------------------------------------------------
 namespace {
 
+// A request for a gradient-weighted attention map (sgl_backward_*_pa), checked before the step enqueues anything.
+// block: a block's (N x N) maps; otherwise the pooling head's probe row.
+int check_attn_grad_req(const Call& c, const sgl_attn_grad_req* req, bool block, bool available) {
+  if (!req) return SGL_OK;
+  sgl_ctx* ctx = c.ctx;
+  if (!req->out) return SGL_ERR_NULL;
+  if (ctx->recompute || ctx->mx || !available) return SGL_ERR_UNSUPPORTED;
+  if (req->mode != SGL_ATTN_PROBS_FULL && req->mode != SGL_ATTN_PROBS_HEAD_MEAN) return SGL_ERR_UNSUPPORTED;
+  if (req->kind != SGL_ATTN_GRAD_DP && req->kind != SGL_ATTN_GRAD_PDP && req->kind != SGL_ATTN_GRAD_RELEVANCE)
+    return SGL_ERR_UNSUPPORTED;
+  // a block's launch has its own grid limit: refused here, not after the step's first GEMM is enqueued
+  const size_t rows = block ? (size_t)c.lay.N : 1;
+  if (block && !attn_grad_probs_shape_ok(ctx->split ? DT_F32_MFMA : ctx->dt, c.lay.B, ctx->H, c.lay.N, ctx->dh, ctx->DP))
+    return SGL_ERR_BAD_SHAPE;
+  const size_t heads = req->mode == SGL_ATTN_PROBS_FULL ? (size_t)ctx->H : 1;
+  if (req->out_bytes < (size_t)c.lay.B * heads * rows * (size_t)c.lay.N * sizeof(float)) return SGL_ERR_WORKSPACE;
+  return SGL_OK;
+}
+
 // Pooling head backward from d_pooled: the head's parameter gradients, and dlast [M][D] = the gradient w.r.t. the
 // post_layernorm output, d_last_hidden (nullable) included
 int head_backward(const Call& c, const sgl_weights* w, const sgl_grads* g, const float* d_pooled,
-                  const float* d_last_hidden, float* dlast) {
+                  const float* d_last_hidden, float* dlast, const sgl_attn_grad_req* req) {
   sgl_ctx* ctx = c.ctx;
   const Layout& lay = c.lay;
   hipStream_t s = c.s;
@@ -951,6 +970,9 @@ int head_backward(const Call& c, const sgl_weights* w, const sgl_grads* g, const
   CK(c.gemm_nt(hg, D, c.sh(ctx->sh_hwo_t), D, B, D, D, EPI_F32, DT_F32, epi_f32(hdao, D)));
   if (g->out_proj_w) CK(c.gemm_tn(hg, D, act + lay.a_ao, D, B, D, D, g->out_proj_w, D, acc, false));
   RET(c.bias_grad(hg, D, B, D, D, g->out_proj_b, acc));
+  if (req)
+    CK(pool_attn_grad_probs(kv + c.head_bytes(), dt, c.actf(lay.a_probs), hdao, req->out, B, ctx->H, lay.N, ctx->dh,
+                            ctx->DP, req->kind, req->mode, s));
   // attention pool backward
   void* dkv = c.wsp(lay.w_dqkv);  // [M][2D]
   float* dqpart = c.wsf(lay.w_hdqpart);
@@ -1043,7 +1065,7 @@ int mlp_backward(const Call& c, const sgl_layer_weights& lw, const sgl_layer_gra
 // The block's attention: xmid = x_in + out_proj(attn(qkv(LN1 x_in))).  In: gbuf = lowp(d xmid), gsum = colsum(d xmid).
 // Out: dqkv [M][3D] and the gradients of out_proj and the three projections; dx is not touched (the residual).
 int attn_backward(const Call& c, const sgl_layer_weights& lw, const sgl_layer_grads& lg, const ShadowLayer& sl,
-                  const char* lb, int acc) {
+                  const char* lb, int acc, const sgl_attn_grad_req* req) {
   sgl_ctx* ctx = c.ctx;
   const Layout& lay = c.lay;
   hipStream_t s = c.s;
@@ -1054,6 +1076,11 @@ int attn_backward(const Call& c, const sgl_layer_weights& lw, const sgl_layer_gr
   float* gsum = c.wsf(lay.w_gsum);
   const char* q = lb + lay.r_qkv;
   CK(c.gemm_nt(gbuf, D, c.sh(sl.wo_t), D, M, D, D, EPI_STORE, dt, epi_store(dattn, D)));
+  // dattn = dO lives until ln1_backward reuses its buffer: the one point where q, k, v, lse and dO are all at hand
+  if (req)
+    CK(attn_grad_probs(q, q + c.head_bytes(), q + 2 * c.head_bytes(), dattn, reinterpret_cast<const float*>(lb + lay.r_lse),
+                       req->out, ctx->split ? DT_F32_MFMA : dt, lay.B, ctx->H, lay.N, ctx->dh, ctx->DP, req->kind,
+                       req->mode, s));
   if (lg.o_w) CK(c.gemm_tn(gbuf, D, lb + lay.r_attn, D, M, D, D, lg.o_w, D, acc, true));
   CK(attn_bwd(q, q + c.head_bytes(), q + 2 * c.head_bytes(), lb + lay.r_attn, dattn,
               reinterpret_cast<const float*>(lb + lay.r_lse), ctx->split ? DT_F32_MFMA : dt, dqkv, c.wsf(lay.w_delta),
@@ -1122,9 +1149,18 @@ int sgl_backward_begin_p(sgl_ctx* ctx, const sgl_weights* w, const void* shadow,
                          const float* hs_last, const float* d_last_hidden, const float* d_pooled,
                          const float* d_tap_last, const void* saved, size_t saved_bytes, void* ws, size_t ws_bytes,
                          sgl_stream stream) {
+  return sgl_backward_begin_pa(ctx, w, shadow, g, B, H, W, hs_last, d_last_hidden, d_pooled, d_tap_last, saved,
+                               saved_bytes, ws, ws_bytes, stream, nullptr);
+}
+
+int sgl_backward_begin_pa(sgl_ctx* ctx, const sgl_weights* w, const void* shadow, const sgl_grads* g, int B, int H, int W,
+                          const float* hs_last, const float* d_last_hidden, const float* d_pooled,
+                          const float* d_tap_last, const void* saved, size_t saved_bytes, void* ws, size_t ws_bytes,
+                          sgl_stream stream, const sgl_attn_grad_req* req) {
   if (!ctx || !w || !shadow || !g || !hs_last) return SGL_ERR_NULL;
   Call c;
   RET(begin_call(c, BACKWARD, ctx, shadow, B, H, W, saved, saved_bytes, ws, ws_bytes, stream));
+  RET(check_attn_grad_req(c, req, false, ctx->cfg.use_head && d_pooled));
   const Layout& lay = c.lay;
   hipStream_t s = c.s;
   const int D = ctx->D, M = lay.M;
@@ -1134,7 +1170,7 @@ int sgl_backward_begin_p(sgl_ctx* ctx, const sgl_weights* w, const void* shadow,
   const float* dlast = d_last_hidden;  // gradient w.r.t. post_layernorm output
   if (ctx->cfg.use_head && d_pooled) {
     float* dlast_buf = c.wsf(lay.w_dlast);
-    RET(head_backward(c, w, g, d_pooled, d_last_hidden, dlast_buf));
+    RET(head_backward(c, w, g, d_pooled, d_last_hidden, dlast_buf, req));
     dlast = dlast_buf;
   }
   RET(zero_dead_grads(c, g, !d_pooled, !dlast));
@@ -1167,10 +1203,19 @@ int sgl_backward_layer(sgl_ctx* ctx, const sgl_weights* w, const void* shadow, c
 int sgl_backward_layer_p(sgl_ctx* ctx, const sgl_weights* w, const void* shadow, const sgl_grads* g, int layer, int B,
                          int H, int W, const float* hs_in, const float* d_tap, int need_dx, const void* saved,
                          size_t saved_bytes, void* ws, size_t ws_bytes, sgl_stream stream) {
+  return sgl_backward_layer_pa(ctx, w, shadow, g, layer, B, H, W, hs_in, d_tap, need_dx, saved, saved_bytes, ws, ws_bytes,
+                               stream, nullptr);
+}
+
+int sgl_backward_layer_pa(sgl_ctx* ctx, const sgl_weights* w, const void* shadow, const sgl_grads* g, int layer, int B,
+                          int H, int W, const float* hs_in, const float* d_tap, int need_dx, const void* saved,
+                          size_t saved_bytes, void* ws, size_t ws_bytes, sgl_stream stream,
+                          const sgl_attn_grad_req* req) {
   if (!ctx || !w || !shadow || !g || !hs_in || !g->layers || !w->layers) return SGL_ERR_NULL;
   if (layer < 0 || layer >= ctx->L) return SGL_ERR_BAD_SHAPE;
   Call c;
   RET(begin_call(c, BACKWARD, ctx, shadow, B, H, W, saved, saved_bytes, ws, ws_bytes, stream));
+  RET(check_attn_grad_req(c, req, true, true));
   const int acc = g->accumulate;
   const sgl_layer_weights& lw = w->layers[layer];
   const sgl_layer_grads& lg = g->layers[layer];
@@ -1180,7 +1225,7 @@ int sgl_backward_layer_p(sgl_ctx* ctx, const sgl_weights* w, const void* shadow,
   char* lb = c.block(layer);
   if (c.lay.rc) RET(block_to_fc1(c, lw, sl, lb, hs_in, true));
   RET(mlp_backward(c, lw, lg, sl, lb, acc));
-  RET(attn_backward(c, lw, lg, sl, lb, acc));
+  RET(attn_backward(c, lw, lg, sl, lb, acc, req));
   float* dx = c.wsf(c.lay.w_dx);
   if (d_tap) CK(add_f32(dx, d_tap, dx, (size_t)c.lay.M * ctx->D, c.s));
   if (need_dx || lg.ln1_w || lg.ln1_b) RET(ln1_backward(c, lw, lg, sl, lb, hs_in, acc));
@@ -1413,6 +1458,19 @@ int sgl_op_attn_probs(int dtype, const void* q, const void* k, const float* lse,
   return SGL_OK;
 }
 
+int sgl_op_attn_grad_probs(int dtype, const void* q, const void* k, const void* v, const void* dout, const float* lse,
+                           float* out, int B, int H, int N, int head_dim, int head_dim_pad, int kind, int mode,
+                           sgl_stream stream) {
+  if (!q || !k || !v || !dout || !lse || !out) return SGL_ERR_NULL;
+  if (B < 1 || H < 1 || N < 1 || head_dim < 1 || head_dim_pad < 1 || head_dim > head_dim_pad) return SGL_ERR_BAD_SHAPE;
+  if (dtype != DT_F32 && dtype != DT_BF16 && dtype != DT_F32_MFMA && dtype != DT_F16) return SGL_ERR_UNSUPPORTED;
+  if (mode != SGL_ATTN_PROBS_FULL && mode != SGL_ATTN_PROBS_HEAD_MEAN) return SGL_ERR_UNSUPPORTED;
+  if (kind != SGL_ATTN_GRAD_DP && kind != SGL_ATTN_GRAD_PDP && kind != SGL_ATTN_GRAD_RELEVANCE) return SGL_ERR_UNSUPPORTED;
+  if (!attn_grad_probs_shape_ok(dtype, B, H, N, head_dim, head_dim_pad)) return SGL_ERR_BAD_SHAPE;
+  CKV(attn_grad_probs(q, k, v, dout, lse, out, dtype, B, H, N, head_dim, head_dim_pad, kind, mode, (hipStream_t)stream));
+  return SGL_OK;
+}
+
 int sgl_attention_probs(sgl_ctx* ctx, int B, int H, int W, const void* saved, size_t saved_bytes, int layer, int mode,
                         float* out, size_t out_bytes, sgl_stream stream) {
   if (!ctx || !saved || !out) return SGL_ERR_NULL;
@@ -1489,6 +1547,18 @@ int sgl_op_pool_attn_bwd(int dtype, const float* q, const void* K, const void* V
     return SGL_ERR_BAD_SHAPE;
   if (!lo_dtype_ok(dtype) || !aligned16(K) || !aligned16(V) || !aligned16(dkv)) return SGL_ERR_UNSUPPORTED;
   CKV(pool_attn_bwd(q, K, V, dtype, probs, dout, dkv, dq_partial, B, H, N, head_dim, head_dim_pad, (hipStream_t)stream));
+  return SGL_OK;
+}
+
+int sgl_op_pool_attn_grad_probs(int dtype, const void* V, const float* probs, const float* dout, float* out, int B, int H,
+                                int N, int head_dim, int head_dim_pad, int kind, int mode, sgl_stream stream) {
+  if (!V || !probs || !dout || !out) return SGL_ERR_NULL;
+  if (B <= 0 || H <= 0 || N <= 0 || head_dim <= 0 || head_dim % 8 || head_dim_pad % 8 || head_dim > head_dim_pad)
+    return SGL_ERR_BAD_SHAPE;
+  if (!lo_dtype_ok(dtype) || !aligned16(V)) return SGL_ERR_UNSUPPORTED;
+  if (mode != SGL_ATTN_PROBS_FULL && mode != SGL_ATTN_PROBS_HEAD_MEAN) return SGL_ERR_UNSUPPORTED;
+  if (kind != SGL_ATTN_GRAD_DP && kind != SGL_ATTN_GRAD_PDP && kind != SGL_ATTN_GRAD_RELEVANCE) return SGL_ERR_UNSUPPORTED;
+  CKV(pool_attn_grad_probs(V, dtype, probs, dout, out, B, H, N, head_dim, head_dim_pad, kind, mode, (hipStream_t)stream));
   return SGL_OK;
 }
 

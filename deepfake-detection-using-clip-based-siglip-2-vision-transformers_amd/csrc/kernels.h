@@ -273,4 +273,17 @@ hipError_t attn_probs(const void* q, const void* k, const float* lse, float* out
 // out [B][N] = (sum_h probs[b][h][n]) / H, heads in ascending order (the pooling head's probe map, head mean)
 hipError_t probs_head_mean(const float* probs, float* out, int B, int H, int N, hipStream_t s);
 
+// ---- attention_grad_probs.hip ----------------------------------------------------------------------------
+// dP[b,h,i,j] = sum_d dout[b,i,h*dh+d] * v[b,h,j,d] (kind SGL_ATTN_GRAD_DP), P * dP (PDP) or its NaN-keeping relu
+// (RELEVANCE), P as attn_probs.  q, k, v head-major [B][H][N][DP]; dout token-major [B*N][H*dh] in the operand dtype (what
+// attn_bwd takes); modes, output shapes, stores and refusals as attn_probs, plus an unknown kind.  The shape contract is
+// attn_probs' and, for 16-bit operands, 32-bit byte offsets into one image's dout rows.
+bool attn_grad_probs_shape_ok(int dtype, int B, int H, int N, int dh, int DP);
+hipError_t attn_grad_probs(const void* q, const void* k, const void* v, const void* dout, const float* lse, float* out,
+                           int dtype, int B, int H, int N, int dh, int DP, int kind, int mode, hipStream_t s);
+// attention_pool.hip: the probe row's form.  da[b,h,n] = sum_d dout[b,h*dh+d] * V[b,h,n,d], combined with probs [B][H][N]
+// by `kind`; out (B,H,N) or, head mean, (B,N).  Operands as pool_attn_bwd.
+hipError_t pool_attn_grad_probs(const void* V, int dtype, const float* probs, const float* dout /*[B][H*dh] fp32*/,
+                                float* out, int B, int H, int N, int dh, int DP, int kind, int mode, hipStream_t s);
+
 }  // namespace sgl

@@ -5,6 +5,7 @@ Surface H (HuggingFace-style; ``Siglip2sidafrozen.py:753,757-768,771,787-793``):
     ``SiglipVisionModelHIP.from_pretrained(path_or_name)``, ``model(pixel_values=..., output_hidden_states=True,
     interpolate_pos_encoding=True)`` → ``.pooler_output`` / ``.last_hidden_state`` / ``.hidden_states``;
     ``output_attentions=True`` → ``.attentions`` / ``.pooling_attention`` (detached), ``model.attention_rollout(x)``;
+    ``model.capture_attention_gradients()`` round a forward + backward, ``model.attention_relevance(x, score_fn)``;
     ``.config.hidden_size``; ``.vision_model.embeddings`` / ``.vision_model.encoder.layers[i]`` for freezing;
     ``state_dict`` keys equal HF ``SiglipVisionModel`` keys.
 Surface O (open_clip-style; ``cifake_binary_classifier.py:625-638,721``, ``hidf_video_classifier.py:259-273,307``):
@@ -328,6 +329,70 @@ class SiglipVisionModelHIP(nn.Module):
             r = attention_rollout(out.attentions, residual, pooling=out.pooling_attention)
         P = self.config.patch_size
         return r.view(r.shape[0], pixel_values.shape[-2] // P, pixel_values.shape[-1] // P)
+
+    @torch.compiler.disable
+    def capture_attention_gradients(self, layers=None, heads: str = "mean", kind: str = "relevance", sink=None):
+        """Context manager round a forward + backward of this model: the backward also writes, per requested block, the
+        gradient of whatever was differentiated with respect to the block's attention probabilities P, formed by a HIP
+        kernel at the one point of the backward where q, k, v, the log-sum-exp and dO all exist.  ``kind``: ``"grad"``
+        (dScore/dP, what HF's eager ``attentions[l].grad`` holds), ``"prob_grad"`` (P * dScore/dP) or ``"relevance"``
+        (its relu; a NaN stays NaN).  ``heads``: ``"mean"`` gives (B,N,N) per block (the per-head tensor never exists),
+        ``"all"`` (B,heads,N,N).  ``layers``: block indices (negative ones count from the end; default: every block).
+
+            with model.capture_attention_gradients() as cap:
+                model(pixel_values=x.requires_grad_()).pooler_output[:, 1].sum().backward()
+            cap.maps[layer], cap.pooling
+
+        ``cap.pooling`` is the pooling head's map, (B,N) / (B,heads,N), when the score went through ``pooler_output``.
+        With ``sink(layer, tensor)`` one buffer is reused: the sink is called after each block's kernel is enqueued,
+        blocks in descending order, and ``cap.maps`` stays empty.  The maps are detached; every gradient the backward
+        produces is bit-identical with and without the capture.  At exit a requested block the backward never reached
+        (a frozen prefix without an input gradient) raises RuntimeError.  Not on a ``recompute=True`` model and not with
+        ``compute_dtype="mxfp8"`` (RuntimeError).  A graph break under ``torch.compile``."""
+        from .encoder_state import ATTN_GRAD_KINDS, AttnGradCapture
+        if self._recompute:
+            raise RuntimeError("capture_attention_gradients on a recompute=True model: recompute keeps no per-block q, k to "
+                               "rebuild the maps from; use a model without recompute for attention gradients")
+        if self.compute_dtype in INFERENCE_ONLY:
+            raise RuntimeError(f"capture_attention_gradients with compute_dtype={self.compute_dtype!r}: the inference-only "
+                               "mode has no backward; use compute_dtype='bf16' / 'fp16' / 'bf16x3' / 'fp32' for attention "
+                               "gradients")
+        if kind not in ATTN_GRAD_KINDS:
+            raise ValueError(f"kind must be one of {sorted(ATTN_GRAD_KINDS)}, got {kind!r}")
+        blocks, head_mean = self._attention_request(layers, heads)
+        return AttnGradCapture(self._grads, self.config.num_hidden_layers, blocks, head_mean, ATTN_GRAD_KINDS[kind], sink)
+
+    @torch.compiler.disable
+    def attention_relevance(self, pixel_values, score_fn, interpolate_pos_encoding: bool = True):
+        """Class-specific relevance of every patch for ``score_fn(VisionModelOutput) -> (B,)`` or a scalar (e.g.
+        ``lambda o: head(o.pooler_output)[:, 1]``): gradient-weighted attention relevance (``heads.attention_relevance``),
+        (B, gh, gw), detached.  One saving forward on a detached copy of the input that requires a gradient (so every
+        block is differentiated) and one ``torch.autograd.grad`` of the summed score, during which the row vector
+        ``r <- r + r A_l`` is propagated from the pooling head's map down through the blocks: one (B,N,N) buffer lives
+        at a time.  No parameter's ``.grad`` and nothing of the caller's tensor is touched."""
+        if not self.use_head:
+            raise RuntimeError("attention_relevance reads the relevance through the pooling head's map and this model has "
+                               "none; capture the block maps with capture_attention_gradients() and use "
+                               "heads.attention_relevance(maps) for the (B,N,N) relevance")
+        x = pixel_values.detach().clone().requires_grad_(True)
+        state = {}
+
+        def sink(layer, A):
+            r = state.get("r", cap.pooling)
+            if r is not None:
+                state["r"] = r + torch.bmm(r.unsqueeze(1), A).squeeze(1)
+
+        with torch.enable_grad(), self.capture_attention_gradients(heads="mean", kind="relevance", sink=sink) as cap:
+            out = self(pixel_values=x, interpolate_pos_encoding=interpolate_pos_encoding)
+            score = score_fn(out)
+            torch.autograd.grad(score.sum(), x)
+        if cap.pooling is None:
+            raise RuntimeError("attention_relevance: score_fn did not depend on pooler_output, so the pooling head has no "
+                               "map to read the relevance through; use capture_attention_gradients() and "
+                               "heads.attention_relevance(maps) instead")
+        r = state.get("r", cap.pooling)
+        P = self.config.patch_size
+        return r.detach().view(r.shape[0], x.shape[-2] // P, x.shape[-1] // P)
 
     def _run(self, pixel_values, output_hidden_states, interpolate_pos_encoding, hidden_state_ids, patches,
              keep_arena: bool = False):

@@ -169,8 +169,9 @@ def encoder_bwd(grads: Sequence[Optional[torch.Tensor]], taps: Sequence[torch.Te
                 hs_rest: torch.Tensor, params: Sequence[torch.Tensor], handle: int, image_hw: Sequence[int],
                 interp: bool, want_pooled: bool, tap_ids: Sequence[int], needs: Sequence[bool],
                 recompute: bool = False, want_px: bool = False, px_channels_last: bool = False) -> List[torch.Tensor]:
-    """sgl_backward_begin_p -> sgl_backward_layer_p (L-1 ... first trainable block) -> sgl_backward_embed, on the context
-    of the policy the forward ran with (recompute: each sgl_backward_layer_p recomputes its block first).
+    """sgl_backward_begin_pa -> sgl_backward_layer_pa (L-1 ... first trainable block) -> sgl_backward_embed, on the context
+    of the policy the forward ran with (recompute: each sgl_backward_layer_pa recomputes its block first).  The request
+    argument of the two is NULL (the plain _p step) unless a ``capture_attention_gradients`` of the module is active.
     grads = [d pooled, d last_hidden_state, d tap...] (None = no gradient).  Returns the flat fp32 gradient chunks of
     ``GradPlan.layout(needs)`` (the DDP all-reduce units); the autograd formula slices the per-parameter views out of
     them outside the op, so no output of the op aliases another.
@@ -223,17 +224,32 @@ def encoder_bwd(grads: Sequence[Optional[torch.Tensor]], taps: Sequence[torch.Te
         stream = _lib.current_stream_handle(dev)
         _, wts, shadow = shadows.binding()
         cx = contexts.get(bool(recompute))
-        st = lib.sgl_backward_begin_p(cx, C.byref(wts), shadow.data_ptr(), C.byref(g), B, H, W, hs_ptr[L],
-                                      _lib.ptr(d_last), _lib.ptr(d_pooled), _lib.ptr(tap_grads[L]),
-                                      saved.data_ptr(), sizes[1], ws.data_ptr(), sizes[2], stream)
-        _lib.check(st, "sgl_backward_begin_p", cx)
+        # an active capture_attention_gradients: the steps it wants a map from carry a request (NULL: the plain step)
+        cap = plan.capture
+        heads, N = cfg.num_attention_heads, hs_rest.shape[1] // B
+
+        def attn_grad_request(step):
+            if cap is None or (step == L and d_pooled is None):
+                return None, None
+            return cap.request(step, B, heads, N, dev)
+
+        amap, req = attn_grad_request(L)
+        st = lib.sgl_backward_begin_pa(cx, C.byref(wts), shadow.data_ptr(), C.byref(g), B, H, W, hs_ptr[L],
+                                       _lib.ptr(d_last), _lib.ptr(d_pooled), _lib.ptr(tap_grads[L]), saved.data_ptr(),
+                                       sizes[1], ws.data_ptr(), sizes[2], stream, C.byref(req) if req else None)
+        _lib.check(st, "sgl_backward_begin_pa", cx)
+        if req:
+            cap.delivered(L, amap)
         group_done("head")
         for l in range(L - 1, stop - 1, -1):
             need_dx = 1 if (l > stop or train_emb or want_px) else 0
-            st = lib.sgl_backward_layer_p(cx, C.byref(wts), shadow.data_ptr(), C.byref(g), l, B, H, W, hs_ptr[l],
-                                          _lib.ptr(tap_grads[l]), need_dx, saved.data_ptr(), sizes[1], ws.data_ptr(),
-                                          sizes[2], stream)
-            _lib.check(st, f"sgl_backward_layer_p[{l}]", cx)
+            amap, req = attn_grad_request(l)
+            st = lib.sgl_backward_layer_pa(cx, C.byref(wts), shadow.data_ptr(), C.byref(g), l, B, H, W, hs_ptr[l],
+                                           _lib.ptr(tap_grads[l]), need_dx, saved.data_ptr(), sizes[1], ws.data_ptr(),
+                                           sizes[2], stream, C.byref(req) if req else None)
+            _lib.check(st, f"sgl_backward_layer_pa[{l}]", cx)
+            if req:
+                cap.delivered(l, amap)
             group_done(table.block_label[l])
         d_pixels = None
         if want_px:

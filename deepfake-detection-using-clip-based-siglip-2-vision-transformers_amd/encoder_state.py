@@ -4,7 +4,8 @@
 ``Contexts``        the C contexts (plain / recompute), the ``sgl_query_sizes`` cache and the workspace; destroys the
                     contexts when it dies, which is the only place they are destroyed;
 ``WeightShadows``   the shadow arena, what it is current for, the weights struct, and which generation a forward used;
-``GradPlan``        the gradient chunk layout, the flat buffers behind it and the grads struct.
+``GradPlan``        the gradient chunk layout, the flat buffers behind it and the grads struct; and, while one is
+                    active, the ``AttnGradCapture`` the next backward writes attention-gradient maps for.
 
 None of them is copied or pickled with the module: a copy gets fresh ones (``SiglipVisionModelHIP.__copy__``).
 """
@@ -326,6 +327,7 @@ class GradPlan:
     def __init__(self, table: ParamTable):
         self.table = table
         self.reducer = None
+        self.capture = None         # the active AttnGradCapture (capture_attention_gradients), consulted by encoder_bwd
         self._layouts = {}
         self._buffers = {}
         self._forwards = 0          # training forwards so far: a buffer is not reused within one autograd pass
@@ -409,3 +411,70 @@ class GradPlan:
         g, layers = self.table.fill(_lib.SglGrads, lambda i: _lib.ptr(slot[i]))
         g.accumulate = 0
         return g, layers
+
+
+# ---------------------------------------------------------------------------------------------------------
+# attention-gradient capture
+# ---------------------------------------------------------------------------------------------------------
+ATTN_GRAD_KINDS = {"grad": _lib.ATTN_GRAD_DP, "prob_grad": _lib.ATTN_GRAD_PDP, "relevance": _lib.ATTN_GRAD_RELEVANCE}
+
+
+class AttnGradCapture:
+    """What ``SiglipVisionModelHIP.capture_attention_gradients`` returns: a context manager round a forward + backward.
+    While it is active, ``encoder_bwd`` asks it for a request per backward step (``request``) and tells it when the
+    step's call is enqueued (``delivered``).  Afterwards ``maps[layer]`` holds the map of each requested block the
+    backward reached, (B,N,N) or (B,heads,N,N), and ``pooling`` the pooling head's, (B,N) or (B,heads,N) (None when the
+    model has no head or the score did not go through ``pooler_output``).  With ``sink`` the blocks share ONE buffer:
+    ``sink(layer, tensor)`` is called after each block's call is enqueued (blocks arrive in descending order, on the
+    current stream) and must consume the tensor before returning control to the backward: the next block overwrites it."""
+
+    def __init__(self, plan, num_layers: int, layers, head_mean: bool, kind: int, sink=None):
+        self._plan, self.L = plan, num_layers
+        self.layers, self.head_mean, self.kind, self.sink = list(layers), head_mean, kind, sink
+        self.mode = _lib.ATTN_PROBS_HEAD_MEAN if head_mean else _lib.ATTN_PROBS_FULL
+        self.maps, self.pooling = {}, None
+        self._wanted = set(self.layers)
+        self._seen = set()
+        self._buf = None
+
+    def __enter__(self):
+        if self._plan.capture is not None:
+            raise RuntimeError("capture_attention_gradients: another capture is already active on this model")
+        self._plan.capture = self
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        self._plan.capture = None
+        self._buf = None
+        if exc_type is None:
+            missing = sorted(self._wanted - self._seen)
+            if missing:
+                raise RuntimeError(
+                    f"capture_attention_gradients: the backward never reached block(s) {missing}: blocks below the first "
+                    "trainable one get no gradient unless the input does; call pixel_values.requires_grad_() before the "
+                    "forward (model.attention_relevance does), or request only blocks that train")
+        return False
+
+    def request(self, layer: int, B: int, heads: int, N: int, dev):
+        """(tensor, SglAttnGradReq) for backward step ``layer`` (L: the pooling head), or (None, None)."""
+        pool = layer == self.L
+        if not pool and layer not in self._wanted:
+            return None, None
+        shape = ((B,) if self.head_mean else (B, heads)) + ((N,) if pool else (N, N))
+        if self.sink is not None and not pool:
+            if self._buf is None or self._buf.shape != shape or self._buf.device != dev:
+                self._buf = torch.empty(shape, dtype=torch.float32, device=dev)
+            out = self._buf
+        else:
+            out = torch.empty(shape, dtype=torch.float32, device=dev)
+        return out, _lib.SglAttnGradReq(out.data_ptr(), out.numel() * 4, self.kind, self.mode)
+
+    def delivered(self, layer: int, out: torch.Tensor) -> None:
+        if layer == self.L:
+            self.pooling = out
+            return
+        self._seen.add(layer)
+        if self.sink is not None:
+            self.sink(layer, out)
+        else:
+            self.maps[layer] = out

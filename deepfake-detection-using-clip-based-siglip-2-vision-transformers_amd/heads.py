@@ -189,6 +189,32 @@ def attention_rollout(attentions, residual: float = 0.5, pooling: Optional[torch
     return torch.bmm(p.unsqueeze(1), R).squeeze(1)
 
 
+def attention_relevance(maps, pooling: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Gradient-weighted attention relevance (Chefer et al. 2021, "Generic Attention-model Explainability") from the
+    per-block maps ``A_l = mean_h relu(P_l * dScore/dP_l)``, e.g. the ``.maps`` of
+    ``SiglipVisionModelHIP.capture_attention_gradients(kind="relevance")``, first block first ((B,H,N,N) tensors are
+    averaged over heads, (B,N,N) ones taken as is).  ``R <- R + A_l R`` from ``R = I``: the product of ``I + A_l``, last
+    block leftmost, (B,N,N) in fp32.  With ``pooling`` (the pooling head's map, (B,H,N) or its head mean (B,N)) the
+    result is the row ``pooling @ R``: (B,N), one relevance value per patch.  Plain torch (``bmm``)."""
+    R = None
+    for A in maps:
+        A = A.float()
+        if A.dim() == 4:
+            A = A.mean(1)
+        if R is None:
+            R = A + torch.eye(A.shape[-1], dtype=A.dtype, device=A.device)
+        else:
+            R = R + torch.bmm(A, R)
+    if R is None:
+        raise ValueError("attention_relevance needs at least one map")
+    if pooling is None:
+        return R
+    p = pooling.float()
+    if p.dim() == 3:
+        p = p.mean(1)
+    return torch.bmm(p.unsqueeze(1), R).squeeze(1)
+
+
 def l2_normalize(f: torch.Tensor, eps: float = 0.0) -> torch.Tensor:
     """`f / f.norm(dim=-1, keepdim=True)` (cifake_binary_classifier.py:728, hidf_video_classifier.py:308);
     eps=1e-6 is the `train_fusion_head_only.py:106` form."""

@@ -18,6 +18,7 @@ SEG_EVAL_AUC_BINS = 4096       # SGL_SEG_EVAL_AUC_BINS
 SEG_TERM_FOCAL, SEG_TERM_BOUNDARY, SEG_TERM_TV = 1, 2, 4   # SGL_SEG_TERM_*: optional terms of sgl_op_seg_loss_ex_*
 SGL_RECOMPUTE_NONE, SGL_RECOMPUTE_BLOCKS = 0, 1   # sgl_create_ex activation policies
 ATTN_PROBS_FULL, ATTN_PROBS_HEAD_MEAN = 0, 1      # SGL_ATTN_PROBS_*: modes of sgl_op_attn_probs / sgl_attention_probs
+ATTN_GRAD_DP, ATTN_GRAD_PDP, ATTN_GRAD_RELEVANCE = 0, 1, 2   # SGL_ATTN_GRAD_*: kinds of sgl_op_attn_grad_probs
 EPI_STORE, EPI_BIAS_GELU, EPI_RES_F32, EPI_QKV, EPI_GELU_BWD, EPI_POS_F32, EPI_F32 = range(7)
 STATUS = {0: "ok", -1: "bad shape", -2: "unsupported configuration", -3: "buffer too small", -4: "HIP error",
           -5: "null pointer"}
@@ -66,6 +67,10 @@ class SglAdamwAux(C.Structure):
 class SglAmpState(C.Structure):
     _fields_ = [("found_inf", C.c_float), ("skipped", C.c_int32), ("inv_bc1", C.c_float), ("inv_sqrt_bc2", C.c_float),
                 ("reserved", C.c_int32 * 4)]
+
+
+class SglAttnGradReq(C.Structure):
+    _fields_ = [("out", _fp), ("out_bytes", C.c_size_t), ("kind", C.c_int), ("mode", C.c_int)]
 
 
 class SglCastMat(C.Structure):
@@ -133,6 +138,11 @@ def load():
                                           _fp, _fp, _fp, sz, _fp, sz, _fp])
     _sig(lib, "sgl_backward_layer_p", i, [C.c_void_p, C.POINTER(SglWeights), _fp, C.POINTER(SglGrads), i, i, i, i, _fp,
                                           _fp, i, _fp, sz, _fp, sz, _fp])
+    preq = C.POINTER(SglAttnGradReq)
+    _sig(lib, "sgl_backward_begin_pa", i, [C.c_void_p, C.POINTER(SglWeights), _fp, C.POINTER(SglGrads), i, i, i, _fp, _fp,
+                                           _fp, _fp, _fp, sz, _fp, sz, _fp, preq])
+    _sig(lib, "sgl_backward_layer_pa", i, [C.c_void_p, C.POINTER(SglWeights), _fp, C.POINTER(SglGrads), i, i, i, i, _fp,
+                                           _fp, i, _fp, sz, _fp, sz, _fp, preq])
     _sig(lib, "sgl_backward_begin", i, [C.c_void_p, C.POINTER(SglWeights), _fp, C.POINTER(SglGrads), i, i, i, _fp, _fp,
                                         _fp, _fp, _fp, sz, _fp, sz, _fp])
     _sig(lib, "sgl_backward_layer", i, [C.c_void_p, C.POINTER(SglWeights), _fp, C.POINTER(SglGrads), i, i, i, i, _fp,
@@ -156,6 +166,8 @@ def load():
     _sig(lib, "sgl_op_attn_fwd", i, [i, _fp, _fp, _fp, _fp, _fp, i, i, i, i, i, i, _fp])
     _sig(lib, "sgl_op_attn_bwd", i, [i, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, i, i, i, i, i, i, _fp])
     _sig(lib, "sgl_op_attn_probs", i, [i, _fp, _fp, _fp, _fp, i, i, i, i, i, i, _fp])
+    _sig(lib, "sgl_op_attn_grad_probs", i, [i, _fp, _fp, _fp, _fp, _fp, _fp, i, i, i, i, i, i, i, _fp])
+    _sig(lib, "sgl_op_pool_attn_grad_probs", i, [i, _fp, _fp, _fp, _fp, i, i, i, i, i, i, i, _fp])
     _sig(lib, "sgl_attention_probs", i, [C.c_void_p, i, i, i, _fp, sz, i, i, _fp, sz, _fp])
     _sig(lib, "sgl_op_colsum", i, [i, _fp, i, i, i, _fp, i, _fp, sz, _fp])
     _sig(lib, "sgl_op_im2col", i, [_fp, i, _fp, i, i, i, i, i, i, _fp])

@@ -339,6 +339,55 @@ int sgl_op_attn_probs(int dtype, const void* q, const void* k, const float* lse,
  * sgl_query_sizes(train = 1) reports, or out_bytes below the result -> SGL_ERR_WORKSPACE. */
 int sgl_attention_probs(sgl_ctx* ctx, int B, int H, int W, const void* saved, size_t saved_bytes, int layer, int mode,
                         float* out, size_t out_bytes, sgl_stream stream);
+/* ---- gradient-weighted attention maps (new symbols; sgl_abi_version() stays 3: nothing existing changed) --------------
+ * The gradient of a score with respect to the attention probabilities of a block, formed where the backward has every
+ * operand: q, k, v head-major [B][H][N][head_dim_pad] with zero pad columns and lse [B][H][N] as sgl_op_attn_probs takes
+ * them, and dout token-major [B*N][H*head_dim] in the operand dtype, exactly what sgl_op_attn_bwd takes.
+ *   dP[b,h,i,j] = sum_d dout[b*N+i, h*head_dim+d] * v[b,h,j,d]      P = the expression of sgl_op_attn_probs
+ *   kind SGL_ATTN_GRAD_DP: dP (what autograd leaves in `.grad` of an eager softmax);  SGL_ATTN_GRAD_PDP: P * dP;
+ *   SGL_ATTN_GRAD_RELEVANCE: x > 0 ? x : (x != x ? x : 0) of x = P * dP, a relu that keeps a NaN.
+ * mode SGL_ATTN_PROBS_FULL: out fp32 (B,H,N,N); SGL_ATTN_PROBS_HEAD_MEAN: out fp32 (B,N,N), heads summed in ascending
+ * order in registers, one division by H.  dtype as sgl_op_attn_fwd.  Every input is const; every element of out is written
+ * by exactly one plain store: two calls give the same bits.  A head reads its own head_dim columns of dout only: the
+ * 16-byte chunk of a padded k-step that lies in the next head is read as zero, never multiplied by v's zero pad.
+ * Errors, in the order and with the codes of sgl_op_attn_probs (v and dout join the NULL and alignment checks), plus an
+ * unknown kind -> SGL_ERR_UNSUPPORTED; 16-bit operands also need N * H * head_dim * 2 < 2^31 (SGL_ERR_BAD_SHAPE). */
+enum { SGL_ATTN_GRAD_DP = 0, SGL_ATTN_GRAD_PDP = 1, SGL_ATTN_GRAD_RELEVANCE = 2 };
+int sgl_op_attn_grad_probs(int dtype, const void* q, const void* k, const void* v, const void* dout, const float* lse,
+                           float* out, int B, int H, int N, int head_dim, int head_dim_pad, int kind, int mode,
+                           sgl_stream stream);
+/* The pooling head's form: da[b,h,n] = sum_d dout[b, h*head_dim+d] * V[b,h,n,d], combined with probs [B][H][N] by `kind`
+ * as above; out fp32 (B,H,N) (FULL) or (B,N) (HEAD_MEAN).  V, probs, dout as sgl_op_pool_attn_bwd takes them (dtype
+ * SGL_DTYPE_F32 / BF16 / F16, V 16-byte aligned, head_dim % 8 == 0, head_dim_pad % 8 == 0).  Errors: a NULL pointer ->
+ * SGL_ERR_NULL; a dimension < 1 or an inconsistent head_dim -> SGL_ERR_BAD_SHAPE; an unknown dtype, kind or mode, or a
+ * misaligned V -> SGL_ERR_UNSUPPORTED. */
+int sgl_op_pool_attn_grad_probs(int dtype, const void* V, const float* probs, const float* dout, float* out, int B, int H,
+                                int N, int head_dim, int head_dim_pad, int kind, int mode, sgl_stream stream);
+/* A request to write one such map during a backward step.  out: fp32 device buffer of out_bytes >= the result. */
+typedef struct {
+  float* out;
+  size_t out_bytes;
+  int kind; /* SGL_ATTN_GRAD_* */
+  int mode; /* SGL_ATTN_PROBS_* */
+} sgl_attn_grad_req;
+/* sgl_backward_layer_p / sgl_backward_begin_p with an optional request; req == NULL is exactly those functions.
+ * sgl_backward_layer_pa: once the out_proj dX GEMM has written the gradient of the block's attention output, the map of
+ * block `layer` is enqueued on the same stream from the block's saved q, k, v, lse with the context's attention dtype;
+ * out (B,heads,N,N) or (B,N,N).  sgl_backward_begin_pa: the pooling head's map, once the gradient of its attention output
+ * exists; out (B,heads,N) or (B,N).  Nothing but req->out is written, and every gradient and workspace byte the backward
+ * produces is bit-identical with and without a request.
+ * Errors of a request, after the argument and arena checks of the plain call and before anything is enqueued: req->out
+ * NULL -> SGL_ERR_NULL; a recompute or SGL_DTYPE_MXFP8 context, the begin variant on a model without the head or without
+ * d_pooled, or an unknown kind or mode -> SGL_ERR_UNSUPPORTED; the block variant at a (B, N) whose launch
+ * sgl_op_attn_grad_probs refuses -> SGL_ERR_BAD_SHAPE; req->out_bytes below the result -> SGL_ERR_WORKSPACE. */
+int sgl_backward_layer_pa(sgl_ctx* ctx, const sgl_weights* w, const void* shadow, const sgl_grads* g, int layer, int B,
+                          int H, int W, const float* hs_in, const float* d_tap, int need_dx, const void* saved,
+                          size_t saved_bytes, void* ws, size_t ws_bytes, sgl_stream stream,
+                          const sgl_attn_grad_req* req);
+int sgl_backward_begin_pa(sgl_ctx* ctx, const sgl_weights* w, const void* shadow, const sgl_grads* g, int B, int H, int W,
+                          const float* hs_last, const float* d_last_hidden, const float* d_pooled,
+                          const float* d_tap_last, const void* saved, size_t saved_bytes, void* ws, size_t ws_bytes,
+                          sgl_stream stream, const sgl_attn_grad_req* req);
 int sgl_op_colsum(int dtype, const void* in, int ld, int M, int N, float* out, int accumulate, float* scratch,
                   size_t scratch_bytes, sgl_stream stream);
 int sgl_op_im2col(const float* pixels, int channels_last, void* out, int out_dtype, int B, int H, int W, int P, int Kp,
