@@ -66,6 +66,26 @@ __device__ __forceinline__ void epi_qkv(float* v, const float* bias, TOut* dst, 
     for (int k = 1; k <= pad_chunks; ++k) Vec<TOut, NV>::st_nt(dst + k * NV, z);
   }
 }
+// One 16-byte chunk of the head-major QKV walk (store_tile_qkv_heads, gemm_bf16_v2.hip): the chunk's eight values, bias
+// already added, arrive as two halves read from LDS in either order (`swapped`: `first` holds columns 4..7; the order is
+// what keeps those reads free of bank conflicts), are rounded like Vec<TOut, 8>::st_nt rounds them and leave as one
+// streaming store.  `pad`: a chunk of the columns [head_dim, head_dim_pad), stored as +0 in-stream with the data chunks
+// round it instead of by a second, branched store.
+template <typename TOut>
+__device__ __forceinline__ void epi_qkv_halves(f32x4 first, f32x4 second, bool swapped, bool pad, TOut* dst) {
+  static_assert(sizeof(TOut) == 2, "16-bit outputs: eight columns are one 16-byte chunk");
+  lo_x4<TOut> pf, ps;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    pf[j] = (TOut)first[j];
+    ps[j] = (TOut)second[j];
+  }
+  const u32x2 uf = __builtin_bit_cast(u32x2, pf), us = __builtin_bit_cast(u32x2, ps);
+  const u32x2 lo = swapped ? us : uf, hi = swapped ? uf : us;
+  u32x4 o = {lo[0], lo[1], hi[0], hi[1]};
+  if (pad) o = u32x4{0u, 0u, 0u, 0u};
+  __builtin_nontemporal_store(o, reinterpret_cast<u32x4*>(dst));
+}
 // u: the saved pre-activation, or gelu'(u) itself with EpiParams::gelu_grad_form; leaves the stored values in v
 template <typename TOut, int NV>
 __device__ __forceinline__ void epi_gelu_bwd(const EpiParams& p, float* v, const float* u, TOut* dst) {

@@ -317,9 +317,19 @@ static hipError_t gemm_nt_mfma(const void* A, int lda, const void* B, int ldb, i
     // 1.125 x the work instead of 1,825 at the bench batch, same sums bit for bit.  Measured at M = 93,312 it is 6-7 %
     // faster except with the fp32-residual epilogue at K = 1152 (out_proj: 308 against 310 us, inside the run-to-run
     // spread: that launch is bound by its 860 MB of residual traffic, not by tiles), which therefore stays on the 256x256
-    // tile like everything else (N = 3456 with the QKV scatter, 4352, 768, ...).  SGL_NT_TILE=256|384 (developer switch,
-    // read once) forces one tile for every shape and epilogue it supports.
+    // tile like everything else (N = 4352, 768, ..., the QKV scatter of models whose heads are not 72 wide, and the fp32
+    // QKV output of the bf16x3 strict mode).
+    // The QKV scatter with a 16-bit output, 72-wide heads stored 80 wide and N = 3 heads 72 a multiple of 288 (so400m: N =
+    // 3456 = 12 tiles where the 256-wide tile runs 14) takes the 256x288 tile: four whole heads per tile, written head by
+    // head in runs of whole 160-byte rows (store_tile_qkv_heads), same sums bit for bit.
+    // SGL_NT_TILE=256|384|288 (developer switch, read once) forces one tile for every shape and epilogue it supports;
+    // under 288 a QKV scatter that tile cannot take is refused, not sent elsewhere.
     static const int tile_env = getenv("SGL_NT_TILE") ? atoi(getenv("SGL_NT_TILE")) : 0;
+    if (epi == EPI_QKV && out_dtype == (std::is_same<TIn, f16>::value ? DT_F16 : DT_BF16)) {   // as dispatch_epilogue
+      const bool can288 = nt288_takes_qkv(N, p);
+      if (tile_env == 288 && !can288) return hipErrorInvalidValue;
+      if (can288 && (tile_env == 288 || tile_env == 0)) return gemm_nt288<TIn>(A, lda, B, ldb, M, N, K, epi, out_dtype, p, s);
+    }
     const bool can384 = epi == EPI_STORE || epi == EPI_RES_F32;
     const bool pays384 = N % 192 == 0 && N % 256 != 0 && (epi == EPI_STORE || K >= 2048);
     const bool want384 = tile_env == 384 || (tile_env != 256 && pays384);

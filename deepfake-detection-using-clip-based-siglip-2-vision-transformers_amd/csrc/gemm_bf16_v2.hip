@@ -1,11 +1,13 @@
 // bf16 / fp16 MFMA GEMMs for gfx950, K-step 64, 512 threads = 8 waves, operands streamed global -> LDS by LDS-DMA
 // (buffer_load_dwordx4 ... lds, 1 KiB per wave instruction, no VGPR staging), two LDS stages.  Two kernels:
-//   gemm_nt6_kernel<Tile, ...>   NT on a tile geometry: NtTile256 (256 x 256) or NtTile384 (384 x 192), see the structs
-//   gemm_tn6_kernel<Tile, ...>   TN on the same two geometries
+//   gemm_nt6_kernel<Tile, ...>   NT on a tile geometry: NtTile256 (256 x 256), NtTile384 (384 x 192) or NtTile288 (256 x 288,
+//                                the QKV scatter of 72-wide heads only), see the structs
+//   gemm_tn6_kernel<Tile, ...>   TN on the first two geometries
 // Both main loops run anti-phase wave groups, four barrier-separated slots per K-step (see the comments above them),
-// and share the LDS images, the tile order and one staged epilogue (store_tile_pp).  gemm_nt_bf16 / gemm_tn_bf16
-// (gemm_bf16.hip) send the shapes that fill the chip here, through gemm_nt256 / gemm_nt384 / gemm_tn256 / gemm_tn384 at the
-// end of this file, and hold the rules that choose the tile (and, for TN, the split).
+// and share the LDS images, the tile order and one staged epilogue (store_tile_pp; store_tile_qkv_heads where a tile is
+// whole heads).  gemm_nt_bf16 / gemm_tn_bf16 (gemm_bf16.hip) send the shapes that fill the chip here, through gemm_nt256 /
+// gemm_nt384 / gemm_nt288 / gemm_tn256 / gemm_tn384 at the end of this file, and hold the rules that choose the tile (and,
+// for TN, the split).
 //
 //   nt : C[M,N]   = A[M,K] · B[N,K]ᵀ           (forward projections, dX with transposed weight shadows)
 //   tn : C[N1,N2] (+)= Σ_m A[m,N1] · B[m,N2]    (dW; token index is the MFMA k index via ds_read_b64_tr_b16)
@@ -39,20 +41,38 @@ constexpr int T_BK = 64;
 // Tile geometries.  A geometry states the tile, the MI x MJ accumulator blocks (16 x 16) of a wave, the wave map and
 // which 8-row pieces of the B image a wave's DMA instructions move; everything else follows here, once.
 // ------------------------------------------------------------------------------------------------------
-template <int BM_, int BN_, int MI_, int MJ_>
+template <int BM_, int BN_, int MI_, int MJ_, bool SPLIT_B_ = false, int CT_LD_ = BN_ + 4, int QKV_HD_ = 0, int QKV_HDP_ = 0>
 struct NtTileShape {
   static constexpr int BM = BM_, BN = BN_, MI = MI_, MJ = MJ_;
   static constexpr int WM = 16 * MI, WN = 16 * MJ;     // wave tile
   static constexpr int NWR = BM / WM, NWC = BN / WN;   // wave grid
+  static constexpr int BNI = (BN + 63) / 64 * 64;      // rows of the B image: DMA pieces are dealt in whole 64-row rounds, rows
+                                                       // past BN are requested out of range (zeros) and never read
   static constexpr int OPA = BM * T_BK * 2;            // bytes of A per stage; the B image follows it
-  static constexpr int STAGE = (BM + BN) * T_BK * 2;
+  static constexpr int STAGE = (BM + BNI) * T_BK * 2;
   static constexpr int LDS = 2 * STAGE;
-  // DMA instructions (8 image rows = 1 KiB each) per wave: PA for each half of A, PB for B, NI per K-step.  NI is also
-  // the vmcnt immediate of the read slots (see the schedule above gemm_nt6_kernel).
-  static constexpr int PA = BM / 128, PB = BN / 64, NI = 2 * PA + PB;
-  static constexpr int CT_LD = BN + 4;                 // fp32 epilogue staging stride: 4 mod 64 banks
+  // Which operand the main loop reads in halves (see the schedule above gemm_nt6_kernel).  SPLIT_B = false: A by row
+  // blocks (units A0, B, A1); true: B by column blocks (units A, B0, B1; B0 = the first J0 column blocks of every wave
+  // column, B1 = the other J1).  The choice balances the fragment reads of the two read slots.
+  static constexpr bool SPLIT_B = SPLIT_B_;
+  static constexpr int J0 = (MJ + 1) / 2, J1 = MJ - J0;
+  // DMA instructions (8 image rows = 1 KiB each) per wave and unit, in stream order; NI per K-step is also the vmcnt
+  // immediate of the read slots.  The pad rows of the B image ride with B0, which makes its pieces a multiple of 8.
+  static constexpr int P0 = SPLIT_B ? BM / 64 : BM / 128;
+  static constexpr int P1 = SPLIT_B ? (NWC * J0 * 16 + BNI - BN) / 64 : BNI / 64;
+  static constexpr int P2 = SPLIT_B ? (NWC * J1 * 16) / 64 : BM / 128;
+  static constexpr int NI = P0 + P1 + P2;
+  static constexpr int CT_LD = CT_LD_;                 // fp32 epilogue staging stride (default: 4 mod 64 banks)
+  // EPI_QKV with whole heads per tile (BN % QKV_HD == 0): the head-major epilogue walk (store_tile_qkv_heads) for heads
+  // of QKV_HD columns stored QKV_HDP wide; 0 = the row-major walk of store_tile_pp
+  static constexpr int QKV_HD = QKV_HD_, QKV_HDP = QKV_HDP_;
   static_assert(NWR * WM == BM && NWC * WN == BN && NWR * NWC == 8, "8 waves = 512 threads cover the tile");
-  static_assert(MI % 2 == 0 && BM % 128 == 0 && BN % 64 == 0 && 64 % NWR == 0 && (64 / NWR) % 16 == 0, "halves, pieces, passes");
+  static_assert(BM % 128 == 0 && 64 % NWR == 0 && (64 / NWR) % 16 == 0, "pieces, passes");
+  static_assert(SPLIT_B ? ((NWC * J0 * 16 + BNI - BN) % 64 == 0 && (NWC * J1 * 16) % 64 == 0 && (J0 * 16) % 8 == 0)
+                        : (MI % 2 == 0 && BN % 64 == 0), "every wave issues the same number of pieces of every unit");
+  static_assert(QKV_HD == 0 || (BN % QKV_HD == 0 && QKV_HD % 8 == 0 && QKV_HDP % 8 == 0 && QKV_HDP >= QKV_HD &&
+                                (64 * (BN / QKV_HD) * (QKV_HDP / 8)) % 512 == 0), "whole heads, whole chunk rounds");
+  static_assert(CT_LD >= BN && CT_LD % 4 == 0, "16-byte aligned staging rows");
   static_assert(LDS <= 160 * 1024 && 64 * CT_LD * 4 <= LDS, "two stages, and the epilogue image, in 160 KiB of LDS");
 };
 
@@ -64,7 +84,7 @@ struct NtTileShape {
 struct NtTile256 : NtTileShape<256, 256, 8, 4> {
   static __device__ __forceinline__ int wr(int w) { return (w >> 1) & 1; }
   static __device__ __forceinline__ int wc(int w) { return (w & 1) + 2 * (w >> 2); }
-  // B piece q (of PB = 4) of wave w: q < 2 is "BX", the first 32 columns of every wave column, q >= 2 "BY", the other 32
+  // B piece q (of P1 = 4) of wave w: q < 2 is "BX", the first 32 columns of every wave column, q >= 2 "BY", the other 32
   static __device__ __forceinline__ int b_row(int w, int q) {
     const int ul = 16 * w + 8 * (q & 1);
     return (ul >> 5) * 64 + (ul & 31) + 32 * (q >> 1);
@@ -82,6 +102,31 @@ struct NtTile384 : NtTileShape<384, 192, 6, 6> {
   static __device__ __forceinline__ int wc(int w) { return w >> 2; }
   static __device__ __forceinline__ int b_row(int w, int q) { return 8 * (3 * w + q); }
   static constexpr bool takes(int epi) { return epi == EPI_STORE || epi == EPI_RES_F32 || epi == EPI_F32; }
+};
+
+// 256 x 288 (2 x 72 KiB): waves 4 (rows) x 2 (columns), 64 x 144 each, the two waves of a SIMD in different column
+// halves.  288 = 4 x 72: for the QKV projection of a model with 72-wide heads (N = 3 heads 72, heads % 4 == 0) a tile
+// holds heads 4 tile_n .. 4 tile_n + 3 from its column 0, N = 3456 is 12 whole tiles where NtTile256 runs 13.5 (14), and
+// the epilogue writes every head's rows as one run of 160-byte rows (store_tile_qkv_heads).  B is the operand read in
+// halves: all of A plus column blocks 0-4 make 18 fragment reads in R1, column blocks 5-8 make 8 in R2 (A in halves
+// would be 22 + 4).  The B image has 320 rows; rows 288..319 are the four pad pieces of unit B0 (24 pieces = 3 per wave),
+// always out of range.  CT_LD = 336: with it the 32-byte chunk reads of the head-major walk (two ds_read_b128 per lane,
+// halves swapped on lane bit 3) touch every bank once per 16-lane group in all 5 x 8 wave reads of a pass; the staging
+// stores are 2-way with it (4 rows = 0 mod 32 banks), which a ds_write_b32 hides behind its register transfer, and no
+// stride has both (profiles/nt288_resources.txt).  EPI_QKV with 16-bit outputs only; gemm_nt_mfma checks head_dim, head_dim_pad and N before it sends a launch here.
+struct NtTile288 : NtTileShape<256, 288, 4, 9, true, 336, 72, 80> {
+  static __device__ __forceinline__ int wr(int w) { return w & 3; }
+  static __device__ __forceinline__ int wc(int w) { return w >> 2; }
+  // B piece q of wave w in unit B0 (half 0, P1 = 3 per wave) / B1 (half 1, P2 = 2 per wave)
+  static __device__ __forceinline__ int b_row(int w, int half, int q) {
+    if (half == 0) {
+      const int piece = P1 * w + q;   // 0..19: 2 J0 = 10 pieces of each wave column; 20..23: the pad rows
+      return piece < NWC * 2 * J0 ? WN * (piece / (2 * J0)) + 8 * (piece % (2 * J0)) : BN + 8 * (piece - NWC * 2 * J0);
+    }
+    const int piece = P2 * w + q;     // 0..15: 2 J1 = 8 pieces of each wave column
+    return WN * (piece / (2 * J1)) + 16 * J0 + 8 * (piece % (2 * J1));
+  }
+  static constexpr bool takes(int epi) { return epi == EPI_QKV; }
 };
 
 constexpr int gcd_of(int a, int b) { return b == 0 ? a : gcd_of(b, a % b); }
@@ -216,7 +261,9 @@ __device__ __forceinline__ void store_tile_pp(char* smem, f32x4 (&acc)[G::MI][G:
         } else if constexpr (EPI == EPI_QKV) {
           // (Round 3 tried dealing a pass's chunks out head by head so that a wave store covers 6.4 whole 160-byte rows of
           // one head, 1 KiB contiguous instead of eight 144-byte pieces: QKV GEMM 853 -> 886 us, the per-chunk decode costs
-          // more than the store pattern saves.  Not kept.)
+          // more than the store pattern saves.  Not kept on this walk: head boundaries fall differently in every 256-wide
+          // tile.  Where the tile is a whole number of heads the decode is three divisions by constants and the deal pays:
+          // store_tile_qkv_heads below, which NtTile288 takes instead of this branch.)
           int b, n;
           qkv_split_row(grow, p.tokens, b, n);
           epi_qkv<TOut, NV>(v, bias[h],
@@ -245,6 +292,70 @@ __device__ __forceinline__ void store_tile_pp(char* smem, f32x4 (&acc)[G::MI][G:
   if constexpr (EPI == EPI_GELU_BWD) {
     static_assert(P == 1, "the bias-gradient fold needs one column set per thread");
     epi_colsum_fold<512, G::BN, NV>(ct, csum, t, m0, n0, N, p);
+  }
+}
+
+// EPI_QKV on a geometry whose tile is a whole number of heads (G::QKV_HD columns each, stored G::QKV_HDP wide): the staging
+// of store_tile_pp, then a HEAD-major chunk walk.  The tile holds heads HPT tile_n .. HPT tile_n + HPT - 1 from column 0,
+// and inside one image consecutive rows of a head are consecutive 2 QKV_HDP-byte rows of its [tokens][QKV_HDP] matrix, so
+// chunk i = t + 512 q of a pass is
+//     head = i / (64 CPH),  staging row = i % (64 CPH) / CPH,  c = i % CPH      (CPH = QKV_HDP / 8, constants all)
+// and consecutive lanes store consecutive 16-byte chunks: a wave store is 1 KiB of consecutive bytes except where it
+// crosses one of the pass's 16-row runs (the staging keeps every wave row's rows together) or an image boundary.  Chunks
+// c >= QKV_HD / 8 are the pad columns and leave as +0 with the rest (they read the head's last data chunk again, a
+// broadcast).  The bias is added on the accumulator side, MJ values per lane loaded before the first pass: a load issued
+// behind the stores would wait for their acknowledgement (see above).  Same arithmetic as epi_qkv: (acc + bias) rounded
+// to nearest.  A lane reads its 32 bytes as two ds_read_b128, columns 4..7 first on lanes with bit 3 set: with
+// G::CT_LD that order covers the 64 banks exactly once per 16-lane group.
+// The caller guarantees 16-bit outputs, N % G::BN == 0 and heads % HPT == 0 (a tile never straddles q / k / v).
+template <typename G, typename TOut>
+__device__ __forceinline__ void store_tile_qkv_heads(char* smem, f32x4 (&acc)[G::MI][G::MJ], int wr, int wc, int lane,
+                                                     int t, int m0, int n0, int M, const EpiParams& p) {
+  static_assert(G::takes(EPI_QKV) && G::QKV_HD > 0, "this tile geometry does not hold whole heads");
+  float* ct = reinterpret_cast<float*>(smem);
+  const int g = lane >> 4, c16 = lane & 15;
+  constexpr int NV = 8, CT_LD = G::CT_LD;
+  constexpr int HPT = G::BN / G::QKV_HD;                // heads per tile
+  constexpr int CPH = G::QKV_HDP / NV;                  // chunks per head row, pad chunks included
+  constexpr int DCH = G::QKV_HD / NV;                   // data chunks per head row
+  constexpr int CHD = 64 * CPH;                         // chunks per head and pass
+  constexpr int QN = (HPT * CHD) / 512;                 // chunks per thread and pass
+  constexpr int WR_ROWS = 64 / G::NWR, BLK = WR_ROWS / 16, NPASS = G::BM / 64;
+  static_assert(NPASS * BLK == G::MI, "staging image");
+  float bias[G::MJ];
+#pragma unroll
+  for (int j = 0; j < G::MJ; ++j) bias[j] = p.bias[n0 + wc * G::WN + j * 16 + c16];
+  // rows of [tokens][QKV_HDP] in front of (q|k|v, image 0, first head of the tile); head h of the tile is h * tokens further
+  const int gh0 = n0 / G::QKV_HD, which = gh0 / p.heads;
+  const int rows0 = (which * p.batch * p.heads + (gh0 - which * p.heads)) * p.tokens;
+  const bool swapped = (lane >> 3) & 1;
+#pragma unroll
+  for (int pass = 0; pass < NPASS; ++pass) {
+    lds_barrier();   // pass 0: every wave is done with the operand stages; later: the previous pass's chunk reads are done
+#pragma unroll
+    for (int i2 = 0; i2 < BLK; ++i2)
+#pragma unroll
+      for (int j = 0; j < G::MJ; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          ct[(wr * WR_ROWS + i2 * 16 + g * 4 + r) * CT_LD + wc * G::WN + j * 16 + c16] = acc[BLK * pass + i2][j][r] + bias[j];
+    lds_barrier();
+#pragma unroll
+    for (int q = 0; q < QN; ++q) {
+      const int i = t + 512 * q;
+      const int head = i / CHD, rem = i % CHD, row = rem / CPH, c = rem % CPH;
+      const int grow = m0 + (row / WR_ROWS) * G::WM + pass * WR_ROWS + row % WR_ROWS;
+      if (grow < M) {
+        const float* src = ct + row * CT_LD + head * G::QKV_HD + NV * (c < DCH ? c : DCH - 1);
+        const f32x4 first = *reinterpret_cast<const f32x4*>(src + (swapped ? 4 : 0));
+        const f32x4 second = *reinterpret_cast<const f32x4*>(src + (swapped ? 0 : 4));
+        int b, n;
+        qkv_split_row(grow, p.tokens, b, n);
+        const int drow = rows0 + (b * p.heads + head) * p.tokens + n;
+        epi_qkv_halves<TOut>(first, second, swapped, c >= DCH,
+                             reinterpret_cast<TOut*>(p.out) + (size_t)drow * G::QKV_HDP + NV * c);
+      }
+    }
   }
 }
 
@@ -338,7 +449,7 @@ __device__ unsigned long long g_tn6_tl[12];   // [group][phase 0..4, slot-pair c
 // NT on a tile geometry G, four slots per K-step.  The global->LDS stream moves three units per K-step in the fixed
 // round-robin order
 //     A0(t) = the first WM/2 rows of every wave row,  B(t) = all BN columns,  A1(t) = the other WM/2 rows,  A0(t+1), ...
-// of PA, PB and PA wave-instructions per wave (NI = 2 PA + PB per K-step).  Piece PA w + q of A0 / A1 covers image rows
+// of P0, P1 and P2 = P0 wave-instructions per wave (NI = P0 + P1 + P2 per K-step).  Piece P0 w + q of A0 / A1 covers image rows
 // WM (piece / ppw) + 8 (piece % ppw) (+ WM/2 for A1), ppw = WM/16 pieces per wave row; the B pieces are G::b_row.
 // Per wave and K-step t, with HI = MI/2:
 //     R1(t): fragment reads of B (MJ column blocks) and A0 (row blocks 0..HI-1), both k-halves   + DMA unit A1(t+1)
@@ -356,9 +467,29 @@ __device__ unsigned long long g_tn6_tl[12];   // [group][phase 0..4, slot-pair c
 //       A1(t+1) over A1(t-1), last read in slot 4t-1, issued from slot 4t; A0/B(t+2) over A0/B(t), last read in slot
 //       4t+1, issued from slot 4t+2;
 //   (d) every wave passes 4 barriers per K-step + 2 whatever its `active` state or group.
-//              tile       waves   MI x MJ   PA  PB  NI = vmcnt   reads R1 / R2   MFMAs per slot   LDS
-//   NtTile256  256 x 256  2 x 4   8 x 4     2   4   8            16 / 8          32               128 KiB
-//   NtTile384  384 x 192  4 x 2   6 x 6     3   3   9            18 / 6          36               144 KiB
+// A geometry with SPLIT_B reads B in halves instead (NtTile288: A in halves would put 22 fragment reads into R1 and 4
+// into R2).  The three units, in the same round-robin order and the same slots, are then
+//     A(t) = all BM rows,  B0(t) = column blocks 0..J0-1 of every wave column (+ the image's pad rows),  B1(t) = the other J1,
+// of P0, P1 and P2 wave-instructions per wave (the same for every wave: the pad rows even B0 out), and
+//     R1(t): fragment reads of A (all MI row blocks) and B0, both k-halves     + DMA unit B1(t+1)
+//     M1(t): A x B0   2 MI J0 MFMAs
+//     R2(t): fragment reads of B1, both k-halves; A stays in its registers      + DMA units A(t+2), B0(t+2)
+//     M2(t): A x B1   2 MI J1 MFMAs
+// i.e. the schedule above with (A0, B, A1) -> (A, B0, B1): what R1 reads is units 0 and 1, what R2 reads is unit 2.  The
+// waits are the same: after R1(t) the NI younger instructions are A(t+1), B0(t+1), B1(t+1), so B1(t) has landed for R2(t);
+// after R2(t) they are B1(t+1), A(t+2), B0(t+2), so A(t+1) and B0(t+1) have landed for R1(t+1).  The invariants, re-derived:
+//   (a) B1(t+1) is issued in R1(t) and published by the wait of R1(t+1); A/B0(t+2) in R2(t), published by R2(t+1): 4 slots;
+//   (b) as above: the publishing wait is followed by the read slot's barrier, and the reading slot of either group
+//       comes at least one barrier after the later group's wait;
+//   (c) B1(t+1) overwrites B1(t-1), last read in R2(t-1) (G1: slot 4t-1), issued from slot 4t; A/B0(t+2) overwrite A/B0(t),
+//       last read in R1(t) (G1: slot 4t+1), issued from slot 4t+2.  A's registers are read by M2(t) after the stage's A
+//       image may already be overwritten by A(t+2): they were loaded in R1(t), the image is not read again;
+//   (d) unchanged: the slot structure is the same.
+// Accumulator (i, j) is touched by M1 only (j < J0) or by M2 only, k-half 0 then 1: the chain order is the same.
+//              tile       waves   MI x MJ   P0  P1  P2  NI = vmcnt   reads R1 / R2   MFMAs M1 / M2   LDS
+//   NtTile256  256 x 256  2 x 4   8 x 4     2   4   2   8            16 / 8          32 / 32         128 KiB
+//   NtTile384  384 x 192  4 x 2   6 x 6     3   3   3   9            18 / 6          36 / 36         144 KiB
+//   NtTile288  256 x 288  4 x 2   4 x 9     4   3   2   9            18 / 8          40 / 32         144 KiB   (SPLIT_B)
 // Operands are reached only through the two bounded buffer descriptors (rows past M / N and k past K come back as
 // zeros), so ragged M, N and K need no branches.
 // Two other schedules were measured on NtTile384 at M = 93,312, N = 1152, K = 4352 (NtTile256: 766 us): splitting the
@@ -380,7 +511,8 @@ __global__ __launch_bounds__(512, 2) void gemm_nt6_kernel(const TIn* __restrict_
     if (unit >= ntiles) return;  // whole block exits together
     tile_of_unit(unit, tiles_m, tiles_n, tile_m, tile_n, band_h);
   }
-  constexpr int MI = G::MI, MJ = G::MJ, HI = MI / 2, PA = G::PA, PB = G::PB, NI = G::NI;
+  constexpr int MI = G::MI, MJ = G::MJ, HI = MI / 2, J0 = G::J0, J1 = G::J1, NI = G::NI;
+  constexpr bool SB = G::SPLIT_B;
   const int t = threadIdx.x, lane = t & 63;
   const int w = __builtin_amdgcn_readfirstlane(t >> 6);
   const int wr = G::wr(w), wc = G::wc(w), grp = w >> 2;
@@ -392,18 +524,24 @@ __global__ __launch_bounds__(512, 2) void gemm_nt6_kernel(const TIn* __restrict_
   const uint32_t lds0 = (uint32_t)(size_t)((SGL_LDS char*)smem);
 
   // DMA plan: per unit and instruction the lane's source offset and the instruction's LDS address
-  enum { U_A0 = 0, U_B = 1, U_A1 = 2 };
-  constexpr int PMAX = PA > PB ? PA : PB;
+  // units in stream order: U0 and U1 are read in R1, U2 in R2 (A0, B, A1; with SPLIT_B: A, B0, B1)
+  constexpr int PU[3] = {G::P0, G::P1, G::P2};
+  constexpr int PMAX = G::P0 > G::P1 ? (G::P0 > G::P2 ? G::P0 : G::P2) : (G::P1 > G::P2 ? G::P1 : G::P2);
   const int drow = lane >> 3, dchunk = (lane & 7) ^ drow;
   uint32_t voff[3][PMAX], ldst[3][PMAX];
 #pragma unroll
   for (int u = 0; u < 3; ++u)
 #pragma unroll
-    for (int q = 0; q < (u == U_B ? PB : PA); ++q) {
-      const bool isA = u != U_B;
-      constexpr int ppw = G::WM / 16;
-      const int piece = PA * w + q;
-      const int r0 = isA ? G::WM * (piece / ppw) + 8 * (piece % ppw) + (u == U_A1 ? G::WM / 2 : 0) : G::b_row(w, q);
+    for (int q = 0; q < PU[u]; ++q) {
+      const bool isA = SB ? u == 0 : u != 1;
+      int r0;
+      if constexpr (SB) {
+        r0 = isA ? 8 * (G::P0 * w + q) : G::b_row(w, u - 1, q);
+      } else {
+        constexpr int ppw = G::WM / 16;
+        const int piece = G::P0 * w + q;
+        r0 = isA ? G::WM * (piece / ppw) + 8 * (piece % ppw) + (u == 2 ? G::WM / 2 : 0) : G::b_row(w, q);
+      }
       const int row = r0 + drow;
       voff[u][q] = (row < (isA ? rows_a : rows_b)) ? (uint32_t)(row * (isA ? lda : ldb) + dchunk * 8) * 2u : SGL_OOB;
       ldst[u][q] = lds0 + (isA ? 0 : G::OPA) + (uint32_t)r0 * 128u;
@@ -413,9 +551,10 @@ __global__ __launch_bounds__(512, 2) void gemm_nt6_kernel(const TIn* __restrict_
     const int k0 = kt * T_BK;
     const bool kok = (kt < nk) && (k0 + dchunk * 8 < K);
     const uint32_t sb = (uint32_t)((kt & 1) * G::STAGE);
+    const bool isA = SB ? u == 0 : u != 1;
 #pragma unroll
-    for (int q = 0; q < (u == U_B ? PB : PA); ++q)
-      pp_dma16(u == U_B ? db : da, ldst[u][q] + sb, (kok && voff[u][q] != SGL_OOB) ? voff[u][q] + (uint32_t)k0 * 2u : SGL_OOB);
+    for (int q = 0; q < PU[u]; ++q)
+      pp_dma16(isA ? da : db, ldst[u][q] + sb, (kok && voff[u][q] != SGL_OOB) ? voff[u][q] + (uint32_t)k0 * 2u : SGL_OOB);
   };
 
   const int frow = lane & 15, fg = lane >> 4, fsw = frow & 7;
@@ -430,24 +569,30 @@ __global__ __launch_bounds__(512, 2) void gemm_nt6_kernel(const TIn* __restrict_
 #pragma unroll
     for (int j = 0; j < MJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  issue(U_A0, 0); issue(U_B, 0); issue(U_A1, 0);
-  issue(U_A0, 1); issue(U_B, 1);
-  pp_end_read<NI>();                 // A0(0), B(0) of every wave have landed
+  issue(0, 0); issue(1, 0); issue(2, 0);
+  issue(0, 1); issue(1, 1);
+  pp_end_read<NI>();                 // U0(0), U1(0) of every wave have landed
   if (grp == 1) SGL_PP_END_MFMA();   // G1 runs one slot behind G0 from here on
 
-  lo_x8<TIn> fa[2 * HI], fb[2 * MJ];   // [k-half][block]
-  // M1 (i0 = 0) / M2 (i0 = HI): row blocks i0..i0+HI-1 x B.  Order: k-half, row block, column block (do not reorder: it
-  // is what makes the geometries agree bit for bit)
-  auto mfma_slot = [&](int i0) {
+  // the fragments of one slot, [k-half][block]: NA row blocks of A, NB column blocks of B (SPLIT_B: all of A stays live
+  // from R1 to M2 and B changes; otherwise all of B stays and A changes)
+  constexpr int NA = SB ? MI : HI, NB = SB ? J0 : MJ;
+  lo_x8<TIn> fa[2 * NA], fb[2 * NB];
+  // M1 (half 0) / M2 (half 1): row blocks i0..i0+ni-1 x column blocks j0..j0+nj-1.  Order: k-half, row block, column block
+  // (do not reorder: it is what makes the geometries agree bit for bit)
+  auto mfma_slot = [&](auto half) {
+    constexpr int hf = decltype(half)::value;
+    constexpr int i0 = SB ? 0 : hf * HI, ni = SB ? MI : HI;
+    constexpr int j0 = SB ? hf * J0 : 0, nj = SB ? (hf ? J1 : J0) : MJ;
     if (active) {
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int h = 0; h < 2; ++h)
 #pragma unroll
-        for (int i = 0; i < HI; ++i)
+        for (int i = 0; i < ni; ++i)
 #pragma unroll
-          for (int j = 0; j < MJ; ++j)
-            acc[i0 + i][j] = mfma_16x16x32(fa[HI * h + i], fb[MJ * h + j], acc[i0 + i][j]);
+          for (int j = 0; j < nj; ++j)
+            acc[i0 + i][j0 + j] = mfma_16x16x32(fa[ni * h + i], fb[nj * h + j], acc[i0 + i][j0 + j]);
       __builtin_amdgcn_s_setprio(0);
     }
     SGL_PP_END_MFMA();
@@ -456,24 +601,29 @@ __global__ __launch_bounds__(512, 2) void gemm_nt6_kernel(const TIn* __restrict_
     const char* base = smem + (kt & 1) * G::STAGE;
     const char* pa = base + fa_base;
     const char* pb = base + fb_base;
-    // ---- R1: B, A0
+    // ---- R1: B and A0 (SPLIT_B: B0 and A)
     if (active) {
 #pragma unroll
-      for (int f = 0; f < 2 * MJ; ++f) fb[f] = *reinterpret_cast<const lo_x8<TIn>*>(pb + (f % MJ) * 2048 + ((f / MJ) ? c1 : c0));
+      for (int f = 0; f < 2 * NB; ++f) fb[f] = *reinterpret_cast<const lo_x8<TIn>*>(pb + (f % NB) * 2048 + ((f / NB) ? c1 : c0));
 #pragma unroll
-      for (int f = 0; f < 2 * HI; ++f) fa[f] = *reinterpret_cast<const lo_x8<TIn>*>(pa + (f % HI) * 2048 + ((f / HI) ? c1 : c0));
+      for (int f = 0; f < 2 * NA; ++f) fa[f] = *reinterpret_cast<const lo_x8<TIn>*>(pa + (f % NA) * 2048 + ((f / NA) ? c1 : c0));
     }
-    issue(U_A1, kt + 1);
+    issue(2, kt + 1);
     pp_end_read<NI>();
-    mfma_slot(0);
-    // ---- R2: A1
+    mfma_slot(std::integral_constant<int, 0>{});
+    // ---- R2: A1 (SPLIT_B: B1)
     if (active) {
+      if constexpr (SB) {
 #pragma unroll
-      for (int f = 0; f < 2 * HI; ++f) fa[f] = *reinterpret_cast<const lo_x8<TIn>*>(pa + (HI + f % HI) * 2048 + ((f / HI) ? c1 : c0));
+        for (int f = 0; f < 2 * J1; ++f) fb[f] = *reinterpret_cast<const lo_x8<TIn>*>(pb + (J0 + f % J1) * 2048 + ((f / J1) ? c1 : c0));
+      } else {
+#pragma unroll
+        for (int f = 0; f < 2 * HI; ++f) fa[f] = *reinterpret_cast<const lo_x8<TIn>*>(pa + (HI + f % HI) * 2048 + ((f / HI) ? c1 : c0));
+      }
     }
-    issue(U_A0, kt + 2); issue(U_B, kt + 2);
+    issue(0, kt + 2); issue(1, kt + 2);
     pp_end_read<NI>();
-    mfma_slot(HI);
+    mfma_slot(std::integral_constant<int, 1>{});
   }
   if (grp == 0) SGL_PP_END_MFMA();   // G0 waits for G1's last slot
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // trailing (all-zero) units must land before the LDS is reused
@@ -481,7 +631,10 @@ __global__ __launch_bounds__(512, 2) void gemm_nt6_kernel(const TIn* __restrict_
   if (p.atomic == 77) return;   // developer build only (SGL_NT6_SKIP_EPI): main loop without its epilogue
 #endif
   SGL_TL_STAMP(tl1);
-  store_tile_pp<G, EPI, TOut>(smem, acc, wr, wc, lane, t, m0, n0, M, N, p);
+  if constexpr (EPI == EPI_QKV && G::QKV_HD > 0)
+    store_tile_qkv_heads<G, TOut>(smem, acc, wr, wc, lane, t, m0, n0, M, p);
+  else
+    store_tile_pp<G, EPI, TOut>(smem, acc, wr, wc, lane, t, m0, n0, M, N, p);
 #ifdef SGL_TIMELINE
   SGL_TL_STAMP(tl2);
   if (t == 0) {
@@ -739,7 +892,7 @@ static hipError_t gemm_nt_pp(const void* A, int lda, const void* B, int ldb, int
                              const EpiParams& p, hipStream_t s) {
   return dispatch_epilogue<TIn>(epi, out_dtype, [&](auto tag) {
     using T = decltype(tag);
-    if constexpr (G::takes(T::epi))
+    if constexpr (G::takes(T::epi) && (G::QKV_HD == 0 || sizeof(typename T::out) == 2))
       return launch_nt_pp<G, T::epi, typename T::out, TIn>((const TIn*)A, lda, (const TIn*)B, ldb, M, N, K, p, s);
     else
       return hipErrorInvalidValue;
@@ -754,6 +907,15 @@ template <typename TIn>
 hipError_t gemm_nt384(const void* A, int lda, const void* B, int ldb, int M, int N, int K, int epi, int out_dtype,
                       const EpiParams& p, hipStream_t s) {
   return gemm_nt_pp<NtTile384, TIn>(A, lda, B, ldb, M, N, K, epi, out_dtype, p, s);
+}
+// heads of this many columns, stored this wide, make whole 288-column tiles (gemm_nt_mfma checks the rest)
+static_assert(NtTile288::QKV_HD == NT288_HEAD_DIM && NtTile288::QKV_HDP == NT288_HEAD_DIM_PAD && NtTile288::BN == NT288_BN, "kernels.h");
+template <typename TIn>
+hipError_t gemm_nt288(const void* A, int lda, const void* B, int ldb, int M, int N, int K, int epi, int out_dtype,
+                      const EpiParams& p, hipStream_t s) {
+  // the head-major epilogue addresses with the geometry's constants: nothing else may reach it
+  if (epi != EPI_QKV || !nt288_takes_qkv(N, p)) return hipErrorInvalidValue;
+  return gemm_nt_pp<NtTile288, TIn>(A, lda, B, ldb, M, N, K, epi, out_dtype, p, s);
 }
 
 template <typename G, typename TIn>
@@ -792,6 +954,8 @@ hipError_t gemm_tn384(const void* A, int lda, const void* B, int ldb, int Mred, 
   template hipError_t gemm_nt256<TIn>(const void*, int, const void*, int, int, int, int, int, int, const EpiParams&,   \
                                       hipStream_t);                                                                    \
   template hipError_t gemm_nt384<TIn>(const void*, int, const void*, int, int, int, int, int, int, const EpiParams&,   \
+                                      hipStream_t);                                                                    \
+  template hipError_t gemm_nt288<TIn>(const void*, int, const void*, int, int, int, int, int, int, const EpiParams&,   \
                                       hipStream_t);                                                                    \
   template hipError_t gemm_tn256<TIn>(const void*, int, const void*, int, int, int, int, int, int, const EpiParams&,   \
                                       hipStream_t);                                                                    \

@@ -193,13 +193,23 @@ hipError_t gemm_nt_f16(const void* A, int lda, const void* B, int ldb, int M, in
 hipError_t gemm_tn_f16(const void* A, int lda, const void* B, int ldb, int Mred, int N1, int N2, int splits,
                        const EpiParams& p, hipStream_t s, float* split_ws = nullptr, size_t split_ws_bytes = 0);
 // The LDS-DMA kernels of gemm_bf16_v2.hip, which the four above send the shapes that fill the chip to; TIn = bf16 or f16
-// (instantiated there).  gemm_nt384 takes EPI_STORE and EPI_RES_F32 only (hipErrorInvalidValue otherwise); gemm_tn256 /
+// (instantiated there).  gemm_nt384 takes EPI_STORE and EPI_RES_F32 only, gemm_nt288 EPI_QKV only (hipErrorInvalidValue otherwise); gemm_tn256 /
 // gemm_tn384 run `splits` ranges of m_per tokens (EpiParams::split_stride / atomic say where a split's tile goes).
 template <typename TIn>
 hipError_t gemm_nt256(const void* A, int lda, const void* B, int ldb, int M, int N, int K, int epi, int out_dtype,
                       const EpiParams& p, hipStream_t s);
 template <typename TIn>
 hipError_t gemm_nt384(const void* A, int lda, const void* B, int ldb, int M, int N, int K, int epi, int out_dtype,
+                      const EpiParams& p, hipStream_t s);
+// gemm_nt288: EPI_QKV with a 16-bit output only, 256 x 288 tiles of four whole heads.  Refuses (hipErrorInvalidValue) what nt288_takes_qkv does not hold for:
+// the kernel's head-major epilogue addresses with these constants instead of EpiParams::head_dim / head_dim_pad.
+constexpr int NT288_BN = 288, NT288_HEAD_DIM = 72, NT288_HEAD_DIM_PAD = 80;
+inline bool nt288_takes_qkv(int N, const EpiParams& p) {
+  return p.head_dim == NT288_HEAD_DIM && p.head_dim_pad == NT288_HEAD_DIM_PAD && p.heads > 0 &&
+         N == 3 * p.heads * NT288_HEAD_DIM && N % NT288_BN == 0;   // the last two: heads % 4 == 0, a tile is inside q, k or v
+}
+template <typename TIn>
+hipError_t gemm_nt288(const void* A, int lda, const void* B, int ldb, int M, int N, int K, int epi, int out_dtype,
                       const EpiParams& p, hipStream_t s);
 template <typename TIn>
 hipError_t gemm_tn256(const void* A, int lda, const void* B, int ldb, int Mred, int N1, int N2, int m_per, int splits,

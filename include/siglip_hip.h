@@ -264,7 +264,13 @@ int sgl_op_layernorm_bwd(const void* dy, int dy_dtype, const float* x, const flo
 enum { SGL_EPI_STORE = 0, SGL_EPI_BIAS_GELU = 1, SGL_EPI_RES_F32 = 2, SGL_EPI_QKV = 3, SGL_EPI_GELU_BWD = 4,
        SGL_EPI_POS_F32 = 5, SGL_EPI_F32 = 6 };
 /* C[M,N] = A[M,K] * B[N,K]^T with a fused epilogue; dtype is the operand dtype (bf16 / fp16 -> MFMA kernel; the 16-bit
- * outputs of EPI_STORE / BIAS_GELU / QKV / GELU_BWD are in the operand dtype). */
+ * outputs of EPI_STORE / BIAS_GELU / QKV / GELU_BWD are in the operand dtype).
+ * SGL_EPI_QKV (N = 3 * heads * head_dim, M = batch * tokens; ldo is not used) is the write side of the head-major layout
+ *   sgl_op_attn_fwd reads with ld_qkv == 0, the one the encoder uses: column which * heads * head_dim + h * head_dim + d of
+ *   row b * tokens + n goes to out[which][b][h][n][d] of [3][batch][heads][tokens][head_dim_pad], and the pad columns
+ *   [head_dim, head_dim_pad) of every row are written as +0 (head_dim % 8 == 0, head_dim_pad % 8 == 0).  Every head's
+ *   [tokens][head_dim_pad] matrix is contiguous; for 16-bit outputs with head_dim 72 / head_dim_pad 80 and heads % 4 == 0
+ *   (so400m) the large-M kernel works on tiles of four whole heads and writes each head's rows as runs of whole rows. */
 int sgl_op_gemm_nt(int dtype, const void* A, int lda, const void* B, int ldb, int M, int N, int K, int epi, void* out,
                    int ldo, void* out2, int ldo2, const float* bias, const float* res, int ldr, const void* aux,
                    int ldaux, const float* pos, int pos_rows, int tokens, int heads, int head_dim, int head_dim_pad,
