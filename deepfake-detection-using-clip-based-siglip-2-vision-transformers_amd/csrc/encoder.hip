@@ -510,34 +510,47 @@ int head_forward(const Call& c, const sgl_weights* w, const float* last_hidden, 
   return SGL_OK;
 }
 
-// Largest token count M = B * grid a recompute context trains on (size audit).  The MFMA GEMM
-// dispatchers refuse any operand of 2^32 bytes or more (32-bit buffer-descriptor ranges): the widest operand with M rows
-// on the training path is [M][max(Ip, 3D, Kp)] (u / a / du, dqkv, im2col), three times as wide after the bf16x3 split,
-// 4-byte in strict fp32.  The EPI_QKV row division is exact for rows < 2^22.
-long rc_max_tokens(const sgl_ctx* c) {
-  long w = c->Ip;
-  if (3l * c->D > w) w = 3l * c->D;
+// Largest token count M = B * grid a pass accepts, on every context (size audit).  The MFMA GEMM
+// dispatchers refuse any operand of 2^32 bytes or more (32-bit buffer-descriptor ranges), so the limit is what keeps the
+// widest operand with M rows that the pass hands to gemm_nt / gemm_tn below that:
+//   forward   [M][max(Ip, D, Kp)]    a (fc2), h1 / attn / h2 / the head's cast of the last hidden state, im2col
+//   training  [M][max(Ip, 3D, Kp)]   the forward's, and u / du, dqkv (dX and dW of the QKV projection)
+// three times as wide after the bf16x3 split ([M][3 * round_up(K, 8)] bf16), 4-byte in strict fp32 (gemm_f32_generic has
+// no such guard; its limit is the same operand extent, which is what has been audited and is tested).  The EPI_QKV row
+// division (qkv_split_row) is exact for rows < 2^22: every context is capped there, the blocks' and the head's K/V scatter
+// both use it.  MX-fp8: its own kernels index with size_t and divide exactly, and gemm_nt_mx has no operand guard; what
+// bounds it are the bf16 GEMMs it still runs (im2col [M][Kp], the head's [M][D] cast) and the 65 535 row tiles of
+// gemm_nt_mx's grid.y.
+long max_tokens(const sgl_ctx* c, bool train) {
+  const long cap = (1l << 22) - 1;
+  long w = c->Ip, row_bytes;
+  if ((long)c->D > w) w = c->D;
   if ((long)c->Kp > w) w = c->Kp;
-  const long row_bytes = c->split ? 3 * (long)round_up((int)w, 8) * 2 : w * (long)c->es;
-  const long m = ((1l << 32) - 1) / row_bytes;
-  return m < (1l << 22) - 1 ? m : (1l << 22) - 1;
+  if (c->mx) {
+    row_bytes = 2 * (long)std::max(c->D, c->Kp);
+  } else {
+    if (train && 3l * c->D > w) w = 3l * c->D;
+    row_bytes = c->split ? 3 * (long)round_up((int)w, 8) * 2 : w * (long)c->es;
+  }
+  long m = ((1l << 32) - 1) / row_bytes;
+  if (c->mx && m > 65535l * 128) m = 65535l * 128;
+  return m < cap ? m : cap;
 }
 
-bool shape_ok(const sgl_ctx* c, int B, int H, int W) {
+bool shape_ok(const sgl_ctx* c, int B, int H, int W, bool train = false) {
   if (B <= 0 || H <= 0 || W <= 0) return false;
   if (H < c->P || W < c->P) return false;  // 'valid' conv: trailing pixels beyond gh*P are ignored
   const long N = (long)(H / c->P) * (W / c->P);
-  if ((long)B * N > (1l << 24)) return false;
+  if ((long)B * N > max_tokens(c, train)) return false;
   if (c->cfg.use_head && N > pool_attn_max_tokens(c->DP, 0)) return false;   // the pooling head's LDS window (kernels.h)
   return true;
 }
 
-// shape_ok plus the pooling head's (smaller) backward token limit and, on a recompute context, the training token limit
+// shape_ok with the training token limit, plus the pooling head's (smaller) backward token limit
 bool train_shape_ok(const sgl_ctx* c, int B, int H, int W) {
-  if (!shape_ok(c, B, H, W)) return false;
+  if (!shape_ok(c, B, H, W, true)) return false;
   const long N = (long)(H / c->P) * (W / c->P);
-  if (c->cfg.use_head && N > pool_attn_max_tokens(c->DP, 1)) return false;
-  return !c->recompute || (long)B * N <= rc_max_tokens(c);
+  return !(c->cfg.use_head && N > pool_attn_max_tokens(c->DP, 1));
 }
 
 // The prologue of every encoder call, after the entry point's own pointer checks (ctx among them) and before anything is

@@ -311,6 +311,7 @@ static hipError_t gemm_nt_mfma(const void* A, int lda, const void* B, int ldb, i
   if ((lda % 8) || (ldb % 8) || (K % 8) || K <= 0) return hipErrorInvalidValue;
   if (epi != EPI_F32 && (N % 8)) return hipErrorInvalidValue;
   if ((size_t)M * lda * 2 >= (1ull << 32) || (size_t)N * ldb * 2 >= (1ull << 32)) return hipErrorInvalidValue;
+  if (epi == EPI_QKV && M >= (1 << 22)) return hipErrorInvalidValue;   // qkv_split_row (epilogue.hip.h) is exact below that
   if (M >= 2048 && N >= 256) {
     // Outputs whose width is a whole number of 192-column tiles but not of 256-column ones (the encoder's 1152: fc2 and
     // the three plain-store dX GEMMs) take the 384x192 tile, which has no half-empty last column tile: 1,458 tiles of

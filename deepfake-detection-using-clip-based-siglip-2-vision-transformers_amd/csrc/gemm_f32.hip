@@ -70,6 +70,7 @@ hipError_t gemm_f32_generic(const float* A, long sam, long sak, const float* B, 
                             int K, int epi, int out_dtype, const EpiParams& p, hipStream_t s) {
   if (M == 0 || N == 0) return hipSuccess;
   if (epi != EPI_F32 && (N % 4)) return hipErrorInvalidValue;
+  if (epi == EPI_QKV && M >= (1 << 22)) return hipErrorInvalidValue;   // qkv_split_row (epilogue.hip.h) is exact below that
   return dispatch_epilogue(epi, out_dtype, [&](auto tag) {
     using T = decltype(tag);
     return launch_f32<T::epi, typename T::out>(A, sam, sak, B, sbn, sbk, M, N, K, p, s);

@@ -151,12 +151,16 @@ int sgl_abi_version(void);
  *     `ws` has to survive from the forward to the backward;
  *   - sgl_backward_layer*(layer) first recomputes block `layer` from its input hidden state into the shared region (LN1,
  *     QKV, attention, out_proj + residual, LN2, fc1 + GELU; not fc2), then runs the plain backward of the block.  The call
- *     sequence and the gradient carried in `ws` between calls are unchanged;
- *   - training token limit: B * grid must not exceed floor((2^32 - 1) / R), R = the bytes of one row of the widest GEMM
- *     operand, max(round_up(I, 128), 3 * hidden_size, round_up(3 * p^2, 64)) elements of the compute dtype (two bytes in
- *     bf16 / fp16, four in fp32, 6 * round_up(that, 8) for the bf16x3 split operand), and not 2^22 - 1: the GEMMs refuse an
- *     operand of 2^32 bytes.  Larger training shapes return SGL_ERR_BAD_SHAPE from sgl_query_sizes(train = 1),
- *     sgl_forward* with saved != NULL and sgl_backward_*.  so400m in bf16: 493 447 tokens (B = 676 at 384 px). */
+ *     sequence and the gradient carried in `ws` between calls are unchanged.
+ * Token limit (every context, plain and recompute, every pass): B * grid must not exceed floor((2^32 - 1) / R), R = the
+ * bytes of one row of the widest GEMM operand of the pass, nor exceed 2^22 - 1 (the QKV scatter's row split).  The widest
+ * row is max(round_up(I, 128), hidden_size, round_up(3 * p^2, 64)) elements at inference and max(that, 3 * hidden_size)
+ * when training, of the compute dtype: two bytes in bf16 / fp16, four in fp32, 6 * round_up(that, 8) for the bf16x3 split
+ * operand.  The GEMMs refuse an operand of 2^32 bytes.  MX-fp8: R = 2 * max(hidden_size, round_up(3 * p^2, 64)), the bf16
+ * patch and head GEMMs it still runs, and at most 65 535 * 128 tokens (the MX GEMM's grid).  Larger shapes return
+ * SGL_ERR_BAD_SHAPE from sgl_query_sizes, sgl_forward* and sgl_backward_* before anything is enqueued.  so400m: 493 447
+ * tokens in bf16 / fp16 (B = 676 at 384 px), 246 723 in fp32, 164 482 in bf16x3, for inference and training alike (its
+ * widest row is the MLP's 4352 on both); 1 864 135 in MX-fp8. */
 int sgl_query_sizes(const sgl_ctx* ctx, int B, int H, int W, int train, size_t* shadow_bytes, size_t* saved_bytes,
                     size_t* ws_bytes);
 
@@ -270,7 +274,10 @@ enum { SGL_EPI_STORE = 0, SGL_EPI_BIAS_GELU = 1, SGL_EPI_RES_F32 = 2, SGL_EPI_QK
  *   row b * tokens + n goes to out[which][b][h][n][d] of [3][batch][heads][tokens][head_dim_pad], and the pad columns
  *   [head_dim, head_dim_pad) of every row are written as +0 (head_dim % 8 == 0, head_dim_pad % 8 == 0).  Every head's
  *   [tokens][head_dim_pad] matrix is contiguous; for 16-bit outputs with head_dim 72 / head_dim_pad 80 and heads % 4 == 0
- *   (so400m) the large-M kernel works on tiles of four whole heads and writes each head's rows as runs of whole rows. */
+ *   (so400m) the large-M kernel works on tiles of four whole heads and writes each head's rows as runs of whole rows.
+ *   SGL_EPI_QKV with M >= 2^22 is refused (SGL_ERR_UNSUPPORTED, nothing written): the epilogue's row split (row / tokens by a
+ *   reciprocal estimate and one correction) is exact for rows below 2^22 only.  A 16-bit operand of 2^32 bytes or more
+ *   (M * lda * 2, N * ldb * 2) is refused the same way. */
 int sgl_op_gemm_nt(int dtype, const void* A, int lda, const void* B, int ldb, int M, int N, int K, int epi, void* out,
                    int ldo, void* out2, int ldo2, const float* bias, const float* res, int ldr, const void* aux,
                    int ldaux, const float* pos, int pos_rows, int tokens, int heads, int head_dim, int head_dim_pad,

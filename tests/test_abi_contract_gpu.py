@@ -688,6 +688,35 @@ def test_raw_abi_refuses_546px_and_touches_nothing(pkg, hiplib, mode):
         assert_finite(run.outputs(pooled=False), "546 px without the head")
 
 
+def test_raw_abi_refuses_token_limit_plus_one_and_touches_nothing(pkg, hiplib):
+    """so400m-1layer, bf16 inference on one-patch-high images (14 x 14 px: one token each), B = 493 448 = the token limit
+    + 1: its fc2 operand `a` [M][4352] bf16 would be the first of 2^32 bytes, which the GEMM refuses.  sgl_forward returns
+    SGL_ERR_BAD_SHAPE from its prologue: every arena (sized for 64 such images, filled with 0xFF) keeps every byte and its
+    guards.  The limit itself is accepted by sgl_query_sizes; through the package the refusal is SglError from
+    sgl_query_sizes (host arithmetic, nothing launched)."""
+    limit = 493_447
+    with Session(pkg, hiplib, "so400m-1layer", "bf16", 0, seed=19) as ses:
+        assert ses.sizes(limit, 14, 14, False)[0] == ah.OK
+        assert ses.sizes(limit + 1, 14, 14, False)[0] == ah.ERR_BAD_SHAPE
+        shadow = ses.new_shadow(0xFF)
+        assert ses.prepare(shadow, full=True) == ah.OK
+        run = Run(ses, 64, 14, 14, False, 0xFF)
+        run.B = limit + 1
+        px = ses.pixels(64, 14, 14, 1)          # never read: the shape is refused (and the arenas are too small) first
+        torch.cuda.synchronize()
+        assert ses.forward(run, shadow, px) == ah.ERR_BAD_SHAPE
+        torch.cuda.synchronize()
+        for name, a in run.arenas():
+            assert a.untouched() and a.guards_intact(), f"`{name}` was written by a refused sgl_forward"
+    cfg = pkg.get_config("so400m-1layer")
+    model = pkg.SiglipVisionModelHIP(cfg, compute_dtype="bf16").to(DEV).eval()
+    x = torch.empty(limit + 1, 3, 14, 14, device=DEV)      # 1.16 GB; refused before it is read
+    with torch.no_grad(), pytest.raises(pkg.lib.SglError, match="sgl_query_sizes: bad shape"):
+        model(pixel_values=x, interpolate_pos_encoding=True)
+    del x, model
+    torch.cuda.empty_cache()
+
+
 @pytest.mark.parametrize("mode", ["fp32", "bf16"])
 def test_package_refuses_546px_before_any_launch(pkg, hiplib, mode):
     """39 x 39 = 1521 tokens is above the pooling head's 1488: the package raises its status error, and raises it from

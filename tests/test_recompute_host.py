@@ -100,8 +100,8 @@ def test_so400m_b128_sizes(pkg, hiplib, dt):
 
 @pytest.mark.parametrize("dt,limit", [(1, 493_447), (3, 493_447), (0, 246_723), (2, 164_482)])
 def test_training_token_limit(pkg, hiplib, dt, limit):
-    """The recompute context refuses training shapes whose widest GEMM operand would reach 2^32 bytes (the GEMMs'
-    32-bit buffer ranges): SGL_ERR_BAD_SHAPE from sgl_query_sizes(train=1); inference and the plain context unchanged."""
+    """Every context refuses shapes whose widest GEMM operand would reach 2^32 bytes (the GEMMs' 32-bit buffer ranges):
+    SGL_ERR_BAD_SHAPE from sgl_query_sizes, training and inference, recompute and plain context alike."""
     L = pkg.lib
     a = _create(hiplib, L, SO400M, dt, 0)
     r = _create(hiplib, L, SO400M, dt, 1)
@@ -109,14 +109,90 @@ def test_training_token_limit(pkg, hiplib, dt, limit):
         bmax = limit // 729
         assert _sizes(hiplib, r, bmax, 384, 1)[0] == 0
         assert _sizes(hiplib, r, bmax + 1, 384, 1)[0] == -1
-        assert _sizes(hiplib, r, bmax + 1, 384, 0)[0] == 0
-        assert _sizes(hiplib, a, bmax + 1, 384, 1)[0] == 0
+        assert _sizes(hiplib, r, bmax + 1, 384, 0)[0] == -1
+        assert _sizes(hiplib, a, bmax + 1, 384, 1)[0] == -1
         # exact boundary in tokens (patch 14 on a one-patch-high image: B tokens)
         assert _sizes(hiplib, r, limit, 14, 1)[0] == 0
         assert _sizes(hiplib, r, limit + 1, 14, 1)[0] == -1
     finally:
         hiplib.sgl_destroy(a)
         hiplib.sgl_destroy(r)
+
+
+def _token_limit(cfg, dt, train):
+    """The token limit restated from the operands each pass hands to the GEMMs (see test_token_limit_every_context)."""
+    D, I, _, _, P = cfg[:5]
+    Ip, Kp = (I + 127) // 128 * 128, (3 * P * P + 63) // 64 * 64
+    if dt == 5:   # MX-fp8
+        return min((2 ** 32 - 1) // (2 * max(D, Kp)), 65535 * 128, 2 ** 22 - 1)
+    w = max(Ip, D, Kp, 3 * D if train else 0)
+    row = {0: 4 * w, 1: 2 * w, 3: 2 * w, 2: 3 * ((w + 7) // 8 * 8) * 2}[dt]
+    return min((2 ** 32 - 1) // row, 2 ** 22 - 1)
+
+
+# so400m: Ip = 4352 > 3 D = 3456 > Kp = 640, so the forward's widest row and the training path's are the same 4352
+LIMITS = {(SO400M, 1): 493_447, (SO400M, 3): 493_447, (SO400M, 0): 246_723, (SO400M, 2): 164_482}
+
+
+@pytest.mark.parametrize("train", [0, 1])
+@pytest.mark.parametrize("recompute", [0, 1])
+@pytest.mark.parametrize("dt", [0, 1, 2, 3])
+@pytest.mark.parametrize("cfg", [SO400M, TINY, HOSTILE], ids=["so400m", "tiny", "hostile"])
+def test_token_limit_every_context(pkg, hiplib, cfg, dt, recompute, train):
+    """One token limit for plain and recompute contexts, inference and training: the limit is accepted, one token more is
+    SGL_ERR_BAD_SHAPE, at 384 px (B = limit // 729) and token-exact on a one-patch-high image (B tokens).
+
+    Derivation, from the operands a pass hands to gemm_nt / gemm_tn with M = B * grid rows (csrc/encoder.hip): the forward
+    reads im2col [M][Kp] (patch GEMM), h1 / attn / h2 [M][D] (QKV, out_proj, fc1), a [M][Ip] (fc2) and the head's cast of the
+    last hidden state [M][D]; its widest row is max(Ip, D, Kp) elements.  Training adds u / du [M][Ip] and dqkv [M][3 D]
+    (dX and dW of the QKV projection): max(Ip, 3 D, Kp).  gemm_nt_mfma / gemm_tn_mfma refuse M * row_bytes >= 2^32, so
+    limit = floor((2^32 - 1) / row_bytes): 2 bytes per element in bf16 / fp16, 4 in strict fp32, and the bf16x3 operand is
+    [M][3 * round_up(w, 8)] bf16.  so400m: w = 4352 both ways (Ip > 3 D), hence 4294967295 // 8704 = 493 447,
+    // 17408 = 246 723, // 26112 = 164 482 for inference as for training.  tiny (w = 128, 192 training) is narrow: its
+    quotient is above the 2^22 - 1 rows up to which the EPI_QKV row split is exact, which is then the limit (4 194 303)
+    on a plain context and on inference too, but for bf16x3 training (4294967295 // 1152 = 3 728 270).  hostile (w = 640 = Ip = Kp) lies
+    between: 3 355 443 in bf16 / fp16, 1 677 721 in fp32, 1 118 481 in bf16x3."""
+    L = pkg.lib
+    limit = _token_limit(cfg, dt, train)
+    if (cfg, dt) in LIMITS:
+        assert limit == LIMITS[(cfg, dt)]
+    elif cfg is TINY:
+        assert limit == (3_728_270 if (dt, train) == (2, 1) else 2 ** 22 - 1)
+    else:
+        assert limit == {1: 3_355_443, 3: 3_355_443, 0: 1_677_721, 2: 1_118_481}[dt]
+    P = cfg[4]
+    ctx = _create(hiplib, L, cfg, dt, recompute)
+    try:
+        assert _sizes(hiplib, ctx, limit, P, train)[0] == 0
+        assert _sizes(hiplib, ctx, limit + 1, P, train)[0] == -1
+        res = 384 if cfg is SO400M else 27 * P          # 729 tokens per image
+        bmax = limit // 729
+        assert _sizes(hiplib, ctx, bmax, res, train)[0] == 0
+        assert _sizes(hiplib, ctx, bmax + 1, res, train)[0] == -1
+    finally:
+        hiplib.sgl_destroy(ctx)
+
+
+@pytest.mark.parametrize("cfg,limit", [(SO400M, 1_864_135), (TINY, 4_194_303), (HOSTILE, 3_355_443)],
+                         ids=["so400m", "tiny", "hostile"])
+def test_token_limit_mxfp8(pkg, hiplib, cfg, limit):
+    """MX-fp8 (inference only): its own kernels index with size_t and gemm_nt_mx has no operand guard; the bound comes from
+    the bf16 GEMMs it still runs, the patch GEMM's im2col [M][Kp] and the head's cast of the last hidden state [M][D]
+    (so400m: 4294967295 // 2304), from gemm_nt_mx's 65 535 row tiles of 128 and from the head's EPI_QKV row split."""
+    L = pkg.lib
+    assert _token_limit(cfg, 5, 0) == limit
+    ctx = _create(hiplib, L, cfg, L.SGL_DTYPE_MXFP8, 0)
+    try:
+        P = cfg[4]
+        assert _sizes(hiplib, ctx, limit, P, 0)[0] == 0
+        assert _sizes(hiplib, ctx, limit + 1, P, 0)[0] == -1
+        assert _sizes(hiplib, ctx, limit // 729, 27 * P, 0)[0] == 0
+        assert _sizes(hiplib, ctx, limit // 729 + 1, 27 * P, 0)[0] == -1
+        assert _sizes(hiplib, ctx, limit, P, 1)[0] == -2            # a shape that passes: MX-fp8 has no training pass
+        assert _sizes(hiplib, ctx, limit + 1, P, 1)[0] == -1        # the shape is judged first
+        # the mode has no recompute context (sgl_create_ex returns NULL: test_create_ex_policies), so plain is all there is
+    finally:
+        hiplib.sgl_destroy(ctx)
 
 
 # ---- Python surface ---------------------------------------------------------------------------------------------------
