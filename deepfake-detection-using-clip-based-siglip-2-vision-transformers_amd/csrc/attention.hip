@@ -282,6 +282,159 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 }
 
 // ======================================================================================================
+// forward, ragged batch: attn_fwd_kernel<T, DP, false> on segment `seg` of a packed batch (seg_block, attention.hip.h)
+// ======================================================================================================
+// A sibling, not a template variant, of attn_fwd_kernel: that kernel's kernel arguments and scalar prologue are pinned.
+// Q, K, V head-major [H][T][DP]; the head's descriptors start at the segment's first row and span its N = n_s rows, so
+// rows past N read as zeros (never the next segment's rows), and query blocks and key tiles count from the segment's
+// first row.  From the descriptors on, the statements are attn_fwd_kernel's, operation for operation, on the same values:
+// a segment gets the bits attn_fwd_kernel gives an image of N tokens.  out [T][H*dh], lse [H][T].
+template <typename T, int DP>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void attn_fwd_varlen_kernel(
+    const T* __restrict__ Q, const T* __restrict__ K, const T* __restrict__ V, T* __restrict__ out, float* __restrict__ lse,
+    const int* __restrict__ cu, int S, int Ttot, int max_n, int H, int dh, float c, float scale) {
+  using C = AttnCfg<DP>;
+  constexpr int KT = 64;
+  constexpr int KBYTES = KT * C::RSTR, VBYTES = KT * C::TSTR, STAGE = KBYTES + VBYTES;
+  constexpr int SCK = C::RSTR / 16, SCV = C::TSTR / 16;
+  constexpr int NIK = KT * SCK / 64, NIV = KT * SCV / 64, NSLOT = NIK + NIV;
+  constexpr int NPW = (NSLOT + 3) / 4;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int t = threadIdx.x, lane = t & 63;
+  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+  SegBlock sb;
+  if (!seg_block(cu, S, Ttot, max_n, H, (max_n + 127) / 128, 128, sb)) return;
+  const int N = sb.n, hd = sb.hd;
+  const int q0 = sb.xb * 128 + w * 32;
+  HeadSrc src;
+  src.rowbytes = (uint32_t)DP * 2u;
+  src.nc = (uint32_t)DP / 8u;
+  src.bytes = (uint32_t)((size_t)N * DP * 2);
+  src.base = ((size_t)hd * Ttot + sb.row0) * (size_t)DP;
+  const __amdgpu_buffer_rsrc_t rq = make_rsrc(Q + src.base, src.bytes);
+  const u32x4 dk_ = att_desc(K + src.base, src.bytes);
+  const u32x4 dv_ = att_desc(V + src.base, src.bytes);
+  const uint32_t lds0 = (uint32_t)(size_t)((SGL_LDS char*)smem);
+
+  const int qi = lane & 31, hh = lane >> 5;
+  lo_x8<T> qf[C::KS];
+#pragma unroll
+  for (int ks = 0; ks < C::KS; ++ks) {
+    const uint32_t ch = (uint32_t)(2 * ks + hh);
+    qf[ks] = as_x8<T>(a_ldg(rq, (q0 + qi < N && ch < src.nc) ? (uint32_t)(q0 + qi) * src.rowbytes + ch * 16u : SGL_OOB));
+  }
+
+  uint32_t voff[NPW];
+#pragma unroll
+  for (int j = 0; j < NPW; ++j) {
+    const int sl = w + 4 * j;
+    voff[j] = (sl < NIK) ? att_chunk_off(sl * 64 + lane, KT, SCK, (int)src.nc, src.rowbytes)
+                         : att_chunk_off((sl - NIK) * 64 + lane, KT, SCV, (int)src.nc, src.rowbytes);
+  }
+  const uint32_t tile_adv = (uint32_t)KT * src.rowbytes;
+  auto issue = [&](int stage) {
+    const uint32_t sbase = lds0 + (uint32_t)(stage * STAGE);
+#pragma unroll
+    for (int j = 0; j < NPW; ++j) {
+      const int sl = w + 4 * j;
+      if (sl < NSLOT) att_dma16(sl < NIK ? dk_ : dv_, sbase + (uint32_t)sl * 1024u, voff[j]);
+      voff[j] += tile_adv;
+    }
+  };
+
+  float m_run = -INFINITY, l_run = 0.f;
+  f32x16 o[C::DT];
+#pragma unroll
+  for (int dt = 0; dt < C::DT; ++dt)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) o[dt][r] = 0.f;
+
+  const int ntiles = (N + KT - 1) / KT;
+#pragma unroll
+  for (int ks = 0; ks < C::KS; ++ks) asm volatile("" ::"v"(qf[ks]));
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  issue(0);
+  for (int tile = 0; tile < ntiles; ++tile) {
+    const int cur = tile & 1;
+    SGL_ATT_WAIT_BARRIER(0);
+    if (tile + 1 < ntiles) issue(cur ^ 1);
+    const char* kb = smem + cur * STAGE;
+    const char* vb = kb + KBYTES;
+    f32x16 s0, s1;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { s0[r] = 0.f; s1[r] = 0.f; }
+#pragma unroll
+    for (int ks = 0; ks < C::KS; ++ks) {
+      const lo_x8<T> k0 = lds_row8<T>(kb + qi * C::RSTR + (16 * ks + 8 * hh) * 2);
+      const lo_x8<T> k1 = lds_row8<T>(kb + (qi + 32) * C::RSTR + (16 * ks + 8 * hh) * 2);
+      s0 = MFMA32(k0, qf[ks], s0);
+      s1 = MFMA32(k1, qf[ks], s1);
+    }
+    if (tile == ntiles - 1) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int key = tile * KT + (r & 3) + 8 * (r >> 2) + 4 * hh;
+        if (key >= N) s0[r] = -INFINITY;
+        if (key + 32 >= N) s1[r] = -INFINITY;
+      }
+    }
+    float mx = s0[0];
+#pragma unroll
+    for (int r = 1; r < 16; ++r) mx = fmaxf(mx, s0[r]);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s1[r]);
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    const float m_new = fmaxf(m_run, mx);
+    const bool grew = __any(m_new > m_run);
+    const float alpha = grew ? fast_exp2(c * (m_run - m_new)) : 1.0f;
+    const float mc = m_new * c;
+    float rs = 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      s0[r] = fast_exp2(fmaf(s0[r], c, -mc));
+      s1[r] = fast_exp2(fmaf(s1[r], c, -mc));
+      rs += s0[r] + s1[r];
+    }
+    l_run = l_run * alpha + rs;
+    m_run = m_new;
+    if (grew) {
+#pragma unroll
+      for (int dt = 0; dt < C::DT; ++dt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o[dt][r] *= alpha;
+    }
+    lo_x8<T> pb[4];
+    pb[0] = pack8<T>(s0, 0);
+    pb[1] = pack8<T>(s0, 8);
+    pb[2] = pack8<T>(s1, 0);
+    pb[3] = pack8<T>(s1, 8);
+#pragma unroll
+    for (int dt = 0; dt < C::DT; ++dt)
+#pragma unroll
+      for (int kk = 0; kk < 4; ++kk) o[dt] = MFMA32(lds_trfrag<T>(vb, C::TSTR, kk, dt * 32, lane), pb[kk], o[dt]);
+  }
+  const float l = l_run + __shfl_xor(l_run, 32, 64);
+  const float inv = 1.0f / l;
+  const int q = q0 + qi;
+  if (q < N) {
+    T* orow = out + (size_t)(sb.row0 + q) * ((size_t)H * dh) + hd * dh;
+#pragma unroll
+    for (int dt = 0; dt < C::DT; ++dt)
+#pragma unroll
+      for (int g4 = 0; g4 < 4; ++g4) {
+        const int d = dt * 32 + 8 * g4 + 4 * hh;
+        if (d < dh) {
+          lo_x4<T> v4;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) v4[r] = (T)(o[dt][4 * g4 + r] * inv);
+          *reinterpret_cast<lo_x4<T>*>(orow + d) = v4;
+        }
+      }
+    if (hh == 0) lse[(size_t)hd * Ttot + sb.row0 + q] = m_run * scale + __logf(l);
+  }
+}
+
+// ======================================================================================================
 // backward: dK, dV   (wave owns 32 keys; sweeps 32-query tiles staged in LDS)
 // ======================================================================================================
 template <typename T, int DP, bool TOK>
@@ -735,6 +888,35 @@ hipError_t attn_fwd(const void* q, const void* k, const void* v, int dtype, void
                          tok.value ? ld : 0, sc.c, sc.scale);
       return hipGetLastError();
     });
+  });
+}
+
+// What attn_fwd refuses for one image of max_n tokens is refused here; T bounds the packed buffers' rows.
+bool attn_varlen_shape_ok(int dtype, int S, int T, int max_n, int H, int dh, int DP) {
+  if (S < 1 || T < 1 || max_n < 1 || H < 1 || dh < 1 || dh > DP) return false;
+  if (!attn_shape_ok(dtype, 1, H, max_n, dh, DP, 0, ATTN_FWD)) return false;
+  const int rows = dtype == DT_F32 ? 4 : 128;   // query rows of a workgroup
+  return seg_grid_ok(S, H, (max_n + rows - 1) / rows);
+}
+
+hipError_t attn_fwd_varlen(const void* q, const void* k, const void* v, int dtype, void* out, float* lse, const int* cu,
+                           int S, int T, int max_n, int H, int dh, int DP, hipStream_t s) {
+  if (!attn_varlen_shape_ok(dtype, S, T, max_n, H, dh, DP)) return hipErrorInvalidValue;
+  if (dtype == DT_F32)
+    return attn_ref_fwd_varlen((const float*)q, (const float*)k, (const float*)v, (float*)out, lse, cu, S, T, max_n, H, dh,
+                               DP, s);
+  if (dtype == DT_F32_MFMA)
+    return attn_f32_fwd_varlen((const float*)q, (const float*)k, (const float*)v, (float*)out, lse, cu, S, T, max_n, H, dh,
+                               DP, s);
+  if (!attn_aligned16(q, k, v)) return hipErrorInvalidValue;
+  const AttnScales sc = attn_scales(dh);
+  return dispatch_attn(dtype, DP, [&](auto tag) {
+    using T16 = typename decltype(tag)::type;
+    constexpr int DPV = decltype(tag)::dp;
+    hipLaunchKernelGGL((attn_fwd_varlen_kernel<T16, DPV>), seg_grid((max_n + 127) / 128, S * H), dim3(256),
+                       AttnCfg<DPV>::SMEM_FWD, s, (const T16*)q, (const T16*)k, (const T16*)v, (T16*)out, lse, cu, S, T,
+                       max_n, H, dh, sc.c, sc.scale);
+    return hipGetLastError();
   });
 }
 

@@ -56,6 +56,40 @@ __device__ __forceinline__ size_t head_rows(int ld, int b, int h, int H, int N, 
   return head_src(ld, b, h, H, N, dh, DP).base;
 }
 
+// ---- ragged (varlen) addressing ---------------------------------------------------------------------------------------
+// Packed layout of the *_varlen kernels: segment s owns rows cu[s] .. cu[s+1]-1 of every [T]-row buffer, q/k/v are
+// head-major [H][T][DP].  A workgroup serves one (segment, head) pair and one block of `rows` query rows of it; the 1-D
+// launch and the XCD map are head_block's of attention.hip (XCD x owns pairs x, x+8, ...; 8 * ceil(S*H / 8) * nb
+// workgroups).  What is read from cu is clamped: 0 <= row0 <= row0 + n <= T and n <= max_n, so a wrong table gives wrong
+// numbers and never an address outside the buffers.  False: a padding pair, or a block that starts past the segment's end
+// (the whole workgroup returns before its first barrier).
+struct SegBlock {
+  int seg, hd, xb;   // segment, head, block index within the segment
+  int row0, n;       // first row of the segment in the packed buffers, its token count
+};
+// the clamp: rows [row0, row0 + n) of segment seg < S
+__device__ __forceinline__ void seg_range(const int* __restrict__ cu, int seg, int T, int max_n, int& row0, int& n) {
+  const int lo = min(max(cu[seg], 0), T);
+  const int hi = min(max(cu[seg + 1], lo), T);
+  row0 = lo;
+  n = min(hi - lo, max_n);
+}
+__device__ __forceinline__ bool seg_block(const int* __restrict__ cu, int S, int T, int max_n, int H, int nb, int rows,
+                                          SegBlock& sb) {
+  const int pid = blockIdx.x, xcd = pid & 7, slot = pid >> 3;
+  const int hq = slot / nb;
+  const int sh = hq * 8 + xcd;
+  if (sh >= S * H) return false;
+  sb.xb = slot - hq * nb;
+  sb.seg = sh / H;
+  sb.hd = sh - sb.seg * H;
+  seg_range(cu, sb.seg, T, max_n, sb.row0, sb.n);
+  return sb.xb * rows < sb.n;
+}
+static inline dim3 seg_grid(int nb, int SH) { return dim3((unsigned)(8 * ((SH + 7) / 8) * nb)); }
+// S * H pairs times nb blocks in a 1-D grid
+static inline bool seg_grid_ok(int S, int H, int nb) { return (size_t)8 * (((size_t)S * H + 7) / 8) * (size_t)nb < (1ull << 31); }
+
 // ---- the shape contract ---------------------------------------------------------------------------------------------
 // head_dim_pad values of the 16-bit kernels: the contract accepts exactly these and dispatch_attn instantiates exactly these
 constexpr int kAttnDP[] = {16, 32, 48, 64, 80, 96};
@@ -116,5 +150,10 @@ hipError_t attn_ref_fwd(const float* q, const float* k, const float* v, float* o
 hipError_t attn_ref_bwd(const float* q, const float* k, const float* v, const float* out, const float* dout,
                         const float* lse, float* dqkv, float* delta, int B, int H, int N, int dh, int DP, int ld,
                         hipStream_t s);
+// the ragged forwards of the two fp32 routes (attn_fwd_varlen has checked the shapes): q, k, v [H][T][DP], cu on the device
+hipError_t attn_f32_fwd_varlen(const float* q, const float* k, const float* v, float* out, float* lse, const int* cu, int S,
+                               int T, int max_n, int H, int dh, int DP, hipStream_t s);
+hipError_t attn_ref_fwd_varlen(const float* q, const float* k, const float* v, float* out, float* lse, const int* cu, int S,
+                               int T, int max_n, int H, int dh, int DP, hipStream_t s);
 
 }  // namespace sgl

@@ -153,6 +153,109 @@ __global__ __launch_bounds__(256) void attn_f32_fwd_kernel(const float* __restri
 }
 
 // ======================================================================================================
+// Ragged batch: attn_f32_fwd_kernel on segment `seg` of a packed batch (seg_block, attention.hip.h).  Q, K, V head-major
+// [H][T][DP]; hb is the head's first row of the segment and N its length, and every fetch is guarded by `< N` as above, so
+// nothing of a neighbouring segment is read.  The statements after the addressing are attn_f32_fwd_kernel's on the same
+// values: a segment gets the bits that kernel gives an image of N tokens.  out [T][H*dh], lse [H][T].
+__global__ __launch_bounds__(256) void attn_f32_fwd_varlen_kernel(const float* __restrict__ Q, const float* __restrict__ K,
+                                                                  const float* __restrict__ V, float* __restrict__ out,
+                                                                  float* __restrict__ lse, const int* __restrict__ cu,
+                                                                  int S, int T, int max_n, int H, int dh, int DP,
+                                                                  float scale) {
+  __shared__ float ktile[AF_TILE], vtile[AF_TILE];
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int li = lane & 31, hh = lane >> 5;
+  SegBlock sb;
+  if (!seg_block(cu, S, T, max_n, H, (max_n + 127) / 128, 128, sb)) return;
+  const int N = sb.n, h = sb.hd, rs = DP;
+  const size_t hb = ((size_t)h * T + sb.row0) * (size_t)DP;
+  const int q = sb.xb * 128 + w * 32 + li;
+  const int ks = (dh + 1) / 2;
+  const int ndt = (dh + 31) / 32;
+  float qf[AF_MAXD / 2];
+#pragma unroll
+  for (int s = 0; s < AF_MAXD / 2; ++s)
+    qf[s] = (s < ks && q < N && 2 * s + hh < dh) ? Q[hb + (size_t)q * rs + 2 * s + hh] : 0.f;
+  f32x16 o[3];
+#pragma unroll
+  for (int dt = 0; dt < 3; ++dt)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) o[dt][i] = 0.f;
+  float m_run = -INFINITY, l_run = 0.f;
+  const int nc4 = dh >> 2;
+  f32x4 pk[AF_NLD], pv[AF_NLD];
+  af_zero(ktile, t);
+  af_zero(vtile, t);
+  af_load(pk, K + hb, rs, 0, N, nc4, t);
+  af_load(pv, V + hb, rs, 0, N, nc4, t);
+  for (int k0 = 0; k0 < N; k0 += 32) {
+    __syncthreads();
+    af_store(ktile, pk, nc4, t);
+    af_store(vtile, pv, nc4, t);
+    __syncthreads();
+    if (k0 + 32 < N) {
+      af_load(pk, K + hb, rs, k0 + 32, N, nc4, t);
+      af_load(pv, V + hb, rs, k0 + 32, N, nc4, t);
+    }
+    f32x16 s16;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) s16[i] = 0.f;
+#pragma unroll
+    for (int s = 0; s < AF_MAXD / 2; ++s)
+      if (s < ks) s16 = MFMA_F32(ktile[li * AF_RS + 2 * s + hh], qf[s], s16);
+    float mx = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int key = k0 + ctile_row(i, hh);
+      s16[i] = (key < N) ? s16[i] * scale : -INFINITY;
+      mx = fmaxf(mx, s16[i]);
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    const float m_new = fmaxf(m_run, mx);
+    const float alpha = expf(m_run - m_new);
+    float rsum = 0.f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      s16[i] = expf(s16[i] - m_new);
+      rsum += s16[i];
+    }
+    l_run = l_run * alpha + rsum;
+    m_run = m_new;
+#pragma unroll
+    for (int dt = 0; dt < 3; ++dt)
+      if (dt < ndt) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) o[dt][i] *= alpha;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          const int krow = ctile_row(i, hh);
+          o[dt] = MFMA_F32(vtile[krow * AF_RS + dt * 32 + li], s16[i], o[dt]);
+        }
+      }
+  }
+  const float l = l_run + __shfl_xor(l_run, 32, 64);
+  const float inv = 1.0f / l;
+  if (q < N) {
+    float* orow = out + (size_t)(sb.row0 + q) * ((size_t)H * dh) + h * dh;
+#pragma unroll
+    for (int dt = 0; dt < 3; ++dt)
+      if (dt < ndt) {
+#pragma unroll
+        for (int g4 = 0; g4 < 4; ++g4) {
+          const int d = dt * 32 + 8 * g4 + 4 * hh;
+          if (d < dh) {
+            f32x4 v4;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) v4[r] = o[dt][4 * g4 + r] * inv;
+            *reinterpret_cast<f32x4*>(orow + d) = v4;
+          }
+        }
+      }
+    if (hh == 0) lse[(size_t)h * T + sb.row0 + q] = m_run + logf(l);
+  }
+}
+
+// ======================================================================================================
 // dQ (+ delta = rowsum(dO ∘ O) into `delta`, plain [B][H][N] floats for the dK/dV kernel)
 __global__ __launch_bounds__(256) void attn_f32_bwd_q_kernel(const float* __restrict__ Q, const float* __restrict__ K,
                                                              const float* __restrict__ V, const float* __restrict__ O,
@@ -351,6 +454,13 @@ hipError_t attn_f32_fwd(const float* q, const float* k, const float* v, float* o
                         int dh, int DP, int ld, hipStream_t s) {
   hipLaunchKernelGGL(attn_f32_fwd_kernel, dim3((N + 127) / 128, B * H), dim3(256), 0, s, q, k, v, out, lse, H, N, dh, DP,
                      ld, attn_scales(dh).scale);
+  return hipGetLastError();
+}
+
+hipError_t attn_f32_fwd_varlen(const float* q, const float* k, const float* v, float* out, float* lse, const int* cu, int S,
+                               int T, int max_n, int H, int dh, int DP, hipStream_t s) {
+  hipLaunchKernelGGL(attn_f32_fwd_varlen_kernel, seg_grid((max_n + 127) / 128, S * H), dim3(256), 0, s, q, k, v, out, lse,
+                     cu, S, T, max_n, H, dh, DP, attn_scales(dh).scale);
   return hipGetLastError();
 }
 

@@ -1,4 +1,5 @@
 // The attention-pooling head's kernels (sgl_op_pool_attn_fwd / _bwd and the encoder's head stage).
+#include "attention.hip.h"
 #include "common.hip.h"
 #include "kernels.h"
 
@@ -114,6 +115,136 @@ hipError_t pool_attn_fwd(const float* q, const void* K, const void* V, int dtype
     hipLaunchKernelGGL(pool_attn_fwd_kernel<T>, dim3(B * H), dim3(256), smem, s, q, (const T*)K, (const T*)V, (T*)out,
                        probs, H, N, dh, DP);
   });
+}
+
+// Ragged batch: pool_attn_fwd_kernel on segment `seg` of a packed batch.  K, V head-major [H][T][DP]; one block per
+// (segment, head) works on the segment's N rows from its first row (seg_range's clamp, attention.hip.h), with the same
+// per-thread row walk and the same reduction order, so a segment gets the bits pool_attn_fwd_kernel gives an image of N
+// tokens.  The LDS window is sized for max_n.  out [S][H*dh], probs [H][T].
+template <typename T>
+__global__ __launch_bounds__(256) void pool_attn_fwd_varlen_kernel(const float* __restrict__ q, const T* __restrict__ K,
+                                                                   const T* __restrict__ V, T* __restrict__ out,
+                                                                   float* __restrict__ probs, const int* __restrict__ cu,
+                                                                   int Ttot, int max_n, int H, int dh, int DP) {
+  extern __shared__ __attribute__((aligned(16))) float pa_smem[];  // [N*CPR] chunk partials, [N] probabilities, [8] scratch
+  const int CPR = DP >> 3, RP = 256 / CPR;
+  const int bh = blockIdx.x, h = bh % H, b = bh / H;
+  int row0, N;
+  seg_range(cu, b, Ttot, max_n, row0, N);
+  float* part = pa_smem;
+  float* pr = part + (size_t)N * CPR;
+  float* red = pr + N;
+  const T* Kb = K + ((size_t)h * Ttot + row0) * DP;
+  const T* Vb = V + ((size_t)h * Ttot + row0) * DP;
+  float* prow = probs + (size_t)h * Ttot + row0;
+  const float scale = rsqrtf((float)dh);
+  const int t = threadIdx.x, c = t % CPR, r0 = t / CPR;
+  const bool act = t < RP * CPR;
+  float qv[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) qv[j] = (c * 8 + j < dh) ? q[h * dh + c * 8 + j] : 0.f;
+  if (act)
+    for (int n = r0; n < N; n += RP) {
+      float kv[8];
+      Vec<T, 8>::ld(Kb + (size_t)n * DP + c * 8, kv);
+      float s = 0.f;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) s = fmaf(qv[j], kv[j], s);
+      part[n * CPR + c] = s;
+    }
+  __syncthreads();
+  float mx = -INFINITY;
+  for (int n = t; n < N; n += 256) {
+    float s = 0.f;
+    for (int j = 0; j < CPR; ++j) s += part[n * CPR + j];
+    s *= scale;
+    pr[n] = s;
+    mx = fmaxf(mx, s);
+  }
+  mx = block_reduce_256<T>(mx, red, true);
+  float sum = 0.f;
+  for (int n = t; n < N; n += 256) {
+    const float e = __expf(pr[n] - mx);
+    pr[n] = e;
+    sum += e;
+  }
+  sum = block_reduce_256<T>(sum, red, false);
+  const float inv = 1.0f / sum;
+  for (int n = t; n < N; n += 256) {
+    const float pv = pr[n] * inv;
+    pr[n] = pv;
+    prow[n] = pv;
+  }
+  __syncthreads();
+  float acc[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) acc[j] = 0.f;
+  if (act)
+    for (int n = r0; n < N; n += RP) {
+      float vv[8];
+      Vec<T, 8>::ld(Vb + (size_t)n * DP + c * 8, vv);
+      const float pv = pr[n];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) acc[j] = fmaf(pv, vv[j], acc[j]);
+    }
+  __syncthreads();   // part[] is free again
+  if (act) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) part[(r0 * CPR + c) * 8 + j] = acc[j];
+  }
+  __syncthreads();
+  for (int d = t; d < dh; d += 256) {
+    float a = 0.f;
+    for (int r = 0; r < RP; ++r) a += part[(r * CPR + (d >> 3)) * 8 + (d & 7)];
+    Elem<T>::st(out + (size_t)b * H * dh + h * dh + d, a);
+  }
+}
+
+hipError_t pool_attn_fwd_varlen(const float* q, const void* K, const void* V, int dtype, void* out, float* probs,
+                                const int* cu, int S, int T, int max_n, int H, int dh, int DP, hipStream_t s) {
+  if (S < 1 || H < 1 || T < 1 || (size_t)S * H >= (1ull << 31)) return hipErrorInvalidValue;
+  if (DP % 8 || DP < 8 || DP > 2048) return hipErrorInvalidValue;
+  if (max_n < 1 || max_n > pool_attn_max_tokens(DP, 0)) return hipErrorInvalidValue;   // the default LDS window (kernels.h)
+  const size_t smem = pool_attn_lds_floats(max_n, DP, 0) * sizeof(float);
+  return pool_dispatch(dtype, [&](auto elem) {
+    using E = decltype(elem);
+    hipLaunchKernelGGL(pool_attn_fwd_varlen_kernel<E>, dim3(S * H), dim3(256), smem, s, q, (const E*)K, (const E*)V,
+                       (E*)out, probs, cu, T, max_n, H, dh, DP);
+  });
+}
+
+// The device table of a ragged batch from host lengths: cu[i] = lens[0] + ... + lens[i-1], i = 0 .. S.  The prefix sums
+// are formed on the host and travel BY VALUE in the kernel arguments, 256 per launch (as sgl_op_preprocess_views moves its
+// records): no copy from host memory, no allocation, no synchronisation, the caller's stream only; plain vector stores.
+constexpr int kSegChunk = 256;
+struct SegChunk {
+  int v[kSegChunk];
+};
+__global__ __launch_bounds__(kSegChunk) void seg_offsets_kernel(SegChunk chunk, int n, int* __restrict__ cu) {
+  const int i = threadIdx.x;
+  if (i < n) cu[i] = chunk.v[i];
+}
+
+hipError_t seg_offsets(const int* lens, int S, int* cu, hipStream_t s) {
+  static_assert(sizeof(SegChunk) <= 2048, "a chunk of offsets must fit the kernel arguments");
+  if (S < 1) return hipErrorInvalidValue;
+  long long total = 0;
+  for (int i = 0; i < S; ++i) {
+    if (lens[i] < 0) return hipErrorInvalidValue;
+    total += lens[i];
+  }
+  if (total > 0x7fffffffLL) return hipErrorInvalidValue;
+  int run = 0;
+  for (int i0 = 0; i0 <= S; i0 += kSegChunk) {
+    const int n = S + 1 - i0 < kSegChunk ? S + 1 - i0 : kSegChunk;
+    SegChunk chunk = {};
+    for (int i = 0; i < n; ++i) {
+      chunk.v[i] = run;
+      if (i0 + i < S) run += lens[i0 + i];
+    }
+    hipLaunchKernelGGL(seg_offsets_kernel, dim3(1), dim3(kSegChunk), 0, s, chunk, n, cu + i0);
+  }
+  return hipGetLastError();
 }
 
 // backward: dV[n,d] = p_n * do[d];  dp_n = do·V[n];  ds_n = p_n (dp_n - Σ p dp) * scale;

@@ -54,6 +54,58 @@ __global__ __launch_bounds__(256) void attn_ref_fwd_kernel(const float* __restri
   if (lane == 0) lse[(size_t)bh * N + i] = mx + logf(sum);
 }
 
+// Ragged batch: attn_ref_fwd_kernel on segment `seg` of a packed batch (seg_block, attention.hip.h), four query rows per
+// workgroup.  Q, K, V head-major [H][T][DP]; the loops run over the segment's N rows from its first row, in the order
+// above, so a segment gets the bits attn_ref_fwd_kernel gives an image of N tokens.  The per-wave LDS regions are max_n
+// apart (the launch sizes them for the longest segment).  out [T][H*dh], lse [H][T].
+__global__ __launch_bounds__(256) void attn_ref_fwd_varlen_kernel(const float* __restrict__ Q, const float* __restrict__ K,
+                                                                  const float* __restrict__ V, float* __restrict__ out,
+                                                                  float* __restrict__ lse, const int* __restrict__ cu,
+                                                                  int S, int T, int max_n, int H, int dh, int DP) {
+  extern __shared__ __attribute__((aligned(16))) float ar_smem[];  // per wave: [max_n] scores + [128] q
+  const int w = wave_id(), lane = lane_id();
+  float* sc = ar_smem + (size_t)w * (max_n + 128);
+  float* qs = sc + max_n;
+  SegBlock sb;
+  if (!seg_block(cu, S, T, max_n, H, (max_n + 3) / 4, 4, sb)) return;
+  const int N = sb.n, h = sb.hd, rs = DP;
+  const int i = sb.xb * 4 + w;
+  if (i >= N) return;
+  const size_t hb = ((size_t)h * T + sb.row0) * (size_t)DP;
+  const float* Qb = Q + hb + (size_t)i * rs;
+  const float* Kb = K + hb;
+  const float* Vb = V + hb;
+  const float scale = 1.0f / sqrtf((float)dh);
+  for (int d = lane; d < dh; d += 64) qs[d] = Qb[d];
+  __builtin_amdgcn_wave_barrier();
+  float mx = -INFINITY;
+  for (int n = lane; n < N; n += 64) {
+    const float* kr = Kb + (size_t)n * rs;
+    float s = 0.f;
+    for (int d = 0; d < dh; ++d) s = fmaf(qs[d], kr[d], s);
+    s *= scale;
+    sc[n] = s;
+    mx = fmaxf(mx, s);
+  }
+  mx = wave_max(mx);
+  float sum = 0.f;
+  for (int n = lane; n < N; n += 64) {
+    const float e = expf(sc[n] - mx);
+    sc[n] = e;
+    sum += e;
+  }
+  sum = wave_sum(sum);
+  const float inv = 1.0f / sum;
+  __builtin_amdgcn_wave_barrier();
+  float* orow = out + (size_t)(sb.row0 + i) * (H * dh) + h * dh;
+  for (int d = lane; d < dh; d += 64) {
+    float acc = 0.f;
+    for (int n = 0; n < N; ++n) acc = fmaf(sc[n], Vb[(size_t)n * rs + d], acc);
+    orow[d] = acc * inv;
+  }
+  if (lane == 0) lse[(size_t)h * T + sb.row0 + i] = mx + logf(sum);
+}
+
 // dQ (+ delta): one wave per query
 __global__ __launch_bounds__(256) void attn_ref_bwd_q_kernel(const float* __restrict__ Q, const float* __restrict__ K,
                                                              const float* __restrict__ V, const float* __restrict__ O,
@@ -174,6 +226,16 @@ hipError_t attn_ref_fwd(const float* q, const float* k, const float* v, float* o
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(attn_ref_fwd_kernel, dim3((N + 3) / 4, B * H), dim3(256), smem, s, q, k, v, out, lse, H, N, dh,
                      DP, ld);
+  return hipGetLastError();
+}
+
+hipError_t attn_ref_fwd_varlen(const float* q, const float* k, const float* v, float* out, float* lse, const int* cu, int S,
+                               int T, int max_n, int H, int dh, int DP, hipStream_t s) {
+  const size_t smem = attn_ref_lds(max_n, 1, 1);
+  const hipError_t e = ar_allow_lds(&attn_ref_fwd_varlen_kernel, smem);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(attn_ref_fwd_varlen_kernel, seg_grid((max_n + 3) / 4, S * H), dim3(256), smem, s, q, k, v, out, lse,
+                     cu, S, T, max_n, H, dh, DP);
   return hipGetLastError();
 }
 

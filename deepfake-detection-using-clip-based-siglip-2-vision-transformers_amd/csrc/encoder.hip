@@ -82,6 +82,7 @@ inline size_t head_bytes(const sgl_ctx* c, int B, int N) { return (size_t)B * c-
 // Per-call activation / workspace layout (pure function of ctx, B, grid, train).
 struct Layout {
   int B = 0, gh = 0, gw = 0, N = 0, M = 0;
+  int PB = 0;   // rows of the pooling head's per-image buffers: B, or the S segments of a ragged batch
   bool train = false;
   // activation region ("saved" when training, a slice of ws otherwise)
   size_t a_im2col = 0, a_pos = 0;
@@ -91,6 +92,7 @@ struct Layout {
   size_t a_pstats = 0, a_lastlp = 0, a_kvh = 0, a_qp = 0, a_probs = 0, a_ao = 0, a_h0 = 0, a_hstats = 0, a_hl = 0, a_hu = 0,
          a_ha = 0;
   size_t a_spa = 0, a_spb = 0, w_spa = 0, w_spb = 0;   // bf16x3 split operands (forward: in act; backward: in ws)
+  size_t a_cu = 0;   // ragged batch only: the device table cu, int32 [S + 1], last in the activation region
   size_t act_total = 0;
   // backward scratch (ws): all zero unless training
   size_t w_dx = 0, w_g = 0, w_du = 0, w_dh = 0, w_dqkv = 0, w_delta = 0, w_splitws = 0, w_lnpart = 0, w_cspart = 0,
@@ -105,12 +107,25 @@ struct Layout {
 
   Layout() = default;
   Layout(const sgl_ctx* c, int B_, int Himg, int Wimg, bool train_) {
-    B = B_;
-    train = train_;
-    rc = train && c->recompute;
     gh = Himg / c->P;
     gw = Wimg / c->P;
-    N = gh * gw;
+    init(c, B_, gh * gw, B_, train_, 0);
+  }
+  // A ragged inference batch of S images, T tokens in all: the layout of (B = 1, N = T) with S rows in the pooling head's
+  // per-image buffers, and cu behind it.  For S = 1 it is the fixed inference layout of that image plus the 256 bytes of cu.
+  static Layout ragged(const sgl_ctx* c, int T, int S) {
+    Layout l;
+    l.init(c, 1, T, S, false, S + 1);
+    return l;
+  }
+
+ private:
+  void init(const sgl_ctx* c, int B_, int N_, int PB_, bool train_, int cu_entries) {
+    B = B_;
+    PB = PB_;
+    train = train_;
+    rc = train && c->recompute;
+    N = N_;
     M = B * N;
     const size_t es = c->es, D = c->D, Ip = c->Ip, Mz = (size_t)M;
     Bump a;
@@ -139,22 +154,23 @@ struct Layout {
     a_kvh = a.take(2 * head_bytes(c, B, N));
     a_qp = a.take(D * 4);
     a_probs = a.take((size_t)B * c->H * N * 4);
-    a_ao = a.take((size_t)B * D * es);
-    a_h0 = a.take((size_t)B * D * 4);
-    a_hstats = a.take((size_t)B * 2 * 4);
-    a_hl = a.take((size_t)B * D * es);
-    a_hu = a.take((size_t)B * Ip * es);
-    a_ha = a.take((size_t)B * Ip * es);
+    a_ao = a.take((size_t)PB * D * es);
+    a_h0 = a.take((size_t)PB * D * 4);
+    a_hstats = a.take((size_t)PB * 2 * 4);
+    a_hl = a.take((size_t)PB * D * es);
+    a_hu = a.take((size_t)PB * Ip * es);
+    a_ha = a.take((size_t)PB * Ip * es);
     // widest GEMM operand: [rows, W] with rows <= max(M, W) on the activation side, [W, max(D, Kp)] on the weight side
     const size_t widest = std::max(Ip, 3 * D), Kp = (size_t)c->Kp;
     const size_t Wd = (size_t)round_up((int)std::max(widest, Kp), 8);
-    const size_t sp_act = 3 * std::max(Mz, (size_t)B) * Wd * 2;
+    const size_t sp_act = 3 * std::max(Mz, (size_t)PB) * Wd * 2;
     const size_t sp_wgt = 3 * Wd * (size_t)round_up((int)std::max(D, Kp), 8) * 2;
     const size_t sp_bytes = std::max(sp_act, sp_wgt);
     if (c->split && !rc) {
       a_spa = a.take(sp_bytes);
       a_spb = a.take(sp_bytes);
     }
+    if (cu_entries) a_cu = a.take((size_t)cu_entries * 4);
     act_total = a.off;
 
     Bump w;
@@ -196,6 +212,8 @@ struct Layout {
     }
     if (ws_total == 0) ws_total = 256;
   }
+
+ public:
   size_t layer_base(int l) const { return a_layer0 + a_layer_stride * (size_t)l; }
 };
 
@@ -312,6 +330,9 @@ struct Call {
   void* ws = nullptr;
   void* sp_a = nullptr;   // bf16x3: split operands of the GEMM being launched (calls on one ctx are stream-ordered)
   void* sp_b = nullptr;
+  // a ragged batch (sgl_forward_ragged): the device table of its S segments and the longest one; NULL on every other call
+  const int* cu = nullptr;
+  int S = 0, max_n = 0;
 
   char* wsp(size_t off) const { return at(ws, off); }
   float* wsf(size_t off) const { return reinterpret_cast<float*>(at(ws, off)); }
@@ -333,6 +354,20 @@ struct Call {
     p.head_dim_pad = ctx->DP;
     p.batch = lay.B;
     return p;
+  }
+
+  // the block attention of this call on head-major q | k | v: per image, or per segment of a ragged batch
+  hipError_t attention(const char* q, int dtype, void* out, float* lse) const {
+    const char *k = q + head_bytes(), *v = q + 2 * head_bytes();
+    if (cu) return attn_fwd_varlen(q, k, v, dtype, out, lse, cu, S, lay.N, max_n, ctx->H, ctx->dh, ctx->DP, s);
+    return attn_fwd(q, k, v, dtype, out, lse, lay.B, ctx->H, lay.N, ctx->dh, ctx->DP, 0, s);
+  }
+  // the pooling head's probe attention on head-major k | v, likewise
+  hipError_t pool_attention(const float* qp, const char* kv, void* out, float* probs) const {
+    if (cu)
+      return pool_attn_fwd_varlen(qp, kv, kv + head_bytes(), ctx->dt, out, probs, cu, S, lay.N, max_n, ctx->H, ctx->dh,
+                                  ctx->DP, s);
+    return pool_attn_fwd(qp, kv, kv + head_bytes(), ctx->dt, out, probs, lay.B, ctx->H, lay.N, ctx->dh, ctx->DP, s);
   }
 
   // C[M,N] = A[M,K] · B[N,K]^T through epilogue epi
@@ -416,8 +451,7 @@ int mx_block(const Call& c, const sgl_layer_weights& lw, const ShadowLayer& sl, 
   CK(layernorm_fwd_mx(x, lw.ln1_w, lw.ln1_b, h1, h1 + Mz * Dp, M, D, Dp, eps, s));
   CK(gemm_nt_mx(h1, h1 + Mz * Dp, c.sh(sl.wqkv), c.sh(sl.wqkv_s), M, 3 * D, Dp, EPI_QKV, c.epi_qkv(q, c.shf(sl.bqkv)),
                 nullptr, s));
-  CK(attn_fwd(q, q + c.head_bytes(), q + 2 * c.head_bytes(), DT_BF16, lb + lay.r_attn,
-              reinterpret_cast<float*>(lb + lay.r_lse), lay.B, ctx->H, lay.N, ctx->dh, ctx->DP, 0, s));
+  CK(c.attention(q, DT_BF16, lb + lay.r_attn, reinterpret_cast<float*>(lb + lay.r_lse)));
   // a 32-block of the attention output straddles heads when head_dim = 72: a pass of its own, not an attention epilogue
   CK(quantize_mx(lb + lay.r_attn, DT_BF16, D, M, D, Dp, aq, aq + Mz * Dp, s));
   CK(gemm_nt_mx(aq, aq + Mz * Dp, c.sh(sl.wo), c.sh(sl.wo_s), M, D, Dp, EPI_RES_F32, epi_res_f32(xmid, lw.o_b, x, D),
@@ -451,8 +485,7 @@ int block_to_fc1(const Call& c, const sgl_layer_weights& lw, const ShadowLayer& 
   // touches 14 cache lines instead of 8, and K/V are re-read by six workgroups per head and three kernels): +0.75 ms
   // per step net, so the 144-byte granularity is paid once, on the write side.
   CK(c.gemm_nt(lb + lay.r_h1, D, c.sh(sl.wqkv), D, M, 3 * D, D, EPI_QKV, dt, c.epi_qkv(q, c.shf(sl.bqkv))));
-  CK(attn_fwd(q, q + c.head_bytes(), q + 2 * c.head_bytes(), ctx->split ? DT_F32_MFMA : dt, lb + lay.r_attn,
-              reinterpret_cast<float*>(lb + lay.r_lse), lay.B, ctx->H, lay.N, ctx->dh, ctx->DP, 0, s));
+  CK(c.attention(q, ctx->split ? DT_F32_MFMA : dt, lb + lay.r_attn, reinterpret_cast<float*>(lb + lay.r_lse)));
   CK(c.gemm_nt(lb + lay.r_attn, D, c.sh(sl.wo), D, M, D, D, EPI_RES_F32, DT_F32, epi_res_f32(xmid, lw.o_b, x, D)));
   CK(layernorm_fwd(xmid, lw.ln2_w, lw.ln2_b, lb + lay.r_h2, dt, D, st2, st2 + M, M, D, eps, s));
   // r_u holds gelu'(u) in bf16 / fp16 mode (the backward only ever needs that)
@@ -489,7 +522,7 @@ int head_forward(const Call& c, const sgl_weights* w, const float* last_hidden, 
   sgl_ctx* ctx = c.ctx;
   const Layout& lay = c.lay;
   hipStream_t s = c.s;
-  const int D = ctx->D, Ip = ctx->Ip, M = lay.M, B = lay.B, dt = ctx->dt;
+  const int D = ctx->D, Ip = ctx->Ip, M = lay.M, B = lay.PB, dt = ctx->dt;   // B: pooled rows (images, or segments)
   char* act = c.act;
   char* kv = act + lay.a_kvh;
   float* qp = c.actf(lay.a_qp);
@@ -498,8 +531,7 @@ int head_forward(const Call& c, const sgl_weights* w, const float* last_hidden, 
   CK(cast_f32(last_hidden, act + lay.a_lastlp, dt, (size_t)M * D, s));
   CK(c.gemm_nt(act + lay.a_lastlp, D, c.sh(ctx->sh_hwkv), D, M, 2 * D, D, EPI_QKV, dt, c.epi_qkv(kv, w->in_proj_b + D)));
   CK(gemm_f32_generic(w->probe, D, 1, w->in_proj_w, D, 1, 1, D, D, EPI_F32, DT_F32, epi_f32(qp, D, w->in_proj_b), s));
-  CK(pool_attn_fwd(qp, kv, kv + c.head_bytes(), dt, act + lay.a_ao, c.actf(lay.a_probs), B, ctx->H, lay.N, ctx->dh,
-                   ctx->DP, s));
+  CK(c.pool_attention(qp, kv, act + lay.a_ao, c.actf(lay.a_probs)));
   CK(c.gemm_nt(act + lay.a_ao, D, c.sh(ctx->sh_hwo), D, B, D, D, EPI_F32, DT_F32, epi_f32(h0, D, w->out_proj_b)));
   CK(layernorm_fwd(h0, w->head_ln_w, w->head_ln_b, act + lay.a_hl, dt, D, hst, hst + B, B, D, ctx->cfg.layer_norm_eps, s));
   // the head keeps the pre-activation u in every mode (gelu_grad_form = 0), unlike the blocks
@@ -918,6 +950,121 @@ int sgl_forward_slots(sgl_ctx* ctx, const sgl_weights* w, const void* shadow, co
     }
     // u is kept for the blocks the backward will differentiate, unless it recomputes them
     RET(block_to_fc1(c, lw, sl, lb, hs_slots[l], train && !lay.rc && l >= first_trainable_block));
+    CK(c.gemm_nt(lb + lay.r_a, ctx->Ip, c.sh(sl.w2), ctx->Ip, lay.M, ctx->D, ctx->Ip, EPI_RES_F32, DT_F32,
+                 epi_res_f32(hs_slots[l + 1], lw.fc2_b, reinterpret_cast<const float*>(lb + lay.r_xmid), ctx->D)));
+  }
+  float* pst = c.actf(lay.a_pstats);
+  CK(layernorm_fwd(hs_slots[ctx->L], w->post_ln_w, w->post_ln_b, last_hidden, DT_F32, ctx->D, pst, pst + lay.M, lay.M,
+                   ctx->D, ctx->cfg.layer_norm_eps, c.s));
+  if (ctx->cfg.use_head && pooled) RET(head_forward(c, w, last_hidden, pooled));
+  return SGL_OK;
+}
+
+// -------------------------------------------------------------------------------------------------------
+// ragged batches (inference): S images of different grids packed into one (B = 1, N = T) pass
+// -------------------------------------------------------------------------------------------------------
+namespace {
+
+// The shape rules of a ragged batch, in the order they are reported: S, every grid side, the token limit, the pooling
+// head's per-image limit, and what the context's attention route refuses for the longest image.
+int ragged_shape(const sgl_ctx* ctx, const int* grids, int S, int& T, int& max_n) {
+  if (S < 1) return SGL_ERR_BAD_SHAPE;
+  for (int s = 0; s < S; ++s)
+    if (grids[2 * s] < 1 || grids[2 * s + 1] < 1) return SGL_ERR_BAD_SHAPE;
+  const long cap = max_tokens(ctx, false);
+  long total = 0, longest = 0;
+  for (int s = 0; s < S; ++s) {
+    const long n = (long)grids[2 * s] * grids[2 * s + 1];
+    total += n;
+    if (n > longest) longest = n;
+    if (total > cap) return SGL_ERR_BAD_SHAPE;
+  }
+  if (ctx->cfg.use_head && longest > pool_attn_max_tokens(ctx->DP, 0)) return SGL_ERR_BAD_SHAPE;
+  T = (int)total;
+  max_n = (int)longest;
+  if (!attn_varlen_shape_ok(ctx->split ? DT_F32_MFMA : ctx->dt, S, T, max_n, ctx->H, ctx->dh, ctx->DP))
+    return SGL_ERR_BAD_SHAPE;
+  return SGL_OK;
+}
+
+// The packed position table [T][D]: per segment the stored table (native grid), a copy of an earlier segment of the same
+// grid, or the table resized to the segment's grid: what embed_forward adds for that image alone.
+int ragged_positions(const Call& c, const sgl_weights* w, const int* grids, const std::vector<int>& row0, float* pos) {
+  sgl_ctx* ctx = c.ctx;
+  const size_t D = (size_t)ctx->D;
+  for (int s = 0; s < c.S; ++s) {
+    const int gh = grids[2 * s], gw = grids[2 * s + 1];
+    float* dst = pos + (size_t)row0[s] * D;
+    const size_t bytes = (size_t)gh * gw * D * 4;
+    const float* src = (gh == ctx->g0 && gw == ctx->g0) ? w->pos : nullptr;
+    for (int e = 0; e < s && !src; ++e)
+      if (grids[2 * e] == gh && grids[2 * e + 1] == gw) src = pos + (size_t)row0[e] * D;
+    if (src)
+      CK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, c.s));
+    else
+      CK(pos_resize(w->pos, ctx->g0, dst, gh, gw, ctx->D, c.s));
+  }
+  return SGL_OK;
+}
+
+}  // namespace
+
+int sgl_query_sizes_ragged(const sgl_ctx* ctx, const int* grids, int S, size_t* ws_bytes) {
+  if (!ctx || !grids) return SGL_ERR_NULL;
+  int T, max_n;
+  RET(ragged_shape(ctx, grids, S, T, max_n));
+  if (ws_bytes) *ws_bytes = Layout::ragged(ctx, T, S).ws_total;
+  return SGL_OK;
+}
+
+int sgl_forward_ragged(sgl_ctx* ctx, const sgl_weights* w, const void* shadow, const void* patches, const int* grids, int S,
+                       float* const* hs_slots, float* last_hidden, float* pooled, void* ws, size_t ws_bytes,
+                       sgl_stream stream) {
+  if (!ctx || !w || !shadow || !patches || !grids || !hs_slots || !last_hidden || !ws || (ctx->L > 0 && !w->layers))
+    return SGL_ERR_NULL;
+  int T, max_n;
+  RET(ragged_shape(ctx, grids, S, T, max_n));
+  for (int l = 0; l <= ctx->L; ++l)
+    if (!hs_slots[l]) return SGL_ERR_NULL;
+  Call c;
+  c.lay = Layout::ragged(ctx, T, S);
+  const Layout& lay = c.lay;
+  if (ws_bytes < lay.ws_total) return SGL_ERR_WORKSPACE;
+  c.ctx = ctx;
+  c.s = (hipStream_t)stream;
+  c.shadow = shadow;
+  c.ws = ws;
+  c.act = at(ws, lay.ws_act_off);
+  if (ctx->split) {
+    c.sp_a = c.act + lay.a_spa;
+    c.sp_b = c.act + lay.a_spb;
+  }
+  c.S = S;
+  c.max_n = max_n;
+  std::vector<int> lens(S), row0(S);
+  for (int s = 0, run = 0; s < S; ++s) {
+    lens[s] = grids[2 * s] * grids[2 * s + 1];
+    row0[s] = run;
+    run += lens[s];
+  }
+  int* cu = reinterpret_cast<int*>(c.act + lay.a_cu);
+  CK(seg_offsets(lens.data(), S, cu, c.s));
+  c.cu = cu;
+
+  float* pos = c.actf(lay.a_pos);
+  RET(ragged_positions(c, w, grids, row0, pos));
+  // `patches` is the GEMM's operand as it stands (inference keeps no copy); every row has its own position row
+  CK(c.gemm_nt(patches, ctx->Kp, c.sh(ctx->sh_wpatch), ctx->Kp, T, ctx->D, ctx->Kp, EPI_POS_F32, DT_F32,
+               epi_pos_f32(hs_slots[0], ctx->D, w->patch_b, pos, T)));
+  for (int l = 0; l < ctx->L; ++l) {
+    const sgl_layer_weights& lw = w->layers[l];
+    const ShadowLayer& sl = ctx->sh_layers[l];
+    char* lb = c.block(l);
+    if (ctx->mx) {
+      RET(mx_block(c, lw, sl, lb, hs_slots[l], hs_slots[l + 1]));
+      continue;
+    }
+    RET(block_to_fc1(c, lw, sl, lb, hs_slots[l], false));
     CK(c.gemm_nt(lb + lay.r_a, ctx->Ip, c.sh(sl.w2), ctx->Ip, lay.M, ctx->D, ctx->Ip, EPI_RES_F32, DT_F32,
                  epi_res_f32(hs_slots[l + 1], lw.fc2_b, reinterpret_cast<const float*>(lb + lay.r_xmid), ctx->D)));
   }
@@ -1549,6 +1696,43 @@ int sgl_op_pool_attn_fwd(int dtype, const float* q, const void* K, const void* V
     return SGL_ERR_BAD_SHAPE;
   if (!lo_dtype_ok(dtype) || !aligned16(K) || !aligned16(V)) return SGL_ERR_UNSUPPORTED;
   CKV(pool_attn_fwd(q, K, V, dtype, out, probs, B, H, N, head_dim, head_dim_pad, (hipStream_t)stream));
+  return SGL_OK;
+}
+
+// ---- ragged batches: the two varlen kernels and the table writer -----------------------------------------------------
+int sgl_op_attn_fwd_varlen(int dtype, const void* q, const void* k, const void* v, void* out, float* lse, const int* cu,
+                           int S, int T, int max_n, int H, int head_dim, int head_dim_pad, sgl_stream stream) {
+  if (!q || !k || !v || !out || !lse || !cu) return SGL_ERR_NULL;
+  if (S < 1 || T < 1 || max_n < 1 || H < 1 || head_dim < 1 || head_dim_pad < 1 || head_dim > head_dim_pad)
+    return SGL_ERR_BAD_SHAPE;
+  if (dtype != DT_F32 && dtype != DT_BF16 && dtype != DT_F32_MFMA && dtype != DT_F16) return SGL_ERR_UNSUPPORTED;
+  if (!attn_varlen_shape_ok(dtype, S, T, max_n, H, head_dim, head_dim_pad)) return SGL_ERR_BAD_SHAPE;
+  CKV(attn_fwd_varlen(q, k, v, dtype, out, lse, cu, S, T, max_n, H, head_dim, head_dim_pad, (hipStream_t)stream));
+  return SGL_OK;
+}
+
+int sgl_op_pool_attn_fwd_varlen(int dtype, const float* q, const void* K, const void* V, void* out, float* probs,
+                                const int* cu, int S, int T, int max_n, int H, int head_dim, int head_dim_pad,
+                                sgl_stream stream) {
+  if (!q || !K || !V || !out || !probs || !cu) return SGL_ERR_NULL;
+  if (S <= 0 || T <= 0 || max_n <= 0 || H <= 0 || head_dim <= 0 || head_dim % 8 || head_dim_pad % 8 ||
+      head_dim > head_dim_pad)
+    return SGL_ERR_BAD_SHAPE;
+  if (!lo_dtype_ok(dtype) || !aligned16(K) || !aligned16(V)) return SGL_ERR_UNSUPPORTED;
+  CKV(pool_attn_fwd_varlen(q, K, V, dtype, out, probs, cu, S, T, max_n, H, head_dim, head_dim_pad, (hipStream_t)stream));
+  return SGL_OK;
+}
+
+int sgl_op_seg_offsets(const int* lens, int S, int* cu, sgl_stream stream) {
+  if (!lens || !cu) return SGL_ERR_NULL;
+  if (S < 1) return SGL_ERR_BAD_SHAPE;
+  long long total = 0;
+  for (int i = 0; i < S; ++i) {
+    if (lens[i] < 0) return SGL_ERR_BAD_SHAPE;
+    total += lens[i];
+  }
+  if (total > 0x7fffffffLL) return SGL_ERR_BAD_SHAPE;
+  CKV(seg_offsets(lens, S, cu, (hipStream_t)stream));
   return SGL_OK;
 }
 

@@ -166,6 +166,14 @@ static inline int pool_attn_max_tokens(int DP, int backward) {
 }
 hipError_t pool_attn_fwd(const float* q, const void* K, const void* V, int dtype, void* out /*[B][H*dh]*/,
                          float* probs /*[B][H][N]*/, int B, int H, int N, int dh, int DP, hipStream_t s);
+// Ragged batch (attention.hip.h, "ragged addressing"): K/V head-major [H][T][DP], segment s = rows cu[s] .. cu[s+1]-1; one
+// workgroup per (segment, head) on the segment's rows, the LDS window sized for max_n (refused above
+// pool_attn_max_tokens(DP, 0)).  Per segment the bits of pool_attn_fwd on that segment alone.
+hipError_t pool_attn_fwd_varlen(const float* q, const void* K, const void* V, int dtype, void* out /*[S][H*dh]*/,
+                                float* probs /*[H][T]*/, const int* cu /*device [S+1]*/, int S, int T, int max_n, int H,
+                                int dh, int DP, hipStream_t s);
+// cu[0..S] on the device = exclusive prefix sums of the HOST lengths lens[0..S), carried in kernel arguments (no host copy)
+hipError_t seg_offsets(const int* lens, int S, int* cu, hipStream_t s);
 hipError_t pool_attn_bwd(const float* q, const void* K, const void* V, int dtype, const float* probs,
                          const float* dout /*[B][H*dh] fp32*/, void* dkv /*[B*N][2*H*dh] T*/,
                          float* dq_partial /*[B][H*dh]*/, int B, int H, int N, int dh, int DP, hipStream_t s);
@@ -266,6 +274,12 @@ static_assert(tn_plan_is(2048, 512, 512, kTnSlabBytes, 256, 2) && tn_plan(2048, 
 // out: token-major [B*N][H*dh]; lse: [B][H][N] (natural log units)
 hipError_t attn_fwd(const void* q, const void* k, const void* v, int dtype, void* out, float* lse, int B, int H,
                     int N, int dh, int DP, int ld_qkv, hipStream_t s);
+// Ragged batch: q,k,v head-major [H][T][DP] (the ld_qkv == 0 layout at B = 1, N = T), segment s = rows cu[s] .. cu[s+1]-1
+// (cu: device int32 [S+1], clamped against T and max_n by the kernels); out token-major [T][H*dh]; lse [H][T].  Per segment
+// the bits of attn_fwd(B = 1, N = n_s) on that segment alone.  attn_varlen_shape_ok: what attn_fwd_varlen accepts.
+bool attn_varlen_shape_ok(int dtype, int S, int T, int max_n, int H, int dh, int DP);
+hipError_t attn_fwd_varlen(const void* q, const void* k, const void* v, int dtype, void* out, float* lse, const int* cu,
+                           int S, int T, int max_n, int H, int dh, int DP, hipStream_t s);
 // dout: token-major [B*N][H*dh] (T); dqkv: token-major [B*N][3*H*dh] (T); delta: scratch of 2*B*H*N floats
 hipError_t attn_bwd(const void* q, const void* k, const void* v, const void* out, const void* dout,
                     const float* lse, int dtype, void* dqkv, float* delta, int B, int H, int N, int dh, int DP,

@@ -121,6 +121,29 @@ class VisionModelOutput:
         return (self.last_hidden_state, self.pooler_output, self.hidden_states)[i]
 
 
+@dataclass
+class RaggedVisionModelOutput:
+    """What ``forward_ragged`` returns for S images of different sizes.  Token-major tensors are PACKED: image i owns rows
+    ``cu_seqlens[i] : cu_seqlens[i + 1]`` (its ``grids[i][0] * grids[i][1]`` patches in row-major order), T rows in all,
+    no padding."""
+    last_hidden_state: torch.Tensor                           # (T, D)
+    pooler_output: Optional[torch.Tensor]                     # (S, D); None without the pooling head
+    hidden_states: Optional[Tuple[torch.Tensor, ...]] = None  # (T, D) each
+    grids: Tuple[Tuple[int, int], ...] = ()                   # (gh_i, gw_i)
+    cu_seqlens: Tuple[int, ...] = (0,)                        # S + 1 row offsets (host integers)
+
+    def unpack(self, t: torch.Tensor):
+        """The S per-image views (n_i, D) of a packed (T, D) tensor."""
+        if t.shape[0] != self.cu_seqlens[-1]:
+            raise ValueError(f"expected a packed tensor of {self.cu_seqlens[-1]} rows, got {tuple(t.shape)}")
+        return [t[a:b] for a, b in zip(self.cu_seqlens[:-1], self.cu_seqlens[1:])]
+
+    def token_grid(self, t: torch.Tensor, i: int):
+        """Image i's tokens of a packed (T, D) tensor as a (gh_i, gw_i, D) view."""
+        gh, gw = self.grids[i]
+        return self.unpack(t)[i].view(gh, gw, t.shape[-1])
+
+
 # ---------------------------------------------------------------------------------------------------------
 # surface H
 # ---------------------------------------------------------------------------------------------------------
@@ -450,6 +473,46 @@ class SiglipVisionModelHIP(nn.Module):
             return out, None, None
         return out, outs[-2], encoder_ops._input_geometry(self.config, pixel_values, layout, img_h, img_w)[:3]
 
+    @torch.compiler.disable
+    def forward_ragged(self, pixel_values, output_hidden_states: bool = False, hidden_state_ids=None):
+        """Images of DIFFERENT sizes in one encoder call, without resizing and without padding (flash-attention "varlen"
+        style).  ``pixel_values``: a sequence of normalised ``(3, H_i, W_i)`` or ``(1, 3, H_i, W_i)`` tensors on the GPU.
+        The position table is always fitted to each image's grid (``interpolate_pos_encoding=True``).  Returns a
+        ``RaggedVisionModelOutput`` (packed ``(T, D)`` token tensors, ``(S, D)`` ``pooler_output``); every value is
+        bit-identical to ``model(pixel_values=x_i[None], interpolate_pos_encoding=True)`` of the image alone.
+
+        Inference only.  It works under ``no_grad``, and with grad enabled when neither an input nor an encoder
+        parameter requires a gradient (a head that trains on ``pooler_output`` of a frozen backbone); the outputs are
+        outside autograd.  ``output_attentions``, ``patches=`` and the capture contexts are not offered here.  Not a custom
+        op: under ``torch.compile`` the call is a graph break."""
+        views, grids = encoder_ops.ragged_geometry(self.config, pixel_values)
+        if torch.is_grad_enabled():
+            one_per_size = ("forward_ragged is inference-only; to differentiate, make one call per image size: "
+                            "model(pixel_values=batch_of_one_size, interpolate_pos_encoding=True)")
+            if any(x.requires_grad for x in views):
+                raise RuntimeError("forward_ragged: an input image requires a gradient. " + one_per_size)
+            if any(p.requires_grad for p in self._table.params()):
+                raise RuntimeError("forward_ragged: an encoder parameter requires a gradient (freeze the encoder with "
+                                   "requires_grad_(False), or run under torch.no_grad()). " + one_per_size)
+        if any(x.device.type != "cuda" for x in views):
+            raise RuntimeError("SiglipVisionModelHIP runs only on an AMD GPU through libsiglip_hip.so "
+                               "(no CPU fallback); move the model and every image to 'cuda'")
+        L = self.config.num_hidden_layers
+        if hidden_state_ids is not None:
+            tap_ids = tuple(int(i) % (L + 1) for i in hidden_state_ids)
+        elif output_hidden_states:
+            tap_ids = tuple(range(L + 1))
+        else:
+            tap_ids = ()
+        uniq = sorted(set(tap_ids))
+        pooled, last, taps = encoder_ops.forward_ragged(self, views, grids, uniq)
+        cu = [0]
+        for gh, gw in grids:
+            cu.append(cu[-1] + gh * gw)
+        hs = tuple(taps[uniq.index(i)] for i in tap_ids) if tap_ids else None
+        return RaggedVisionModelOutput(last_hidden_state=last, pooler_output=pooled, hidden_states=hs,
+                                       grids=tuple(grids), cu_seqlens=tuple(cu))
+
     # ---- plumbing ----------------------------------------------------------------------------------------
     _RUNTIME = ("_table", "_contexts", "_shadows", "_grads", "_handle")
 
@@ -564,6 +627,17 @@ class OpenClipStyleEncoder(nn.Module):
     def encode_image(self, x=None, normalize: bool = False, patches=None):
         out = self.visual(pixel_values=x, interpolate_pos_encoding=False, patches=patches)
         f = out.pooler_output
+        if normalize:
+            f = f / f.norm(dim=-1, keepdim=True)
+        return f
+
+    def encode_image_ragged(self, images, normalize: bool = False):
+        """``encode_image`` for a sequence of images of different sizes (``SiglipVisionModelHIP.forward_ragged``): (S, D),
+        each row bit-identical to ``encode_image`` of that image with the position table fitted to its grid.  Inference
+        only."""
+        if not self.visual.use_head:
+            raise RuntimeError("encode_image_ragged returns the pooling head's embedding and this model has no head")
+        f = self.visual.forward_ragged(images).pooler_output
         if normalize:
             f = f / f.norm(dim=-1, keepdim=True)
         return f

@@ -345,6 +345,75 @@ def _encoder_backward(ctx, grads):
 encoder_fwd.register_autograd(_encoder_backward, setup_context=_encoder_setup_context)
 
 
+_OPERAND_CODE = {torch.float32: _lib.SGL_DTYPE_F32, torch.bfloat16: _lib.SGL_DTYPE_BF16, torch.float16: _lib.SGL_DTYPE_F16}
+
+
+def ragged_geometry(cfg, images):
+    """[(gh, gw)] of a ragged batch, the images as (3, H, W) views; the checks need no device work."""
+    if isinstance(images, torch.Tensor) or len(images) == 0:
+        raise ValueError("forward_ragged takes a non-empty sequence of (3,H,W) or (1,3,H,W) tensors, one per image; "
+                         "a (B,3,H,W) batch of one size goes through model(pixel_values=...)")
+    P = cfg.patch_size
+    views, grids = [], []
+    for i, x in enumerate(images):
+        if x.dim() == 4 and x.shape[0] == 1:
+            x = x[0]
+        if x.dim() != 3 or x.shape[0] != 3:
+            raise ValueError(f"image {i} must be (3,H,W) or (1,3,H,W), got {tuple(x.shape)}")
+        if x.shape[1] < P or x.shape[2] < P:
+            raise ValueError(f"image {i}: size ({x.shape[1]},{x.shape[2]}) is smaller than patch_size {P}")
+        views.append(x)
+        grids.append((x.shape[1] // P, x.shape[2] // P))
+    return views, grids
+
+
+def forward_ragged(mod, views, grids, tap_ids: Sequence[int]):
+    """sgl_forward_ragged on images of different sizes: each goes through sgl_op_im2col (B = 1) into its rows of one packed
+    patch operand [T, Kp], then one encoder call.  Returns (pooled (S,D) or None, last_hidden_state (T,D), one (T,D) tensor
+    per entry of tap_ids (distinct, ascending)).  Inference only; the outputs are outside autograd.  Not a custom op: a graph
+    break under torch.compile."""
+    cfg = mod.config
+    L, D, P = cfg.num_hidden_layers, cfg.hidden_size, cfg.patch_size
+    lib = _lib.load()
+    dev = views[0].device
+    S = len(views)
+    lens = [gh * gw for gh, gw in grids]
+    T = sum(lens)
+    kp = (3 * P * P + 63) // 64 * 64
+    op_dtype = OPERAND_DTYPE[mod.compute_dtype]
+    with torch.cuda.device(dev):
+        params = mod._table.params()
+        shadow, weights = mod._shadows.prepared(dev, params)
+        ws_bytes = mod._contexts.ragged_sizes(grids)     # refuses a bad batch before anything is enqueued
+        ws = mod._contexts.workspace(ws_bytes, dev)
+        stream = _lib.current_stream_handle(dev)
+        operand = torch.empty((T, kp), dtype=op_dtype, device=dev)
+        row = 0
+        for x, n in zip(views, lens):
+            x = x.detach()
+            if x.dtype != torch.float32:
+                x = x.float()
+            x = x.contiguous()
+            st = lib.sgl_op_im2col(x.data_ptr(), 0, operand[row:].data_ptr(), _OPERAND_CODE[op_dtype], 1, x.shape[1],
+                                   x.shape[2], P, kp, stream)
+            _lib.check(st, "sgl_op_im2col")
+            row += n
+        taps = [torch.empty((T, D), dtype=torch.float32, device=dev) for _ in tap_ids]
+        n_rest, plan = _slot_plan(tap_ids, False, L)
+        hs_rest = torch.empty((n_rest, T, D), dtype=torch.float32, device=dev)
+        slots = (_lib._fp * (L + 1))()
+        for l, (is_tap, i) in enumerate(plan):
+            slots[l] = (taps[i] if is_tap else hs_rest[i]).data_ptr()
+        last = torch.empty((T, D), dtype=torch.float32, device=dev)
+        pooled = torch.empty((S, D), dtype=torch.float32, device=dev) if mod.use_head else None
+        flat = (C.c_int * (2 * S))(*[v for g in grids for v in g])
+        ctx = mod._contexts.get(False)
+        st = lib.sgl_forward_ragged(ctx, C.byref(weights), shadow.data_ptr(), operand.data_ptr(), flat, S, slots,
+                                    last.data_ptr(), _lib.ptr(pooled), ws.data_ptr(), ws_bytes, stream)
+        _lib.check(st, "sgl_forward_ragged", ctx)
+    return pooled, last, taps
+
+
 def attention_maps(mod, saved: torch.Tensor, B: int, H: int, W: int, layers: Sequence[int], head_mean: bool):
     """sgl_attention_probs for each entry of ``layers`` (block index, or L for the pooling head) on the activation arena
     ``saved`` of a saving forward of ``mod`` at (B, H, W): fresh fp32 tensors, (B,heads,N,N) / (B,heads,N) each, without

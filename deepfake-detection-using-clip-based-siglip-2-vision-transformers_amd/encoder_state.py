@@ -150,6 +150,20 @@ class Contexts:
             self._sizes[key] = (a.value, b.value, c.value)
         return self._sizes[key]
 
+    def ragged_sizes(self, grids):
+        """Workspace bytes of ``sgl_query_sizes_ragged`` for a ragged batch of these (gh, gw) grids, cached."""
+        key = ("ragged", tuple(grids))
+        if key not in self._sizes:
+            if len(self._sizes) > 4096:     # every new mix of sizes is a new key
+                self._sizes.clear()
+            ctx = self.get(False)
+            flat = (C.c_int * (2 * len(grids)))(*[v for g in grids for v in g])
+            n = C.c_size_t()
+            st = _lib.load().sgl_query_sizes_ragged(ctx, flat, len(grids), C.byref(n))
+            _lib.check(st, "sgl_query_sizes_ragged", ctx)
+            self._sizes[key] = n.value
+        return self._sizes[key]
+
     def workspace(self, nbytes, dev):
         """Scratch reused across calls (stream-ordered; the C side only needs it intact within one forward / backward)."""
         ws = self._ws

@@ -134,6 +134,9 @@ def load():
                                     _fp, sz, i, _fp])
     _sig(lib, "sgl_forward_slots", i, [C.c_void_p, C.POINTER(SglWeights), _fp, _fp, i, i, i, i, i, C.POINTER(_fp), _fp, _fp,
                                        _fp, sz, _fp, sz, i, _fp])
+    _sig(lib, "sgl_query_sizes_ragged", i, [C.c_void_p, C.POINTER(C.c_int), i, psz])
+    _sig(lib, "sgl_forward_ragged", i, [C.c_void_p, C.POINTER(SglWeights), _fp, _fp, C.POINTER(C.c_int), i, C.POINTER(_fp),
+                                        _fp, _fp, _fp, sz, _fp])
     _sig(lib, "sgl_backward_begin_p", i, [C.c_void_p, C.POINTER(SglWeights), _fp, C.POINTER(SglGrads), i, i, i, _fp, _fp,
                                           _fp, _fp, _fp, sz, _fp, sz, _fp])
     _sig(lib, "sgl_backward_layer_p", i, [C.c_void_p, C.POINTER(SglWeights), _fp, C.POINTER(SglGrads), i, i, i, i, _fp,
@@ -174,6 +177,9 @@ def load():
     _sig(lib, "sgl_op_col2im", i, [_fp, i, i, i, i, i, _fp, i, _fp])
     _sig(lib, "sgl_op_pos_resize", i, [_fp, i, _fp, i, i, i, _fp])
     _sig(lib, "sgl_op_pool_attn_fwd", i, [i, _fp, _fp, _fp, _fp, _fp, i, i, i, i, i, _fp])
+    _sig(lib, "sgl_op_attn_fwd_varlen", i, [i, _fp, _fp, _fp, _fp, _fp, _fp, i, i, i, i, i, i, _fp])
+    _sig(lib, "sgl_op_pool_attn_fwd_varlen", i, [i, _fp, _fp, _fp, _fp, _fp, _fp, i, i, i, i, i, i, _fp])
+    _sig(lib, "sgl_op_seg_offsets", i, [C.POINTER(C.c_int), i, _fp, _fp])
     _sig(lib, "sgl_op_pool_attn_bwd", i, [i, _fp, _fp, _fp, _fp, _fp, _fp, _fp, i, i, i, i, i, _fp])
     _sig(lib, "sgl_op_pos_resize_bwd", i, [_fp, i, i, _fp, i, i, _fp])
     _sig(lib, "sgl_op_cast_pad", i, [_fp, i, i, i, _fp, i, i, i, i, _fp])

@@ -205,6 +205,36 @@ int sgl_forward_slots(sgl_ctx* ctx, const sgl_weights* w, const void* shadow, co
                       float* pooled, void* saved, size_t saved_bytes, void* ws, size_t ws_bytes,
                       int first_trainable_block, sgl_stream stream);
 
+/* ---- ragged batches: images of different sizes in one forward (new symbols; sgl_abi_version() stays 3) ------------------
+ * Inference only: there is no `saved` argument, so training cannot be asked for.  Works in all five compute modes, on
+ * plain and recompute contexts alike (inference on a recompute context equals a plain one).
+ * Packed layout: the S images of a call have grids (gh_s, gw_s), grids = HOST int32 [S][2], and n_s = gh_s * gw_s tokens.
+ *   Image s owns rows cu[s] .. cu[s+1]-1 of every token-major buffer, cu = the exclusive prefix sum of the n_s;
+ *   T = cu[S] rows in all; max_n = the largest n_s.  There are no padding rows.
+ * patches: the patch-major operand [T][round_up(3p^2, 64)] in the compute dtype (the channels_last == 2 form of
+ *   sgl_forward); image s occupies its n_s rows in row-major patch order, as sgl_op_im2col writes them for B = 1.  It is
+ *   only read.
+ * hs_slots: HOST array of L+1 device pointers, each [T][D] fp32; ping-pong allowed as in sgl_forward_slots (slots l and
+ *   l+1 must differ).  last_hidden: [T][D].  pooled: [S][D] or NULL.
+ * The position table is always fitted to each image's grid (interpolate_pos != 0 of sgl_forward): the stored table for a
+ * native grid, the bicubic resize otherwise.
+ * Numerics: LayerNorm, the GEMMs and their epilogues and the MX quantiser work row by row, and the two attention stages run
+ * sgl_op_attn_fwd_varlen / sgl_op_pool_attn_fwd_varlen (below), so every row of every output holds the bits that
+ * sgl_forward_slots(B = 1, interpolate_pos = 1) gives the image alone.
+ * ws: ws_bytes >= what sgl_query_sizes_ragged reports: the inference workspace of (B = 1, N = T) with S rows in the pooling
+ *   head's per-image buffers, the packed position table [T][D] and, last, cu.  For S = 1 that is what
+ *   sgl_query_sizes(B = 1, train = 0) reports for the image plus 256 bytes (cu); it never shrinks when T grows.
+ * Errors, in this order, before anything is enqueued: a NULL pointer (ctx, w, shadow, patches, grids, hs_slots,
+ *   last_hidden, ws, w->layers with L > 0) -> SGL_ERR_NULL; S < 1, a grid side < 1, T above the inference token limit of
+ *   sgl_query_sizes, with the pooling head max_n above sgl_op_pool_attn_fwd's forward limit, or a max_n the context's
+ *   attention route refuses for one image (strict fp32: its scores no longer fit the LDS) -> SGL_ERR_BAD_SHAPE; a NULL
+ *   entry of hs_slots -> SGL_ERR_NULL; ws_bytes too small -> SGL_ERR_WORKSPACE.  sgl_query_sizes_ragged: ctx / grids NULL,
+ *   then the same shape checks. */
+int sgl_query_sizes_ragged(const sgl_ctx* ctx, const int* grids, int S, size_t* ws_bytes);
+int sgl_forward_ragged(sgl_ctx* ctx, const sgl_weights* w, const void* shadow, const void* patches, const int* grids, int S,
+                       float* const* hs_slots, float* last_hidden, float* pooled, void* ws, size_t ws_bytes,
+                       sgl_stream stream);
+
 /* ---- backward (stepwise so that a data-parallel caller can all-reduce each block's gradients while the
  *      next block's backward runs; sgl_backward is the plain loop over the three steps) ------------------ */
 /* d_last_hidden [B*N][D], d_pooled [B][D], d_tap_last [B*N][D] (gradient w.r.t. hidden_states[L]); any may be
@@ -425,6 +455,33 @@ int sgl_op_pos_resize(const float* table, int native_grid, float* out, int gh, i
  * backward (head_dim_pad 80: 1488 / 1364; 64: 1819 / 1637), SGL_ERR_UNSUPPORTED above. */
 int sgl_op_pool_attn_fwd(int dtype, const float* q, const void* K, const void* V, void* out, float* probs, int B, int H,
                          int N, int head_dim, int head_dim_pad, sgl_stream stream);
+/* ---- ragged (varlen) kernels (new symbols; sgl_abi_version() stays 3) ---------------------------------------------------
+ * Packed layout as sgl_forward_ragged: segment s = rows cu[s] .. cu[s+1]-1, cu a DEVICE int32 [S+1] table (what
+ * sgl_op_seg_offsets writes), T rows in all, max_n >= the longest segment (a larger max_n changes no bit, only the launch).
+ * sgl_op_attn_fwd_varlen: q, k, v head-major [H][T][head_dim_pad] with zero pad columns (the ld_qkv == 0 layout at B = 1,
+ *   N = T); out token-major [T][H * head_dim]; lse [H][T]; dtype as sgl_op_attn_fwd, all four routes.  The launch covers
+ *   S * H (segment, head) pairs times ceil(max_n / 128) query blocks (the strict fp32 route: ceil(max_n / 4)); a workgroup
+ *   whose first query row lies past its segment exits.  Query blocks and key tiles start at the segment's first row and the
+ *   fetches are bounded to the segment's rows (rows past n_s read as zeros, never as the neighbour's rows), so segment s gets,
+ *   bit for bit, the out and lse of sgl_op_attn_fwd(B = 1, N = n_s, ld_qkv = 0) on its rows alone.
+ * sgl_op_pool_attn_fwd_varlen: q, K, V as sgl_op_pool_attn_fwd with K, V [H][T][head_dim_pad]; out [S][H * head_dim];
+ *   probs [H][T]; one workgroup per (segment, head), its LDS window sized by max_n: max_n above the forward limit of
+ *   sgl_op_pool_attn_fwd is SGL_ERR_UNSUPPORTED.  Segment s gets the bits of sgl_op_pool_attn_fwd(B = 1, N = n_s).
+ * Clamp contract: the kernels use lo = clamp(cu[s], 0, T), hi = clamp(cu[s+1], lo, T) and n_s = min(hi - lo, max_n).  A
+ *   wrong table gives wrong numbers; it cannot make a kernel read or write outside the buffers as sized by T, S and H.
+ * Errors, before anything is enqueued: a NULL pointer -> SGL_ERR_NULL; a dimension < 1, head_dim > head_dim_pad, or a
+ *   (max_n, head_dim, head_dim_pad) that sgl_op_attn_fwd refuses for an image of max_n tokens -> SGL_ERR_BAD_SHAPE; an
+ *   unknown dtype or misaligned 16-bit operands -> SGL_ERR_UNSUPPORTED.
+ * sgl_op_seg_offsets: cu[i] = lens[0] + ... + lens[i-1] for i = 0 .. S from HOST lengths.  The sums travel by value in the
+ *   arguments of a small kernel, 256 per launch: no copy from host memory, no allocation, no synchronisation, the caller's
+ *   stream only, so it may be captured into a graph.  lens / cu NULL -> SGL_ERR_NULL; S < 1, a negative length or a total
+ *   above 2^31 - 1 -> SGL_ERR_BAD_SHAPE. */
+int sgl_op_attn_fwd_varlen(int dtype, const void* q, const void* k, const void* v, void* out, float* lse, const int* cu,
+                           int S, int T, int max_n, int H, int head_dim, int head_dim_pad, sgl_stream stream);
+int sgl_op_pool_attn_fwd_varlen(int dtype, const float* q, const void* K, const void* V, void* out, float* probs,
+                                const int* cu, int S, int T, int max_n, int H, int head_dim, int head_dim_pad,
+                                sgl_stream stream);
+int sgl_op_seg_offsets(const int* lens, int S, int* cu, sgl_stream stream);
 /* probs as written by the forward, dout fp32 [B][H * head_dim] -> dkv token-major [B * N][2 * H * head_dim] of `dtype`
  * (dK block, then dV block; 16-byte aligned; every element written) and dq_partial fp32 [B][H * head_dim] (the per-image
  * gradient of q, summed over images by the caller). */
